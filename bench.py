@@ -5,11 +5,19 @@ Adam) per step.  Prints ONE JSON line (rank 0).
 Headline workload (N = 1): BASELINE.json configs[2], the largest single-GPU configuration -- a ScanNet-scene0000_00-class
 room (bound and intrinsics declared in tests/scenes.py: the reference has no such config), 5000 rays x 48 samples, colour-stage
 iteration (renders the middle + fine + colour decoders, i.e. a superset of the fine stage; the fine-stage iteration of the same
-workload, configs[1] (config/nice_slam.yaml, 1000 rays) and a configs[3] shard (1250 rays) are reported under "extras").
+workload, configs[1] (config/nice_slam.yaml, 1000 rays) and a configs[3] shard (1250 rays) are reported under "extras" with --full).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5                       # the headline figure alone
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full                # + per-kernel times, roofline, extras, CPU baselines
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps once, and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the configuration, the final loss).  Everything else -- the per-kernel HIP-event pass and the rooflines priced on it, the
+replayed counter passes, the extras (other workloads, stages, operand modes, the K5 loop) and the CPU baselines -- runs with --full,
+where the timed block is also repeated (--repeats, default 9 there) and its median reported.  With --dump-outputs the last timed step
+starts from the seeded scene and a fresh optimiser (restored with the clock stopped), so that what it computes is the same on every run.
 
 Rays shard across ranks with no data-path exchange except ONE all-reduce (RCCL, sum, fp32) of the gradient slab per step
 (SURVEY.md 8e); per-GPU work is fixed, so scaling is "weak".
@@ -199,13 +207,49 @@ def cpu_baseline_aten(sc, rays_list, stage, lr, w_color, seconds):
 
 
 TUNE = []
+DUMP_LIMIT_BYTES = 64 << 20            # --dump-outputs: at most this much in all (a fixed, seeded sample of an output that does not fit)
+
+
+def step_outputs(ctx, stage, loss, rendered, train_color):
+    """what a caller of the timed path holds after a step: the step's loss, its rendered colour / depth / depth variance (the optional
+    outputs of nsk_map_step), and the parameters its Adam step updated (the grids of the stage's levels, the colour decoder when it
+    trains), as float32 host arrays"""
+    outs = {"loss": loss.detach().float().cpu().numpy().reshape(-1)}
+    for k, t in zip(("render_rgb", "render_depth", "render_var"), rendered):
+        outs[k] = t.cpu().numpy()
+    for k in STAGE_DECODERS[stage]:
+        outs["grid_" + k] = ctx.grid_download(k)
+    if train_color:
+        outs["decoder_color"] = ctx.decoder_download("color")
+    return outs
+
+
+def write_outputs(path, outs):
+    """DIR/<name>.npy in float32; if the whole exceeds DUMP_LIMIT_BYTES, the large arrays are cut to the same fixed, seeded sample of
+    their flattened elements on every run (written as <name>_sample.npy, with the element indices in <name>_sample_index.npy)"""
+    os.makedirs(path, exist_ok=True)
+    outs = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in outs.items()}
+    total = sum(v.nbytes for v in outs.values())
+    frac = 1.0 if total <= DUMP_LIMIT_BYTES else 0.45 * DUMP_LIMIT_BYTES / total      # value + int32 index per kept element
+    for k, v in outs.items():
+        if frac < 1.0 and v.size > 4096:
+            idx = np.sort(np.random.default_rng(1234).choice(v.size, max(4096, int(v.size * frac)), replace=False)).astype(np.int32)
+            np.save(os.path.join(path, k + "_sample.npy"), v.reshape(-1)[idx])
+            np.save(os.path.join(path, k + "_sample_index.npy"), idx)
+        else:
+            np.save(os.path.join(path, k + ".npy"), v)
 
 
 def run_workload(wl, stage, N, steps, warmup, local, rank, world, dist, graph=False, frustum=True, matmul_mode=None, pipeline=False,
-                 comm=None, rays_total=None, repeats=1, backward_mode=None, forward_only=False):
+                 comm=None, rays_total=None, repeats=1, backward_mode=None, forward_only=False, profile=True, want_outputs=False,
+                 fixed_last_step=False):
     """time `steps` mapping iterations of workload `wl` at `N` rays per GPU (rays_total: a FIXED batch of that many rays sharded over
     the ranks instead -- strong scaling); returns dict(dt, prof, loss, scene, pool, ...).  comm: an RCCL communicator for the C-ABI
-    exchange (nsk_allreduce_grads), None = torch.distributed on the packed buffer"""
+    exchange (nsk_allreduce_grads), None = torch.distributed on the packed buffer.  profile: after the timed steps, run the per-kernel
+    HIP-event pass and size the exchange (prof / exchange_floats are None without it).  want_outputs: outputs = what the last timed step
+    computed (step_outputs), taken before anything else runs.  fixed_last_step (every rank alike): the last timed step starts from the seeded
+    scene and a fresh optimiser, restored with the clock stopped -- the steps before it leave state that differs from run to run by the order
+    of the gradient atomics (Adam turns rounding-sized gradients into +-lr steps), so only then are its inputs the same on every run"""
     import nice_slam_cpp_amd as pkg
     import nice_slam_cpp_amd.dist as nd
     import scenes
@@ -253,6 +297,8 @@ def run_workload(wl, stage, N, steps, warmup, local, rank, world, dist, graph=Fa
         gmax = nd.global_depth_max(gd)                           # batch-global max(gt_depth) (Renderer.cpp:76,93)
         batches.append((cu(r["rays_o"]), cu(r["rays_d"]), gd, cu(r["gt_color"]), gmax))
     loss = torch.zeros(1, device=dev)
+    # --dump-outputs: every step also hands back its rendering (nsk_map_step's optional outputs), so the last one is there to write
+    rendered = (torch.zeros(N, 3, device=dev), torch.zeros(N, device=dev), torch.zeros(N, device=dev)) if want_outputs and not forward_only else None
     flags = pkg.nsk.GRAD_GRIDS | (pkg.nsk.GRAD_DECODERS if train_color else 0)
     xev = []                                                     # (start, stop) events around the exchange when it goes through torch.distributed
 
@@ -268,7 +314,7 @@ def run_workload(wl, stage, N, steps, warmup, local, rank, world, dist, graph=Fa
             if pipeline and not graph:                           # the next batch is registered first: its sampling + cell sort ride in this step's
                 nro, nrd, ngd, _, ngmax = batches[(i + 1) % len(batches)]      # composite / backward / Adam launches (nsk_map_prepare)
                 ctx.map_prepare(stage, nro, nrd, ngd, ngmax, flags=flags)
-            ctx.map_step(stage, ro, rd, gd, gc, gmax, w_color, stage == "color", flags=flags, loss=loss)
+            ctx.map_step(stage, ro, rd, gd, gc, gmax, w_color, stage == "color", flags=flags, loss=loss, outputs=rendered)
             if world > 1:                                        # the one exchange of the path: the marked voxels of the touched levels,
                 if comm is not None:                             # the colour decoder's gradient and the loss
                     ctx.allreduce_grads_rccl(comm)               # pack -> ncclAllReduce -> unpack on the context's stream, no Python between them
@@ -305,6 +351,13 @@ def run_workload(wl, stage, N, steps, warmup, local, rank, world, dist, graph=Fa
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(steps):
+                if fixed_last_step and rep == max(1, repeats) - 1 and i == steps - 1:
+                    torch.cuda.synchronize()                     # clock stopped: the seeded parameters back in place (same buffers, so
+                    tp = time.perf_counter()                     # captured graphs stay valid), moments and step counts dropped --
+                    ctx.load_scene(sc["bound"], sc["grids"], sc["decoders"])      # what the reference's Mapper does at the start of
+                    ctx.adam_reset()                                               # every optimize_map call (src/Mapper.cpp:330)
+                    torch.cuda.synchronize()
+                    t0 += time.perf_counter() - tp
                 step(warmup + rep * steps + i)
             torch.cuda.synchronize()
             if dist is not None:
@@ -316,26 +369,30 @@ def run_workload(wl, stage, N, steps, warmup, local, rank, world, dist, graph=Fa
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             blocks = [float(x) for x in t]
         dt = float(np.median(blocks))
-        # per-kernel durations: HIP events recorded on the context's stream around every launch (same steps again)
-        ctx.profile_begin()
-        timing[0] = True
-        for i in range(steps):
-            eager_step(warmup + i)
-        timing[0] = False
-        prof = ctx.profile_end()
-        if xev:
-            torch.cuda.synchronize()
-            prof["allreduce"] = (len(xev), sum(a.elapsed_time(b) for a, b in xev))
+        outputs = step_outputs(ctx, stage, loss, rendered, train_color) if rendered is not None else None
         final_loss = float(loss)
-        # what an exchange carries (reported also for N = 1)
-        ctx.map_step(stage, *batches[0][:4], batches[0][4], w_color, stage == "color", flags=flags, loss=loss)
-        xn[0] = ctx.grad_pack().numel()
-        ctx.zero_grads()
+        prof = None
+        if profile:
+            # per-kernel durations: HIP events recorded on the context's stream around every launch (same steps again)
+            ctx.profile_begin()
+            timing[0] = True
+            for i in range(steps):
+                eager_step(warmup + i)
+            timing[0] = False
+            prof = ctx.profile_end()
+            if xev:
+                torch.cuda.synchronize()
+                prof["allreduce"] = (len(xev), sum(a.elapsed_time(b) for a, b in xev))
+            final_loss = float(loss)
+            # what an exchange carries (reported also for N = 1)
+            ctx.map_step(stage, *batches[0][:4], batches[0][4], w_color, stage == "color", flags=flags, loss=loss)
+            xn[0] = ctx.grad_pack().numel()
+            ctx.zero_grads()
     marked = None
     if mask_frac is not None:
         marked = sum(mask_frac[k] * sc["grids"][k].size for k in STAGE_DECODERS[stage])
     out = dict(dt=dt, blocks=blocks, prof=prof, loss=final_loss, sc=sc, pool=pool, lr=lr, w_color=w_color, slab_floats=int(ctx.grad_slab().numel()),
-               exchange_floats=int(xn[0]), mask_frac=mask_frac, marked_params=marked, rays_per_gpu=N)
+               exchange_floats=int(xn[0]) if profile else None, mask_frac=mask_frac, marked_params=marked, rays_per_gpu=N, outputs=outputs)
     ctx.close()
     return out
 
@@ -489,9 +546,17 @@ def counter_fracs(sq, dur_s):
 
 
 def summarize(res, stage, N, steps, world, with_counters=False):
+    """the timing figures of a run; with its per-kernel pass (res["prof"]) also the kernels, the rooflines and the counters"""
+    step_s = res["dt"] / steps
+    blocks = res.get("blocks") or [res["dt"]]
+    timing = {"value": world * N / step_s, "ms_per_step": 1e3 * step_s, "repeats": len(blocks),
+              "block_ms_per_step": {"median": 1e3 * step_s, "min": 1e3 * min(blocks) / steps, "max": 1e3 * max(blocks) / steps, "first": 1e3 * blocks[0] / steps},
+              "final_loss": res["loss"]}
+    prof = res["prof"]
+    if prof is None:
+        return timing
     S = 48
     M = N * S
-    prof = res["prof"]
     per_kernel = {k: {"launches": c, "avg_us": 1e3 * ms / c} for k, (c, ms) in prof.items()}
     cnt = alg_counts(stage, stage == "color")
     fwd_name = "decode_fwd_multi" if "decode_fwd_multi" in prof else next(k for k in prof if k.startswith("decode_fwd"))
@@ -529,7 +594,6 @@ def summarize(res, stage, N, steps, world, with_counters=False):
             roof["sibling"] = dict({"kernel": other, "avg_launch_us": o_s * 1e6, "achieved": o_tf, "frac": o_tf / PEAK_FP32_MFMA_TFLOPS,
                                     "frac_16bit": o_tf * alg[other]["products"] / PEAK_16BIT_MFMA_TFLOPS},
                                    **{k: v for k, v in counter_fracs(sq2, o_s).items() if k != "simd_cycles"})
-    step_s = res["dt"] / steps
     nparam = sum(res["sc"]["grids"][k].size for k in STAGE_DECODERS[stage])
     marked = res["marked_params"] if res.get("marked_params") is not None else nparam
     if stage == "color":
@@ -537,14 +601,12 @@ def summarize(res, stage, N, steps, world, with_counters=False):
     alg_step = float(cnt["fwd"]["alg_bytes"] + cnt["bwd"]["alg_bytes"]) * M + ADAM_BYTES_PER_PARAM * marked
     impl_step = float(cnt["fwd"]["impl_bytes"] + cnt["bwd"]["impl_bytes"]) * M + ADAM_BYTES_PER_PARAM * marked
     step_flops = 2.0 * (cnt["fwd"]["mac"] + cnt["bwd"]["mac"]) * M + 1000.0 * M     # + sampling / compositing
-    blocks = res.get("blocks") or [res["dt"]]
-    return {"value": world * N / step_s, "ms_per_step": 1e3 * step_s, "repeats": len(blocks),
-            "block_ms_per_step": {"median": 1e3 * step_s, "min": 1e3 * min(blocks) / steps, "max": 1e3 * max(blocks) / steps, "first": 1e3 * blocks[0] / steps},
+    return dict(timing, **{
             "roofline": roof,
             "step_rooflines": {"alg_bytes_per_step": alg_step, "hbm_frac": alg_step / step_s / 1e9 / PEAK_HBM_GBS,
                                "impl_bytes_per_step": impl_step, "adam_marked_params": marked,
                                "alg_flops_per_step": step_flops, "fp32_frac": step_flops / step_s / 1e12 / PEAK_FP32_MFMA_TFLOPS},
-            "kernels": per_kernel, "final_loss": res["loss"]}
+            "kernels": per_kernel})
 
 
 def extra_line(name, wl, stage, r, s, steps):
@@ -562,7 +624,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=9, help="the timed block of --steps steps is run this many times back to back; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed block of --steps steps is run this many times back to back; the median block is "
+                    "reported (default: 1, so that --steps is the number of timed steps; 9 with --full)")
     ap.add_argument("--workload", default="K3", choices=["K3", "K2", "K4"])
     ap.add_argument("--rays", type=int, default=0, help="rays per GPU per step (0 = the workload's own count)")
     ap.add_argument("--stage", default="color")
@@ -576,7 +639,17 @@ def main():
     ap.add_argument("--tune", action="append", default=[], help="key=value for nsk_set_tuning (experiments), repeatable")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound of each CPU baseline's timed sample")
     ap.add_argument("--k5-only", action="store_true", help="experiments: only the K5_loop extra (BASELINE configs[4] as a loop), printed as its own JSON line")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the per-kernel HIP-event pass and the rooflines priced on it, "
+                    "the replayed counter passes, the extras (unless --no-extras) and the CPU baselines (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (its loss, "
+                    "rendered colour / depth / variance, the grids and decoder its Adam step updated) as DIR/<name>.npy, float32, at most 64 MB in all.  "
+                    "That step starts from the seeded scene and a fresh optimiser (restored outside the timed region), so with the same arguments "
+                    "its inputs, and what it computes up to rounding, are the same on every run")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.graph:      # two replayed runs differ by +-lr in some colour parameters: the replayed step's
+        ap.error("--dump-outputs is not reproducible with --graph; dump an eager run")     # colour gradients carry order-dependent rounding
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
     TUNE[:] = args.tune
 
     rank = int(os.environ.get("RANK", "0"))
@@ -618,13 +691,16 @@ def main():
     N = args.rays or wl["rays"]
     frustum = not args.no_frustum_mask
     res = run_workload(wl, args.stage, N, args.steps, args.warmup, local, rank, world, dist, graph=args.graph, frustum=frustum, pipeline=pipeline, comm=comm,
-                       repeats=args.repeats)
+                       repeats=args.repeats, profile=args.full, want_outputs=args.dump_outputs is not None and rank == 0,
+                       fixed_last_step=args.dump_outputs is not None)
+    if rank == 0 and args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, res["outputs"])
     headline_cfg = args.workload == "K3" and N == W["K3"]["rays"] and args.stage == "color" and frustum
     head = summarize(res, args.stage, N, args.steps, world, with_counters=headline_cfg) if rank == 0 else None
     # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes of this same (default) command:
     # FETCH_SIZE and WRITE_SIZE collected in separate passes, KB; FETCH_SIZE doubled as the MI355X guide prescribes for gfx950
     pmc_name = _first_profile(PMC_FILES)
-    if rank == 0 and pmc_name is not None and headline_cfg:
+    if rank == 0 and pmc_name is not None and headline_cfg and args.full:
         pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
         prefix = KERNEL_PREFIX.get(head["roofline"]["kernel"])
         get = lambda c: next((v for k, v in pmc.items() if prefix and k.startswith(prefix) and k.endswith("|" + c)), None)
@@ -654,14 +730,19 @@ def main():
                        "pipeline_detail": ("every timed step holds one batch's sampling + cell sort, forward, loss, backward and Adam; the sampling and sort are those of the "
                                            "NEXT batch, registered before the step (nsk_map_prepare), and ride in this step's composite / backward / Adam launches "
                                            "instead of three launches of their own in front of the forward") if pipeline else "every step samples and sorts its own batch first",
-                       "parallelism": "rays sharded x%d, 1 all-reduce/step of %d floats (%.2f MB: marked voxels of the trained levels + colour decoder + loss; "
-                                      "the dense gradient slab is %d floats)" % (world, res["exchange_floats"], 4e-6 * res["exchange_floats"], res["slab_floats"])},
-            "roofline": head["roofline"], "step_rooflines": head["step_rooflines"], "kernels": head["kernels"], "final_loss": head["final_loss"],
+                       "parallelism": ("rays sharded x%d, 1 all-reduce/step of %d floats (%.2f MB: marked voxels of the trained levels + colour decoder + loss; "
+                                       "the dense gradient slab is %d floats)" % (world, res["exchange_floats"], 4e-6 * res["exchange_floats"], res["slab_floats"])
+                                       if res["exchange_floats"] is not None else
+                                       "rays sharded x%d, 1 all-reduce/step (marked voxels of the trained levels + colour decoder + loss; sized with --full; "
+                                       "the dense gradient slab is %d floats)" % (world, res["slab_floats"]))},
+            "final_loss": head["final_loss"],
         }
-        if "allreduce" in head["kernels"]:
+        if "kernels" in head:
+            out.update(roofline=head["roofline"], step_rooflines=head["step_rooflines"], kernels=head["kernels"])
+        if "allreduce" in head.get("kernels", {}):
             out["allreduce_us"] = head["kernels"]["allreduce"]["avg_us"]
             out["exchange_bytes"] = 4 * res["exchange_floats"]
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # every rank runs the extras (at N > 1 they exchange); rank 0 reports.  N = 1: the other BASELINE configs and the operand modes;
         # N > 1: configs[3] as BASELINE states it (a FIXED 10000-ray batch sharded over the ranks: strong scaling), configs[1], and the
         # headline with the pipeline setting flipped -- the driver's one run per N is the only node time there is
@@ -718,7 +799,7 @@ def main():
                 nd.rccl_comm_destroy(comm)
             dist.destroy_process_group()
         return
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_aten(res["sc"], res["pool"], args.stage, res["lr"], res["w_color"], args.cpu_seconds)
         out["cpu_baseline_c_port"] = cpu_baseline_c(res["sc"], res["pool"], args.stage, res["lr"], res["w_color"], args.cpu_seconds)
     else:

@@ -503,7 +503,7 @@ def test_rccl_communicator_bootstrapped_from_a_process_group():
 
 
 def test_bench_multi_rank_line_rehearsal(tmp_path):
-    """bench.py as the driver launches it at N > 1 (torch.distributed.run, one process per rank), rehearsed with two ranks on this one GPU
+    """bench.py --full as the driver launches it at N > 1 (torch.distributed.run, one process per rank), rehearsed with two ranks on this one GPU
     over gloo (NSK_BENCH_REHEARSE=1: numbers mean nothing, the code path is the N > 1 one): the line must carry the all-reduce time alone and
     its message size, BASELINE configs[3] as a FIXED 10000-ray batch sharded over the ranks (strong scaling), configs[1], the headline with
     the pipeline setting flipped, and BASELINE configs[4] as a loop (K5_loop: Tracker on rank 0, its pose to all ranks, sharded Mapper iterations
@@ -517,7 +517,7 @@ def test_bench_multi_rank_line_rehearsal(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, NSK_BENCH_REHEARSE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rays", "600"],
+                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rays", "600", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@ mkdir -p $out
 for w in "$@"; do
   for lib in prev new prev new; do
     if [ $lib = prev ]; then export NSK_LIB=$PWD/nice-slam-cpp_amd/csrc/libnsk_prev.so; else unset NSK_LIB; fi
-    python bench.py --workload $w --no-extras --no-cpu --steps 300 --warmup 30 > $out/b_${w}_$lib.json 2>&1 || exit 1
+    python bench.py --full --workload $w --no-extras --no-cpu --steps 300 --warmup 30 > $out/b_${w}_$lib.json 2>&1 || exit 1
     python - "$out/b_${w}_$lib.json" "$w $lib" <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")][-1]; d = json.loads(l)

@@ -3,7 +3,7 @@
 out=$1; shift
 mkdir -p $out
 for w in "$@"; do for p in 0 1 0 1; do
-  python bench.py --workload $w --no-extras --no-cpu --steps 300 --warmup 30 --pipeline $p > $out/p_${w}_$p.json 2>&1 || { tail -5 $out/p_${w}_$p.json; exit 1; }
+  python bench.py --full --workload $w --no-extras --no-cpu --steps 300 --warmup 30 --pipeline $p > $out/p_${w}_$p.json 2>&1 || { tail -5 $out/p_${w}_$p.json; exit 1; }
   python - $out/p_${w}_$p.json "$w pipeline=$p" <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")][-1]; d = json.loads(l)
