@@ -219,6 +219,24 @@ def loss_track(depth, color, var, gt_depth, gt_color, w_color, use_color, handle
     return loss
 
 
+def inside_mask(bound, rays_o, rays_d, gt_depth):
+    """the bounding-box pre-filter src/Tracker.cpp:48-54 / src/Mapper.cpp:416-422 (under NoGradGuard); the caller compacts with it"""
+    with torch.no_grad():
+        t_ = (bound.unsqueeze(0) - rays_o.detach().unsqueeze(-1)) / rays_d.detach().unsqueeze(-1)
+        t = torch.min(torch.max(t_, 2)[0], 1)[0]
+        return t >= gt_depth
+
+
+def masked_leaf(grid, mask):
+    """frustum feature selection src/Mapper.cpp:254-290: the optimiser parameter is grid[mask] (mask [Z,Y,X] tiled over the channels), a
+    leaf of its own; the level the decoders read is the grid with that leaf scattered back in, out of place.  grid [1,C,Z,Y,X].
+    Returns (leaf, assemble): assemble() rebuilds the level from the leaf's current values."""
+    m = mask[None, None].expand_as(grid)
+    leaf = grid[m].detach().clone().requires_grad_(True)
+    base = grid.detach()
+    return leaf, (lambda: base.masked_scatter(m, leaf))
+
+
 def quad2rotation(quad):
     """include/torchlib/utils.h:174-195 (written out-of-place so autograd can differentiate it)"""
     qr, qi, qj, qk = quad[:, 0], quad[:, 1], quad[:, 2], quad[:, 3]
