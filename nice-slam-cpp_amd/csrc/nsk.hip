@@ -799,7 +799,6 @@ struct nsk_ctx {
     bool roctx = false;                     // roctx ranges around every profiled launch group (libroctx64, loaded on demand)
     int tune_fwd_occ_cost = 0, tune_no_occ_role = 0;         // the merged middle + fine role of the forward: its cost against the colour role's (0 = 460); 1 = never merged, 2 = always
     int tune_fwd_fine_cost = 0, tune_fwd_color_cost = 0;     // experiments: forward role costs (nsk_set_tuning "fwd_fine_cost" / "fwd_color_cost")
-    int tune_skew = 0;                      // start offset of the upper four waves of a decoder workgroup, x 1024 cycles (wave_skew, nsk_device.h)
     bool median_fused_pending = false;
     int tune_no_deferred_median = 0;        // 1: the threshold inside the compositing launch (grid barrier) even where the backward could find it (round 3's form)
     int tune_no_fused_median = 0;           // 1: the Tracker's median threshold in its own launch even where the fused form applies (experiments, tests)
@@ -1026,7 +1025,6 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "fwd_occ_cost")) { c->tune_fwd_occ_cost = value; return 0; }
     if (!strcmp(key, "no_occ_role")) { c->tune_no_occ_role = value; return 0; }
     if (!strcmp(key, "fwd_color_cost")) { c->tune_fwd_color_cost = value; return 0; }
-    if (!strcmp(key, "skew")) { if (value < 0 || value > 299) return fail("nsk_set_tuning: skew out of range"); c->tune_skew = value; return 0; }
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
     return fail("nsk_set_tuning: unknown key '%s'", key);
@@ -1502,7 +1500,6 @@ static void fill_args(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* 
     A.img16 = c->dec[w].fimg16;
     A.bimg16 = c->dec[w].bimg16;
     A.out = w == 3 ? c->ws.rgb4 : c->ws.occ[w];
-    A.skew = c->tune_skew;
 }
 
 static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, const float* pts, bool save_masks)
@@ -1763,7 +1760,7 @@ static bool sort_pays(nsk_ctx* c, int stage, int M, unsigned flags)
     if (c->sort_mode >= 0) return c->sort_mode == 1;
     if (!(flags & NSK_GRAD_GRIDS)) return false;             // (the Tracker: 200 rays, no scatter)
     // Bundle adjustment (grids + rays): in cell order a tile's 16 samples belong to 16 rays, so the ray-gradient sums go lane by lane instead of
-    // one add per tile -- and the scatter still wins: per-role stamps at 1000 / 5000 rays (tools/exp_ts_ba.py) 168 -> 136 us / 742 -> 432 us.
+    // one add per tile -- and the scatter still wins: per-role stamps at 1000 / 5000 rays 168 -> 136 us / 742 -> 432 us.
     // Measured (tools/exp_sort_threshold.py, host_test): on the reference's grids (41 k fine cells) the two extra launches pay from ~300
     // rays x 48 on (200 rays: 92 us in ray order, 97 us sorted; 1000 rays: 236 against 162 us); on a small grid (792 cells, 9600 samples)
     // many samples share the few cells, ray order serialises their atomics and sorting wins much earlier (118 against 102 us).
@@ -1997,11 +1994,7 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
         A.g_rays_o = g_ro; A.g_rays_d = g_rd;
         A.dyn_resid = dyn_resid; A.dyn_n = N;
         A.g_dec = train ? c->ws.dec_slabs : c->slab + c->dec[w].g_off;
-#ifdef NSK_EXPERIMENT
-        A.flags = flags & 0xffffu;                                  // experiment builds pass the debug bits 9.. through (tools/exp_bwd.py)
-#else
         A.flags = flags & 0xffu;
-#endif
         if (w != 0 && (!train || w != 2)) CHK(ensure_bimg16(c, w));
         if (train && w != 2) {
             if (c->ws.hsave_M[w] != M) return fail("backward of trainable decoder %d: its forward must run with the decoder already trainable (block outputs not saved)", w);
@@ -2340,34 +2333,6 @@ extern "C" int nsk_debug_preact(nsk_ctx* c, int which, int N, const float* ro, c
     HIPCHK(hipGetLastError());
     return 0;
 }
-
-#ifdef NSK_EXPERIMENT
-extern "C" int nsk_dbg_set(nsk_ctx* c, int flags)
-{
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(nsk_dbg_flags), &flags, sizeof(int)));
-    return 0;
-}
-extern "C" int nsk_dbg_read_ph(nsk_ctx* c, unsigned long long* out)      // [8][8][96]
-{
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(nsk_dbg_ph), sizeof(unsigned long long) * 8 * 8 * 96));
-    return 0;
-}
-extern "C" int nsk_dbg_read_oob(nsk_ctx* c, unsigned* out, int clear)      // [8]: out-of-range index counts by site (NSK_IDX, nsk_device.h)
-{
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(nsk_dbg_oob), sizeof(unsigned) * 8));
-    if (clear) { unsigned z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(nsk_dbg_oob), z, sizeof(z))); }
-    return 0;
-}
-extern "C" int nsk_dbg_read_ts(nsk_ctx* c, unsigned long long* out)      // [2][1024][4]
-{
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(nsk_dbg_ts), sizeof(unsigned long long) * 2 * 1024 * 4));
-    return 0;
-}
-#endif
 
 extern "C" int nsk_frustum_mask(nsk_ctx* c, int level, const float* d_depth, int H, int W, float fx, float fy, float cx, float cy,
                                 const float h_c2w[16], uint8_t* h_mask_out)

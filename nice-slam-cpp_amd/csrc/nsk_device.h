@@ -22,15 +22,6 @@ struct GridD {              // one feature grid level, voxel-major [Z][Y][X][32]
 };
 
 #define NSK_INF __builtin_huge_valf()
-#ifdef NSK_EXPERIMENT
-__device__ int nsk_dbg_flags;
-// range audit of every index that addresses a per-sample array in the decoder bodies (experiment builds; tools/exp_idx.py): counts of
-// indices outside [0, n) by site -- 0 perm entry, 1 sample index, 2 slot (ReLU bits), 3 tile (saved block outputs), 4 ray
-__device__ unsigned nsk_dbg_oob[8];
-#define NSK_IDX(site, i, n) do { if ((long long)(i) < 0 || (long long)(i) >= (long long)(n)) atomicAdd(&nsk_dbg_oob[site], 1u); } while (0)
-#else
-#define NSK_IDX(site, i, n)
-#endif
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -164,13 +155,6 @@ __device__ __forceinline__ int cell_index(int GX, int GY, int GZ, const float* b
 #define NSK_SAMPLE_RAYS 8           // rays (waves) per workgroup of k_sample (16: 19.6 us at 5000 rays, 8: 18.1, 4: 20.9; 1000 rays: 11.5 / 10.6 / 12.3)
 #endif
 #define NSK_SAMPLE_TABLE 2048       // slots of its cell table (>= 2 x NSK_SAMPLE_RAYS x 64 keeps probing short)
-#ifdef NSK_EXPERIMENT
-extern __device__ unsigned long long nsk_dbg_ts[2][1024][4];
-// stamps of one workgroup of the sampling (tools/exp_sample.py): slot k of the unused tail of the forward's stamp array
-#define NSK_SS(k) do { if (bid == 300 && threadIdx.x == 0) nsk_dbg_ts[0][1000 + (k)][0] = __builtin_readcyclecounter(); } while (0)
-#else
-#define NSK_SS(k)
-#endif
 struct SampArgs {
     RParams R; int N, S;
     const float* rays_o; const float* rays_d; const float* gt_depth; float gtmax_host; const float* gtmax_dev; const uint8_t* keep;
@@ -193,7 +177,6 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
     const int n = bid * NSK_SAMPLE_RAYS + wave;
     const bool active = n < N;                          // whole waves; inactive ones only take part in the barriers below
     const int nc = active ? n : N - 1;
-    NSK_SS(0);
     const bool has_gt = gt_depth != nullptr;
     const int ns = R.n_samples;
     const int nsurf = S - ns;
@@ -264,13 +247,11 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         z = sh2[wave][lane];
     }
     if (active && lane < S) z_out[(size_t)n * S + lane] = z;
-    NSK_SS(1);
     if (!skey) return;                                                      // uniform over the launch
     // ---- cell keys and ranks for the cell sort -----------------------------------------------------------------------------
     if (bid == 0 && threadIdx.x == 0) hist[-1] = 0;                 // the bump cursor of k_sort_scan (one int in front of the histogram)
     for (int i = threadIdx.x; i < NSK_SAMPLE_TABLE; i += 64 * NSK_SAMPLE_RAYS) { tkey[i] = -1; tcnt[i] = 0; }
     if (threadIdx.x == 0) nlist = 0;
-    NSK_SS(2);
     int cell = -1;
     if (active && lane < S) {
         const float px = add_rn(ox, mul_rn(dx, z)), py = add_rn(oy, mul_rn(dy, z)), pz = add_rn(oz, mul_rn(dz, z));   // = sample_finish
@@ -289,7 +270,6 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
     // runs of the workgroup's rays are first merged in an LDS table (rays of one frame all start in the cells around the camera,
     // and a thousand adds on one 64-byte line take 25 us: same-line atomics serialise at the memory side), then every
     // distinct cell of the workgroup makes ONE returning add on the global histogram.
-    NSK_SS(3);
     const int prev = __shfl_up(cell, 1);
     const bool leader = active && lane < S && (lane == 0 || prev != cell);
     const unsigned long long lead = __builtin_amdgcn_ballot_w64(leader);
@@ -310,18 +290,14 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         slot = (int)h;
         off = atomicAdd(&tcnt[h], next - lane);
     }
-    NSK_SS(4);
     __syncthreads();
-    NSK_SS(5);
     // one returning add per distinct cell, ONE per thread (at most 64 x rays distinct cells): walking the table itself, a thread met up to
     // four occupied slots and made their adds one after the other -- two to three round trips of the 18 us this launch took at 5000 rays
     if ((int)threadIdx.x < nlist) { const int i = tlist[threadIdx.x]; tbase[i] = atomicAdd(hist + hist_slot(tkey[i], ncell2), tcnt[i]); }
     __syncthreads();
-    NSK_SS(6);
     int base = leader ? tbase[slot] + off : 0;
     base = __shfl(base, start);
     if (active && lane < S) { skey[(size_t)n * S + lane] = cell; srank[(size_t)n * S + lane] = base + (lane - start); }
-    NSK_SS(7);
 }
 __global__ __launch_bounds__(64 * NSK_SAMPLE_RAYS) void k_sample(SampArgs P) { sample_body(P, blockIdx.x); }
 
@@ -843,22 +819,9 @@ struct DecArgs {
     float* g_dec;             // canonical decoder gradient (trainable) or nullptr
     unsigned flags;
     float* dump;              // test aid (nsk_debug_preact): ReLU inputs [M][5][32] by sample, or nullptr
-    int skew;                 // start offset of a workgroup's upper four waves, in units of 1024 cycles (wave_skew)
     const float* dyn_resid;   // k_decode_bwd_track: per-ray |gt - depth| [dyn_n] (+inf: ray masked) -- the Tracker's median mask is applied HERE (see lower_median_x10)
     int dyn_n;
 };
-
-// The two waves that share a SIMD (w and w + 4 of a 512-thread workgroup) start a kernel in step, and a tile is a long vector-unit
-// phase (sample, gather, embedding, operand split) followed by a long matrix-core phase; in step they queue on the same unit in
-// both phases while the other unit idles (counters: MFMA busy 28 %, VALU 55 %, co-execution 11 % of the MFMA cycles).  Holding the
-// upper four waves back once, by about one vector phase, lets one wave's MFMA chain run under the other's vector work from then on.
-__device__ __forceinline__ void wave_skew(const DecArgs& A, int wave, int nw)
-{
-    const int mode = A.skew / 100, n = A.skew % 100;
-    const bool late = mode == 0 ? wave >= nw / 2 : (mode == 1 ? (wave & 1) : ((wave >> 1) & 1));
-    if (late)
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(16);
-}
 
 // ray of sample mm = mm / S without the generic division (~25 vector instructions): umulhi by ceil(2^32 / S), exact for mm < 2^32 / S
 // a load at base + a 32-bit BYTE offset: scalar base, one unsigned vector offset -- no sign extension and no 64-bit shift-add per access (an
@@ -871,9 +834,7 @@ struct __attribute__((packed, aligned(4))) Ray3 { float x, y, z; };
 __device__ __forceinline__ void sample_point(const DecArgs& A, int mm, float& px, float& py, float& pz, float& zz, int& n)
 {
     if (A.pts) { px = A.pts[3 * mm]; py = A.pts[3 * mm + 1]; pz = A.pts[3 * mm + 2]; zz = 0.f; n = 0; return; }
-    NSK_IDX(1, mm, A.M);
     n = ray_of(A, mm);           // = mm / A.S (the generic division is ~25 vector instructions)
-    NSK_IDX(4, n, (A.M + A.S - 1) / A.S);
     zz = A.z[mm];
     const Ray3 o = *reinterpret_cast<const Ray3*>(A.rays_o + 3 * n), d = *reinterpret_cast<const Ray3*>(A.rays_d + 3 * n);
     px = add_rn(o.x, mul_rn(d.x, zz));           // reference src/Renderer.cpp:121
@@ -886,19 +847,17 @@ __device__ __forceinline__ void sample_point(const DecArgs& A, int mm, float& px
 // the forward got 7 us SLOWER at K3 on the same box, sampling + sort 6 us slower -- the ray arrays are cache-resident, the records stream --
 // and parity moved: forming p in another kernel changes whether the compiler fuses o + d z, p moves by an ulp, p.B by ~1e-5 rad, and
 // ReLUs within that of zero flip: K3 colour-grid gradient 3.5e-4 -> 1.15e-3 from the oracle, the very figure round 2's 32-bit addressing
-// experiment met; the index audit of tools/exp_idx.py is clean, so that discrepancy was this rounding effect, not an out-of-range read.)
+// experiment met; the range audit of every per-sample index (tools/README.md, retired instruments) was clean, so that discrepancy was this rounding effect, not an out-of-range read.)
 struct SampleRaw { float z, o[3], d[3]; };
 
 __device__ __forceinline__ void sample_load(const DecArgs& A, int mm, SampleRaw& R)
 {
     if (A.pts) { R.o[0] = A.pts[3 * mm]; R.o[1] = A.pts[3 * mm + 1]; R.o[2] = A.pts[3 * mm + 2]; R.z = 0.f; R.d[0] = R.d[1] = R.d[2] = 0.f; return; }
-    NSK_IDX(1, mm, A.M);
     const int n = ray_of(A, mm);     // = mm / A.S
-    NSK_IDX(4, n, (A.M + A.S - 1) / A.S);
     R.z = ld32<float>(A.z, (unsigned)mm * 4u);
     // a ray's origin and direction as ONE 12-byte load each (global_load_dwordx3 needs dword alignment only): the 16 samples of a cell-sorted tile
     // come from 16 rays, so every load instruction touches 16 cache lines, and seven of them per tile and wave kept the CU's address unit busy
-    // for ~2 500 cycles of a trainable iteration (tools/exp_ph3.py: the stage_a segment); three do the same work
+    // for ~2 500 cycles of a trainable iteration (the stage_a segment); three do the same work
     const Ray3 o = ld32<Ray3>(A.rays_o, (unsigned)n * 12u), d = ld32<Ray3>(A.rays_d, (unsigned)n * 12u);
     R.o[0] = o.x; R.o[1] = o.y; R.o[2] = o.z; R.d[0] = d.x; R.d[1] = d.y; R.d[2] = d.z;
 }
@@ -916,10 +875,6 @@ __device__ __forceinline__ void sample_finish(const DecArgs& A, const SampleRaw&
 __device__ __forceinline__ int slot_sample(const DecArgs& A, int slot)
 {
     const int s = min(slot, A.M - 1);
-    NSK_IDX(2, s, A.M);
-#ifdef NSK_EXPERIMENT
-    if (A.perm) { const int v = A.perm[s]; NSK_IDX(0, v, A.M); return v; }
-#endif
     return A.perm ? ld32<int>(A.perm, (unsigned)s * 4u) : s;
 }
 
@@ -1030,20 +985,9 @@ __device__ __forceinline__ void block_sum(const float* __restrict__ x, int n, fl
     if (threadIdx.x == 0) { for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += sh[w]; *out = s; }
 }
 // (a 1024-thread form, 4 waves per SIMD at 128 VGPRs, measured 126 us against 73 us for this one at 1000 rays)
-#ifdef NSK_EXPERIMENT
-// per-workgroup (start, end, role, xcc) stamps of the last fwd [0] / bwd [1] multi launch (tools/exp_ts.py)
-__device__ unsigned long long nsk_dbg_ts[2][1024][4];
-#define NSK_TS_BEGIN(K) unsigned long long ts0_ = wall_clock64()
-#define NSK_TS_END(K, role) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < 1024) { unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); \
-    nsk_dbg_ts[K][blockIdx.x][0] = ts0_; nsk_dbg_ts[K][blockIdx.x][1] = wall_clock64(); nsk_dbg_ts[K][blockIdx.x][2] = (role); nsk_dbg_ts[K][blockIdx.x][3] = xcc & 15; } } while (0)
-#else
-#define NSK_TS_BEGIN(K)
-#define NSK_TS_END(K, role)
-#endif
 
 __global__ __launch_bounds__(512) void k_decode_fwd_multi(MultiArgs MA)
 {
-    NSK_TS_BEGIN(0);
     int r = 0;
     while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;
     const int b0 = r == 0 ? 0 : MA.wg_end[r - 1];
@@ -1054,7 +998,6 @@ __global__ __launch_bounds__(512) void k_decode_fwd_multi(MultiArgs MA)
     case 2: decode_fwd_body<2, 8>(MA.a[r], bid, nb); break;
     default: decode_fwd_body<3, 8>(MA.a[r], bid, nb); break;
     }
-    NSK_TS_END(0, r);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1406,20 +1349,12 @@ __device__ __forceinline__ void scatter_tile(const GridD& G, const Tri& T, const
         for (int c = 0; c < 8; ++c) wT[c * 20 + j] = valid ? T.w[c] : 0.f;
     }
     lds_fence();
-#ifdef NSK_SCATTER_NO_WALK      // timing experiment: the tile's operands go to LDS, nothing else happens
-    return;
-#endif
     const int q = lane & 3, cg = lane >> 5, ch = (lane >> 2) & 7;
     const float* arow = wT + (4 * cg + q) * 20;             // this lane's A row: the weights of corner 4 cg + q, by sample
     const float* brow = gT + (4 * ch + q) * 20;             // this lane's B column: channel 4 ch + q, by sample
     char* const gbase = reinterpret_cast<char*>(G.g);
     const unsigned coff = (unsigned)(4 * ch + q) * 4u;      // byte offset of the lane's channel inside a voxel row (128 bytes; a level has < 2^25 voxels)
     const unsigned zsel = cg ? 0xffffffffu : 0u;
-#if defined(NSK_EXPERIMENT) && !defined(NSK_SCATTER_PLAIN)
-    const int dbg = __builtin_amdgcn_readfirstlane(nsk_dbg_flags);      // tools/exp_ts.py: 1 no atomics (addresses kept), 2 no matrix instructions (their branches cost ~10 us at 1000 rays: -DNSK_SCATTER_PLAIN leaves them out)
-#else
-    constexpr int dbg = 0;
-#endif
     f4 d = (f4)(0.f);
     // The voxel rows of a run: corner c = 4 dz + 2 dy + dx sits at vox[0] + dx ox + dy oy + dz oz (tri_setup: the clamped neighbour along an axis
     // is the voxel itself or one stride further), so four scalars read from the lane of the run's first sample -- vox[0], vox[1], vox[2], vox[4] --
@@ -1436,13 +1371,7 @@ __device__ __forceinline__ void scatter_tile(const GridD& G, const Tri& T, const
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float* dst = reinterpret_cast<float*>(gbase + (((unsigned)sv[i] << 7) + vb));
-#if defined(NSK_SCATTER_WG_SCOPE)      // timing experiments only: the atomics at workgroup scope (wrong sums across XCDs) / no atomics
-            __hip_atomic_fetch_add(dst, d[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#elif defined(NSK_SCATTER_NO_ATOMICS)
-            asm volatile("" :: "v"(dst), "v"(d[i]));
-#else
-            if (dbg & 1) asm volatile("" :: "v"(dst), "v"(d[i])); else atomicAdd(dst, d[i]);
-#endif
+            atomicAdd(dst, d[i]);
         }
     };
     run_start(0);
@@ -1459,7 +1388,7 @@ __device__ __forceinline__ void scatter_tile(const GridD& G, const Tri& T, const
                 run_start(s);
                 d = (f4)(0.f);
             }
-            if (dbg & 2) d[0] += a4[t] * b4[t]; else d = mfma_outer(a4[t], b4[t], d);
+            d = mfma_outer(a4[t], b4[t], d);
         }
     }
     flush();
@@ -1488,12 +1417,6 @@ __device__ __forceinline__ void tri_grad_p(const GridD& G, const Tri& T, int g, 
     for (int k = 0; k < 3; ++k) gp[k] += gi[k] * T.gmul[k];
 }
 
-#ifdef NSK_EXPERIMENT
-#define NSK_DBG(A, bit) (((A).flags >> (bit)) & 1u)
-#else
-#define NSK_DBG(A, bit) 0u
-#endif
-
 // ------------------------------------------------------------------------------------------------------
 // K4 (frozen decoders): backward over 16-sample tiles from the ReLU bits the forward saved:
 // g_out -> chain of transposed products -> g_c (-> run-deduplicated scatter into the grid gradient)
@@ -1502,7 +1425,7 @@ __device__ __forceinline__ void tri_grad_p(const GridD& G, const Tri& T, int g, 
 // The same copy in two halves, so that a body can put the first tile's own loads between them: the image loads are issued, then the
 // sample loads (which wait only for the sample index fetched before the image: loads return in order), then the image is stored.
 // Until round 3 a body copied its image, met at the barrier and only then started the chain index -> sample -> corners: three round
-// trips behind the image's one (tools/exp_ph3.py: "first stage" 9 000 cycles after an image copy of 2 000).
+// trips behind the image's one ("first stage" 9 000 cycles after an image copy of 2 000).
 template <int K> struct ImgRegs { f4 v[K]; };
 template <int NT, int K>
 __device__ __forceinline__ void image_issue(ImgRegs<K>& R, const f4* __restrict__ src, int n4)
@@ -1556,7 +1479,6 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
     auto slot_of = [&](int task_) { return min(min(task_, ntasks - 1) * 16 + j, A.M - 1); };
     auto stage = [&](int task_, int mm_, Staged& S_) {
         const int sl_ = slot_of(task_);
-        NSK_IDX(2, sl_, A.M);
         sample_load(A, mm_, S_.r);
         S_.gr = ld32<f4>(A.g_raw, (unsigned)mm_ * 16u);
         S_.mask = ld32<unsigned long long>(A.masks, ((unsigned)sl_ * 4u + (unsigned)g) * 8u);
@@ -1586,7 +1508,6 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
     }
     int mm_next = slot_sample(A, slot_of(tile_of(1, wg, nw, tsh)));
     const bool det = (A.flags & 0x8000u) != 0;      // deterministic debug mode: every wave walks all kmax rounds (they meet at barriers)
-    if (!det) wave_skew(A, wave, NW);
     for (int k = 0; k < kmax; ++k) {
         const int task = tile_of(k, wg, nw, tsh);
         if (task >= ntasks && !det) break;
@@ -1724,7 +1645,7 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
                 if (det) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
-        if ((A.flags & 1u) && A.grid.g && !NSK_DBG(A, 9)) {
+        if ((A.flags & 1u) && A.grid.g) {
             if (det) {                      // deterministic debug mode (one workgroup): the waves scatter in turn, so every atomic add has a fixed place in time
                 for (int w = 0; w < NW; ++w) { if (wave == w) { scatter_tile(A.grid, T, gc, lane, valid, scratch); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } __syncthreads(); }
             } else scatter_tile(A.grid, T, gc, lane, valid, scratch);

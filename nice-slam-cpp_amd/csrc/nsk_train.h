@@ -111,7 +111,7 @@ __device__ __forceinline__ void split2_pair(float x0, float x1, unsigned& h01, u
 
 // transpose one D-layout quad (16 feature rows x this wave's 16 samples) into the panel at row `row0`.
 // Until round 3 every lane stored its four rows as 16-bit values, eight ds_write_b16 per quad: an LDS store takes its four cycles whatever its
-// width, 368 of them per wave and iteration kept the put phases on the LDS store path (11.8 k cycles CU-wide, tools/exp_ph3.py).  Now the two
+// width, 368 of them per wave and iteration kept the put phases on the LDS store path (11.8 k cycles CU-wide).  Now the two
 // lanes of adjacent samples share the work: the even lane keeps rows 0, 1 of both samples, the odd lane rows 2, 3 (one DPP exchange of the dword
 // the partner needs, two byte permutes), and each stores two 32-bit words per plane -- half the store instructions for +6 vector instructions.
 __device__ __forceinline__ void pair_words(unsigned v01, unsigned v23, bool odd, unsigned selA, unsigned selB, unsigned& wA, unsigned& wB)
@@ -259,19 +259,10 @@ __device__ __forceinline__ void pn_flush(float* __restrict__ g_dec, const TrainP
     }
 }
 
-#ifdef NSK_EXPERIMENT
-__device__ unsigned long long nsk_dbg_ph[8][8][96];      // [workgroup < 8][wave][point]: s_memtime at points of the LAST iteration
-#define NSK_PH(k) do { if (bid < 8 && lane == 0) nsk_dbg_ph[bid][wave][k] = __builtin_readcyclecounter(); } while (0)
-#define NSK_PHI(k) do { if (bid < 8 && lane == 0 && it < 2) nsk_dbg_ph[bid][wave][32 + 32 * it + (k)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define NSK_PH(k)
-#define NSK_PHI(k)
-#endif
 // workgroup barrier for LDS data only: __syncthreads() also drains vmcnt, i.e. every outstanding global load, store and
 // atomic of the wave (an atomic stays counted for thousands of cycles), although nothing in global memory is exchanged here
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// (no experiment switch removes these barriers: the scatter's run table shares LDS with the panel, and a run without them faulted the GPU)
-#define NSK_BAR() lds_barrier()
+// (none of these barriers may ever be skipped: the scatter's run table shares LDS with the panel, and a run without them faulted the GPU)
 
 template <int WHICH, bool RAYS, bool FULL = false>      // FULL: the chain's products on the fp32 MFMA (nsk_set_backward_mode 0); the weight-gradient panels keep two bf16 pieces
 __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid, int nb)
@@ -322,7 +313,7 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
 
     const int ntasks = (A.M + 15) >> 4;
     const int iters = tiles_per_wave(ntasks, nb * 8, 0);
-    const bool scat = (A.flags & 1u) && A.grid.g && !NSK_DBG(A, 9);
+    const bool scat = (A.flags & 1u) && A.grid.g;
     // Everything iteration it+1 reads from global memory (its samples, upstream gradient, gathered features, and the
     // forward image) is fetched at the end of iteration it BEFORE that iteration's scatter: vmcnt retires in order, so a
     // load issued after the atomics would wait for all of them (measured: 13k cycles at the top of an iteration).
@@ -363,7 +354,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
         // rebuilt from it with immediate offsets instead of being hoisted out of the loop, where ~50 of them were spilled to scratch
         // (and every reload inside the loop is a vmcnt wait behind the previous iteration's atomics)
         lane = lane0; asm volatile("" : "+v"(lane)); j = lane & 15; g = lane >> 4;
-        NSK_PH(0); NSK_PHI(0);
         if (it > 0) lds_barrier();                   // the head of the panel was the waves' scatter scratch until here
         const bool valid = nx.valid;
         float px = nx.px, py = nx.py, pz = nx.pz, zz = nx.zz; const int n = nx.n;
@@ -397,7 +387,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             CC.xc[0] = nx.xc[0]; CC.xc[1] = nx.xc[1];
             CC.h[4][0] = nx.h4[0]; CC.h[4][1] = nx.h4[1]; mask = nx.mask;
         }
-        NSK_PH(1); NSK_PHI(1);
         f4 gh[2];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -410,16 +399,15 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             }
         // ---- phase OUT: G = g_out (rows >= OD zero), X = h4 ------------------------------------------------
         {
-            if (!NSK_DBG(A, 14)) pn_put(pn, PM, 0, wave, lane, go);
+            pn_put(pn, PM, 0, wave, lane, go);
             const f4* h4 = XYZ ? C.h[4] : CC.h[4];
-            if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS, wave, lane, h4[0]);
-            if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS + 16, wave, lane, h4[1]);
-            NSK_BAR();
+            pn_put(pn, PM, PN_GROWS, wave, lane, h4[0]);
+            pn_put(pn, PM, PN_GROWS + 16, wave, lane, h4[1]);
+            lds_barrier();
             constexpr TrainPhase P = plan.p[PL::P_OUT];
-            if (!NSK_DBG(A, 13)) pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0);
-            NSK_BAR();
+            pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0);
+            lds_barrier();
         }
-        NSK_PH(2); NSK_PHI(2);
         f4 gc[2] = {(f4)(0.f), (f4)(0.f)};
         f4 ge[6];
 #pragma unroll
@@ -437,7 +425,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             // h[l-1] is the X operand of this layer's weight phase.  It is fetched a whole layer ahead (h[3] at the top of the iteration):
             // one phase ahead, as it was, every W phase opened with s_waitcnt vmcnt on a load issued ~1000 cycles earlier
             if constexpr (SAVED && l >= 2) load_h(std::integral_constant<int, l - 2>{});
-            if constexpr (l == 2) NSK_PH(20);
             if constexpr (XYZ) {
                 if constexpr (H16) {        // (the low accumulators join g_c layer by layer: eight registers fewer across the panel phases)
                     const H2 xg = split_block_h(gh[0], gh[1]);
@@ -445,22 +432,16 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                     gemm_h(imgh, MlpBwdImgH::FT(l), lane, xg, gc, gl);
                     gc[0] += gl[0] * (1.f / NSK_H16_SCALE); gc[1] += gl[1] * (1.f / NSK_H16_SCALE);
                 } else gemm<2, 2>(bimg, MlpBwdImg::FT(l), lane, gh, gc);                 // g_c += fc[l]^T g_h
-                if constexpr (l == 2) NSK_PH(21);
                 // ---- phase FC_l: G = g_h, X = c ------------------------------------------------------------
-                if (!NSK_DBG(A, 14)) pn_put(pn, PM, 0, wave, lane, gh[0], us);
-                if (!NSK_DBG(A, 14)) pn_put(pn, PM, 16, wave, lane, gh[1], us);
+                pn_put(pn, PM, 0, wave, lane, gh[0], us);
+                pn_put(pn, PM, 16, wave, lane, gh[1], us);
 #pragma unroll
-                for (int q = 0; q < CQ; ++q) if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS + 16 * q, wave, lane, C.xc[q]);
-                if constexpr (l == 2) NSK_PH(22);
-                NSK_BAR();
-                if constexpr (l == 2) NSK_PH(23);
+                for (int q = 0; q < CQ; ++q) pn_put(pn, PM, PN_GROWS + 16 * q, wave, lane, C.xc[q]);
+                lds_barrier();
                 constexpr TrainPhase P = plan.p[PL::P_FC0 + l];
-                if (!NSK_DBG(A, 13)) pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0);
-                if constexpr (l == 2) NSK_PH(24);
-                NSK_BAR();
-                if constexpr (l == 2) NSK_PH(25);
+                pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0);
+                lds_barrier();
             }
-            if constexpr (l == 3) NSK_PH(13); NSK_PHI(13);
             f4 ga[2];
 #pragma unroll
             for (int r = 0; r < 2; ++r)
@@ -470,48 +451,42 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             if constexpr (H16) xa = split_block_h(ga[0], ga[1]);       // (split again rather than masking g_h's pieces: those would stay live across phase FC)
             // ---- phase W_l: G = g_a, X = layer input ----------------------------------------------------------
             {
-                if (!NSK_DBG(A, 14)) pn_put(pn, PM, 0, wave, lane, ga[0], us);
-                if (!NSK_DBG(A, 14)) pn_put(pn, PM, 16, wave, lane, ga[1], us);
+                pn_put(pn, PM, 0, wave, lane, ga[0], us);
+                pn_put(pn, PM, 16, wave, lane, ga[1], us);
                 if constexpr (XYZ) {
                     if constexpr (l == 0) {
                     } else if constexpr (l == 3) {
                         // layer 3 has two inputs, e (its own panel rows) and h2: h2 goes into the X rows in the same phase -- the G panel
                         // is the same for both products (this used to be a phase of its own: two more barriers per iteration)
-                        if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS, wave, lane, C.h[2][0]);
-                        if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS + 16, wave, lane, C.h[2][1]);
+                        pn_put(pn, PM, PN_GROWS, wave, lane, C.h[2][0]);
+                        pn_put(pn, PM, PN_GROWS + 16, wave, lane, C.h[2][1]);
                     } else {
-                        if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS, wave, lane, C.h[l - 1][0]);
-                        if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS + 16, wave, lane, C.h[l - 1][1]);
+                        pn_put(pn, PM, PN_GROWS, wave, lane, C.h[l - 1][0]);
+                        pn_put(pn, PM, PN_GROWS + 16, wave, lane, C.h[l - 1][1]);
                     }
                 } else {
                     if constexpr (l == 0 || l == 3) { pn_put(pn, PM, PN_GROWS, wave, lane, CC.xc[0]); pn_put(pn, PM, PN_GROWS + 16, wave, lane, CC.xc[1]); }
                     else { pn_put(pn, PM, PN_GROWS, wave, lane, CC.h[l - 1][0]); pn_put(pn, PM, PN_GROWS + 16, wave, lane, CC.h[l - 1][1]); }
                 }
-                if constexpr (l == 2) NSK_PH(26);
-                NSK_BAR();
-                if constexpr (l == 2) NSK_PH(27);
+                lds_barrier();
                 constexpr TrainPhase P = plan.p[PL::P_W0 + l];
                 constexpr int xrow0 = (XYZ && (l == 0 || l == 3)) ? PN_EROWS(CQ) : PN_GROWS;
-                if (!NSK_DBG(A, 13)) pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0, xrow0);
+                pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0, xrow0);
                 if constexpr (XYZ && l == 3) {        // second input of layer 3 (h2, in the X rows), same phase; its four tiles go to waves 4..7
                     constexpr TrainPhase P2 = plan.p[PL::P_W3H];      // (the e tiles above give waves 0..5 two tiles and waves 6, 7 one)
-                    if (!NSK_DBG(A, 13)) pn_tiles<P2.nslots>(pn, PM, P2.RT, P2.NC, P2.rowsum, (wave + 4) & 7, lane, acc + P2.slot0);
+                    pn_tiles<P2.nslots>(pn, PM, P2.RT, P2.NC, P2.rowsum, (wave + 4) & 7, lane, acc + P2.slot0);
                 }
-                if constexpr (l == 2) NSK_PH(28);
-                NSK_BAR();
-                if constexpr (l == 2) NSK_PH(29);
-                if constexpr (l == 3) NSK_PH(14); NSK_PHI(14);
+                lds_barrier();
                 if constexpr (!XYZ && l == 3) {        // coarse decoder: second input panel of layer 3: h2 (G panel unchanged)
                     const f4* h2 = CC.h[2];
-                    if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS, wave, lane, h2[0]);
-                    if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_GROWS + 16, wave, lane, h2[1]);
-                    NSK_BAR();
+                    pn_put(pn, PM, PN_GROWS, wave, lane, h2[0]);
+                    pn_put(pn, PM, PN_GROWS + 16, wave, lane, h2[1]);
+                    lds_barrier();
                     constexpr TrainPhase P2 = plan.p[PL::P_W3H];
-                    if (!NSK_DBG(A, 13)) pn_tiles<P2.nslots>(pn, PM, P2.RT, P2.NC, P2.rowsum, wave, lane, acc + P2.slot0);
-                    NSK_BAR();
+                    pn_tiles<P2.nslots>(pn, PM, P2.RT, P2.NC, P2.rowsum, wave, lane, acc + P2.slot0);
+                    lds_barrier();
                 }
             }
-            if constexpr (l == 3) NSK_PH(15); NSK_PHI(15);
             if constexpr (H16) {
                 // g_e = W3e^T g_a3 + W0e^T g_a0 is needed only after the chain: layer 3 keeps the pieces of g_a3 (8 registers) instead of
                 // forming its share of g_e (24 registers) three layers early
@@ -521,17 +496,14 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                     f4 ghn[2] = {(f4)(0.f), (f4)(0.f)}, ghl[2] = {(f4)(0.f), (f4)(0.f)};
                     gemm_h(imgh, MlpBwdImgH::WT(l), lane, xa, ghn, ghl);
                     gh[0] = ghn[0] + ghl[0] * (1.f / NSK_H16_SCALE); gh[1] = ghn[1] + ghl[1] * (1.f / NSK_H16_SCALE);
-                    if constexpr (l == 2) NSK_PH(30);
                 }
             } else if constexpr (XYZ) {
                 if constexpr (l == 3) gemm_e(bimg, MlpBwdImg::W3ET, lane, ga, ge);
-                if constexpr (l == 3) NSK_PH(16); NSK_PHI(16);
                 if constexpr (l == 0) gemm_e(bimg, MlpBwdImg::W0ET, lane, ga, ge);
                 if constexpr (l >= 1) {
                     f4 ghn[2] = {(f4)(0.f), (f4)(0.f)};
                     gemm<2, 2>(bimg, MlpBwdImg::WT(l), lane, ga, ghn);
                     gh[0] = ghn[0]; gh[1] = ghn[1];
-                    if constexpr (l == 2) NSK_PH(30);
                 }
             } else {
                 if constexpr (l == 3) gemm<2, 2>(bimg, CoarseBwdImg::W3CT, lane, ga, gc);
@@ -545,17 +517,11 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             }
         };
         layer(std::integral_constant<int, 4>{});
-        NSK_PH(3); NSK_PHI(3);
         layer(std::integral_constant<int, 3>{});
-        NSK_PH(4); NSK_PHI(4);
         layer(std::integral_constant<int, 2>{});
-        NSK_PH(5); NSK_PHI(5);
         layer(std::integral_constant<int, 1>{});
-        NSK_PH(6); NSK_PHI(6);
         layer(std::integral_constant<int, 0>{});
-        NSK_PH(7); NSK_PHI(7);
         if (it + 1 < iters) { stage_a(it + 1, mm_next, nx); mm_next = slot_sample(A, slot_of(it + 2)); }
-        NSK_PH(8); NSK_PHI(8);
         if constexpr (H16) {        // take the sample's scale off g_c (g_e keeps it: phase DB and g_p below)
             gc[0] *= us; gc[1] *= us;
         }
@@ -571,13 +537,13 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                 f4 pq;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { int row = 4 * g + i; pq[i] = !valid ? 0.f : (row == 0 ? px : (row == 1 ? py : (row == 2 ? pz : 0.f))); }
-                if (!NSK_DBG(A, 14)) pn_put(pn, PM, 0, wave, lane, pq, us);          // (H16: g_s below still carries the sample's scale; it comes off on this side of the product)
+                pn_put(pn, PM, 0, wave, lane, pq, us);          // (H16: g_s below still carries the sample's scale; it comes off on this side of the product)
 #pragma unroll
-                for (int q = 0; q < 6; ++q) if (!NSK_DBG(A, 14)) pn_put(pn, PM, PN_EROWS(CQ) + 16 * q, wave, lane, ge[q]);
-                NSK_BAR();
+                for (int q = 0; q < 6; ++q) pn_put(pn, PM, PN_EROWS(CQ) + 16 * q, wave, lane, ge[q]);
+                lds_barrier();
                 constexpr TrainPhase P = plan.p[PL::P_DB];
-                if (!NSK_DBG(A, 13)) pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0, PN_EROWS(CQ));
-                NSK_BAR();
+                pn_tiles<P.nslots>(pn, PM, P.RT, P.NC, P.rowsum, wave, lane, acc + P.slot0, PN_EROWS(CQ));
+                lds_barrier();
             }
             if constexpr (RAYS) {
 #pragma unroll
@@ -618,7 +584,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                 }
             }
         }
-        NSK_PH(9); NSK_PHI(9);
         if (it + 1 < iters) {
             stage_b(nx);
         }
@@ -628,15 +593,12 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
         // waitcnt pass is path-insensitive, and under the `if` above it still saw a path (loads issued, use skipped) that reaches the
         // loop header with the loads pending.
         if constexpr (SAVED) asm volatile("" : "+v"(nx.h4[0]), "+v"(nx.h4[1]), "+v"(nx.gr), "+v"(nx.mask), "+v"(mm_next));
-        NSK_PH(17); NSK_PHI(17);
         if (scat) {
             if (A.flags & 0x8000u) {        // deterministic debug mode: see decode_bwd_body
                 for (int w = 0; w < 8; ++w) { if (wave == w) { scatter_tile(A.grid, T, gc, lane, valid, scratch); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } __syncthreads(); }
             } else scatter_tile(A.grid, T, gc, lane, valid, scratch);
         }
-        NSK_PH(10); NSK_PHI(10);
     }
-    NSK_PH(11);
     // ---- single flush of this wave's output tiles -------------------------------------------------------------
     float* slab = A.g_dec + (size_t)bid * ((plan_total<WHICH>() + 3) & ~3);
     pn_flush<plan.p[PL::P_OUT].nslots>(slab, plan.p[PL::P_OUT], wave, lane, acc + plan.p[PL::P_OUT].slot0);
@@ -647,7 +609,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
     if constexpr (plan.p[PL::P_W3H].nslots > 0)
         pn_flush<plan.p[PL::P_W3H].nslots>(slab, plan.p[PL::P_W3H], XYZ ? (wave + 4) & 7 : wave, lane, acc + plan.p[PL::P_W3H].slot0);
 #undef NSK_FLUSH
-    NSK_PH(12);
 }
 
 
@@ -725,11 +686,7 @@ __device__ __forceinline__ void gemm_e2_global(const h8* __restrict__ gimg, int 
     F[0] = load_frag_e(gimg, 0, lane);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-#ifdef NSK_V_NOGE
-        if (a > 0) F[a] = load_frag_e(gimg, a, lane);
-#else
         if (a + 1 < 3) F[a + 1] = load_frag_e(gimg, a + 1, lane);
-#endif
         f4 tH[2] = {acc[2 * a], acc[2 * a + 1]}, tL[2] = {(f4)(0.f), (f4)(0.f)};
         mac_block_h(F[a].a30, F[a].a31, x3, tH, tL);
         mac_block_h(F[a].a00, F[a].a01, x0, tH, tL);
@@ -741,7 +698,7 @@ __device__ __forceinline__ void gemm_e2_global(const h8* __restrict__ gimg, int 
 // A job = one wave, one 16-row block of G (the A operand) and up to four 16x16 output tiles that share it: X blocks (the B operands) or the
 // row sums (bias gradients).  The A fragments are read once per job and K-step instead of once per tile (a layer's twelve tiles read 160
 // fragments, its four to eight jobs 96 to 128: the tile phases are bound by LDS reads, not by the matrix pipe -- 1 000 cycles per tile and wave
-// against 256 of MFMA, tools/exp_ph3.py), and the jobs of every phase are dealt so that the two waves of each SIMD (w, w + 4) carry the same
+// against 256 of MFMA), and the jobs of every phase are dealt so that the two waves of each SIMD (w, w + 4) carry the same
 // number of tiles and no wave owns more than twelve tiles in all: 48 accumulator registers instead of 60.
 struct TJob { int wave, grow, nt; int xrow[4]; int ph[4]; int rt; int ch[4]; };      // ch < 0: row sums (xrow unused)
 template <int WHICH>
@@ -924,14 +881,13 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
     float* smf = reinterpret_cast<float*>(smem);
     char* pn = reinterpret_cast<char*>(smf + PM_IMG_F);
     constexpr int PM = PM_ROWS * PN_RB;                  // plane M behind plane H
-    NSK_PH(28);
     float* scratch = smf + PM_IMG_F + wave * 1056;       // per-wave scatter scratch: plane H of rows 0..124 (G1, G2, XC, XH), all rewritten only after the next iteration's first barrier
     static_assert(8 * 1056 * 4 <= PM_E * PN_RB, "scatter scratch must end before the E rows");
     // (the image copy itself sits further down, around the first tile's sample loads: image_issue, nsk_device.h)
     const h8* imgh = reinterpret_cast<const h8*>(smem);
     // The e-part fragments (W0e^T, W3e^T: 12 groups, 24 KB) have no room in LDS beside the panel.  Until round 3 every wave read them from L2 for
     // every tile: 192 KB per iteration through the CU's vector cache, ~3 000 cycles of streaming in front of everything issued behind them
-    // (tools/exp_ph3.py).  Now the workgroup copies them ONCE per iteration into panel rows that are dead between layer 0's tiles and the next
+    // (DESIGN.md section 4.3, round 3).  Now the workgroup copies them ONCE per iteration into panel rows that are dead between layer 0's tiles and the next
     // iteration (plane H of G2 / XC / XH, rows 32..127: 26 112 B): global loads issued before layer 0, LDS stores after its last barrier.
     const f4* gimg_e = reinterpret_cast<const f4*>(A.bimg16) + (size_t)MlpBwdImgH::W0ET * 2 * 1024 / 16;      // groups 18..29, contiguous
     constexpr int EIMG_F4 = 12 * 2 * 1024 / 16;                      // 1536 float4 = 3 per thread
@@ -948,15 +904,13 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
 
     const int ntasks = (A.M + 15) >> 4;
     const int iters = tiles_per_wave(ntasks, nb * 8, 0);
-    const bool scat = (A.flags & 1u) && A.grid.g && !NSK_DBG(A, 9);
-    const bool no_put = NSK_DBG(A, 14), no_tiles = NSK_DBG(A, 13);      // experiment builds only (constant false otherwise); the barriers always stay
-    (void)no_put; (void)no_tiles;
+    const bool scat = (A.flags & 1u) && A.grid.g;
     // Staged: what iteration it + 1 needs, fetched during iteration it in three steps, none of which waits for a load it has just issued:
     //   stage_a   (after the chain)        sample data as loaded (z, ray), upstream gradient, ReLU bits, h4   -- issue only
     //   stage_b1  (before phase DB's barrier)  the point p, its cell, and the 16 corner loads of the gather    -- issue only
     //   stage_b2  (after phase DB)         the trilinear reduction of those corners into xc
     // (until round 3 stage_a computed p at once and stage_b reduced its gather at once: ~2 700 + ~5 000 cycles of an iteration spent
-    // waiting for round trips to L2 with nothing else to issue -- tools/exp_ph3.py)
+    // waiting for round trips to L2 with nothing else to issue -- DESIGN.md section 4.3, round 3)
     struct Staged { SampleRaw r; float px, py, pz; int mm; bool valid; f4 gr; f4 xc[CQ]; f4 h4[2]; unsigned long long mask; } nx;
     auto task_of = [&](int it_) { return tile_of(it_, bid * 8 + wave, nb * 8, 0); };
     auto slot_of = [&](int it_) { return task_of(it_) * 16 + j; };
@@ -965,12 +919,11 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
         const int slot = task * 16 + j;
         S_.valid = slot < A.M;
         S_.mm = mm;
-        if (!NSK_DBG(A, 10)) sample_load(A, mm, S_.r);                       // (experiment bits 10, 11, 15: which of these loads stalls the issue -- tools/exp_ph3.py)
-        if (!NSK_DBG(A, 11)) S_.gr = ld32<f4>(A.g_raw, (unsigned)mm * 16u);
+        sample_load(A, mm, S_.r);
+        S_.gr = ld32<f4>(A.g_raw, (unsigned)mm * 16u);
         const int tk = min(task, ntasks - 1);
-        NSK_IDX(3, tk, ntasks); NSK_IDX(2, min(slot, A.M - 1), A.M);
-        if (!NSK_DBG(A, 11)) S_.mask = ld32<unsigned long long>(A.masks, ((unsigned)min(slot, A.M - 1) * 4u + (unsigned)g) * 8u);
-        if (!NSK_DBG(A, 15)) { S_.h4[0] = A.hsave[((size_t)tk * 10 + 8) * 64 + lane]; S_.h4[1] = A.hsave[((size_t)tk * 10 + 9) * 64 + lane]; }
+        S_.mask = ld32<unsigned long long>(A.masks, ((unsigned)min(slot, A.M - 1) * 4u + (unsigned)g) * 8u);
+        S_.h4[0] = A.hsave[((size_t)tk * 10 + 8) * 64 + lane]; S_.h4[1] = A.hsave[((size_t)tk * 10 + 9) * 64 + lane];
     };
     Tri Tn; GatherRaw GR;                                // the next tile's cell and its corner lines in flight
     auto stage_b1 = [&](Staged& S_) {
@@ -991,17 +944,14 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
         image_commit<512>(smem, ir0, src, PM_IMG_FRAG_F / 4);
         image_commit<512>(smem + PM_IMG_FRAG_F / 4, ir1, src + MlpBwdImgH::P_WO / 4, (128 + 288) / 4);
         __syncthreads();
-        NSK_PH(29);
         if (iters > 0) { stage_b1(nx); stage_b2(nx); mm_next = slot_sample(A, slot_of(1)); }
     }
     asm volatile("" : "+v"(nx.h4[0]), "+v"(nx.h4[1]), "+v"(nx.gr), "+v"(nx.mask), "+v"(mm_next));
     f4 accB[2] = {(f4)(0.f), (f4)(0.f)};                // d loss / d B, this wave's tiles (see the loop's tail)
     (void)accB;
-    NSK_PH(30);
     for (int it = 0; it < iters; ++it) {
         asm volatile("" ::: "memory");
         lane = lane0; asm volatile("" : "+v"(lane)); j = lane & 15; g = lane >> 4;      // (see decode_bwd_train_body)
-        NSK_PH(0); NSK_PHI(0);
         if (it > 0) lds_barrier();                   // scratch (G1 / G2), XC and E are rewritten from here on
         const bool valid = nx.valid;
         float px = nx.px, py = nx.py, pz = nx.pz, zz = A.pts ? 0.f : nx.r.z; const int n = A.pts ? 0 : ray_of(A, nx.mm);
@@ -1019,7 +969,6 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
         const float us = chain_scale<OD>(gout);
         const unsigned long long mask = nx.mask;
         const int htask = min(task_of(it), ntasks - 1);
-        NSK_IDX(3, htask, ntasks);
         f4 hq[5][2];                                      // block outputs h0..h4 as they are fetched
         hq[4][0] = nx.h4[0]; hq[4][1] = nx.h4[1];
         auto load_h = [&](auto KC) {
@@ -1032,11 +981,10 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
             f4 xe[6], dummy[6];
             embed<false>(Bm, g, px, py, pz, xe, dummy);
 #pragma unroll
-            for (int q = 0; q < 6; ++q) if (!no_put) pn_put(pn, PM, PM_E + 16 * q, wave, lane, xe[q]);
+            for (int q = 0; q < 6; ++q) pn_put(pn, PM, PM_E + 16 * q, wave, lane, xe[q]);
         }
-        if (!no_put) pn_put(pn, PM, PM_XC, wave, lane, nx.xc[0]);
-        if (!no_put) pn_put(pn, PM, PM_XC + 16, wave, lane, nx.xc[1]);
-        NSK_PH(1); NSK_PHI(1);
+        pn_put(pn, PM, PM_XC, wave, lane, nx.xc[0]);
+        pn_put(pn, PM, PM_XC + 16, wave, lane, nx.xc[1]);
         f4 gh[2];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1049,14 +997,13 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
             }
         // ---- phase OUT: G = g_out (rows >= OD zero), X = h4 --------------------------------------------------------------------
         {
-            if (!no_put) pn_put(pn, PM, PM_G1, wave, lane, go);
-            if (!no_put) pn_put(pn, PM, PM_XH, wave, lane, hq[4][0]);
-            if (!no_put) pn_put(pn, PM, PM_XH + 16, wave, lane, hq[4][1]);
+            pn_put(pn, PM, PM_G1, wave, lane, go);
+            pn_put(pn, PM, PM_XH, wave, lane, hq[4][0]);
+            pn_put(pn, PM, PM_XH + 16, wave, lane, hq[4][1]);
             lds_barrier();
-            if (!no_tiles) pn_phase_jobs<WHICH, JobPlan<WHICH>::PH_OUT>(pn, PM, wave, lane, acc);
+            pn_phase_jobs<WHICH, JobPlan<WHICH>::PH_OUT>(pn, PM, wave, lane, acc);
             lds_barrier();
         }
-        NSK_PH(2); NSK_PHI(2);
         f4 gc[2] = {(f4)(0.f), (f4)(0.f)};
         H2 xa3, xa;
         auto layer = [&](auto LC) {
@@ -1064,7 +1011,6 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
             if constexpr (l >= 2) load_h(std::integral_constant<int, l - 2>{});      // a whole layer ahead (see decode_bwd_train_body)
             // g_a = ReLU'(.) g_h: the same half-word masks give the fp16 pieces of g_a (the chain's next operand) from those of g_h and the
             // bf16 panel pieces of g_a from the panel pieces of g_h -- one split each instead of two, no fp32 select
-            if constexpr (l == 2) NSK_PH(20);
             const Mask4 RM = relu_mask_dwords(mask, l);
             {
                 const H2 xg = split_block_h(gh[0], gh[1]);
@@ -1074,47 +1020,34 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
                 xa = mask_block_h4(xg, RM);
             }
             // ---- the layer's phase: dFc_l = g_h c^T (G1 x XC), dW_l = g_a x^T (G2 x XH or E) ------------------------------------
-            if constexpr (l == 2) NSK_PH(21);
-            if (!no_put) pn_put_masked(pn, PM, PM_G1, PM_G2, wave, lane, gh[0], us, RM.d[0], RM.d[1]);
-            if (!no_put) pn_put_masked(pn, PM, PM_G1 + 16, PM_G2 + 16, wave, lane, gh[1], us, RM.d[2], RM.d[3]);
+            pn_put_masked(pn, PM, PM_G1, PM_G2, wave, lane, gh[0], us, RM.d[0], RM.d[1]);
+            pn_put_masked(pn, PM, PM_G1 + 16, PM_G2 + 16, wave, lane, gh[1], us, RM.d[2], RM.d[3]);
             if constexpr (l >= 1) {
                 constexpr int k = l == 3 ? 2 : l - 1;                            // layer 3 reads e (its own rows) and h2
-                if (!no_put) pn_put(pn, PM, PM_XH, wave, lane, hq[k][0]);
-                if (!no_put) pn_put(pn, PM, PM_XH + 16, wave, lane, hq[k][1]);
+                pn_put(pn, PM, PM_XH, wave, lane, hq[k][0]);
+                pn_put(pn, PM, PM_XH + 16, wave, lane, hq[k][1]);
             }
-            if constexpr (l == 2) NSK_PH(22);
             lds_barrier();
-            if constexpr (l == 2) NSK_PH(23);
-            if (!no_tiles) pn_phase_jobs<WHICH, 1 + (4 - l)>(pn, PM, wave, lane, acc);       // dFc_l, dW_l (and their bias rows) as jobs: see JobPlan
-            if constexpr (l == 2) NSK_PH(24);
+            pn_phase_jobs<WHICH, 1 + (4 - l)>(pn, PM, wave, lane, acc);       // dFc_l, dW_l (and their bias rows) as jobs: see JobPlan
             lds_barrier();
-            if constexpr (l == 2) NSK_PH(25);
             if constexpr (l == 3) xa3 = xa;
             if constexpr (l >= 1) {
                 f4 ghn[2] = {(f4)(0.f), (f4)(0.f)}, ghl[2] = {(f4)(0.f), (f4)(0.f)};
                 gemm_h(imgh, MlpBwdImgH::WT(l), lane, xa, ghn, ghl);
                 gh[0] = ghn[0] + ghl[0] * (1.f / NSK_H16_SCALE); gh[1] = ghn[1] + ghl[1] * (1.f / NSK_H16_SCALE);
             }
-            if constexpr (l == 2) NSK_PH(26);
         };
         layer(std::integral_constant<int, 4>{});
-        NSK_PH(3); NSK_PHI(3);
         layer(std::integral_constant<int, 3>{});
-        NSK_PH(4); NSK_PHI(4);
         layer(std::integral_constant<int, 2>{});
-        NSK_PH(5); NSK_PHI(5);
         layer(std::integral_constant<int, 1>{});
-        NSK_PH(6); NSK_PHI(6);
         f4 ecp[3];                                           // this thread's share of the e-part image, in flight across layer 0
 #pragma unroll
         for (int u = 0; u < 3; ++u) ecp[u] = gimg_e[u * 512 + (int)threadIdx.x];
         layer(std::integral_constant<int, 0>{});
-        NSK_PH(7); NSK_PHI(7);
 #pragma unroll
         for (int u = 0; u < 3; ++u) eimg[u * 512 + (int)threadIdx.x] = ecp[u];      // rows 32..127 are dead since layer 0's last barrier
-        NSK_PH(14); NSK_PHI(14);
         lds_barrier();
-        NSK_PH(15); NSK_PHI(15);
         gc[0] *= us; gc[1] *= us;
         float gp[3] = {0.f, 0.f, 0.f};
         Tri T;
@@ -1129,9 +1062,7 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
             // partial sums meet once, in LDS, after the loop.  Column n = 3 (q mod 5) + k of accumulator q / 5 holds block q, coordinate k.
             if (it + 1 < iters) { stage_a(it + 1, mm_next, nx); mm_next = slot_sample(A, slot_of(it + 2)); }
             gemm_e2T_lds(eimgh, lane, xa3, xa, ge);
-            NSK_PH(16); NSK_PHI(16);
             stage_b1(nx);
-            NSK_PH(8); NSK_PHI(8);
             float* xch = reinterpret_cast<float*>(pn + PM + PM_G1 * PN_RB) + wave * 64;          // plane M of the G rows: dead since layer 0's tiles
             if (g == 0) *reinterpret_cast<f4*>(xch + 4 * j) = (f4){px, py, pz, valid ? us : 0.f};
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1172,11 +1103,9 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
 #pragma unroll
             for (int q = 0; q < 6; ++q) ge[q] = (f4)(0.f);
             gemm_e2_lds(eimgh, lane, xa3, xa, ge);              // g_e = W3e^T g_a3 + W0e^T g_a0 (still carries the sample's scale)
-            NSK_PH(16); NSK_PHI(16);
             // the next tile's sample data: issued (not waited for) behind the e-part fragments -- loads return in order, and in front of them
             // these (scattered, often beyond L2) made the first product wait for their round trip -- and ahead of the cosines and panel stores below
             if (it + 1 < iters) { stage_a(it + 1, mm_next, nx); mm_next = slot_sample(A, slot_of(it + 2)); }
-            NSK_PH(8); NSK_PHI(8);
             tri_setup(A.grid, A.bound, px, py, pz, T);
             {
                 f4 e2[6], xcos[6];
@@ -1189,20 +1118,19 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
                 f4 pq;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { int row = 4 * g + i; pq[i] = !valid ? 0.f : (row == 0 ? px : (row == 1 ? py : (row == 2 ? pz : 0.f))); }
-                if (!no_put) pn_put(pn, PM, PM_G1, wave, lane, pq, us);
+                pn_put(pn, PM, PM_G1, wave, lane, pq, us);
 #pragma unroll
-                for (int q = 0; q < 6; ++q) if (!no_put) pn_put(pn, PM, PM_E + 16 * q, wave, lane, ge[q]);
+                for (int q = 0; q < 6; ++q) pn_put(pn, PM, PM_E + 16 * q, wave, lane, ge[q]);
                 // the next tile's gather goes out here: its 16 corner lines travel while the workgroup meets at the barrier and runs the tiles
                 // (unconditional, like its reduction below: under `if (it + 1 < iters)` the compiler cannot tell that both run or neither, keeps the 64
                 // corner registers alive around the whole loop and spills 85 of them; in the last iteration nx still holds this tile's sample,
                 // so the extra gather reads valid lines and its result is never used)
                 stage_b1(nx);
                 lds_barrier();
-                if (!no_tiles) pn_phase_jobs<WHICH, JobPlan<WHICH>::PH_DB>(pn, PM, wave, lane, acc);
+                pn_phase_jobs<WHICH, JobPlan<WHICH>::PH_DB>(pn, PM, wave, lane, acc);
                 lds_barrier();
             }
         }
-        NSK_PH(9); NSK_PHI(9);
         if constexpr (RAYS) {
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
@@ -1242,15 +1170,12 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
         stage_b2(nx);
         // every staged load must have landed before the first atomic below (see decode_bwd_train_body)
         asm volatile("" : "+v"(nx.h4[0]), "+v"(nx.h4[1]), "+v"(nx.gr), "+v"(nx.mask), "+v"(mm_next), "+v"(nx.xc[0]), "+v"(nx.xc[1]));
-        NSK_PH(10); NSK_PHI(10);
         if (scat) {
             if (A.flags & 0x8000u) {        // deterministic debug mode: see decode_bwd_body
                 for (int w = 0; w < 8; ++w) { if (wave == w) { scatter_tile(A.grid, T, gc, lane, valid, scratch); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } __syncthreads(); }
             } else scatter_tile(A.grid, T, gc, lane, valid, scratch);
         }
-        NSK_PH(11); NSK_PHI(11);
     }
-    NSK_PH(12);
     // ---- single flush of this wave's output tiles (job by job) ---------------------------------------
     float* slab = A.g_dec + (size_t)bid * ((plan_total<WHICH>() + 3) & ~3);
     pn_jobs_flush_all<WHICH, !RAYS>(slab, wave, lane, acc, std::make_integer_sequence<int, JobPlan<WHICH>::NJ>{});
@@ -1276,7 +1201,6 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
             }
         }
     }
-    NSK_PH(13);
 }
 
 // which body a trainable decoder's backward runs: the merged-phase form for the middle and colour decoders
@@ -1301,7 +1225,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_multi(MultiArgs MA)
         // frozen workgroup has been placed and need nothing of this launch
         if ((int)blockIdx.x >= MA.wg_end[MA.n - 1]) { sort_scan_body<2>(MA.scan, (int)blockIdx.x - MA.wg_end[MA.n - 1]); return; }
     }
-    NSK_TS_BEGIN(1);
     int r = 0;
     while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;
     const int b0 = r == 0 ? 0 : MA.wg_end[r - 1];
@@ -1317,7 +1240,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_multi(MultiArgs MA)
     case 6: decode_bwd_body<3, RAYS>(MA.a[r], bid, nb); break;
     default: decode_bwd_train_any<3, RAYS>(MA.a[r], bid, nb); break;
     }
-    NSK_TS_END(1, r);
 }
 
 // The same launch with every chain on the fp32 MFMA (nsk_set_backward_mode 0: full-width operands, what the reference's fp32 autograd multiplies,
