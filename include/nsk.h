@@ -118,7 +118,9 @@ int nsk_set_render_opts(nsk_ctx* ctx, int n_samples, int n_surface, int lindisp,
 
 /* ---- feature grids: c10::Dict<string,Tensor> "grid_<level>" [1,C,Z,Y,X] fp32 (src/main.cpp:33-78) ------ */
 /* h_czyx is the reference layout [C][Z][Y][X] (C must be 32); the device copy is voxel-major [Z][Y][X][C]
- * so that the 32 channels of a voxel are one 128-byte line (conversion happens here). */
+ * so that the 32 channels of a voxel are one 128-byte line (conversion happens here).
+ * A dimension of 1 is valid: grid_sample's align_corners scaling multiplies the normalised coordinate by dim - 1 = 0, so every point reads
+ * voxel 0 along that axis with weight 1 and the lookup has no spatial gradient there (what ATen does; tests/test_local_parity_cpu.py). */
 int nsk_grid_upload(nsk_ctx* ctx, int level, const float* h_czyx, int C, int Z, int Y, int X);
 int nsk_grid_download(nsk_ctx* ctx, int level, float* h_czyx);
 int nsk_grid_grad_download(nsk_ctx* ctx, int level, float* h_czyx);
@@ -161,7 +163,21 @@ int nsk_decoder_set_trainable(nsk_ctx* ctx, int which, int trainable);
  *   d_rays_o, d_rays_d [N][3]; d_gt_depth [N] or NULL (then N_surface = 0, :54-57);
  *   gt_depth_max: max over the WHOLE batch of gt_depth (:76,:93).  Pass < 0 to have it computed on the device
  *   from d_gt_depth; multi-GPU callers pass the global maximum so that sharding rays does not change results.
- *   outputs: d_rgb [N][3], d_depth [N], d_var [N], d_weights [N][S] or NULL (S = n_samples (+ n_surface)). */
+ *   outputs: d_rgb [N][3], d_depth [N], d_var [N], d_weights [N][S] or NULL (S = n_samples (+ n_surface)).
+ * At the geometric edges (every entry point that samples rays; pinned per ray and per voxel by tests/test_gpu_edges.py):
+ *   - a zero direction component is valid: (bound - o) / 0 = +-inf never wins the minimum over the axes;
+ *   - an origin outside the bound is valid: samples outside are looked up at the clamped coordinate, get occupancy 100 (:36), send no
+ *     gradient to the grids and none through the clipped coordinate (ATen's border padding); a ray that misses the bound has far < 0,
+ *     clamped to 0 with ground truth (:76), a descending z without;
+ *   - an origin ON a face with a zero direction component across it (a ray running inside the face) has 0/0 in the box exit.  ATen's max / min
+ *     propagate the NaN: the reference renders every such ray non-finite.  Here (and in the CPU oracle) the comparisons `t0 > t1 ? t0 : t1`,
+ *     `m < far` drop a NaN, except for the upper x face (o_x = bound x1, d_x = 0), whose NaN is taken as the first axis' value unconditionally:
+ *     those rays come out non-finite (outputs and the gradients of the voxels they touch -- all addresses stay inside the grid; a NaN z sorts
+ *     behind every number, as in torch.sort); every other in-face ray is rendered with the exit of the remaining axes.  Which in-face rays
+ *     render is an accident of the comparison order, recorded here because the tests pin it, NOT a promise: callers drop such rays with
+ *     nsk_inside_filter / nsk_set_ray_mask.  A ray the mask drops whose exit is NaN is sampled with far = 0 instead (nsk_map_step,
+ *     nsk_track_step, nsk_render_backward): its outputs (d_rgb, d_depth, d_var) are then finite numbers without meaning, its loss and
+ *     gradients exactly zero, and it cannot reach the sums of the rays that are kept (0 x NaN in a shared voxel row). */
 int nsk_render_forward(nsk_ctx* ctx, int stage, int N, const float* d_rays_o, const float* d_rays_d,
                        const float* d_gt_depth, float gt_depth_max, float* d_rgb, float* d_depth, float* d_var,
                        float* d_weights);

@@ -210,6 +210,9 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         if (far < 0.f) far = 0.f;
         if (far > hi) far = hi;
     }
+    // a ray the mask drops contributes exactly nothing (k_composite zeroes its seeds), but a NaN exit would give it NaN sample points, NaN
+    // trilinear weights, and 0 x NaN in the voxel rows and weight gradients it shares with the kept rays: it is sampled with far = 0 instead
+    if (keep && !keep[nc] && far != far) far = 0.f;
     float z = NSK_INF;
     if (lane < ns) {                                                        // :101-108
         float t = linspace01(lane, ns);
@@ -235,12 +238,16 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         else z = add_rn(mul_rn(0.001f, sub_rn(1.f, t)), mul_rn(gmax, t));
     }
     if (nsurf > 0) {                                                        // :119 sort(cat) as a rank sort
-        sh[wave][lane] = z;
+        // A NaN z (0/0 in the box exit: origin on the upper x face, no x direction; include/nsk.h) ranks as +inf, behind every number as in
+        // torch.sort: compared as itself it is neither smaller nor equal, every NaN lane got rank 0, and the slots they left empty were read
+        // back as whatever the LDS held -- such a ray rendered finite garbage or NaN from run to run (tests/test_gpu_edges.py)
+        const float zr = z != z ? NSK_INF : z;
+        sh[wave][lane] = zr;
         lds_fence();
         int rank = 0;
         for (int k = 0; k < S; ++k) {
             float zk = sh[wave][k];
-            rank += (zk < z || (zk == z && k < lane)) ? 1 : 0;
+            rank += (zk < zr || (zk == zr && k < lane)) ? 1 : 0;
         }
         if (lane < S) sh2[wave][rank] = z;
         lds_fence();
@@ -1267,14 +1274,16 @@ __device__ __forceinline__ void composite_body(const CompArgs& A, int bid, int n
     gD += gV * -2.f * wave_sum(w * dzD);
     float v = gD * z + gV * dzD * dzD + gC[0] * col[0] + gC[1] * col[1] + gC[2] * col[2];
     float vw = act ? v * w : 0.f;
-    // exclusive suffix sum of v*w
-    float suf = vw;
+    // exclusive suffix sum of v*w: the scan starts from the neighbour's term.  (As "inclusive sum minus the own term" it lost everything behind a
+    // heavy sample: a ray that enters the bound from outside has w = 1 on its first, masked sample and 1e-10 behind it, the inclusive sum
+    // rounded to the own term and the difference to 0 -- d loss / d rays_d of such rays came out with the wrong sign, tests/test_gpu_edges.py)
+    float suf = __shfl_down(vw, 1);
+    if (lane == 63) suf = 0.f;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         float dn = __shfl_down(suf, o);
         if (lane + o < 64) suf += dn;
     }
-    suf -= vw;
     float g_alpha = v * T - suf / (1.f - alpha + 1e-10f);
     float g_sigma, g_n = 0.f;
     if (A.R.occupancy) g_sigma = g_alpha * 10.f * alpha * (1.f - alpha);

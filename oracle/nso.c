@@ -236,11 +236,15 @@ static void tri_sample(const nso_grid* g, const tri_coord* tc, real* feat /* [C]
     }
 }
 
-/* backward: scatter g_feat into g_grid (same layout as grid) and/or accumulate g_p[3] */
-static void tri_backward(const nso_grid* g, const tri_coord* tc, const real* g_feat, real* g_grid, real* g_p)
+/* backward: scatter g_feat into g_grid (same layout as grid) and/or accumulate g_p[3].
+ * r_grid (optional, [Z][Y][X]): += w(sample, voxel) * max_c |g_feat[c]|, the scale of what any fp32 evaluation of the sum
+ * g_grid[v][c] = sum_samples w g_feat[c] may lose at voxel v (see nso_render_backward_scaled) */
+static void tri_backward(const nso_grid* g, const tri_coord* tc, const real* g_feat, real* g_grid, real* g_p, real* r_grid)
 {
     const size_t cs = (size_t)g->Z * g->Y * g->X;
     real gi[3] = { 0, 0, 0 };
+    real gmax = 0;
+    if (r_grid) for (int c = 0; c < g->C; ++c) if (r_abs(g_feat[c]) > gmax) gmax = r_abs(g_feat[c]);
     for (int dz = 0; dz < 2; ++dz) for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx) {
         int ix = tc->i0[0] + dx, iy = tc->i0[1] + dy, iz = tc->i0[2] + dz;
         if (!tri_inb(g, ix, iy, iz)) continue;
@@ -249,6 +253,7 @@ static void tri_backward(const nso_grid* g, const tri_coord* tc, const real* g_f
         real wz = dz ? tc->t[2] : (real)1 - tc->t[2];
         size_t off = ((size_t)iz * g->Y + iy) * g->X + ix;
         real dot = 0;
+        if (r_grid) r_grid[off] += wx * wy * wz * gmax;
         for (int c = 0; c < g->C; ++c) {
             if (g_grid) g_grid[c * cs + off] += wx * wy * wz * g_feat[c];
             dot += g->v[c * cs + off] * g_feat[c];
@@ -328,7 +333,7 @@ static void dec_forward(const dec_layout* L, const real* P, const real* p, dec_a
  *   gP (decoder parameter gradient, may be NULL), g_c[c_dim] (feature gradient, overwritten),
  *   g_p[3] (through the embedding only, accumulated, may be NULL). */
 static void dec_backward(const dec_layout* L, const real* P, const real* p, const dec_act* A,
-                         const real* g_out, real* gP, real* g_c, real* g_p)
+                         const real* g_out, real* gP, real* g_c, real* g_p, real* rP)
 {
     real g_h[H_DIM], g_e[E_DIM];
     for (int k = 0; k < 64; ++k) g_c[k] = 0;
@@ -342,6 +347,10 @@ static void dec_backward(const dec_layout* L, const real* P, const real* p, cons
     if (gP) for (int o = 0; o < L->out_dim; ++o) {
         for (int k = 0; k < H_DIM; ++k) gP[L->oWo + o * H_DIM + k] += g_out[o] * A->h[4][k];
         gP[L->obo + o] += g_out[o];
+    }
+    if (rP) for (int o = 0; o < L->out_dim; ++o) {     /* rP: the same sums over |factor| |factor|, the running-error scale of each parameter's gradient */
+        for (int k = 0; k < H_DIM; ++k) rP[L->oWo + o * H_DIM + k] += r_abs(g_out[o] * A->h[4][k]);
+        rP[L->obo + o] += r_abs(g_out[o]);
     }
     for (int i = 4; i >= 0; --i) {
         const int nx = L->in_dim[i];
@@ -365,10 +374,18 @@ static void dec_backward(const dec_layout* L, const real* P, const real* p, cons
                 for (int k = 0; k < L->c_dim; ++k) gP[L->oFw[i] + (size_t)o * L->c_dim + k] += g_h[o] * A->c[k];
                 gP[L->oFb[i] + o] += g_h[o];
             }
+            if (rP) for (int o = 0; o < H_DIM; ++o) {
+                for (int k = 0; k < L->c_dim; ++k) rP[L->oFw[i] + (size_t)o * L->c_dim + k] += r_abs(g_h[o] * A->c[k]);
+                rP[L->oFb[i] + o] += r_abs(g_h[o]);
+            }
         }
         if (gP) for (int o = 0; o < H_DIM; ++o) {
             for (int k = 0; k < nx; ++k) gP[L->oW[i] + (size_t)o * nx + k] += g_a[o] * x[k];
             gP[L->ob[i] + o] += g_a[o];
+        }
+        if (rP) for (int o = 0; o < H_DIM; ++o) {
+            for (int k = 0; k < nx; ++k) rP[L->oW[i] + (size_t)o * nx + k] += r_abs(g_a[o] * x[k]);
+            rP[L->ob[i] + o] += r_abs(g_a[o]);
         }
         const real* W = P + L->oW[i];
         real g_x[E_DIM + H_DIM + 32];
@@ -393,6 +410,7 @@ static void dec_backward(const dec_layout* L, const real* P, const real* p, cons
         for (int k = 0; k < E_DIM; ++k) {
             real gs = g_e[k] * A->ce[k];
             if (gP) for (int a = 0; a < 3; ++a) gP[L->oB + a * E_DIM + k] += p[a] * gs;
+            if (rP) for (int a = 0; a < 3; ++a) rP[L->oB + a * E_DIM + k] += r_abs(p[a] * gs);
             if (g_p) for (int a = 0; a < 3; ++a) g_p[a] += gs * B[a * E_DIM + k];
         }
     }
@@ -508,7 +526,8 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
                                 const real* rays_o, const real* rays_d, const real* gt_depth, real gt_depth_max,
                                 const real* g_rgb, const real* g_depth, const real* g_var,
                                 real* const* g_grids, real* const* g_P, real* g_rays_o, real* g_rays_d,
-                                const unsigned char* const* relu, const unsigned char* sigma_on)
+                                const unsigned char* const* relu, const unsigned char* sigma_on,
+                                real* const* r_grids, real* const* r_P, real* r_rays)
 {
     dec_layout L[4]; for (int i = 0; i < 4; ++i) make_layout(i, &L[i]);
     if (o->n_samples + o->n_surface > MAX_S) return -1;
@@ -520,6 +539,7 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
     {
     pt_state* st = (pt_state*)malloc(sizeof(pt_state) * MAX_S);
     real* tg[4] = { 0, 0, 0, 0 }; real* tp[4] = { 0, 0, 0, 0 };
+    real* rg[4] = { 0, 0, 0, 0 }; real* rp[4] = { 0, 0, 0, 0 };
     int shared_acc = 1;
 #ifdef _OPENMP
     shared_acc = omp_get_num_threads() == 1;
@@ -528,6 +548,8 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
         size_t ng = (size_t)grids[l].C * grids[l].Z * grids[l].Y * grids[l].X;
         if (g_grids && g_grids[l]) tg[l] = shared_acc ? g_grids[l] : (real*)calloc(ng, sizeof(real));
         if (g_P && g_P[l]) tp[l] = shared_acc ? g_P[l] : (real*)calloc(L[l].total, sizeof(real));
+        if (r_grids && r_grids[l]) rg[l] = shared_acc ? r_grids[l] : (real*)calloc(ng / (size_t)grids[l].C, sizeof(real));
+        if (r_P && r_P[l] && tp[l]) rp[l] = shared_acc ? r_P[l] : (real*)calloc(L[l].total, sizeof(real));
     }
 #pragma omp for schedule(dynamic, 4)
     for (int n = 0; n < N; ++n) {
@@ -556,8 +578,9 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
             for (int k = 0; k < 3; ++k) v[s] += g_rgb[3 * n + k] * raw[4 * s + k];
         }
         real nrm = r_sqrt(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2]);
-        real suffix = 0, g_nrm = 0;
+        real suffix = 0, g_nrm = 0, r_nrm = 0;
         real g_o[3] = { 0, 0, 0 }, g_d[3] = { 0, 0, 0 };
+        real r_o = 0, r_d = 0;
         for (int s = S - 1; s >= 0; --s) {
             real g_alpha = v[s] * T[s] - suffix / ((real)1 - al[s] + (real)1e-10);
             suffix += v[s] * w[s];
@@ -572,6 +595,7 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
                 const int on = sigma_on ? sigma_on[(size_t)n * S + s] : (sg > 0);     /* relu(sigma), utils.h:160; tests may force the branch */
                 g_sigma = on ? g_alpha * dist * ex : 0;
                 g_nrm += g_alpha * rs * ex * dz;
+                r_nrm += r_abs(g_alpha * rs * ex * dz);
             }
             if (!st[s].inb) g_sigma = 0;                      /* raw[~mask,3]=100 is a constant */
             real g_col[3];
@@ -585,12 +609,17 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
                 if (wd == 3) { g_out[0] = g_col[0]; g_out[1] = g_col[1]; g_out[2] = g_col[2]; }
                 else g_out[0] = g_sigma;
                 real g_c[64];
-                dec_backward(&L[wd], P[wd], p, &st[s].act[wd], g_out, tp[wd], g_c, want_rays ? g_p : NULL);
+                dec_backward(&L[wd], P[wd], p, &st[s].act[wd], g_out, tp[wd], g_c, want_rays ? g_p : NULL, rp[wd]);
                 /* fine: only the first 32 features (grid_fine) carry gradient (MLP.cpp:81 NoGradGuard) */
-                tri_backward(&grids[wd], &st[s].tc[wd], g_c, tg[wd], want_rays ? g_p : NULL);
+                tri_backward(&grids[wd], &st[s].tc[wd], g_c, tg[wd], want_rays ? g_p : NULL, rg[wd]);
             }
             for (int k = 0; k < 3; ++k) { g_o[k] += g_p[k]; g_d[k] += g_p[k] * z[s]; }
+            {
+                real m = r_abs(g_p[0]); if (r_abs(g_p[1]) > m) m = r_abs(g_p[1]); if (r_abs(g_p[2]) > m) m = r_abs(g_p[2]);
+                r_o += m; r_d += m * r_abs(z[s]);
+            }
         }
+        if (r_rays) { r_rays[2 * n] = r_o; r_rays[2 * n + 1] = r_d + r_nrm; }
         if (nrm > 0) for (int k = 0; k < 3; ++k) g_d[k] += g_nrm * rd[k] / nrm;      /* utils.h:153 norm(rays_d) */
         if (g_rays_o) memcpy(g_rays_o + 3 * n, g_o, sizeof(g_o));
         if (g_rays_d) memcpy(g_rays_d + 3 * n, g_d, sizeof(g_d));
@@ -601,6 +630,8 @@ static int render_backward_impl(const nso_opts* o, const nso_grid* grids, const 
             size_t ng = (size_t)grids[l].C * grids[l].Z * grids[l].Y * grids[l].X;
             if (tg[l]) { for (size_t i = 0; i < ng; ++i) g_grids[l][i] += tg[l][i]; free(tg[l]); }
             if (tp[l]) { for (size_t i = 0; i < L[l].total; ++i) g_P[l][i] += tp[l][i]; free(tp[l]); }
+            if (rg[l]) { for (size_t i = 0; i < ng / (size_t)grids[l].C; ++i) r_grids[l][i] += rg[l][i]; free(rg[l]); }
+            if (rp[l]) { for (size_t i = 0; i < L[l].total; ++i) r_P[l][i] += rp[l][i]; free(rp[l]); }
         }
     }
     free(st);
@@ -614,7 +645,7 @@ NSO_API int nso_render_backward(const nso_opts* o, const nso_grid* grids, const 
                                 real* const* g_grids, real* const* g_P, real* g_rays_o, real* g_rays_d)
 {
     return render_backward_impl(o, grids, P, stage, N, rays_o, rays_d, gt_depth, gt_depth_max, g_rgb, g_depth, g_var,
-                                g_grids, g_P, g_rays_o, g_rays_d, NULL, NULL);
+                                g_grids, g_P, g_rays_o, g_rays_d, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* Test aid (not in the reference): the same backward with the branch of every hidden ReLU GIVEN instead of taken from
@@ -629,7 +660,27 @@ NSO_API int nso_render_backward_forced(const nso_opts* o, const nso_grid* grids,
                                        const unsigned char* const* relu, const unsigned char* sigma_on)
 {
     return render_backward_impl(o, grids, P, stage, N, rays_o, rays_d, gt_depth, gt_depth_max, g_rgb, g_depth, g_var,
-                                g_grids, g_P, g_rays_o, g_rays_d, relu, sigma_on);
+                                g_grids, g_P, g_rays_o, g_rays_d, relu, sigma_on, NULL, NULL, NULL);
+}
+
+/* Test aid: the forced backward (relu / sigma_on may be NULL) that also returns the SCALE of the rounding error any fp32 evaluation of its
+ * sums may commit, so that a comparison can be made per voxel row, per weight and per ray instead of over a whole array:
+ *   r_grids[l] [Z][Y][X]   R = sum_samples w(sample, voxel) max_c |g_feat(sample)[c]|: the running-error scale of g_grid[v][c] = sum w g_feat[c],
+ *                          operand error of the chain that made g_feat included (it is relative to the size of g_feat, not to the possibly
+ *                          cancelled sum).  R == 0 exactly where no sample touches the voxel with a non-zero weight and gradient.
+ *   r_P[w] (packed)        sum |activation| |g| per decoder parameter (needs g_P[w])
+ *   r_rays [N][2]          sum_samples max_k |g_p(sample)[k]| (for g_rays_o) and the same times |z| plus the sum over the samples of the
+ *                          absolute terms of d loss / d |d| (for g_rays_d; the terms of a ray whose samples are all masked cancel)
+ * Each may be NULL.  Buffers are accumulated into (the caller zeroes them). */
+NSO_API int nso_render_backward_scaled(const nso_opts* o, const nso_grid* grids, const real* const* P, int stage, int N,
+                                       const real* rays_o, const real* rays_d, const real* gt_depth, real gt_depth_max,
+                                       const real* g_rgb, const real* g_depth, const real* g_var,
+                                       real* const* g_grids, real* const* g_P, real* g_rays_o, real* g_rays_d,
+                                       const unsigned char* const* relu, const unsigned char* sigma_on,
+                                       real* const* r_grids, real* const* r_P, real* r_rays)
+{
+    return render_backward_impl(o, grids, P, stage, N, rays_o, rays_d, gt_depth, gt_depth_max, g_rgb, g_depth, g_var,
+                                g_grids, g_P, g_rays_o, g_rays_d, relu, sigma_on, r_grids, r_P, r_rays);
 }
 
 /* Test aid: the hidden ReLU inputs of decoder `which` at every sample, a_out[N*S][5][32] (tools/relu_flips.py counts the

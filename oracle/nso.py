@@ -136,9 +136,11 @@ class Oracle:
         return out
 
     def render_backward(self, opts, grids, decoders, stage, rays_o, rays_d, gt_depth, gt_depth_max, g_rgb, g_depth,
-                        g_var=None, want_grids=True, want_decoders=True, want_rays=True, relu=None, sigma_on=None):
+                        g_var=None, want_grids=True, want_decoders=True, want_rays=True, relu=None, sigma_on=None, want_scale=False):
         """relu (test aid): dict decoder name -> [N*S, 5, 32] bool, the ReLU branches the backward takes instead of its own;
-        sigma_on: [N*S] bool, likewise the branch of relu(sigma) in the compositing"""
+        sigma_on: [N*S] bool, likewise the branch of relu(sigma) in the compositing;
+        want_scale (test aid, nso_render_backward_scaled): also return the running-error scales r_grids (level -> [Z,Y,X]), r_decoders
+        (decoder -> packed) and r_rays_o / r_rays_d [N] of the sums behind g_grids, g_decoders, g_rays_o / g_rays_d"""
         ro, rd = self.arr(rays_o, (-1, 3)), self.arr(rays_d, (-1, 3))
         N = ro.shape[0]
         gd = None if gt_depth is None else self.arr(gt_depth, (N,))
@@ -161,7 +163,8 @@ class Oracle:
                 self._p(gd), self.creal(gt_depth_max), self._p(grgb), self._p(gdep),
                 self._p(gvar), gg_ptr if want_grids else None,
                 gp_ptr if want_decoders else None, self._p(gro), self._p(grd))
-        if relu is None and sigma_on is None:
+        rg, rpd, rr = {}, {}, None
+        if relu is None and sigma_on is None and not want_scale:
             rc = self.lib.nso_render_backward(*args)
         else:
             relu = relu or {}
@@ -173,9 +176,24 @@ class Oracle:
                     keep.append(b)
                     rp[i] = b.ctypes.data
             so = None if sigma_on is None else np.ascontiguousarray(np.asarray(sigma_on).astype(np.uint8).reshape(N * S))
-            rc = self.lib.nso_render_backward_forced(*args, rp, self._p(so))
+            if not want_scale:
+                rc = self.lib.nso_render_backward_forced(*args, rp, self._p(so))
+            else:
+                rg_ptr, rp_ptr = (C.c_void_p * 4)(), (C.c_void_p * 4)()
+                for i, name in enumerate(LEVELS):
+                    if name in gg:
+                        rg[name] = np.zeros(gg[name].shape[1:], self.dt)
+                        rg_ptr[i] = rg[name].ctypes.data
+                    if name in gp:
+                        rpd[name] = np.zeros_like(gp[name])
+                        rp_ptr[i] = rpd[name].ctypes.data
+                rr = np.zeros((N, 2), self.dt) if want_rays else None
+                rc = self.lib.nso_render_backward_scaled(*args, rp if relu else None, self._p(so), rg_ptr, rp_ptr, self._p(rr))
         assert rc == 0
-        return dict(g_grids=gg, g_decoders=gp, g_rays_o=gro, g_rays_d=grd)
+        out = dict(g_grids=gg, g_decoders=gp, g_rays_o=gro, g_rays_d=grd)
+        if want_scale:
+            out.update(r_grids=rg, r_decoders=rpd, r_rays_o=None if rr is None else rr[:, 0].copy(), r_rays_d=None if rr is None else rr[:, 1].copy())
+        return out
 
 
     def preacts(self, opts, grids, decoders, stage, which, rays_o, rays_d, gt_depth=None, gt_depth_max=-1.0):

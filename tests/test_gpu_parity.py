@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import local_parity as LP
 import scenes
 from gpu_util import cu, make_ctx, stage_levels
 from scenes import rel_l2
@@ -266,7 +267,7 @@ def test_losses_and_pose_kernels(oracle32):
     assert np.array_equal(keep.cpu().numpy(), oracle32.inside_filter(sc["bound"], rays["rays_o"], rays["rays_d"], rays["gt_depth"]))
 
 
-def test_edge_cases(oracle32):
+def test_edge_cases(oracle32, oracle64):
     """single ray; 16-sample coarse-only (K1 shape); ray leaving the bound; all-zero depth; N not a multiple of 4"""
     sc = _scene(7)
     b = sc["bound"]
@@ -278,6 +279,19 @@ def test_edge_cases(oracle32):
         ref = oracle32.render_forward(oracle32.opts(b), sc["grids"], sc["decoders"], "color", ro, rd, gt)
         rgb, depth, var, w = ctx.render_forward("color", cu(ro), cu(rd), cu(gt))
         assert rel_l2(depth.cpu().numpy(), ref["depth"]) < TOL and rel_l2(rgb.cpu().numpy(), ref["rgb"]) < TOL
+        # the ray leaving the bound, per ray: var and weights too, and the backward voxel row by voxel row (tests/local_parity.py)
+        LP.compare_forward(dict(rgb=rgb.cpu().numpy(), depth=depth.cpu().numpy(), var=var.cpu().numpy(), weights=w.cpu().numpy()), ref, "edge ray gt %.0f" % gtv)
+        if gtv > 0:
+            g_c, g_d, g_v = np.array([[0.3, -0.2, 0.5]], np.float32), np.array([1.0], np.float32), np.array([0.25], np.float32)
+            ctx.zero_grads()
+            g_ro, g_rd = ctx.render_backward("color", cu(ro), cu(rd), cu(gt), -1.0, cu(g_c), cu(g_d), cu(g_v), flags=5)
+            levels = ["middle", "fine", "color"]
+            hip = dict(g_grids={k: ctx.grid_download(k, grad=True) for k in levels}, g_rays_o=g_ro.cpu().numpy(), g_rays_d=g_rd.cpu().numpy())
+            bits = {k: ctx.debug_relu_bits(k, 48) for k in levels}
+            sig_on = (ctx.debug_fetch("occ1", 48) + ctx.debug_fetch("occ2", 48)) > 0
+            rays1 = dict(rays_o=ro, rays_d=rd, gt_depth=gt)
+            r32, r64 = [LP.forced_reference(o, sc, rays1, "color", -1.0, g_c, g_d, g_v, bits, sig_on, decoders=False) for o in (oracle32, oracle64)]
+            LP.compare_backward(hip, r32, r64, levels, "edge ray backward")
     ctx16 = make_ctx(sc, n_samples=16, n_surface=0)
     rays = scenes.make_rays(1, 203, b)
     ref = oracle32.render_forward(oracle32.opts(b, n_samples=16, n_surface=0), sc["grids"], sc["decoders"], "coarse", rays["rays_o"], rays["rays_d"], None)

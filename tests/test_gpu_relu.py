@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import local_parity as LP
 import scenes
 from gpu_util import cu, make_ctx
 from scenes import rel_l2
@@ -121,6 +122,11 @@ def test_gradients_with_the_forward_s_branches_all_rays(case, sort_mode, oracle3
         case, sort_mode, N, {k: "%.1e" % v for k, v in errs.items()}))
     for k, e in errs.items():
         assert e < TOL, (case, sort_mode, k, e)
+    # ---- the same gradients voxel row by voxel row (tests/local_parity.py): kappa against 8 x kappa_ref, untouched voxels exactly zero ---------
+    _, g_d, g_c = oracle32.loss_map(hip["depth"], hip["rgb"], rays["gt_depth"], rays["gt_color"], 0.5, stage == "color")
+    r32, r64 = [LP.forced_reference(o, sc, rays, stage, gmax, g_c, g_d, None, hip["bits"], hip["sigma"] > 0, decoders=stage == "color") for o in (oracle32, oracle64)]
+    LP.compare_backward(dict(g_grids=hip["grads"], g_decoders={"color": hip["grads"].get("colour decoder")}), r32, r64, decs, "%s sort %d" % (case, sort_mode),
+                        decoders=["color"] if stage == "color" else [])
 
 
 def test_forward_bodies_agree_on_every_branch(oracle32):
