@@ -372,6 +372,44 @@ int nsk_grad_extra(nsk_ctx* ctx, float* d_buf, size_t n_floats);
 /* nsk_grad_pack + ncclAllReduce(sum, fp32) on the context's stream + nsk_grad_unpack; comm is an ncclComm_t (RCCL). */
 int nsk_allreduce_grads(nsk_ctx* ctx, void* nccl_comm);
 
+/* ---- scene mesh (config/nice_slam.yaml `meshing:` level_set, resolution; the reference ships no mesher) ---------------- */
+/* Occupancy (channel 3 of nsk_eval_points' raw, with its "100 outside the bound" rule, src/Renderer.cpp:26-36) at the nodes of a
+ * lattice: node (i, j, k) is the point origin_a + i_a * step_a per axis -- the product rounded, then the sum rounded, no FMA, so that
+ * float32 numpy `origin + arange(n).astype(float32) * step` gives the same bits -- and its value goes to d_volume[(k * ny + j) * nx + i]
+ * (x fastest, device memory, nx * ny * nz floats).  Stages 0..2; stage 3 gives the fine stage's occupancy.  Any node count: the lattice
+ * is walked in slabs of max(2^21, the current workspace's samples) nodes (nsk_set_tuning "lattice_slab" n sets the slab to n nodes,
+ * 0 = automatic), each slab below the 2^26 samples of a launch: a small kernel writes the slab's points (12 B / node), the decoders'
+ * forward launches of nsk_eval_points run on them, a finish kernel writes the scalars.  Values equal nsk_eval_points' bit for bit. */
+int nsk_eval_lattice(nsk_ctx* ctx, int stage, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, float* d_volume);
+
+/* Marching cubes on the device over a volume laid out as above (at least 2 nodes per axis, at most 2^28 nodes; steps > 0).
+ *   - a node is INSIDE when value > level (occupancy grows into the solid);
+ *   - a cell is processed when its 8 corners are finite and (d_valid given: one byte per node, device) valid; other cells emit nothing;
+ *   - indexed, welded mesh: every lattice edge belongs to its lower node (three per node: +x, +y, +z).  An edge of a processed cell whose
+ *     ends lie on different sides owns exactly one vertex at p0 + t (p1 - p0), t = (level - v0) / (v1 - v0), p0 / p1 the end nodes' points
+ *     formed as above and every operation rounded on its own (fp32, no FMA);
+ *   - deterministic: vertex index = rank of (node index * 3 + axis) among those edges; triangles ordered by cell index, then by the order
+ *     of nsk_mesh_table; compaction by prefix sums (multi-launch scans: no atomic append, no workgroup waits on another), so two runs give
+ *     the same bytes;
+ *   - triangles are wound so that their normal (v1 - v0) x (v2 - v0) points from the inside to the outside (towards free space).
+ * Synchronises: the counts go to the host.  The mesh stays in context-owned device buffers until the next extract: nsk_mesh_buffers gives
+ * them ([n_vertices][3] floats, [n_triangles][3] int32; NULL when empty), nsk_mesh_download copies them to the host (either may be NULL).
+ * Device memory besides the caller's volume: 13 B per node (edge map 12, cell case 1) + 8 B per 256 nodes of scan scratch (+ its upper
+ * levels, 1/256 of that each) + 12 B per vertex + 12 B per triangle.  An allocation that fails returns an error that names the byte
+ * count; the context stays usable. */
+int nsk_mesh_extract(nsk_ctx* ctx, const float* d_volume, const uint8_t* d_valid, int nx, int ny, int nz, const float h_origin[3],
+                     const float h_step[3], float level, int* n_vertices, int* n_triangles);
+int nsk_mesh_buffers(nsk_ctx* ctx, float** d_vertices, int32_t** d_triangles);
+int nsk_mesh_download(nsk_ctx* ctx, float* h_vertices, int32_t* h_triangles);
+/* The triangle list of one of the 256 corner-sign cases; needs no device.  Returns the number of triangles (at most 5; < 0 on error) and
+ * writes three edge numbers per triangle to h_edges (may be NULL to ask for the count; capacity in entries).
+ *   corner c of a cell has the offsets (x, y, z) = (c & 1, (c >> 1) & 1, c >> 2); bit c of case_index is set when corner c is inside;
+ *   edge e = 4 * axis + idx runs along axis (0 x, 1 y, 2 z) from the corner whose other two offsets, in axis order, are (idx & 1, idx >> 1):
+ *   edges 0..3 along x from (0, y, z), idx = y + 2 z; 4..7 along y from (x, 0, z), idx = x + 2 z; 8..11 along z from (x, y, 0), idx = x + 2 y.
+ * The table is derived when first used: the segments a case leaves on a cube face depend on that face's four corner signs alone (two
+ * inside corners on a face's diagonal are always cut off one by one), which makes neighbouring cells agree on every shared face. */
+int nsk_mesh_table(int case_index, int8_t* h_edges, int capacity);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

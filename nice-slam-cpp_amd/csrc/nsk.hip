@@ -4,6 +4,7 @@
 #include "nsk_device.h"
 #include "nsk_train.h"
 #include "nsk_bf16.h"
+#include "nsk_mesh.h"
 
 #include <dlfcn.h>
 #include <cstdarg>
@@ -823,6 +824,16 @@ struct nsk_ctx {
     int bwd_mode = 2;                       // decoder backward chains: 2 fp16 2-piece split (default), 0 fp32 MFMA (nsk_set_backward_mode: a measuring stick)
     int matmul_mode = 2;                    // decoder forward: 0 fp32 MFMA, 1 bf16 3-piece split, 2 fp16 2-piece split (nsk_bf16.h)
     double last_bytes = 0, last_flops = 0; int last_samples = 0;
+    // mesh extraction (nsk_eval_lattice / nsk_mesh_extract): slab points, per-node scratch, the table's device copy, the last mesh
+    struct Mesh {
+        float* lat_pts = nullptr; size_t lat_cap = 0;       // [slab][3] points of the lattice slab being evaluated
+        int slab = 0;                                        // nsk_set_tuning "lattice_slab": nodes per slab (0 = automatic)
+        uint8_t* cellcase = nullptr; int* emap = nullptr; size_t node_cap = 0;
+        unsigned* scan = nullptr; size_t scan_cap = 0;
+        int8_t* table = nullptr; uint8_t* ntri = nullptr;
+        float* verts = nullptr; size_t vcap = 0; int* tris = nullptr; size_t tcap = 0;
+        int nv = 0, nt = 0;
+    } mesh;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -965,6 +976,8 @@ extern "C" int nsk_ctx_destroy(nsk_ctx* c)
     }
     hipFree(c->xbuf); hipFree(c->slab); hipFree(c->d_bound); hipFree(c->scal); hipFree(c->fr_tmp);
     free_ws(c->ws);
+    hipFree(c->mesh.lat_pts); hipFree(c->mesh.cellcase); hipFree(c->mesh.emap); hipFree(c->mesh.scan); hipFree(c->mesh.table); hipFree(c->mesh.ntri);
+    hipFree(c->mesh.verts); hipFree(c->mesh.tris);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1027,6 +1040,7 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "fwd_color_cost")) { c->tune_fwd_color_cost = value; return 0; }
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
+    if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     return fail("nsk_set_tuning: unknown key '%s'", key);
 }
 
@@ -1955,6 +1969,190 @@ extern "C" int nsk_eval_points(nsk_ctx* c, int stage, int M, const float* pts, f
     HIPCHK(hipGetLastError());
     account(c, stage, M, 0, false, 0);
     return 0;
+}
+
+// ---- scene mesh: lattice evaluation + marching cubes (nsk_mesh.h) ------------------------------------------------
+// a failed allocation reports its size and leaves the context as it was, minus the buffer that was to grow
+static int mesh_alloc(void** p, size_t bytes, const char* what)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return 0;
+    *p = nullptr;
+    (void)hipGetLastError();
+    return fail("mesh: cannot allocate %zu bytes for %s (%s)", bytes, what, hipGetErrorString(e));
+}
+
+static int lattice_checks(const char* fn, nsk_ctx* c, const float* o, const float* s, int nx, int ny, int nz, int nmin)
+{
+    if (!c || !o || !s) return fail("%s: null argument", fn);
+    if (nx < nmin || ny < nmin || nz < nmin) return fail("%s: need at least %d nodes per axis (got %d x %d x %d)", fn, nmin, nx, ny, nz);
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(o[a])) return fail("%s: origin[%d] is not finite", fn, a);
+        if (!(s[a] > 0.f) || !std::isfinite(s[a])) return fail("%s: step[%d] = %g, must be positive and finite", fn, a, (double)s[a]);
+    }
+    if (c->capturing) return fail("%s: not while a graph is being captured", fn);
+    return 0;
+}
+
+extern "C" int nsk_eval_lattice(nsk_ctx* c, int stage, const float* o, const float* s, int nx, int ny, int nz, float* vol)
+{
+    CHK(lattice_checks("nsk_eval_lattice", c, o, s, nx, ny, nz, 1));
+    if (!vol) return fail("nsk_eval_lattice: d_volume is NULL");
+    if (stage < 0 || stage > 3) return fail("bad stage %d", stage);
+    const int st = stage == NSK_COLOR ? NSK_FINE : stage;       // the colour stage's occupancy is the fine stage's (src/models/NICE.cpp:41-50)
+    CHK(check_stage(c, st));
+    HIPCHK(hipSetDevice(c->device));
+    const long long total = (long long)nx * ny * nz;
+    long long slab = c->mesh.slab > 0 ? c->mesh.slab : std::max(c->ws.capM, 1 << 21);
+    slab = std::min(std::min(slab, total), (1LL << 26) - 1);
+    CHK(ensure_ws(c, 1, (int)slab));
+    if ((size_t)slab > c->mesh.lat_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        hipFree(c->mesh.lat_pts); c->mesh.lat_pts = nullptr; c->mesh.lat_cap = 0;
+        CHK(mesh_alloc((void**)&c->mesh.lat_pts, (size_t)slab * 12, "the lattice slab's points"));
+        c->mesh.lat_cap = (size_t)slab;
+    }
+    McGeom G;
+    G.nx = nx; G.ny = ny; G.nz = nz; G.nn = 0; G.level = 0.f;
+    for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
+    float* pts = c->mesh.lat_pts;
+    for (long long n0 = 0; n0 < total; n0 += slab) {
+        const int cnt = (int)std::min(slab, total - n0);
+        { ProfScope ps(c, "lattice_points"); k_lattice_points<<<(cnt + 255) / 256, 256, 0, c->stream>>>(G, n0, cnt, pts); }
+        HIPCHK(hipGetLastError());
+        for (int q = 0; q < 3; ++q) {
+            const int w = STAGE_DEC[st][q];
+            if (w < 0) break;
+            CHK(launch_decode_fwd(c, w, cnt, 1, nullptr, nullptr, pts, false));
+        }
+        { ProfScope ps(c, "lattice_finish");
+          k_lattice_finish<<<(cnt + 255) / 256, 256, 0, c->stream>>>(cnt, pts, c->d_bound, st == 0 ? c->ws.occ[0] : c->ws.occ[1], st >= 2 ? c->ws.occ[2] : nullptr, vol + n0); }
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// levels of the multi-launch scan over n values: [n | ceil(n / 256) | ...] until one workgroup covers a level, each level at a 64-word boundary
+static size_t mc_scan_words(size_t n)
+{
+    size_t words = 0;
+    for (;;) { words += (n + 63) & ~(size_t)63; if (n <= MC_BLOCK) return words; n = (n + MC_BLOCK - 1) / MC_BLOCK; }
+}
+static int mc_scan(nsk_ctx* c, unsigned* d, int n)
+{
+    const int nb = (n + MC_BLOCK - 1) / MC_BLOCK;
+    unsigned* sums = d + ((n + 63) & ~63);
+    k_mc_scan_block<<<nb, MC_BLOCK, 0, c->stream>>>(d, n, nb > 1 ? sums : nullptr);
+    HIPCHK(hipGetLastError());
+    if (nb == 1) return 0;
+    CHK(mc_scan(c, sums, nb));
+    k_mc_scan_add<<<nb, MC_BLOCK, 0, c->stream>>>(d, n, sums);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int nsk_mesh_extract(nsk_ctx* c, const float* vol, const uint8_t* valid, int nx, int ny, int nz, const float* o, const float* s,
+                                float level, int* n_vertices, int* n_triangles)
+{
+    CHK(lattice_checks("nsk_mesh_extract", c, o, s, nx, ny, nz, 2));
+    if (!vol) return fail("nsk_mesh_extract: d_volume is NULL");
+    if (!n_vertices || !n_triangles) return fail("nsk_mesh_extract: n_vertices / n_triangles is NULL");
+    if (std::isnan(level)) return fail("nsk_mesh_extract: level is NaN");
+    const long long total = (long long)nx * ny * nz;
+    if (total > MC_MAX_NODES) return fail("nsk_mesh_extract: %lld nodes, at most %lld per call", total, (long long)MC_MAX_NODES);
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Mesh& M = c->mesh;
+    M.nv = M.nt = 0;
+    *n_vertices = *n_triangles = 0;
+    const int nn = (int)total, nb = (nn + MC_BLOCK - 1) / MC_BLOCK;
+    if (!M.table) {
+        const McTable& T = mc_table();
+        CHK(mesh_alloc((void**)&M.table, sizeof(T.edges), "the case table"));
+        CHK(mesh_alloc((void**)&M.ntri, sizeof(T.ntri), "the case table"));
+        HIPCHK(hipMemcpy(M.table, T.edges, sizeof(T.edges), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(M.ntri, T.ntri, sizeof(T.ntri), hipMemcpyHostToDevice));
+    }
+    if ((size_t)nn > M.node_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        hipFree(M.cellcase); hipFree(M.emap); M.cellcase = nullptr; M.emap = nullptr; M.node_cap = 0;
+        CHK(mesh_alloc((void**)&M.cellcase, (size_t)nn, "the cell cases"));
+        CHK(mesh_alloc((void**)&M.emap, (size_t)nn * 12, "the edge map"));
+        M.node_cap = (size_t)nn;
+    }
+    const size_t words = mc_scan_words((size_t)nb + 1);
+    if (2 * words > M.scan_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        hipFree(M.scan); M.scan = nullptr; M.scan_cap = 0;
+        CHK(mesh_alloc((void**)&M.scan, 2 * words * 4, "the scan scratch"));
+        M.scan_cap = 2 * words;
+    }
+    unsigned* sv = M.scan; unsigned* stri = M.scan + words;
+    McGeom G;
+    G.nx = nx; G.ny = ny; G.nz = nz; G.nn = nn; G.level = level;
+    for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
+    HIPCHK(hipMemsetAsync(M.scan, 0, 2 * words * 4, c->stream));        // (the slot behind the last workgroup count turns into the total)
+    { ProfScope ps(c, "mc_cells"); k_mc_cells<<<nb, MC_BLOCK, 0, c->stream>>>(G, vol, valid, M.ntri, M.cellcase, stri); }
+    HIPCHK(hipGetLastError());
+    { ProfScope ps(c, "mc_edge_count"); k_mc_edges<false><<<nb, MC_BLOCK, 0, c->stream>>>(G, vol, M.cellcase, sv, nullptr, nullptr, nullptr); }
+    HIPCHK(hipGetLastError());
+    { ProfScope ps(c, "mc_scan"); CHK(mc_scan(c, sv, nb + 1)); CHK(mc_scan(c, stri, nb + 1)); }
+    unsigned tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&tot[0], sv + nb, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&tot[1], stri + nb, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (tot[0] > 0x7fffffffu / 3 || tot[1] > 0x7fffffffu / 3) return fail("nsk_mesh_extract: %u vertices, %u triangles do not fit 32-bit indices", tot[0], tot[1]);
+    if (tot[0] > M.vcap) {
+        hipFree(M.verts); M.verts = nullptr; M.vcap = 0;
+        CHK(mesh_alloc((void**)&M.verts, (size_t)tot[0] * 12, "the vertices"));
+        M.vcap = tot[0];
+    }
+    if (tot[1] > M.tcap) {
+        hipFree(M.tris); M.tris = nullptr; M.tcap = 0;
+        CHK(mesh_alloc((void**)&M.tris, (size_t)tot[1] * 12, "the triangles"));
+        M.tcap = tot[1];
+    }
+    if (tot[0]) {
+        { ProfScope ps(c, "mc_vertices"); k_mc_edges<true><<<nb, MC_BLOCK, 0, c->stream>>>(G, vol, M.cellcase, nullptr, sv, M.emap, M.verts); }
+        HIPCHK(hipGetLastError());
+    }
+    if (tot[1]) {
+        { ProfScope ps(c, "mc_triangles"); k_mc_tris<<<nb, MC_BLOCK, 0, c->stream>>>(G, M.cellcase, M.ntri, M.table, stri, M.emap, M.tris); }
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    M.nv = (int)tot[0]; M.nt = (int)tot[1];
+    *n_vertices = M.nv; *n_triangles = M.nt;
+    return 0;
+}
+
+extern "C" int nsk_mesh_buffers(nsk_ctx* c, float** d_vertices, int32_t** d_triangles)
+{
+    if (!c) return fail("null ctx");
+    if (d_vertices) *d_vertices = c->mesh.nv ? c->mesh.verts : nullptr;
+    if (d_triangles) *d_triangles = c->mesh.nt ? c->mesh.tris : nullptr;
+    return 0;
+}
+
+extern "C" int nsk_mesh_download(nsk_ctx* c, float* h_vertices, int32_t* h_triangles)
+{
+    if (!c) return fail("null ctx");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_vertices && c->mesh.nv) HIPCHK(hipMemcpy(h_vertices, c->mesh.verts, (size_t)c->mesh.nv * 12, hipMemcpyDeviceToHost));
+    if (h_triangles && c->mesh.nt) HIPCHK(hipMemcpy(h_triangles, c->mesh.tris, (size_t)c->mesh.nt * 12, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nsk_mesh_table(int case_index, int8_t* h_edges, int capacity)
+{
+    if (case_index < 0 || case_index > 255) return fail("nsk_mesh_table: case %d out of range", case_index);
+    const McTable& T = mc_table();
+    const int n = 3 * T.ntri[case_index];
+    if (h_edges) {
+        if (capacity < n) return fail("nsk_mesh_table: case %d has %d entries, capacity %d", case_index, n, capacity);
+        memcpy(h_edges, T.edges[case_index], (size_t)n);
+    }
+    return T.ntri[case_index];
 }
 
 // decoders' backward after k_composite wrote g_raw: ONE launch for every decoder of the stage that needs it

@@ -1,0 +1,291 @@
+// nsk_mesh.h -- scene mesh extraction: lattice points for the decoders' forward, marching cubes on the occupancy volume.
+// (The reference has no mesher; the behaviour follows the `meshing:` keys of its config/nice_slam.yaml.  include/nsk.h states the contract.)
+//
+// Numbering (also what nsk_mesh_table reports):
+//   corner c of a cell = (x, y, z) offsets (c & 1, (c >> 1) & 1, c >> 2); case index bit c is set when corner c is INSIDE (value > level);
+//   edge e = 4 * axis + idx runs along `axis` (0 x, 1 y, 2 z) from the corner whose two other offsets are (idx & 1, idx >> 1) in axis order:
+//     0..3  along x from (0, y, z) with idx = y + 2 z;   4..7 along y from (x, 0, z) with idx = x + 2 z;   8..11 along z from (x, y, 0) with idx = x + 2 y.
+// The 256-case table is derived, not typed: on each of the six faces the crossing edges are joined by a rule that reads that face's four
+// corner signs only (an ambiguous face -- two inside corners on a diagonal -- always cuts the inside corners off one by one), so two cells
+// that share a face leave the same segments on it, in opposite directions: the mesh has no cracks whatever the cases are.  The directed
+// segments are the boundary of the inside region on the cube's surface (inside on the right, seen from outside the cube: clockwise round
+// an inside corner); they chain into closed loops, and a fan over each loop gives triangles whose normal points from the inside to the outside.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+
+#define MC_ROW 16                   // table row stride in edge numbers: the largest case has 5 triangles (tests/test_mesh_cpu.py asserts it)
+#define MC_BLOCK 256                // nodes per workgroup of the extraction passes, elements per workgroup of the scan passes
+#define MC_MAX_NODES (1ll << 28)    // keeps every 32-bit sum (at most 5 triangles / 3 vertices per node) below 2^32
+
+struct McTable {
+    int8_t edges[256][MC_ROW];      // three edge numbers per triangle, -1 behind the last
+    uint8_t ntri[256];
+    int max_tri;
+};
+
+static inline int mc_edge_of(int p, int q)       // the edge between two corners that differ along one axis
+{
+    const int lo = p < q ? p : q, d = p ^ q;
+    const int x = lo & 1, y = (lo >> 1) & 1, z = lo >> 2;
+    if (d == 1) return 0 + y + 2 * z;
+    if (d == 2) return 4 + x + 2 * z;
+    return 8 + x + 2 * y;
+}
+
+static inline McTable mc_build_table()
+{
+    McTable T;
+    memset(T.edges, -1, sizeof(T.edges));
+    memset(T.ntri, 0, sizeof(T.ntri));
+    T.max_tri = 0;
+    // the four corners of each face, counter-clockwise seen from outside the cube, and which faces an edge lies in
+    int fc[6][4], face_mask[12] = {0};
+    for (int a = 0; a < 3; ++a)
+        for (int s = 0; s < 2; ++s) {
+            const int u = (a + 1) % 3, v = (a + 2) % 3;
+            static const int ccw[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
+            for (int k = 0; k < 4; ++k) {
+                const int kk = s ? k : (4 - k) % 4;                 // seen from the -axis side the same square runs the other way round
+                fc[2 * a + s][k] = (s << a) | (ccw[kk][0] << u) | (ccw[kk][1] << v);
+            }
+            for (int k = 0; k < 4; ++k) face_mask[mc_edge_of(fc[2 * a + s][k], fc[2 * a + s][(k + 1) & 3])] |= 1 << (2 * a + s);
+        }
+    for (int cs = 0; cs < 256; ++cs) {
+        int next[12];
+        for (int e = 0; e < 12; ++e) next[e] = -1;
+        for (int f = 0; f < 6; ++f) {
+            bool in[4]; int nin = 0;
+            for (int k = 0; k < 4; ++k) { in[k] = (cs >> fc[f][k]) & 1; nin += in[k]; }
+            if (nin == 0 || nin == 4) continue;
+            for (int k = 0; k < 4; ++k) {
+                if (!in[k] || in[(k + 3) & 3]) continue;           // k starts a run of inside corners
+                int j = k;
+                while (in[(j + 1) & 3]) j = (j + 1) & 3;
+                next[mc_edge_of(fc[f][(k + 3) & 3], fc[f][k])] = mc_edge_of(fc[f][j], fc[f][(j + 1) & 3]);
+            }
+        }
+        bool seen[12] = {false};
+        int nt = 0;
+        for (int e0 = 0; e0 < 12; ++e0) {
+            if (next[e0] < 0 || seen[e0]) continue;
+            int loop[12], n = 0;
+            for (int e = e0; !seen[e]; e = next[e]) { seen[e] = true; loop[n++] = e; }
+            // fan apex: the corner whose diagonals run through the cell, not inside a face (first such corner; ties to the lowest position)
+            int best = 0, best_bad = 1 << 30;
+            for (int r = 0; r < n; ++r) {
+                int bad = 0;
+                for (int i = 2; i + 1 < n; ++i) bad += (face_mask[loop[r]] & face_mask[loop[(r + i) % n]]) != 0;
+                if (bad < best_bad) { best_bad = bad; best = r; }
+            }
+            for (int i = 1; i + 1 < n; ++i, ++nt) {
+                T.edges[cs][3 * nt] = (int8_t)loop[best];
+                T.edges[cs][3 * nt + 1] = (int8_t)loop[(best + i) % n];
+                T.edges[cs][3 * nt + 2] = (int8_t)loop[(best + i + 1) % n];
+            }
+        }
+        T.ntri[cs] = (uint8_t)nt;
+        if (nt > T.max_tri) T.max_tri = nt;
+    }
+    return T;
+}
+
+static inline const McTable& mc_table()
+{
+    static const McTable T = mc_build_table();
+    return T;
+}
+
+// ---- device ------------------------------------------------------------------------------------------------
+struct McGeom {
+    int nx, ny, nz, nn;            // nodes per axis, nodes in all (<= MC_MAX_NODES)
+    float o[3], s[3];              // node (i, j, k) sits at o + (i, j, k) * s, each product and sum rounded on its own
+    float level;
+};
+
+__device__ __forceinline__ float mc_mul(float a, float b) { float r = a * b; asm("" : "+v"(r)); return r; }      // (keeps the product out of an FMA)
+__device__ __forceinline__ float mc_coord(float o, int i, float s) { return __fadd_rn(o, mc_mul((float)i, s)); }
+
+// the lattice nodes [n0, n0 + cnt) as points for the decoders' forward
+__global__ __launch_bounds__(256) void k_lattice_points(McGeom G, long long n0, int cnt, float* __restrict__ pts)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= cnt) return;
+    const long long n = n0 + m, r = n / G.nx;
+    const int i = (int)(n % G.nx), j = (int)(r % G.ny), k = (int)(r / G.ny);
+    pts[3 * (size_t)m] = mc_coord(G.o[0], i, G.s[0]);
+    pts[3 * (size_t)m + 1] = mc_coord(G.o[1], j, G.s[1]);
+    pts[3 * (size_t)m + 2] = mc_coord(G.o[2], k, G.s[2]);
+}
+
+// occupancy of the slab with the in-bound rule of eval_points (reference src/Renderer.cpp:26-36)
+__global__ __launch_bounds__(256) void k_lattice_finish(int cnt, const float* __restrict__ pts, const float* __restrict__ bound6,
+                                                        const float* __restrict__ occ_a, const float* __restrict__ occ_b, float* __restrict__ vol)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= cnt) return;
+    const float px = pts[3 * (size_t)m], py = pts[3 * (size_t)m + 1], pz = pts[3 * (size_t)m + 2];
+    const bool inb = px < bound6[1] && px > bound6[0] && py < bound6[3] && py > bound6[2] && pz < bound6[5] && pz > bound6[4];
+    float occ = occ_a[m];
+    if (occ_b) occ = occ_b[m] + occ;
+    vol[m] = inb ? occ : 100.f;
+}
+
+// exclusive scan of one value per thread over the 256 threads of a workgroup; *total = the workgroup's sum
+__device__ __forceinline__ unsigned mc_block_scan(unsigned v, unsigned* total)
+{
+    __shared__ unsigned wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
+    __syncthreads();                        // (a second scan in the same kernel must not overtake the readers of the first)
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned base = 0;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    return base + inc - v;
+}
+
+// (D) per cell: case index (0 for a cell that is not processed: such a cell and the two uniform cases emit nothing) and triangle count
+__global__ __launch_bounds__(256) void k_mc_cells(McGeom G, const float* __restrict__ vol, const uint8_t* __restrict__ valid,
+                                                  const uint8_t* __restrict__ ntri, uint8_t* __restrict__ cellcase, unsigned* __restrict__ bsum)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    unsigned cnt = 0;
+    if (n < G.nn) {
+        const int i = n % G.nx, r = n / G.nx, j = r % G.ny, k = r / G.ny;
+        unsigned code = 0;
+        if (i < G.nx - 1 && j < G.ny - 1 && k < G.nz - 1) {
+            bool ok = true;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const size_t q = (size_t)n + (c & 1) + (size_t)((c >> 1) & 1) * G.nx + (size_t)(c >> 2) * G.nx * G.ny;
+                const float v = vol[q];
+                ok = ok && (fabsf(v) <= 3.402823466e38f) && (!valid || valid[q]);       // (the comparison fails for NaN and +-inf)
+                code |= (v > G.level ? 1u : 0u) << c;
+            }
+            if (!ok) code = 0;
+        }
+        cellcase[n] = (uint8_t)code;
+        cnt = ntri[code];
+    }
+    unsigned total;
+    mc_block_scan(cnt, &total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// the three edges a node owns (+x, +y, +z): an edge carries a vertex when its ends lie on different sides of the level and one of the
+// (up to four) cells around it is processed
+__device__ __forceinline__ unsigned mc_edge_flags(const McGeom& G, const float* __restrict__ vol, const uint8_t* __restrict__ cellcase, int n,
+                                                  int i, int j, int k, float v0, float* v1)
+{
+    const size_t sy = (size_t)G.nx, sz = (size_t)G.nx * G.ny;
+    const bool in0 = v0 > G.level;
+    unsigned flags = 0;
+    if (i < G.nx - 1) {
+        v1[0] = vol[(size_t)n + 1];
+        if ((v1[0] > G.level) != in0) {
+            bool p = cellcase[n] != 0;
+            if (j > 0) p = p || cellcase[n - sy] != 0;
+            if (k > 0) p = p || cellcase[n - sz] != 0;
+            if (j > 0 && k > 0) p = p || cellcase[n - sy - sz] != 0;
+            if (p) flags |= 1u;
+        }
+    }
+    if (j < G.ny - 1) {
+        v1[1] = vol[(size_t)n + sy];
+        if ((v1[1] > G.level) != in0) {
+            bool p = cellcase[n] != 0;
+            if (i > 0) p = p || cellcase[n - 1] != 0;
+            if (k > 0) p = p || cellcase[n - sz] != 0;
+            if (i > 0 && k > 0) p = p || cellcase[n - 1 - sz] != 0;
+            if (p) flags |= 2u;
+        }
+    }
+    if (k < G.nz - 1) {
+        v1[2] = vol[(size_t)n + sz];
+        if ((v1[2] > G.level) != in0) {
+            bool p = cellcase[n] != 0;
+            if (i > 0) p = p || cellcase[n - 1] != 0;
+            if (j > 0) p = p || cellcase[n - sy] != 0;
+            if (i > 0 && j > 0) p = p || cellcase[n - 1 - sy] != 0;
+            if (p) flags |= 4u;
+        }
+    }
+    return flags;
+}
+
+// (A) EMIT = false: vertices per workgroup.  (C) EMIT = true: vertex ids by rank (boff = scanned workgroup counts), the edge -> vertex
+// map emap[3 n + axis] (-1: no vertex) and the positions p0 + t (p1 - p0), t = (level - v0) / (v1 - v0), every operation rounded on its own
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_mc_edges(McGeom G, const float* __restrict__ vol, const uint8_t* __restrict__ cellcase,
+                                                  unsigned* __restrict__ bsum, const unsigned* __restrict__ boff, int* __restrict__ emap,
+                                                  float* __restrict__ verts)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    unsigned flags = 0;
+    int i = 0, j = 0, k = 0;
+    float v0 = 0.f, v1[3] = {0.f, 0.f, 0.f};
+    if (n < G.nn) {
+        i = n % G.nx; const int r = n / G.nx; j = r % G.ny; k = r / G.ny;
+        v0 = vol[n];
+        flags = mc_edge_flags(G, vol, cellcase, n, i, j, k, v0, v1);
+    }
+    unsigned total;
+    const unsigned excl = mc_block_scan(__popc(flags), &total);
+    if (!EMIT) { if (threadIdx.x == 0) bsum[blockIdx.x] = total; return; }
+    if (n >= G.nn) return;
+    unsigned id = boff[blockIdx.x] + excl;
+    const int idx[3] = {i, j, k};
+    float p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = mc_coord(G.o[a], idx[a], G.s[a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!(flags & (1u << a))) { emap[3 * (size_t)n + a] = -1; continue; }
+        const float p1 = mc_coord(G.o[a], idx[a] + 1, G.s[a]);
+        const float t = __fdiv_rn(__fsub_rn(G.level, v0), __fsub_rn(v1[a], v0));
+        float q[3] = {p[0], p[1], p[2]};
+        q[a] = __fadd_rn(p[a], mc_mul(t, __fsub_rn(p1, p[a])));
+        verts[3 * (size_t)id] = q[0]; verts[3 * (size_t)id + 1] = q[1]; verts[3 * (size_t)id + 2] = q[2];
+        emap[3 * (size_t)n + a] = (int)id;
+        ++id;
+    }
+}
+
+// (F) triangles by cell index, then table order; vertex ids through the edge map of the node that owns each edge
+__global__ __launch_bounds__(256) void k_mc_tris(McGeom G, const uint8_t* __restrict__ cellcase, const uint8_t* __restrict__ ntri,
+                                                 const int8_t* __restrict__ table, const unsigned* __restrict__ boff, const int* __restrict__ emap,
+                                                 int* __restrict__ tris)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    unsigned code = 0, cnt = 0;
+    if (n < G.nn) { code = cellcase[n]; cnt = ntri[code]; }
+    unsigned total;
+    const unsigned excl = mc_block_scan(cnt, &total);
+    if (!cnt) return;
+    const size_t first = (size_t)boff[blockIdx.x] + excl, sy = (size_t)G.nx, sz = (size_t)G.nx * G.ny;
+    for (unsigned t = 0; t < 3 * cnt; ++t) {
+        const int e = table[code * MC_ROW + t], a = e >> 2, b0 = e & 1, b1 = (e >> 1) & 1;
+        const size_t node = (size_t)n + (a == 0 ? b0 * sy + b1 * sz : a == 1 ? b0 + b1 * sz : b0 + b1 * sy);
+        tris[3 * first + t] = emap[3 * node + a];
+    }
+}
+
+// device-wide exclusive scan in three kinds of launches (workgroup scans -> scan of the workgroup sums -> add): no workgroup waits on another
+__global__ __launch_bounds__(256) void k_mc_scan_block(unsigned* __restrict__ d, int n, unsigned* __restrict__ sums)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    unsigned total;
+    const unsigned excl = mc_block_scan(q < n ? d[q] : 0u, &total);
+    if (q < n) d[q] = excl;
+    if (sums && threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(256) void k_mc_scan_add(unsigned* __restrict__ d, int n, const unsigned* __restrict__ sums)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < n) d[q] += sums[blockIdx.x];
+}

@@ -1,6 +1,7 @@
 // slam_loop.cpp -- the frame loop BASELINE.json's K5 describes (Tracker on every frame, Mapper on every `every`-th, over a posed RGB-D
 // sequence) through the C++ classes with the reference's surface and a SequenceReader; src/main.cpp wires up the Tracker only.
-//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every]
+//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE]
+// --mesh FILE: after the last frame the scene mesh (Mesher, meshing.resolution / meshing.level_set of nice_slam.yaml) goes to FILE as a PLY.
 // <sequence dir>/bound.txt holds the scene bound (6 numbers: x0 x1 y0 y1 z0 z1; the reference hard-codes its own).  Writes est_poses.npy,
 // gt_poses.npy [F,4,4], track_loss.npy [F] (last iteration's loss; 0 for frame 0), map_loss.npy [mapped frames].
 // On a node (BASELINE configs[4], one process per GPU): NSK_RANK / NSK_WORLD / NSK_DEVICE (= local rank) / NSK_RCCL_ID_FILE (a path every rank
@@ -16,6 +17,7 @@
 #include <sstream>
 
 #include "Mapper.h"
+#include "Mesher.h"
 #include "Tracker.h"
 #include "nsk_host.h"
 #include "torchlib/utils.h"
@@ -38,7 +40,15 @@ static void save_npy(const std::string& path, torch::Tensor t)
 
 int main(int argc, char** argv)
 {
-    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every]\n"); return 2; }
+    std::string mesh_path;
+    for (int a = 1; a + 1 < argc; ++a)
+        if (std::string(argv[a]) == "--mesh") {                     // taken out of the positional arguments
+            mesh_path = argv[a + 1];
+            for (int b = a; b + 2 < argc; ++b) argv[b] = argv[b + 2];
+            argc -= 2;
+            break;
+        }
+    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE]\n"); return 2; }
     const std::string kind = argv[1], seq = argv[2], out = std::string(argv[5]) + "/";
     const int max_frames = argc > 6 ? std::atoi(argv[6]) : -1, every = argc > 7 ? std::atoi(argv[7]) : 1;
     try {
@@ -117,6 +127,11 @@ int main(int argc, char** argv)
         save_npy(out + "est_poses.npy", torch::stack(est)); save_npy(out + "gt_poses.npy", torch::stack(gts));
         save_npy(out + "track_loss.npy", torch::tensor(tl)); save_npy(out + "map_loss.npy", torch::tensor(ml));
         for (auto k : keys) save_npy(out + k + ".npy", c.at(k));
+        if (!mesh_path.empty()) {
+            Mesher mesher(ns, bound);
+            mesher.get_mesh(mesh_path, decoders, c, true);
+            std::printf("mesh: %d vertices, %d triangles -> %s\n", mesher.last_vertices, mesher.last_triangles, mesh_path.c_str());
+        }
         std::printf("slam_loop ok\n");
         return 0;
     } catch (const std::exception& e) {

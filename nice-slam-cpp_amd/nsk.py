@@ -25,6 +25,7 @@ SYMBOLS = (
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
     "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
+    "nsk_eval_lattice", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
 )
 
 
@@ -74,6 +75,15 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def mesh_table(case):
+    """the triangles of one of the 256 corner-sign cases as a list of edge triples (numbering: include/nsk.h); needs no GPU"""
+    buf = (C.c_int8 * 64)()
+    n = lib().nsk_mesh_table(int(case), buf, 64)
+    if n < 0:
+        raise NskError(lib().nsk_last_error().decode())
+    return [(int(buf[3 * t]), int(buf[3 * t + 1]), int(buf[3 * t + 2])) for t in range(n)]
+
+
 def _stage(s):
     return STAGES[s] if isinstance(s, str) else int(s)
 
@@ -81,8 +91,8 @@ def _stage(s):
 class _CudaArray:
     """__cuda_array_interface__ view of a raw device pointer so that torch can wrap context-owned memory"""
 
-    def __init__(self, ptr, n):
-        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+    def __init__(self, ptr, n, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
 def _ordered(fn):
@@ -317,6 +327,41 @@ class Context:
         raw = torch.empty(M, 4, device=pts.device)
         _chk(lib().nsk_eval_points(self.h, _stage(stage), M, _ptr(pts), _ptr(raw)))
         return raw
+
+    @_ordered
+    def eval_lattice(self, stage, origin, step, nx, ny, nz):
+        """occupancy at the nodes origin + (i, j, k) * step -> float32 cuda tensor [nz, ny, nx] (nsk_eval_lattice)"""
+        import numpy as np
+        import torch
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
+        vol = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.float32, device="cuda:%d" % self.device)
+        _chk(lib().nsk_eval_lattice(self.h, _stage(stage), o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), _ptr(vol)))
+        return vol
+
+    @_ordered
+    def extract_mesh(self, volume, origin, step, level=0.0, valid=None):
+        """marching cubes over a float32 cuda volume [nz, ny, nx] (valid: uint8 cuda tensor of the same shape or None) ->
+        (vertices [nv, 3] float32, triangles [nt, 3] int32) as cuda tensors of their own (nsk_mesh_extract)"""
+        import numpy as np
+        import torch
+        assert volume.dim() == 3 and volume.dtype == torch.float32
+        if valid is not None:
+            assert valid.dtype == torch.uint8 and valid.numel() == volume.numel()
+        nz, ny, nx = volume.shape
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
+        nv, nt = C.c_int(0), C.c_int(0)
+        _chk(lib().nsk_mesh_extract(self.h, _ptr(volume), _ptr(valid), nx, ny, nz, o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p),
+                                    C.c_float(level), C.byref(nv), C.byref(nt)))
+        pv, pt = C.c_void_p(), C.c_void_p()
+        _chk(lib().nsk_mesh_buffers(self.h, C.byref(pv), C.byref(pt)))
+        dev = volume.device
+        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((nt.value, 3), dtype=torch.int32, device=dev)
+        if nv.value:      # (nsk_mesh_extract has synchronised; the copies run on torch's current stream)
+            verts.view(-1).copy_(torch.as_tensor(_CudaArray(pv.value, 3 * nv.value), device=dev))
+        if nt.value:
+            tris.view(-1).copy_(torch.as_tensor(_CudaArray(pt.value, 3 * nt.value, "<i4"), device=dev))
+        return verts, tris
 
     @_ordered
     def raw2outputs(self, raw, z, rays_d, occupancy=False):

@@ -1,0 +1,69 @@
+"""times of the scene-mesh path on the reference bound: python tools/mesh_times.py [resolutions ...] (default 128 256 384)
+HIP events around every launch group (nsk_profile_begin / _end), 5 warm-ups, 20 repeats, medians in ms.  Per resolution: lattice evaluation
+(fine stage), each extraction pass with the bytes it must move and the time those bytes take at 8 TB/s, the colour query on the vertices.
+For 256 also what the same volume costs without nsk_eval_lattice: points built on the host, uploaded, nsk_eval_points in chunks, raw
+downloaded (host clock around synchronised work, 5 repeats)."""
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np, torch
+import nice_slam_cpp_amd as pkg, scenes
+
+WARM, REPS, HBM = 5, 20, 8.0e12
+res = [int(a) for a in sys.argv[1:]] or [128, 256, 384]
+sc = scenes.make_scene(3, grid_std=0.3, bias_std=0.1)
+ctx = pkg.Context(0); ctx.set_render_opts(); ctx.load_scene(sc["bound"], sc["grids"], sc["decoders"])
+b = sc["bound"]
+CHUNK = 1 << 21
+
+
+def medians(fn):
+    rows = []
+    with torch.cuda.stream(ctx.tstream):
+        for _ in range(WARM):
+            fn()
+        for _ in range(REPS):
+            ctx.profile_begin(); fn(); rows.append(ctx.profile_end())
+    return {k: float(np.median([r[k][1] for r in rows])) for k in rows[0]}, rows[0]
+
+
+for n in res:
+    origin = b[:, 0].astype(np.float32)
+    step = ((b[:, 1] - b[:, 0]) / np.float32(n - 1)).astype(np.float32)
+    nodes = n ** 3
+    out = {}
+    lat, cnt = medians(lambda: out.__setitem__("vol", ctx.eval_lattice("fine", origin, step, n, n, n)))
+    vol = out["vol"]
+    ext, _ = medians(lambda: out.__setitem__("mesh", ctx.extract_mesh(vol, origin, step, 0.0)))
+    verts, tris = out["mesh"]
+    nv, nt = verts.shape[0], tris.shape[0]
+
+    def colour():
+        for v0 in range(0, nv, CHUNK):
+            ctx.eval_points("color", verts[v0:v0 + CHUNK])
+    col, _ = medians(colour)
+    print("== %d^3 nodes (%.1f M), %d vertices, %d triangles, %d slabs" % (n, nodes / 1e6, nv, nt, cnt["lattice_points"][0]))
+    print("lattice evaluation %.3f ms  %s" % (sum(lat.values()), {k: round(v, 3) for k, v in lat.items()}))
+    # bytes each pass must move: volume 4 B / node read, cell case 1 B / node, edge map 12 B / node, vertices / triangles 12 B each
+    must = {"mc_cells": nodes * 5, "mc_edge_count": nodes * 5, "mc_scan": 0, "mc_vertices": nodes * 17 + nv * 12, "mc_triangles": nodes * 1 + nt * 24}
+    for k in ("mc_cells", "mc_edge_count", "mc_scan", "mc_vertices", "mc_triangles"):
+        if k in ext:
+            print("  %-14s %8.3f ms   %7.1f MB   %.3f ms at 8 TB/s" % (k, ext[k], must[k] / 1e6, 1e3 * must[k] / HBM))
+    print("extraction kernels %.3f ms (the call also synchronises twice and reads 8 bytes back)" % sum(ext.values()))
+    print("colour query %.3f ms  %s" % (sum(col.values()), {k: round(v, 3) for k, v in col.items()}))
+    if n == 256:
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            c = [(origin[a] + np.arange(n, dtype=np.float32) * step[a]).astype(np.float32) for a in range(3)]
+            P = np.empty((n, n, n, 3), np.float32)
+            P[..., 0] = c[0][None, None, :]; P[..., 1] = c[1][None, :, None]; P[..., 2] = c[2][:, None, None]
+            P = P.reshape(-1, 3)
+            raw = np.empty((nodes, 4), np.float32)
+            for m0 in range(0, nodes, 1 << 22):
+                d = torch.from_numpy(P[m0:m0 + (1 << 22)]).cuda()
+                raw[m0:m0 + (1 << 22)] = ctx.eval_points("fine", d).cpu().numpy()
+            torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
+        same = bool((raw[:, 3].view(np.int32) == vol.cpu().numpy().reshape(-1).view(np.int32)).all())
+        print("host-built points + chunked nsk_eval_points + download of raw: %.1f ms (median of 5, host clock; same bits: %s)" % (1e3 * float(np.median(ts)), same))
+    del vol, verts, tris, out
