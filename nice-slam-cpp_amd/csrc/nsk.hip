@@ -5,6 +5,7 @@
 #include "nsk_train.h"
 #include "nsk_bf16.h"
 #include "nsk_mesh.h"
+#include "nsk_buf.h"
 
 #include <dlfcn.h>
 #include <cstdarg>
@@ -12,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,26 +37,6 @@ __global__ void k_pack(float* __restrict__ img, const int* __restrict__ idx, con
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { int k = idx[i]; img[i] = k >= 0 ? P[k] : 0.f; }
-}
-
-// torch::optim::Adam (reference src/Mapper.cpp:330,445-446); mask is per voxel (32 floats) or nullptr; zeroes g
-__global__ void k_adam(int n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                       const uint8_t* __restrict__ mask, float step_size, float bc2s, float b1, float b2, float eps)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;       // one f4 per thread
-    if (4 * i >= n) return;
-    f4* g4 = reinterpret_cast<f4*>(g) + i;
-    if (mask && !mask[i >> 3]) { *g4 = (f4)(0.f); return; }
-    f4 gg = *g4, pp = reinterpret_cast<f4*>(p)[i], mm = reinterpret_cast<f4*>(m)[i], vv = reinterpret_cast<f4*>(v)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-        vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-        float denom = sqrtf(vv[k]) / bc2s + eps;
-        pp[k] -= step_size * (mm[k] / denom);
-    }
-    reinterpret_cast<f4*>(p)[i] = pp; reinterpret_cast<f4*>(m)[i] = mm; reinterpret_cast<f4*>(v)[i] = vv;
-    *g4 = (f4)(0.f);
 }
 
 struct AdamSeg { float* p; float* g; float* m; float* v; const int* idx; int nidx; int n; float step_size, bc2s; int blk_end;      // idx: the marked voxels (nullptr = all)
@@ -152,8 +134,7 @@ __global__ void k_adam_multi(AdamArgs A)
 }
 
 // Mask-compacted gradient exchange (multi-GPU): every rank holds the same optimiser mask, so only the marked voxels' gradients need to
-// travel.  k_mask_index lists them in ascending order (one workgroup, deterministic: every rank must build the same list),
-// k_grad_gather / k_grad_scatter move their 32-float lines between the dense gradient slab and the packed exchange buffer.
+// travel.  k_mask_index lists them in ascending order (one workgroup, deterministic: every rank must build the same list).
 __global__ __launch_bounds__(1024) void k_mask_index(int nvox, const uint8_t* __restrict__ mask, int* __restrict__ idx, int* __restrict__ count)
 {
     __shared__ int wsum[16];
@@ -175,20 +156,6 @@ __global__ __launch_bounds__(1024) void k_mask_index(int nvox, const uint8_t* __
         __syncthreads();
     }
     if (threadIdx.x == 0) *count = base;
-}
-__global__ void k_grad_gather(int n, const int* __restrict__ idx, const float* __restrict__ g, float* __restrict__ packed)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;          // one float4 per thread, 8 per voxel
-    if (t >= n * 8) return;
-    const int v = idx ? idx[t >> 3] : (t >> 3);
-    reinterpret_cast<f4*>(packed)[t] = reinterpret_cast<const f4*>(g)[(size_t)v * 8 + (t & 7)];
-}
-__global__ void k_grad_scatter(int n, const int* __restrict__ idx, const float* __restrict__ packed, float* __restrict__ g)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 8) return;
-    const int v = idx ? idx[t >> 3] : (t >> 3);
-    reinterpret_cast<f4*>(g)[(size_t)v * 8 + (t & 7)] = reinterpret_cast<const f4*>(packed)[t];
 }
 
 // the whole packed exchange buffer in ONE launch each way (it was one launch per level plus two copies: eleven small operations per
@@ -725,46 +692,52 @@ __global__ void k_gather_pixels(int n, const int* __restrict__ pi, const int* __
 // ---------------------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------------------
+// Every device buffer of the context is a Buf: freed by its owner's destructor, empty (null, capacity 0) after a failed allocation.
+struct HipAlloc {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+template <typename T> using Buf = DevBuf<T, HipAlloc>;
+
 struct GridState {
     int C = 0, Z = 0, Y = 0, X = 0;
-    size_t n = 0;                // floats = nvox*32
-    float* v = nullptr; float* m = nullptr; float* s = nullptr;
-    uint8_t* mask = nullptr;
+    size_t n = 0;                // floats = nvox*32 (0 = not uploaded)
+    Buf<float> v, m, s;          // one group: allocated together or not at all
+    Buf<uint8_t> mask;
     size_t g_off = 0;            // offset in the gradient slab
-    int* midx = nullptr; int nmask = 0; bool midx_dirty = true;      // ascending list of the marked voxels (packed gradient exchange)
+    Buf<int> midx; int nmask = 0; bool midx_dirty = true;      // ascending list of the marked voxels (packed gradient exchange)
 };
 struct DecState {
-    int n = 0;
-    float* p = nullptr; float* m = nullptr; float* s = nullptr;
-    float* fimg = nullptr; float* bimg = nullptr;
-    int* fidx = nullptr; int* bidx = nullptr;
-    int* finv = nullptr; int* binv = nullptr;     // inverse of fidx / bidx: image position of each canonical parameter
-    int* inv16 = nullptr;                         // inverse of fidx16
-    int* invh = nullptr;                          // inverse of bidx16 (fp16 backward image)
-    float* bimg16 = nullptr; int* bidx16 = nullptr; int bfrag16_n = 0; bool bimg16_dirty = true;   // bf16 3-piece backward image (frozen chain), repacked lazily
-    float* fimg16 = nullptr; int* fidx16 = nullptr; int frag16_n = 0, fimg16_f = 0, tail_off = 0, tail16_off = 0, np16 = 3, cq16 = 2;   // forward image in pieces: 3 bf16 (mode 1) or 2 fp16 (mode 2)
+    int n = 0;                                    // parameter count; set once the one-time setup is complete (0 = never uploaded)
+    Buf<float> p, m, s;
+    Buf<float> fimg, bimg;
+    Buf<int> fidx, bidx;
+    Buf<int> finv, binv;                          // inverse of fidx / bidx: image position of each canonical parameter
+    Buf<int> inv16;                               // inverse of fidx16
+    Buf<int> invh;                                // inverse of bidx16 (fp16 backward image)
+    Buf<float> bimg16; Buf<int> bidx16; int bfrag16_n = 0; bool bimg16_dirty = true;   // bf16 3-piece backward image (frozen chain), repacked lazily
+    Buf<float> fimg16; Buf<int> fidx16; int frag16_n = 0, fimg16_f = 0, tail_off = 0, tail16_off = 0, np16 = 3, cq16 = 2;   // forward image in pieces: 3 bf16 (mode 1) or 2 fp16 (mode 2)
     int fimg_n = 0, bimg_n = 0;
     int trainable = 0;
     bool loaded = false;
     size_t g_off = 0;
 };
 struct Workspace {
-    int capM = 0, capN = 0;
-    float* z = nullptr; float* occ[3] = {nullptr, nullptr, nullptr}; float* rgb4 = nullptr;
-    unsigned long long* masks[4] = {nullptr, nullptr, nullptr, nullptr};
-    f4* hsave[4] = {nullptr, nullptr, nullptr, nullptr};     // block outputs of trainable decoders saved by the forward (save_h)
-    size_t hcap[4] = {0, 0, 0, 0};                              // capacity in tiles
-    int hsave_M[4] = {0, 0, 0, 0};                              // sample count of the forward that filled hsave (0 = stale)
-    float* g_raw = nullptr; float* ray_loss = nullptr;
-    float* tmp_rgb = nullptr; float* tmp_depth = nullptr; float* tmp_var = nullptr;
-    float* dec_slabs = nullptr;      // per-workgroup partial decoder gradients [num_cu][20920]
+    int capM = 0, capN = 0;          // the batch (samples, rays) the group below was allocated for; 0 = not allocated
+    Buf<float> z, occ[3], rgb4;
+    Buf<unsigned long long> masks[4];
+    Buf<f4> hsave[4];                // block outputs of trainable decoders saved by the forward (save_h)
+    int hsave_M[4] = {0, 0, 0, 0};   // sample count of the forward that filled hsave (0 = stale)
+    Buf<float> g_raw, ray_loss;
+    Buf<float> tmp_rgb, tmp_depth, tmp_var;
+    Buf<float> dec_slabs;            // per-workgroup partial decoder gradients [num_cu][20920]
     // cell sort of the samples (k_sample keys -> k_sort_scan -> k_sort_place): perm lists the samples cell by cell
-    int* perm = nullptr; int* skey = nullptr; int* srank = nullptr;     // [capM]
-    int* hist = nullptr; int* offs = nullptr; size_t hist_cap = 0;       // [bins of the key level]; hist is zero between steps
+    Buf<int> perm, skey, srank;      // [capM]
+    Buf<int> hist_raw, offs;         // [bins of the key level] (offs.cap() = bins); the histogram is zero between steps
+    int* hist() const { return hist_raw ? hist_raw.get() + 16 : nullptr; }      // behind one 64-byte line: hist()[-1] is k_sort_scan's cursor
     // second set of the sampling outputs: nsk_map_prepare fills it on the side stream while the current step runs; a step that finds its
-    // batch prepared swaps the pointers above with these
-    float* z_alt = nullptr; int* perm_alt = nullptr; int* skey_alt = nullptr; int* srank_alt = nullptr; int* offs_alt = nullptr;
-    int alt_capM = 0; size_t alt_bins = 0;
+    // batch prepared swaps the buffers above with these
+    Buf<float> z_alt; Buf<int> perm_alt, skey_alt, srank_alt, offs_alt;
 };
 struct nsk_ctx {
     int device = 0;
@@ -772,16 +745,16 @@ struct nsk_ctx {
     bool own_stream = false;
     int num_cu = 256;
     RParams R;
-    float* d_bound = nullptr;
+    Buf<float> d_bound;
     GridState grid[4];
     DecState dec[4];
-    float* slab = nullptr; size_t slab_n = 0;
-    float* xbuf = nullptr; size_t xbuf_cap = 0; size_t xbuf_n = 0;     // packed exchange buffer (nsk_grad_pack) and its current length
+    Buf<float> slab; size_t slab_n = 0;
+    Buf<float> xbuf; size_t xbuf_n = 0;     // packed exchange buffer (nsk_grad_pack) and its current length
     bool x_identity = false;                                              // the last pack handed out the slab itself (no masks)
     bool xlevels[4] = {false, false, false, false}; bool xdecs[4] = {false, false, false, false};      // what the last pack holds
     Workspace ws;
-    float* scal = nullptr;       // [0] gt max, [1] median threshold, [2] loss, [4] frustum max depth (bits)
-    void* fr_tmp = nullptr; size_t fr_cap = 0;      // nsk_frustum_mask scratch
+    Buf<float> scal;             // [0] gt max, [1] median threshold, [2] loss, [4] frustum max depth (bits)
+    Buf<uint8_t> fr_tmp;         // scratch of nsk_frustum_mask and nsk_keyframe_overlap, in bytes
     int adam_step[NSK_NUM_GROUPS] = {0, 0, 0, 0, 0, 0};
     // ---- hipGraph capture of a step (nsk_graph_*): the kernels of the calls made between begin and end are recorded once and
     // replayed with one launch; Adam's bias-correction constants are kernel arguments, so the recorded k_adam_multi node is
@@ -826,18 +799,19 @@ struct nsk_ctx {
     double last_bytes = 0, last_flops = 0; int last_samples = 0;
     // mesh extraction (nsk_eval_lattice / nsk_mesh_extract): slab points, per-node scratch, the table's device copy, the last mesh
     struct Mesh {
-        float* lat_pts = nullptr; size_t lat_cap = 0;       // [slab][3] points of the lattice slab being evaluated
+        Buf<float> lat_pts;                                  // [slab][3] points of the lattice slab being evaluated
         int slab = 0;                                        // nsk_set_tuning "lattice_slab": nodes per slab (0 = automatic)
-        uint8_t* cellcase = nullptr; int* emap = nullptr; size_t node_cap = 0;
-        unsigned* scan = nullptr; size_t scan_cap = 0;
-        int8_t* table = nullptr; uint8_t* ntri = nullptr;
-        float* verts = nullptr; size_t vcap = 0; int* tris = nullptr; size_t tcap = 0;
+        Buf<uint8_t> cellcase; Buf<int> emap;                // [nodes], [nodes][3]: one group
+        Buf<unsigned> scan;
+        Buf<int8_t> table; Buf<uint8_t> ntri;                // one group
+        Buf<float> verts; Buf<int> tris;                     // [nv][3], [nt][3]
         int nv = 0, nt = 0;
     } mesh;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
     std::vector<ProfRec> prof_recs;
+    ~nsk_ctx();                 // graphs, profiling events, an owned stream; the buffers free themselves
 };
 
 // roctx ranges (rocprofv3 --marker-trace shows them around the kernels of each launch group); libroctx64 is loaded on first use
@@ -888,6 +862,43 @@ static void invalidate_graphs(nsk_ctx* c)
     }
 }
 
+nsk_ctx::~nsk_ctx()
+{
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    invalidate_graphs(this);
+    for (auto& r : prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
+    if (own_stream && stream) hipStreamDestroy(stream);
+}
+
+// ---- growing a buffer ---------------------------------------------------------------------------------------------
+// dev_alloc: (re)allocate and report a failure with its size; the buffer is empty afterwards, never dangling.
+template <typename T>
+static int dev_alloc(Buf<T>& b, size_t n, const char* what)
+{
+    const int e = b.alloc(n);
+    if (e == 0) return 0;
+    (void)hipGetLastError();
+    return fail("cannot allocate %zu bytes for %s (%s)", n * sizeof(T), what, hipGetErrorString((hipError_t)e));
+}
+// what has to happen before a buffer that launches (and, per site, recorded graphs) may point into is replaced
+enum { GROW_NO_CAPTURE = 1,         // refuse while a graph is being captured
+       GROW_STALE_GRAPHS = 2 };     // the recorded graphs hold this buffer's address
+static int grow_begin(nsk_ctx* c, unsigned flags)
+{
+    if ((flags & GROW_NO_CAPTURE) && c->capturing) return fail("graph capture: the workspace must grow (run the same step once before nsk_graph_begin)");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flags & GROW_STALE_GRAPHS) invalidate_graphs(c);
+    return 0;
+}
+template <typename T>
+static int grow(nsk_ctx* c, Buf<T>& b, size_t n, const char* what, unsigned flags)
+{
+    if (n <= b.cap()) return 0;
+    CHK(grow_begin(c, flags));
+    return dev_alloc(b, n, what);
+}
+
 extern "C" const char* nsk_last_error(void) { return g_err.c_str(); }
 extern "C" int nsk_version(void) { return NSK_VERSION; }
 
@@ -922,7 +933,8 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail("nsk_ctx_create: device arch %s, this library is built for gfx950 only", prop.gcnArchName);
-    nsk_ctx* c = new nsk_ctx();
+    std::unique_ptr<nsk_ctx> owner(new nsk_ctx());       // every early return below releases what was made, the stream included
+    nsk_ctx* c = owner.get();
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
@@ -930,9 +942,9 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     const float b[6] = {-4.5f, 3.82f, -1.5f, 2.02f, -3.0f, 2.76f};     // reference src/Renderer.cpp:15
     memcpy(c->R.bound, b, sizeof(b));
     c->R.n_samples = 32; c->R.n_surface = 16; c->R.lindisp = 0; c->R.occupancy = 0; c->R.perturb = 0.f; c->R.seed = 0;
-    HIPCHK(hipMalloc(&c->d_bound, 6 * sizeof(float)));
+    CHK(dev_alloc(c->d_bound, 6, "the bound"));
     HIPCHK(hipMemcpy(c->d_bound, b, sizeof(b), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&c->scal, 16 * sizeof(float)));
+    CHK(dev_alloc(c->scal, 16, "the scalars"));
     HIPCHK(hipMemset(c->scal, 0, 16 * sizeof(float)));
     // dynamic LDS limits
     CHK(set_lds(k_decode_fwd<0>, fwd_img_floats(0) * 4)); CHK(set_lds(k_decode_fwd<1>, fwd_img_floats(1) * 4));
@@ -948,37 +960,12 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     CHK(set_lds(k_decode_bwd_frozen<false>, 160 * 1024 - 256));
     CHK(set_lds(k_decode_bwd_track, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<false>, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<true>, 160 * 1024));
     CHK(set_lds(k_decode_fwd_dump<0>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<1>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<2>, 160 * 1024));
-    *out = c;
+    *out = owner.release();
     return 0;
-}
-
-static void free_ws(Workspace& w)
-{
-    hipFree(w.z); for (int i = 0; i < 3; ++i) hipFree(w.occ[i]); hipFree(w.rgb4);
-    for (int i = 0; i < 4; ++i) hipFree(w.masks[i]);
-    for (int i = 0; i < 4; ++i) { hipFree(w.hsave[i]); w.hsave[i] = nullptr; w.hcap[i] = 0; w.hsave_M[i] = 0; }
-    hipFree(w.g_raw); hipFree(w.ray_loss); hipFree(w.tmp_rgb); hipFree(w.tmp_depth); hipFree(w.tmp_var); hipFree(w.dec_slabs);
-    hipFree(w.perm); hipFree(w.skey); hipFree(w.srank); if (w.hist) hipFree(w.hist - 16); hipFree(w.offs);
-    hipFree(w.z_alt); hipFree(w.perm_alt); hipFree(w.skey_alt); hipFree(w.srank_alt); hipFree(w.offs_alt);
-    w = Workspace();
 }
 
 extern "C" int nsk_ctx_destroy(nsk_ctx* c)
 {
-    if (!c) return 0;
-    hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 4; ++i) {
-        hipFree(c->grid[i].v); hipFree(c->grid[i].m); hipFree(c->grid[i].s); hipFree(c->grid[i].mask); hipFree(c->grid[i].midx);
-        hipFree(c->dec[i].p); hipFree(c->dec[i].m); hipFree(c->dec[i].s); hipFree(c->dec[i].fimg); hipFree(c->dec[i].bimg);
-        hipFree(c->dec[i].fidx); hipFree(c->dec[i].bidx); hipFree(c->dec[i].finv); hipFree(c->dec[i].binv); hipFree(c->dec[i].inv16); hipFree(c->dec[i].invh); hipFree(c->dec[i].bimg16); hipFree(c->dec[i].bidx16);
-        hipFree(c->dec[i].fimg16); hipFree(c->dec[i].fidx16);
-    }
-    hipFree(c->xbuf); hipFree(c->slab); hipFree(c->d_bound); hipFree(c->scal); hipFree(c->fr_tmp);
-    free_ws(c->ws);
-    hipFree(c->mesh.lat_pts); hipFree(c->mesh.cellcase); hipFree(c->mesh.emap); hipFree(c->mesh.scan); hipFree(c->mesh.table); hipFree(c->mesh.ntri);
-    hipFree(c->mesh.verts); hipFree(c->mesh.tris);
-    if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
@@ -1085,35 +1072,26 @@ static int rebuild_slab(nsk_ctx* c)
     for (int i = 0; i < 4; ++i) { c->grid[i].g_off = n; n += c->grid[i].n; }
     for (int i = 0; i < 4; ++i) { c->dec[i].g_off = n; n += (size_t)((c->dec[i].n + 3) & ~3); }
     n += 4;
-    if (n != c->slab_n) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        invalidate_graphs(c);
-        if (c->slab) HIPCHK(hipFree(c->slab));
-        HIPCHK(hipMalloc(&c->slab, n * sizeof(float)));
+    if (n != c->slab_n) {                  // (a smaller slab is replaced too: every offset in it has moved)
+        CHK(grow_begin(c, GROW_STALE_GRAPHS));
+        c->slab_n = 0;
+        CHK(dev_alloc(c->slab, n, "the gradient slab"));
         c->slab_n = n;
     }
     HIPCHK(hipMemsetAsync(c->slab, 0, n * sizeof(float), c->stream));
     return 0;
 }
 
-extern "C" int nsk_grid_upload(nsk_ctx* c, int level, const float* h, int C, int Z, int Y, int X)
+static int grid_upload(nsk_ctx* c, GridState& G, const float* h, int C, int Z, int Y, int X)
 {
-    if (!c || !h) return fail("nsk_grid_upload: null argument");
-    if (!which_ok(level)) return fail("nsk_grid_upload: bad level %d", level);
-    if (C != 32) return fail("nsk_grid_upload: C must be 32 (got %d)", C);
-    if (Z < 1 || Y < 1 || X < 1) return fail("nsk_grid_upload: bad shape");
-    if ((size_t)Z * Y * X >= ((size_t)1 << 25)) return fail("nsk_grid_upload: at most 2^25 - 1 voxels per level (32-bit byte offsets in the forward's gather: 128 B per voxel)");
-    HIPCHK(hipSetDevice(c->device));
-    GridState& G = c->grid[level];
     size_t nvox = (size_t)Z * Y * X, n = nvox * 32;
     bool realloc_ = n != G.n;
     if (realloc_) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        invalidate_graphs(c);
-        hipFree(G.v); hipFree(G.m); hipFree(G.s); hipFree(G.mask); G.mask = nullptr; hipFree(G.midx); G.midx = nullptr;
-        HIPCHK(hipMalloc(&G.v, n * 4)); HIPCHK(hipMalloc(&G.m, n * 4)); HIPCHK(hipMalloc(&G.s, n * 4));
+        CHK(grow_begin(c, GROW_STALE_GRAPHS));
+        G = GridState();
+        CHK(dev_alloc(G.v, n, "a grid level")); CHK(dev_alloc(G.m, n, "a grid level's first moment")); CHK(dev_alloc(G.s, n, "a grid level's second moment"));
     }
-    if (G.Z != Z || G.Y != Y || G.X != X) { if (G.mask) { HIPCHK(hipStreamSynchronize(c->stream)); invalidate_graphs(c); hipFree(G.mask); G.mask = nullptr; } }
+    if (G.Z != Z || G.Y != Y || G.X != X) { if (G.mask) { CHK(grow_begin(c, GROW_STALE_GRAPHS)); G.mask.reset(); } }
     G.C = C; G.Z = Z; G.Y = Y; G.X = X; G.n = n; G.midx_dirty = true;
     std::vector<float> t(n);
     for (int ch = 0; ch < 32; ++ch)
@@ -1124,6 +1102,21 @@ extern "C" int nsk_grid_upload(nsk_ctx* c, int level, const float* h, int C, int
     HIPCHK(hipStreamSynchronize(c->stream));
     if (realloc_) CHK(rebuild_slab(c));
     return 0;
+}
+extern "C" int nsk_grid_upload(nsk_ctx* c, int level, const float* h, int C, int Z, int Y, int X)
+{
+    if (!c || !h) return fail("nsk_grid_upload: null argument");
+    if (!which_ok(level)) return fail("nsk_grid_upload: bad level %d", level);
+    if (C != 32) return fail("nsk_grid_upload: C must be 32 (got %d)", C);
+    if (Z < 1 || Y < 1 || X < 1) return fail("nsk_grid_upload: bad shape");
+    if ((size_t)Z * Y * X >= ((size_t)1 << 25)) return fail("nsk_grid_upload: at most 2^25 - 1 voxels per level (32-bit byte offsets in the forward's gather: 128 B per voxel)");
+    HIPCHK(hipSetDevice(c->device));
+    GridState& G = c->grid[level];
+    const bool fresh = (size_t)Z * Y * X * 32 != G.n;
+    const int r = grid_upload(c, G, h, C, Z, Y, X);
+    // a level that was being (re)allocated when something failed is left unloaded: check_stage asks for it, a retry allocates again
+    if (r != 0 && fresh) { invalidate_graphs(c); G = GridState(); }
+    return r;
 }
 
 static int grid_fetch(nsk_ctx* c, int level, const float* src, float* h)
@@ -1173,8 +1166,8 @@ extern "C" int nsk_set_mask(nsk_ctx* c, int level, const uint8_t* h_mask)
     // Unmarked voxels are never visited by the optimiser, so whatever the scatter added to their gradient stays there: a voxel that
     // becomes marked now must not inherit it.  The level's gradient is cleared whenever its mask changes.
     if (c->slab) HIPCHK(hipMemsetAsync(c->slab + G.g_off, 0, G.n * 4, c->stream));
-    if (!h_mask) { if (G.mask) { hipFree(G.mask); G.mask = nullptr; } return 0; }
-    if (!G.mask) HIPCHK(hipMalloc(&G.mask, nvox));
+    if (!h_mask) { G.mask.reset(); return 0; }
+    if (!G.mask) CHK(dev_alloc(G.mask, nvox, "the voxel mask"));
     HIPCHK(hipMemcpy(G.mask, h_mask, nvox, hipMemcpyHostToDevice));
     return 0;
 }
@@ -1281,7 +1274,7 @@ static int ensure_bimg16(nsk_ctx* c, int w)
     DecState& D = c->dec[w];
     if (!D.bimg16 || !D.bimg16_dirty) return 0;
     ProfScope ps(c, "pack_bwd_bf16");
-    k_pack_bf16<<<(D.bfrag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.bimg16), D.bidx16, D.p, D.bfrag16_n, 2);
+    k_pack_bf16<<<(D.bfrag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.bimg16.get()), D.bidx16, D.p, D.bfrag16_n, 2);
     k_pack<<<2, 256, 0, c->stream>>>(D.bimg16 + MlpBwdImgH::P_WO, D.bidx + MlpBwdImg::P_WO, D.p, 128 + 288);     // fp32 tail: Wo, B
     HIPCHK(hipGetLastError());
     D.bimg16_dirty = false;
@@ -1301,7 +1294,7 @@ static int repack16(nsk_ctx* c, int w)
     DecState& D = c->dec[w];
     if (!D.fimg16) return 0;
     set_np16(D, c->matmul_mode == 2 ? 2 : 3);
-    k_pack_bf16<<<(D.frag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.fimg16), D.fidx16, D.p, D.frag16_n, D.np16);
+    k_pack_bf16<<<(D.frag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.fimg16.get()), D.fidx16, D.p, D.frag16_n, D.np16);
     k_pack<<<(740 + 255) / 256, 256, 0, c->stream>>>(D.fimg16 + D.tail16_off, D.fidx + D.tail_off, D.p, 740);     // fp32 tail: biases, Wo, bo, B
     HIPCHK(hipGetLastError());
     return 0;
@@ -1325,57 +1318,63 @@ static void adam_consts(float lr, float b1, float b2, int step, float& step_size
 
 extern "C" size_t nsk_decoder_param_count(int which) { return which_ok(which) ? (size_t)nsk_dec_layout(which).total : 0; }
 
+// one-time setup of a decoder: parameters, moments, fragment images and their index tables, into a DecState of its own
+static int dec_setup(int w, size_t n, DecState& D)
+{
+    const size_t n4 = (n + 3) & ~(size_t)3;
+    auto table = [](Buf<int>& d, const std::vector<int>& h, const char* what) -> int {
+        CHK(dev_alloc(d, h.size(), what));
+        HIPCHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    };
+    // image position of each canonical parameter (-1 none)
+    auto inverse = [&](Buf<int>& d, const std::vector<int>& idx, const char* image) -> int {
+        std::vector<int> inv(n4, -1);
+        for (size_t k = 0; k < idx.size(); ++k) if (idx[k] >= 0) { if (inv[idx[k]] != -1) return fail("decoder %d: parameter %d appears twice in the %s image", w, idx[k], image); inv[idx[k]] = (int)k; }
+        return table(d, inv, "a decoder's inverse index table");
+    };
+    CHK(dev_alloc(D.p, n4, "a decoder's parameters")); CHK(dev_alloc(D.m, n4, "a decoder's first moment")); CHK(dev_alloc(D.s, n4, "a decoder's second moment"));
+    HIPCHK(hipMemset(D.p, 0, n4 * 4));
+    std::vector<int> fi, bi;
+    build_idx(w, fi, bi);
+    D.fimg_n = (int)fi.size(); D.bimg_n = (int)bi.size();
+    CHK(dev_alloc(D.fimg, fi.size(), "a decoder's forward image")); CHK(dev_alloc(D.bimg, bi.size(), "a decoder's backward image"));
+    CHK(table(D.fidx, fi, "a decoder's index table")); CHK(table(D.bidx, bi, "a decoder's index table"));
+    if (w != 0) {
+        std::vector<int> i16;
+        if (w == 2) { build_idx16<4>(nsk_dec_layout(w), i16); D.cq16 = 4; D.tail_off = MlpFwdImg<4>::P_B; }
+        else { build_idx16<2>(nsk_dec_layout(w), i16); D.cq16 = 2; D.tail_off = MlpFwdImg<2>::P_B; }
+        set_np16(D, 3);          // allocate for the larger (3-piece) form
+        D.frag16_n = (int)i16.size();
+        CHK(dev_alloc(D.fimg16, (size_t)D.fimg16_f, "a decoder's forward image in pieces")); CHK(table(D.fidx16, i16, "a decoder's index table"));
+        HIPCHK(hipMemset(D.fimg16, 0, (size_t)D.fimg16_f * 4));
+        std::vector<int> ib;
+        build_idx16b(nsk_dec_layout(w), ib);
+        D.bfrag16_n = (int)ib.size();
+        CHK(dev_alloc(D.bimg16, (size_t)MlpBwdImgH::TOTAL_F, "a decoder's backward image in pieces")); CHK(table(D.bidx16, ib, "a decoder's index table"));
+        HIPCHK(hipMemset(D.bimg16, 0, (size_t)MlpBwdImgH::TOTAL_F * 4));
+        CHK(inverse(D.invh, ib, "fp16 backward"));
+        CHK(inverse(D.inv16, i16, "bf16"));
+    }
+    CHK(inverse(D.finv, fi, "forward"));
+    CHK(inverse(D.binv, bi, "backward"));
+    D.n = (int)n;
+    return 0;
+}
+
 extern "C" int nsk_decoder_upload(nsk_ctx* c, int w, const float* h, size_t n)
 {
     if (!c || !h || !which_ok(w)) return fail("nsk_decoder_upload: bad argument");
     if (n != nsk_decoder_param_count(w)) return fail("nsk_decoder_upload: decoder %d expects %zu parameters, got %zu", w, nsk_decoder_param_count(w), n);
     HIPCHK(hipSetDevice(c->device));
     DecState& D = c->dec[w];
-    if (!D.p) {
-        D.n = (int)n;
-        size_t n4 = (n + 3) & ~(size_t)3;
-        HIPCHK(hipMalloc(&D.p, n4 * 4)); HIPCHK(hipMalloc(&D.m, n4 * 4)); HIPCHK(hipMalloc(&D.s, n4 * 4));
-        HIPCHK(hipMemset(D.p, 0, n4 * 4));
-        std::vector<int> fi, bi;
-        build_idx(w, fi, bi);
-        D.fimg_n = (int)fi.size(); D.bimg_n = (int)bi.size();
-        HIPCHK(hipMalloc(&D.fimg, fi.size() * 4)); HIPCHK(hipMalloc(&D.bimg, bi.size() * 4));
-        HIPCHK(hipMalloc(&D.fidx, fi.size() * 4)); HIPCHK(hipMalloc(&D.bidx, bi.size() * 4));
-        HIPCHK(hipMemcpy(D.fidx, fi.data(), fi.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(D.bidx, bi.data(), bi.size() * 4, hipMemcpyHostToDevice));
-        if (w != 0) {
-            std::vector<int> i16;
-            if (w == 2) { build_idx16<4>(nsk_dec_layout(w), i16); D.cq16 = 4; D.tail_off = MlpFwdImg<4>::P_B; }
-            else { build_idx16<2>(nsk_dec_layout(w), i16); D.cq16 = 2; D.tail_off = MlpFwdImg<2>::P_B; }
-            set_np16(D, 3);          // allocate for the larger (3-piece) form
-            D.frag16_n = (int)i16.size();
-            HIPCHK(hipMalloc(&D.fimg16, (size_t)D.fimg16_f * 4)); HIPCHK(hipMalloc(&D.fidx16, i16.size() * 4));
-            HIPCHK(hipMemset(D.fimg16, 0, (size_t)D.fimg16_f * 4));
-            HIPCHK(hipMemcpy(D.fidx16, i16.data(), i16.size() * 4, hipMemcpyHostToDevice));
-            std::vector<int> ib;
-            build_idx16b(nsk_dec_layout(w), ib);
-            D.bfrag16_n = (int)ib.size();
-            HIPCHK(hipMalloc(&D.bimg16, (size_t)MlpBwdImgH::TOTAL_F * 4)); HIPCHK(hipMalloc(&D.bidx16, ib.size() * 4));
-            HIPCHK(hipMemset(D.bimg16, 0, (size_t)MlpBwdImgH::TOTAL_F * 4));
-            HIPCHK(hipMemcpy(D.bidx16, ib.data(), ib.size() * 4, hipMemcpyHostToDevice));
-            std::vector<int> invh(n4, -1);
-            for (size_t k = 0; k < ib.size(); ++k) if (ib[k] >= 0) { if (invh[ib[k]] != -1) return fail("decoder %d: parameter %d appears twice in the fp16 backward image", w, ib[k]); invh[ib[k]] = (int)k; }
-            HIPCHK(hipMalloc(&D.invh, n4 * 4));
-            HIPCHK(hipMemcpy(D.invh, invh.data(), n4 * 4, hipMemcpyHostToDevice));
-            std::vector<int> inv16(n4, -1);
-            for (size_t k = 0; k < i16.size(); ++k) if (i16[k] >= 0) { if (inv16[i16[k]] != -1) return fail("decoder %d: parameter %d appears twice in the bf16 image", w, i16[k]); inv16[i16[k]] = (int)k; }
-            HIPCHK(hipMalloc(&D.inv16, n4 * 4));
-            HIPCHK(hipMemcpy(D.inv16, inv16.data(), n4 * 4, hipMemcpyHostToDevice));
-        }
-        {
-            std::vector<int> finv(n4, -1), binv(n4, -1);
-            for (size_t k = 0; k < fi.size(); ++k) if (fi[k] >= 0) { if (finv[fi[k]] != -1) return fail("decoder %d: parameter %d appears twice in the forward image", w, fi[k]); finv[fi[k]] = (int)k; }
-            for (size_t k = 0; k < bi.size(); ++k) if (bi[k] >= 0) { if (binv[bi[k]] != -1) return fail("decoder %d: parameter %d appears twice in the backward image", w, bi[k]); binv[bi[k]] = (int)k; }
-            HIPCHK(hipMalloc(&D.finv, n4 * 4)); HIPCHK(hipMalloc(&D.binv, n4 * 4));
-            HIPCHK(hipMemcpy(D.finv, finv.data(), n4 * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(D.binv, binv.data(), n4 * 4, hipMemcpyHostToDevice));
-        }
-        CHK(rebuild_slab(c));
+    if (!D.n) {                 // never set up: the setup completes (and only then replaces D) or leaves the decoder as never uploaded
+        DecState fresh;
+        fresh.trainable = D.trainable;
+        CHK(dec_setup(w, n, fresh));
+        D = std::move(fresh);
+        const int r = rebuild_slab(c);
+        if (r != 0) { const int t = D.trainable; D = DecState(); D.trainable = t; return r; }
     }
     HIPCHK(hipMemcpyAsync(D.p, h, n * 4, hipMemcpyHostToDevice, c->stream));
     size_t n4 = (n + 3) & ~(size_t)3;
@@ -1419,24 +1418,25 @@ static int ensure_ws(nsk_ctx* c, int N, int M)
 {
     Workspace& w = c->ws;
     if (M <= w.capM && N <= w.capN) return 0;
-    if (c->capturing) return fail("graph capture: the workspace must grow (run the same step once before nsk_graph_begin)");
-    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(grow_begin(c, GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
     CHK(prep_drop(c));
-    invalidate_graphs(c);
-    int capM = std::max(M, w.capM), capN = std::max(N, w.capN);
-    free_ws(w);
-    size_t m = (size_t)capM + 64;
-    HIPCHK(hipMalloc(&w.z, m * 4));
-    for (int i = 0; i < 3; ++i) HIPCHK(hipMalloc(&w.occ[i], m * 4));
-    HIPCHK(hipMalloc(&w.rgb4, m * 16));
-    for (int i = 0; i < 4; ++i) HIPCHK(hipMalloc(&w.masks[i], m * 32));
-    HIPCHK(hipMalloc(&w.g_raw, m * 16));
-    size_t n = (size_t)capN + 64;
-    HIPCHK(hipMalloc(&w.ray_loss, n * 4));
-    HIPCHK(hipMalloc(&w.tmp_rgb, n * 12)); HIPCHK(hipMalloc(&w.tmp_depth, n * 4)); HIPCHK(hipMalloc(&w.tmp_var, n * 4));
-    HIPCHK(hipMalloc(&w.dec_slabs, (size_t)c->num_cu * 20920 * 4));
-    HIPCHK(hipMemsetAsync(w.dec_slabs, 0, (size_t)c->num_cu * 20920 * 4, c->stream));
-    HIPCHK(hipMalloc(&w.perm, m * 4)); HIPCHK(hipMalloc(&w.skey, m * 4)); HIPCHK(hipMalloc(&w.srank, m * 4));
+    const int capM = std::max(M, w.capM), capN = std::max(N, w.capN);
+    w = Workspace();             // everything, the histogram, the saved block outputs and the second sampling set included
+    const size_t m = (size_t)capM + 64, n = (size_t)capN + 64, slabs = (size_t)c->num_cu * 20920;
+    const int r = [&]() -> int {
+        CHK(dev_alloc(w.z, m, "the sample depths"));
+        for (int i = 0; i < 3; ++i) CHK(dev_alloc(w.occ[i], m, "the occupancies"));
+        CHK(dev_alloc(w.rgb4, m * 4, "the colours"));
+        for (int i = 0; i < 4; ++i) CHK(dev_alloc(w.masks[i], m * 4, "the ReLU bits"));
+        CHK(dev_alloc(w.g_raw, m * 4, "the sample gradients"));
+        CHK(dev_alloc(w.ray_loss, n, "the ray losses"));
+        CHK(dev_alloc(w.tmp_rgb, n * 3, "the ray colours")); CHK(dev_alloc(w.tmp_depth, n, "the ray depths")); CHK(dev_alloc(w.tmp_var, n, "the ray variances"));
+        CHK(dev_alloc(w.dec_slabs, slabs, "the decoder gradient slabs"));
+        HIPCHK(hipMemsetAsync(w.dec_slabs, 0, slabs * 4, c->stream));
+        CHK(dev_alloc(w.perm, m, "the cell sort")); CHK(dev_alloc(w.skey, m, "the cell sort")); CHK(dev_alloc(w.srank, m, "the cell sort"));
+        return 0;
+    }();
+    if (r != 0) { w = Workspace(); return r; }
     w.capM = capM; w.capN = capN;
     return 0;
 }
@@ -1445,37 +1445,25 @@ static int ensure_ws(nsk_ctx* c, int N, int M)
 static int ensure_hist(nsk_ctx* c, size_t bins)
 {
     Workspace& w = c->ws;
-    if (bins <= w.hist_cap) return 0;
-    if (c->capturing) return fail("graph capture: the workspace must grow (run the same step once before nsk_graph_begin)");
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bins <= w.offs.cap()) return 0;
+    CHK(grow_begin(c, GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
     c->prep.valid = false; c->req.valid = false;       // (the histogram is replaced: nothing to clean)
-    invalidate_graphs(c);
-    if (w.hist) hipFree(w.hist - 16);
-    hipFree(w.offs);
-    const size_t slots = ((bins / 8 + 1) / 2) * 16 + 16;    // hist_slot() layout (bins = 8 keys per cell) + one 64-byte line in front (hist[-1] = k_sort_scan's cursor)
-    int* raw = nullptr;
-    HIPCHK(hipMalloc(&raw, slots * 4)); HIPCHK(hipMalloc(&w.offs, bins * 4));
-    HIPCHK(hipMemsetAsync(raw, 0, slots * 4, c->stream));
-    w.hist = raw + 16;
-    w.hist_cap = bins;
-    return 0;
+    const size_t slots = ((bins / 8 + 1) / 2) * 16 + 16;    // hist_slot() layout (bins = 8 keys per cell) + one 64-byte line in front (Workspace::hist)
+    const int r = [&]() -> int {
+        CHK(dev_alloc(w.hist_raw, slots, "the cell histogram")); CHK(dev_alloc(w.offs, bins, "the cell offsets"));
+        HIPCHK(hipMemsetAsync(w.hist_raw, 0, slots * 4, c->stream));
+        return 0;
+    }();
+    if (r != 0) reset_all(w.hist_raw, w.offs);
+    return r;
 }
 
 // the forward of a trainable decoder (all but the fine one, see nsk_train.h) also stores its block outputs for the backward
 static bool saves_h(nsk_ctx* c, int w, bool save_masks) { return save_masks && w != 2 && c->dec[w].trainable; }
 static int ensure_hsave(nsk_ctx* c, int w, int M)
 {
-    Workspace& ws = c->ws;
     const size_t tiles = (size_t)(M + 15) / 16 + 1;
-    if (tiles > ws.hcap[w]) {
-        if (c->capturing) return fail("graph capture: the workspace must grow (run the same step once before nsk_graph_begin)");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        invalidate_graphs(c);
-        hipFree(ws.hsave[w]);
-        HIPCHK(hipMalloc(&ws.hsave[w], tiles * 10 * 64 * sizeof(f4)));
-        ws.hcap[w] = tiles;
-    }
-    return 0;
+    return grow(c, c->ws.hsave[w], tiles * 10 * 64, "the saved block outputs", GROW_NO_CAPTURE | GROW_STALE_GRAPHS);
 }
 
 static const int STAGE_DEC[4][3] = {{0, -1, -1}, {1, -1, -1}, {1, 2, -1}, {1, 2, 3}};
@@ -1497,6 +1485,7 @@ static int check_stage(nsk_ctx* c, int stage)
         if (!c->grid[w].n) return fail("stage %d needs grid level %d (nsk_grid_upload)", stage, w);
         if (!c->dec[w].loaded) return fail("stage %d needs decoder %d (nsk_decoder_upload)", stage, w);
     }
+    if (!c->slab) return fail("the gradient slab is not allocated (its last allocation failed: upload a grid level or a decoder again)");
     return 0;
 }
 
@@ -1508,8 +1497,8 @@ static void fill_args(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* 
     memcpy(A.bound, c->R.bound, sizeof(A.bound));
     A.grid = grid_dev(c, w, false);
     if (w == 2) A.grid_mid = grid_dev(c, 1, false);
-    A.img = reinterpret_cast<const f4*>(c->dec[w].fimg);
-    A.bimg = reinterpret_cast<const f4*>(c->dec[w].bimg);
+    A.img = reinterpret_cast<const f4*>(c->dec[w].fimg.get());
+    A.bimg = reinterpret_cast<const f4*>(c->dec[w].bimg.get());
     A.img_f4 = c->dec[w].fimg_n / 4;
     A.img16 = c->dec[w].fimg16;
     A.bimg16 = c->dec[w].bimg16;
@@ -1800,14 +1789,14 @@ static void samp_args(nsk_ctx* c, SampArgs& A, const RParams& R, int stage, int 
     memset(&A, 0, sizeof(A));
     A.R = R; A.N = N; A.S = S; A.rays_o = ro; A.rays_d = rd; A.gt_depth = gt; A.gtmax_host = gtmax; A.gtmax_dev = gmax_dev; A.keep = mask; A.z_out = z;
     A.kX = KG.X; A.kY = KG.Y; A.kZ = KG.Z; A.pX = PG ? PG->X : 0; A.pY = PG ? PG->Y : 0; A.pZ = PG ? PG->Z : 0; A.ncell2 = (int)((bins / 8 + 1) / 2);
-    A.skey = sorted ? skey : nullptr; A.srank = srank; A.hist = c->ws.hist;
+    A.skey = sorted ? skey : nullptr; A.srank = srank; A.hist = c->ws.hist();
     if (dm.n > 0) { A.mx_gt = dm.gt; A.mx_keep = dm.keep; A.mx_n = dm.n; } else { A.mx_gt = gt; A.mx_keep = mask; A.mx_n = N; }
 }
 // halves: 256-cell chunks per workgroup (1: k_sort_scan, 2: the role inside k_decode_bwd_multi)
 static ScanArgs scan_args(nsk_ctx* c, int stage, int* offs, int halves)
 {
     const size_t bins = c->grid[stage_key_level(stage)].n / 32 * 8;
-    ScanArgs A; A.nkeys = (int)bins; A.ncell2 = (int)((bins / 8 + 1) / 2); A.hist = c->ws.hist; A.offs = offs;
+    ScanArgs A; A.nkeys = (int)bins; A.ncell2 = (int)((bins / 8 + 1) / 2); A.hist = c->ws.hist(); A.offs = offs;
     A.nblocks = (int)((bins + 2048 * (size_t)halves - 1) / (2048 * (size_t)halves));
     return A;
 }
@@ -1885,8 +1874,8 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
     if (is_this_batch(P)) {
         // this batch was sampled during the previous step (nsk_map_prepare): take its outputs
         Workspace& w = c->ws;
-        std::swap(w.z, w.z_alt); std::swap(w.perm, w.perm_alt); std::swap(w.skey, w.skey_alt); std::swap(w.srank, w.srank_alt);
-        std::swap(w.offs, w.offs_alt);                      // (both sets are kept at the same capacities: ensure_alt)
+        w.z.swap(w.z_alt); w.perm.swap(w.perm_alt); w.skey.swap(w.skey_alt); w.srank.swap(w.srank_alt);
+        w.offs.swap(w.offs_alt);                            // (both sets are kept at the same capacities: ensure_alt)
         c->ws_flip ^= 1;
         P.valid = false;
         c->sorted = sorted;
@@ -1972,16 +1961,6 @@ extern "C" int nsk_eval_points(nsk_ctx* c, int stage, int M, const float* pts, f
 }
 
 // ---- scene mesh: lattice evaluation + marching cubes (nsk_mesh.h) ------------------------------------------------
-// a failed allocation reports its size and leaves the context as it was, minus the buffer that was to grow
-static int mesh_alloc(void** p, size_t bytes, const char* what)
-{
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return 0;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail("mesh: cannot allocate %zu bytes for %s (%s)", bytes, what, hipGetErrorString(e));
-}
-
 static int lattice_checks(const char* fn, nsk_ctx* c, const float* o, const float* s, int nx, int ny, int nz, int nmin)
 {
     if (!c || !o || !s) return fail("%s: null argument", fn);
@@ -2006,12 +1985,7 @@ extern "C" int nsk_eval_lattice(nsk_ctx* c, int stage, const float* o, const flo
     long long slab = c->mesh.slab > 0 ? c->mesh.slab : std::max(c->ws.capM, 1 << 21);
     slab = std::min(std::min(slab, total), (1LL << 26) - 1);
     CHK(ensure_ws(c, 1, (int)slab));
-    if ((size_t)slab > c->mesh.lat_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->mesh.lat_pts); c->mesh.lat_pts = nullptr; c->mesh.lat_cap = 0;
-        CHK(mesh_alloc((void**)&c->mesh.lat_pts, (size_t)slab * 12, "the lattice slab's points"));
-        c->mesh.lat_cap = (size_t)slab;
-    }
+    CHK(grow(c, c->mesh.lat_pts, (size_t)slab * 3, "the lattice slab's points", 0));
     McGeom G;
     G.nx = nx; G.ny = ny; G.nz = nz; G.nn = 0; G.level = 0.f;
     for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
@@ -2065,27 +2039,21 @@ extern "C" int nsk_mesh_extract(nsk_ctx* c, const float* vol, const uint8_t* val
     M.nv = M.nt = 0;
     *n_vertices = *n_triangles = 0;
     const int nn = (int)total, nb = (nn + MC_BLOCK - 1) / MC_BLOCK;
-    if (!M.table) {
+    if (!M.ntri) {
         const McTable& T = mc_table();
-        CHK(mesh_alloc((void**)&M.table, sizeof(T.edges), "the case table"));
-        CHK(mesh_alloc((void**)&M.ntri, sizeof(T.ntri), "the case table"));
-        HIPCHK(hipMemcpy(M.table, T.edges, sizeof(T.edges), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.ntri, T.ntri, sizeof(T.ntri), hipMemcpyHostToDevice));
+        const int r = [&]() -> int {
+            CHK(dev_alloc(M.table, sizeof(T.edges), "the case table")); CHK(dev_alloc(M.ntri, sizeof(T.ntri), "the case table"));
+            HIPCHK(hipMemcpy(M.table, T.edges, sizeof(T.edges), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(M.ntri, T.ntri, sizeof(T.ntri), hipMemcpyHostToDevice));
+            return 0;
+        }();
+        if (r != 0) { reset_all(M.table, M.ntri); return r; }
     }
-    if ((size_t)nn > M.node_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(M.cellcase); hipFree(M.emap); M.cellcase = nullptr; M.emap = nullptr; M.node_cap = 0;
-        CHK(mesh_alloc((void**)&M.cellcase, (size_t)nn, "the cell cases"));
-        CHK(mesh_alloc((void**)&M.emap, (size_t)nn * 12, "the edge map"));
-        M.node_cap = (size_t)nn;
-    }
+    int r = grow(c, M.cellcase, (size_t)nn, "the cell cases", 0);
+    if (r == 0) r = grow(c, M.emap, (size_t)nn * 3, "the edge map", 0);
+    if (r != 0) { reset_all(M.cellcase, M.emap); return r; }
     const size_t words = mc_scan_words((size_t)nb + 1);
-    if (2 * words > M.scan_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(M.scan); M.scan = nullptr; M.scan_cap = 0;
-        CHK(mesh_alloc((void**)&M.scan, 2 * words * 4, "the scan scratch"));
-        M.scan_cap = 2 * words;
-    }
+    CHK(grow(c, M.scan, 2 * words, "the scan scratch", 0));
     unsigned* sv = M.scan; unsigned* stri = M.scan + words;
     McGeom G;
     G.nx = nx; G.ny = ny; G.nz = nz; G.nn = nn; G.level = level;
@@ -2101,16 +2069,8 @@ extern "C" int nsk_mesh_extract(nsk_ctx* c, const float* vol, const uint8_t* val
     HIPCHK(hipMemcpyAsync(&tot[1], stri + nb, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (tot[0] > 0x7fffffffu / 3 || tot[1] > 0x7fffffffu / 3) return fail("nsk_mesh_extract: %u vertices, %u triangles do not fit 32-bit indices", tot[0], tot[1]);
-    if (tot[0] > M.vcap) {
-        hipFree(M.verts); M.verts = nullptr; M.vcap = 0;
-        CHK(mesh_alloc((void**)&M.verts, (size_t)tot[0] * 12, "the vertices"));
-        M.vcap = tot[0];
-    }
-    if (tot[1] > M.tcap) {
-        hipFree(M.tris); M.tris = nullptr; M.tcap = 0;
-        CHK(mesh_alloc((void**)&M.tris, (size_t)tot[1] * 12, "the triangles"));
-        M.tcap = tot[1];
-    }
+    CHK(grow(c, M.verts, (size_t)tot[0] * 3, "the vertices", 0));
+    CHK(grow(c, M.tris, (size_t)tot[1] * 3, "the triangles", 0));
     if (tot[0]) {
         { ProfScope ps(c, "mc_vertices"); k_mc_edges<true><<<nb, MC_BLOCK, 0, c->stream>>>(G, vol, M.cellcase, nullptr, sv, M.emap, M.verts); }
         HIPCHK(hipGetLastError());
@@ -2261,8 +2221,6 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     if (train_role >= 0) {
         int w = MA.which[train_role];
         int nb = MA.wg_end[train_role] - (train_role == 0 ? 0 : MA.wg_end[train_role - 1]);
-        int np = c->dec[w].n, n4 = (np + 3) & ~3;
-        (void)np; (void)n4;
         c->pend_w = w; c->pend_nb = nb;          // summed by k_adam_multi, or by flush_pending when someone reads the slab first
     }
     return 0;
@@ -2291,19 +2249,14 @@ extern "C" int nsk_render_backward(nsk_ctx* c, int stage, int N, const float* ro
 static int ensure_alt(nsk_ctx* c, bool need_offs)
 {
     Workspace& w = c->ws;
-    if (w.alt_capM < w.capM) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(w.z_alt); hipFree(w.perm_alt); hipFree(w.skey_alt); hipFree(w.srank_alt);
-        const size_t m = (size_t)w.capM + 64;
-        HIPCHK(hipMalloc(&w.z_alt, m * 4)); HIPCHK(hipMalloc(&w.perm_alt, m * 4)); HIPCHK(hipMalloc(&w.skey_alt, m * 4)); HIPCHK(hipMalloc(&w.srank_alt, m * 4));
-        w.alt_capM = w.capM;
-    }
-    if (need_offs && w.alt_bins < w.hist_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(w.offs_alt);
-        HIPCHK(hipMalloc(&w.offs_alt, w.hist_cap * 4));
-        w.alt_bins = w.hist_cap;
-    }
+    const size_t m = (size_t)w.capM + 64;
+    const int r = [&]() -> int {
+        CHK(grow(c, w.z_alt, m, "the second sampling set", 0)); CHK(grow(c, w.perm_alt, m, "the second sampling set", 0));
+        CHK(grow(c, w.skey_alt, m, "the second sampling set", 0)); CHK(grow(c, w.srank_alt, m, "the second sampling set", 0));
+        return 0;
+    }();
+    if (r != 0) { reset_all(w.z_alt, w.perm_alt, w.skey_alt, w.srank_alt); return r; }
+    if (need_offs) CHK(grow(c, w.offs_alt, w.offs.cap(), "the second sampling set's offsets", 0));
     return 0;
 }
 
@@ -2546,17 +2499,12 @@ extern "C" int nsk_frustum_mask(nsk_ctx* c, int level, const float* d_depth, int
     for (auto& R : c->graphs) live = live || !R.stale;
     if (live) { HIPCHK(hipStreamSynchronize(c->stream)); invalidate_graphs(c); }      // new mask contents: see nsk_set_mask
     if (c->slab) HIPCHK(hipMemsetAsync(c->slab + G.g_off, 0, G.n * 4, c->stream));       // see nsk_set_mask
-    if (!G.mask) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMalloc(&G.mask, nvox)); }
+    CHK(grow(c, G.mask, nvox, "the voxel mask", 0));
     if (level == NSK_COARSE) {                                   // src/Mapper.cpp:54-59
         HIPCHK(hipMemsetAsync(G.mask, 1, nvox, c->stream));
     } else {
-        if (nvox > c->fr_cap) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            hipFree(c->fr_tmp);
-            HIPCHK(hipMalloc(&c->fr_tmp, nvox * 9 + 16));
-            c->fr_cap = nvox;
-        }
-        float* dep = reinterpret_cast<float*>(c->fr_tmp); float* zz = dep + nvox;
+        CHK(grow(c, c->fr_tmp, nvox * 9 + 16, "the frustum scratch", 0));
+        float* dep = reinterpret_cast<float*>(c->fr_tmp.get()); float* zz = dep + nvox;
         uint8_t* inimg = reinterpret_cast<uint8_t*>(zz + nvox);
         unsigned int* dmax = reinterpret_cast<unsigned int*>(c->scal + 4);
         FrustumArgs A;
@@ -2586,14 +2534,8 @@ extern "C" int nsk_keyframe_overlap(nsk_ctx* c, int N, const float* d_ro, const 
     HIPCHK(hipSetDevice(c->device));
     std::vector<float> w2c((size_t)K * 16);
     for (int k = 0; k < K; ++k) invert4(h_c2w + 16 * k, w2c.data() + 16 * k);
-    const size_t need = (size_t)K * 17 * 4;
-    if (need > c->fr_cap * 9 + 16 || !c->fr_tmp) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->fr_tmp);
-        c->fr_cap = (need + 8) / 9;
-        HIPCHK(hipMalloc(&c->fr_tmp, c->fr_cap * 9 + 16));
-    }
-    float* d_w2c = reinterpret_cast<float*>(c->fr_tmp); float* d_pct = d_w2c + (size_t)K * 16;
+    CHK(grow(c, c->fr_tmp, (size_t)K * 17 * 4, "the keyframe scratch", 0));
+    float* d_w2c = reinterpret_cast<float*>(c->fr_tmp.get()); float* d_pct = d_w2c + (size_t)K * 16;
     HIPCHK(hipMemcpyAsync(d_w2c, w2c.data(), (size_t)K * 64, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));         // w2c is a stack-lifetime host buffer
     OverlapArgs A; A.N = N; A.ns = n_samples; A.H = H; A.W = W; A.K = K; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy;
@@ -2810,13 +2752,13 @@ extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b
             adam_consts(lr[NSK_GROUP_DECODERS], b1, b2, step, S.step_size, S.bc2s);
             S.p = D.p; S.g = c->slab + D.g_off; S.m = D.m; S.v = D.s; S.idx = nullptr; S.nidx = 0; S.n = n4;
             S.inv_f = D.finv; S.inv_b = D.binv; S.fimg = D.fimg; S.bimg = D.bimg;
-            if (D.bimg16) { S.invh = D.invh; S.imgh = reinterpret_cast<unsigned short*>(D.bimg16); S.imgh_tail = D.bimg16 + MlpBwdImgH::P_WO; S.btail_off = MlpBwdImg::P_WO; }
+            if (D.bimg16) { S.invh = D.invh; S.imgh = reinterpret_cast<unsigned short*>(D.bimg16.get()); S.imgh_tail = D.bimg16 + MlpBwdImgH::P_WO; S.btail_off = MlpBwdImg::P_WO; }
             else D.bimg16_dirty = true;
             if (c->pend_w == w) {
                 S.slabs = c->ws.dec_slabs; S.nslabs = c->pend_nb; S.slab_stride = n4; c->pend_w = -1;
                 blocks += (n4 / 4 + 7) / 8 - (n4 / 4 + 255) / 256;         // 8 float4 per block (see k_adam_multi)
             }
-            if (D.fimg16) { S.inv16 = D.inv16; S.img16 = reinterpret_cast<unsigned short*>(D.fimg16); S.img16_tail = D.fimg16 + D.tail16_off; S.tail_off = D.tail_off; S.np16 = D.np16; }
+            if (D.fimg16) { S.inv16 = D.inv16; S.img16 = reinterpret_cast<unsigned short*>(D.fimg16.get()); S.img16_tail = D.fimg16 + D.tail16_off; S.tail_off = D.tail_off; S.np16 = D.np16; }
             blocks += (n4 / 4 + 255) / 256; S.blk_end = blocks;
         }
         c->touched[NSK_GROUP_DECODERS] = false;
@@ -2980,7 +2922,7 @@ static int ensure_midx(nsk_ctx* c, int l)
     if (!G.mask || !G.midx_dirty) return 0;
     if (c->capturing) return fail("graph capture: a mask changed since the last eager step (run the step once after installing masks, then capture)");
     const int nvox = (int)(G.n / 32);
-    if (!G.midx) HIPCHK(hipMalloc(&G.midx, (size_t)nvox * 4));
+    if (!G.midx) CHK(dev_alloc(G.midx, (size_t)nvox, "the marked-voxel list"));
     int* d_count = reinterpret_cast<int*>(c->scal + 8);
     k_mask_index<<<1, 1024, 0, c->stream>>>(nvox, G.mask, G.midx, d_count);
     HIPCHK(hipMemcpyAsync(&G.nmask, d_count, 4, hipMemcpyDeviceToHost, c->stream));
@@ -3062,13 +3004,8 @@ extern "C" int nsk_grad_pack(nsk_ctx* c, float** p, size_t* n)
         return 0;
     }
     c->x_identity = false;
-    if (total > c->xbuf_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        invalidate_graphs(c);
-        hipFree(c->xbuf);
-        HIPCHK(hipMalloc(&c->xbuf, total * 4));
-        c->xbuf_cap = total;
-    }
+    c->xbuf_n = 0;
+    CHK(grow(c, c->xbuf, total, "the exchange buffer", GROW_STALE_GRAPHS));
     c->xbuf_n = total;
     { ProfScope ps(c, "grad_pack"); CHK(pack_move(c, true)); }
     *p = c->xbuf; *n = total;

@@ -235,6 +235,16 @@ def test_readers_survive_truncated_and_corrupted_files(io_dump, tmp_path):
     assert r.returncode == 0 and "io_fuzz ok" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
+def test_device_buffer_owner_survives_every_failed_allocation():
+    """csrc/nsk_buf.h, the owner of every device buffer of the context, over a counting allocator under AddressSanitizer + UBSan (make
+    buf_test_asan): for every k, the k-th allocation failing leaves that buffer null with capacity 0 and a retry allocates; no pointer is freed
+    twice; after destruction allocations equal frees; swap and move hand ownership on without a free; a group reset frees every member"""
+    subprocess.check_call(["make", "-s", "-C", HOST, "buf_test_asan"])
+    r = subprocess.run([os.path.join(HOST, "buf_test_asan")], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1"))
+    assert r.returncode == 0 and "buf_test ok" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
 def test_png_reader(io_dump):
     out, fx, _, _ = io_dump[:4]
     assert np.array_equal(out["rgb8"], fx["rgb8"][:, :, ::-1].astype(np.float32))            # OpenCV order: B,G,R
