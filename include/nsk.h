@@ -65,10 +65,21 @@ void* nsk_stream(nsk_ctx* ctx);                     /* the hipStream_t in use */
 /* How the MLP decoders' FORWARD matrix products are evaluated (results agree within the 1e-4 contract; measured against the fp64
  * oracle all three are equally close, tests/test_gpu_parity.py::test_forward_bf16_split_mode_matches_oracle):
  *   2 = fp32 operands split into two fp16 pieces (x = h + l/2048: 22 significant bits), three v_mfma_f32_16x16x32_f16 per K=32
- *       block, fp32 accumulation (DEFAULT).  Operand range: |x| < 65504 (fp16) for activations, grid features and weights -- far
- *       above anything these decoders produce; larger values come out as inf / NaN in the rendering, never silently wrong;
+ *       block, fp32 accumulation (DEFAULT);
  *   1 = three bf16 pieces (24 significant bits, the full fp32 exponent range), six v_mfma_f32_16x16x32_bf16 per block;
  *   0 = v_mfma_f32_16x16x4_f32, plain fp32.
+ * The mode governs the stages that run several decoders in one launch (fine, colour) of nsk_render_forward and of the steps.  Launches of
+ * one decoder -- nsk_eval_points, nsk_eval_lattice, the coarse and middle stages -- and the coarse decoder everywhere run on the fp32 MFMA
+ * in every mode.
+ * Operand range, as tested (tests/test_gpu_operand_range.py: hidden values, grid features and weights moved by exact powers of two):
+ *   mode 2: the 1e-4 contract holds for activations, grid features and weights with peak magnitudes from 2^-14 up to 2^15 (fp16's largest
+ *       number is 65504); below 2^-14 the pieces lose bits gradually (fp16 subnormals are kept, not flushed).  An operand beyond 65504 has
+ *       the pieces inf and -inf and its products are NaN: every ray that has such a sample is rendered NON-FINITE (NaN or +-inf in depth,
+ *       colour, variance or weights), never as a finite wrong number;
+ *   modes 1 and 0: no upper limit short of fp32's own.
+ * Non-finite values already in the map (a diverged voxel, a NaN weight) propagate as in the reference: the hidden ReLUs and the
+ * compositing's relu(sigma) pass a NaN of either sign on (torch::relu), -inf becomes 0; the outputs that ATen makes non-finite are
+ * non-finite here, every other output is untouched, in all three modes.
  * Independent of the mode: the backward chains of the frozen decoders (without ray gradients) and of a trainable middle / colour
  * decoder run on two fp16 pieces of a per-sample power-of-two multiple of the upstream gradient (exact scaling: no range
  * restriction); frozen chains that carry ray gradients, the coarse decoder and a trainable fine decoder on the fp32 MFMA; the

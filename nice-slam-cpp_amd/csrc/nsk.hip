@@ -561,7 +561,7 @@ __global__ __launch_bounds__(256) void k_raw2outputs(int N, int S, int occupancy
     const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
     const float znext = __shfl_down(z, 1);
     const float dist = ((lane + 1 < S) ? (znext - z) : 1e10f) * nrm;
-    float alpha = occupancy ? 1.f / (1.f + expf(-10.f * r4[3])) : 1.f - expf(-fmaxf(r4[3], 0.f) * dist);
+    float alpha = occupancy ? 1.f / (1.f + expf(-10.f * r4[3])) : 1.f - expf(-relu_keep_nan(r4[3]) * dist);
     if (!act) alpha = 0.f;
     float incl = act ? (1.f - alpha + 1e-10f) : 1.f;
 #pragma unroll

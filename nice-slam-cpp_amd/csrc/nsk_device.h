@@ -93,6 +93,10 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 __device__ __forceinline__ bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == ~0ull; }   // every lane active
+// relu(sigma) of the compositing (include/torchlib/utils.h:160 torch::relu): a NaN passes through, as in ATen -- fmaxf(x, 0) would return 0 for
+// it and render a sample whose decoder output is NaN (a diverged voxel, an operand beyond the fp16 pieces' range) as empty space
+__device__ __forceinline__ float relu_keep_nan(float x) { return x <= 0.f ? 0.f : x; }
+
 __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
@@ -642,10 +646,12 @@ __device__ __forceinline__ void load_bias(const float* __restrict__ b, int g, f4
     acc[1] = *reinterpret_cast<const f4*>(b + 16 + 4 * g);
 }
 
-// ReLU in place, returns the 8 "input was > 0" bits (bit r*4+i).  All in integer arithmetic on the bit patterns, three vector
-// instructions per element: max_i32(bits, 0) is the ReLU (negative floats, -0 and negative NaNs are negative integers), and the result
-// is a non-negative integer that is zero exactly when the ReLU's derivative is, so min_u32(result, 1) is the bit.  (The float form,
-// fmaxf + a compare, costs a canonicalising v_max on MFMA outputs, a v_cmp, a v_cndmask and wait states between them.)
+// ReLU in place, returns the 8 "input was > 0" bits (bit r*4+i).  The ReLU is the select `x <= 0 ? 0 : x` (a compare and a v_cndmask): a NaN
+// fails the comparison and passes through whatever its sign bit, as torch::relu propagates it; -0, negative numbers and -inf give +0.  (Neither
+// maximum does that: max_i32 on the bit patterns, the earlier form, takes a NaN with the sign bit set -- what inf - inf gives in
+// the matrix and vector pipes here -- for a negative integer and returns 0, and fmaxf returns the other operand for any NaN; an overflow in the
+// fp16 pieces or a NaN in the map then came out as an ordinary finite number, tests/test_gpu_operand_range.py.)  The result's bit pattern is
+// zero exactly when the ReLU's derivative is, for every input that is not a NaN, so min_u32(bits, 1) is the bit; a NaN's bit is 1.
 __device__ __forceinline__ uint32_t relu_mask(f4 (&a)[2])
 {
     uint32_t m = 0;
@@ -653,10 +659,11 @@ __device__ __forceinline__ uint32_t relu_mask(f4 (&a)[2])
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int y = max(__float_as_int(a[r][i]), 0);
-            a[r][i] = __int_as_float(y);
+            const float v = a[r][i];
+            a[r][i] = v <= 0.f ? 0.f : v;
+            const int y = __float_as_int(a[r][i]);
             // m |= min(y, 1) << bit, as exactly two instructions (left to itself the compiler turns the min into a compare and a select,
-            // 3.5 instructions per element; their input is the v_max_i32 above, a vector-ALU result: no matrix-pipe hazard inside the asm)
+            // 3.5 instructions per element; their input is the v_cndmask above, a vector-ALU result: no matrix-pipe hazard inside the asm)
             unsigned t;
             asm("v_min_u32 %0, %1, 1" : "=v"(t) : "v"(y));
             asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(m) : "v"(t), "n"(r * 4 + i), "v"(m));
@@ -1158,7 +1165,7 @@ __device__ __forceinline__ void composite_body(const CompArgs& A, int bid, int n
     const float dist = dzv * nrm;
     float alpha, ex = 0.f;
     if (A.R.occupancy) alpha = 1.f / (1.f + expf(-10.f * sg));
-    else { ex = expf(-fmaxf(sg, 0.f) * dist); alpha = 1.f - ex; }
+    else { ex = expf(-relu_keep_nan(sg) * dist); alpha = 1.f - ex; }
     if (!act) alpha = 0.f;
     // T = exclusive prefix product of (1 - alpha + 1e-10)
     float fct = act ? (1.f - alpha + 1e-10f) : 1.f;
@@ -1288,8 +1295,8 @@ __device__ __forceinline__ void composite_body(const CompArgs& A, int bid, int n
     float g_sigma, g_n = 0.f;
     if (A.R.occupancy) g_sigma = g_alpha * 10.f * alpha * (1.f - alpha);
     else {
-        float rs = fmaxf(sg, 0.f);
-        g_sigma = sg > 0.f ? g_alpha * dist * ex : 0.f;
+        float rs = relu_keep_nan(sg);
+        g_sigma = sg <= 0.f ? 0.f : g_alpha * dist * ex;
         g_n = g_alpha * rs * ex * dzv;
     }
     if (!inb) g_sigma = 0.f;

@@ -210,6 +210,24 @@ class Oracle:
         assert rc == 0
         return a
 
+    def point_rays(self, pts):
+        """M points as M one-sample rays for render_forward / preacts with opts(bound, n_samples=1, n_surface=0): origin = the point, direction
+        zero, ground-truth depth 1, so the only sample is z = 0.01 and p = o + 0 z is the point bit for bit (ray_z_vals: near = 0.01 gt; the
+        box exit is +inf and clamps to 1.2 max(gt)).  Points exactly on a face of the bound are not supported (0 / 0 in the box exit)."""
+        p = self.arr(pts, (-1, 3))
+        return p, np.zeros_like(p), np.ones(p.shape[0], self.dt)
+
+    def eval_points(self, bound, grids, decoders, stage, pts):
+        """Renderer::eval_points: raw [M, 4] = (rgb, occupancy; 100 outside the bound) at M points, through nso_render_forward (see point_rays)"""
+        ro, rd, gd = self.point_rays(pts)
+        out = self.render_forward(self.opts(bound, n_samples=1, n_surface=0), grids, decoders, stage, ro, rd, gd, want_aux=True)
+        return out["raw"].reshape(-1, 4)
+
+    def point_preacts(self, bound, grids, decoders, stage, which, pts):
+        """[M, 5, 32]: the hidden ReLU inputs of decoder `which` at M points (preacts over point_rays)"""
+        ro, rd, gd = self.point_rays(pts)
+        return self.preacts(self.opts(bound, n_samples=1, n_surface=0), grids, decoders, stage, which, ro, rd, gd)
+
     def preact_bounds(self, opts, grids, decoders, stage, which, rays_o, rays_d, gt_depth=None, gt_depth_max=-1.0, sin_err=3.2e-7, want=None, geometry_err=True,
                       want_raw0=False, quadrature=False):
         """[N*S, 5, 32]: first-order bound on |ReLU input of an fp32 evaluation - exact| at the samples with want[N*S] set (None: all; zeros
