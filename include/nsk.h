@@ -421,6 +421,40 @@ int nsk_mesh_download(nsk_ctx* ctx, float* h_vertices, int32_t* h_triangles);
  * inside corners on a face's diagonal are always cut off one by one), which makes neighbouring cells agree on every shared face. */
 int nsk_mesh_table(int case_index, int8_t* h_edges, int capacity);
 
+/* The nodes of a lattice (origin, step, nx, ny, nz and the node points as in nsk_eval_lattice; at most 2^28 nodes) that at least one of K
+ * keyframes saw: d_valid[(k * ny + j) * nx + i] = 1, else 0 -- the d_valid of nsk_mesh_extract.  accumulate != 0 ORs the old byte in, so a
+ * long keyframe list can be streamed through in batches of a few depth images; K = 0 with accumulate = 0 clears the mask.  This is a union
+ * of depth-truncated view frusta, per node (not the convex hull of a TSDF fusion that upstream's clean_mesh takes: tighter, no hull library).
+ * d_depth [K][H][W] floats on the device; h_w2c [K][16] row-major world-to-camera on the host (the caller inverts its c2w, so that rounding
+ * is the caller's); the camera looks along -z, as in nsk_frustum_mask and nsk_rays_from_camera.  Keyframe k sees the node p when, every
+ * operation an fp32 operation of its own (no FMA):
+ *   c_a = ((w[4a] p0 + w[4a+1] p1) + w[4a+2] p2) + w[4a+3], a = 0..2;   d = -c_2 > 0;
+ *   u = cx + (fx c_0) / d,  v = cy - (fy c_1) / d;   i = floor(u + 0.5), j = floor(v + 0.5)   (the nearest pixel);
+ *   edge <= i < W - edge and edge <= j < H - edge, decided on the floats (a NaN fails; an edge that leaves no pixel is valid: nothing is seen);
+ *   D = d_depth[k][j][i] is finite and > 0 (a pixel without a measurement sees nothing);   d <= D + trunc.
+ * One thread per node loops over the keyframes (matrices and intrinsics ride in the kernel arguments, 32 keyframes per launch, longer
+ * lists in several launches); a wave leaves the loop once all its nodes are seen.  n_seen (may be NULL) receives the number of set bytes
+ * after the call: asking for it is the call's only synchronisation.  Not while a graph is being captured. */
+int nsk_lattice_seen(nsk_ctx* ctx, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, int K, const float* d_depth,
+                     int H, int W, float fx, float fy, float cx, float cy, const float* h_w2c, int edge, float trunc, int accumulate,
+                     uint8_t* d_valid, long long* n_seen);
+
+/* Connected components of the mesh of the last nsk_mesh_extract, filtered in place (an error when there is none; an empty mesh is none:
+ * n_components = 0).
+ *   - vertices joined by a triangle are connected (the mesh is welded: shared vertex index).  Union-find on the device: roots are hooked
+ *     below smaller indices by compare-and-swap, paths are halved, a flatten pass ends it, so a component's label is its smallest vertex
+ *     index whatever order the atomics ran in;
+ *   - triangle area 0.5 |(v1 - v0) x (v2 - v0)| in fp32, summed per component in fp64 (atomic adds: order-dependent in the last bits only);
+ *   - largest_only = 0: components with area > min_area stay (upstream's remove_small_geometry_threshold, in the units the caller passes);
+ *     largest_only != 0: the component with the largest area stays, ties to the smaller label (get_largest_components); min_area is not read;
+ *   - compaction by the multi-launch scans of nsk_mesh_extract: kept vertices and triangles keep their relative order, triangles are
+ *     re-indexed, vertices without a triangle are dropped; two runs give the same bytes.
+ * Afterwards nsk_mesh_buffers / nsk_mesh_download describe the filtered mesh (NULL and 0 when nothing stays).  n_components counts the
+ * components before the filter, n_kept those that stay.  Synchronises once.  Device memory: 14 B per vertex of scratch, 4 B per vertex and
+ * per triangle of scan scratch, and a second vertex and triangle buffer (12 B each) the result is compacted into; an allocation that
+ * fails names its byte count and leaves context and mesh as they were. */
+int nsk_mesh_filter(nsk_ctx* ctx, float min_area, int largest_only, int* n_vertices, int* n_triangles, int* n_components, int* n_kept);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

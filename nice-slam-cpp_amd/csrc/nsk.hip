@@ -806,6 +806,12 @@ struct nsk_ctx {
         Buf<int8_t> table; Buf<uint8_t> ntri;                // one group
         Buf<float> verts; Buf<int> tris;                     // [nv][3], [nt][3]
         int nv = 0, nt = 0;
+        bool extracted = false;                              // a mesh (possibly empty) is there for nsk_mesh_filter
+        Buf<unsigned long long> seen_count;                  // nsk_lattice_seen's optional count
+        // nsk_mesh_filter: per-vertex scratch (one group), the statistics, the compacted mesh (swapped with verts / tris)
+        Buf<int> cc_label; Buf<double> cc_area; Buf<uint8_t> cc_used, cc_keep;
+        Buf<CcStats> cc_stats;
+        Buf<float> verts2; Buf<int> tris2;
     } mesh;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
@@ -2036,7 +2042,7 @@ extern "C" int nsk_mesh_extract(nsk_ctx* c, const float* vol, const uint8_t* val
     if (total > MC_MAX_NODES) return fail("nsk_mesh_extract: %lld nodes, at most %lld per call", total, (long long)MC_MAX_NODES);
     HIPCHK(hipSetDevice(c->device));
     nsk_ctx::Mesh& M = c->mesh;
-    M.nv = M.nt = 0;
+    M.nv = M.nt = 0; M.extracted = false;
     *n_vertices = *n_triangles = 0;
     const int nn = (int)total, nb = (nn + MC_BLOCK - 1) / MC_BLOCK;
     if (!M.ntri) {
@@ -2080,8 +2086,115 @@ extern "C" int nsk_mesh_extract(nsk_ctx* c, const float* vol, const uint8_t* val
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    M.nv = (int)tot[0]; M.nt = (int)tot[1];
+    M.nv = (int)tot[0]; M.nt = (int)tot[1]; M.extracted = true;
     *n_vertices = M.nv; *n_triangles = M.nt;
+    return 0;
+}
+
+// the nodes of a lattice that at least one of K keyframes sees (k_lattice_seen); keyframe lists longer than a launch holds go in several
+extern "C" int nsk_lattice_seen(nsk_ctx* c, const float* o, const float* s, int nx, int ny, int nz, int K, const float* depth, int H, int W,
+                                float fx, float fy, float cx, float cy, const float* w2c, int edge, float trunc, int accumulate, uint8_t* valid,
+                                long long* n_seen)
+{
+    CHK(lattice_checks("nsk_lattice_seen", c, o, s, nx, ny, nz, 1));
+    if (!valid) return fail("nsk_lattice_seen: d_valid is NULL");
+    if (K < 0) return fail("nsk_lattice_seen: K = %d", K);
+    if (K > 0 && (!depth || !w2c)) return fail("nsk_lattice_seen: d_depth / h_w2c is NULL with K = %d", K);
+    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail("nsk_lattice_seen: image %d x %d, need 1 .. 2^24 pixels per side", H, W);
+    if (edge < 0) return fail("nsk_lattice_seen: edge = %d, must be >= 0", edge);
+    if (std::isnan(trunc)) return fail("nsk_lattice_seen: trunc is NaN");
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy)) return fail("nsk_lattice_seen: intrinsics are not finite");
+    const long long total = (long long)nx * ny * nz;
+    if (total > MC_MAX_NODES) return fail("nsk_lattice_seen: %lld nodes, at most %lld per call", total, (long long)MC_MAX_NODES);
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Mesh& M = c->mesh;
+    if (n_seen) {
+        CHK(grow(c, M.seen_count, 1, "the seen count", 0));
+        HIPCHK(hipMemsetAsync(M.seen_count, 0, 8, c->stream));
+    }
+    McGeom G;
+    G.nx = nx; G.ny = ny; G.nz = nz; G.nn = (int)total; G.level = 0.f;
+    for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
+    SeenArgs A;
+    memset(&A, 0, sizeof(A));
+    A.H = H; A.W = W; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.trunc = trunc;
+    A.ilo = A.jlo = (float)edge;                            // (edge beyond 2^24 rounds, and is beyond W and H either way)
+    A.ihi = (float)((long long)W - edge); A.jhi = (float)((long long)H - edge);
+    const int nb = (G.nn + MC_BLOCK - 1) / MC_BLOCK;
+    int k0 = 0;
+    do {                                                    // (K = 0 still launches once: it clears, or keeps, and counts)
+        A.K = std::min(K - k0, SEEN_MAX_K);
+        A.accumulate = (accumulate || k0 > 0) ? 1 : 0;
+        for (int k = 0; k < A.K; ++k) memcpy(A.w[k], w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
+        const bool last = k0 + A.K >= K;
+        { ProfScope ps(c, "lattice_seen");
+          k_lattice_seen<<<nb, MC_BLOCK, 0, c->stream>>>(G, A, depth ? depth + (size_t)k0 * H * W : nullptr, valid, last && n_seen ? M.seen_count.get() : nullptr); }
+        HIPCHK(hipGetLastError());
+        k0 += A.K;
+    } while (k0 < K);
+    if (n_seen) {
+        unsigned long long cnt = 0;
+        HIPCHK(hipMemcpyAsync(&cnt, M.seen_count, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *n_seen = (long long)cnt;
+    }
+    return 0;
+}
+
+// connected components of the last extracted mesh, the keep rule, compaction by the multi-launch scans (nsk_mesh.h)
+extern "C" int nsk_mesh_filter(nsk_ctx* c, float min_area, int largest_only, int* n_vertices, int* n_triangles, int* n_components, int* n_kept)
+{
+    if (!c) return fail("null ctx");
+    if (!n_vertices || !n_triangles || !n_components || !n_kept) return fail("nsk_mesh_filter: n_vertices / n_triangles / n_components / n_kept is NULL");
+    if (std::isnan(min_area)) return fail("nsk_mesh_filter: min_area is NaN");
+    if (c->capturing) return fail("nsk_mesh_filter: not while a graph is being captured");
+    nsk_ctx::Mesh& M = c->mesh;
+    if (!M.extracted) return fail("nsk_mesh_filter: no mesh (call nsk_mesh_extract first)");
+    HIPCHK(hipSetDevice(c->device));
+    *n_vertices = M.nv; *n_triangles = M.nt; *n_components = *n_kept = 0;
+    if (M.nv == 0 || M.nt == 0) { M.nv = M.nt = 0; *n_vertices = *n_triangles = 0; return 0; }
+    const int nv = M.nv, nt = M.nt, nbv = (nv + MC_BLOCK - 1) / MC_BLOCK, nbt = (nt + MC_BLOCK - 1) / MC_BLOCK, nbm = std::max(nbv, nbt);
+    int r = grow(c, M.cc_label, (size_t)nv, "the component labels", 0);
+    if (r == 0) r = grow(c, M.cc_area, (size_t)nv, "the component areas", 0);
+    if (r == 0) r = grow(c, M.cc_used, (size_t)nv, "the vertex flags", 0);
+    if (r == 0) r = grow(c, M.cc_keep, (size_t)nv, "the keep flags", 0);
+    if (r != 0) { reset_all(M.cc_label, M.cc_area, M.cc_used, M.cc_keep); return r; }
+    CHK(grow(c, M.cc_stats, 1, "the component statistics", 0));
+    const size_t wv = mc_scan_words((size_t)nv + 1), wt = mc_scan_words((size_t)nt + 1);
+    CHK(grow(c, M.scan, wv + wt, "the scan scratch", 0));
+    CHK(grow(c, M.verts2, (size_t)nv * 3, "the filtered vertices", 0));
+    CHK(grow(c, M.tris2, (size_t)nt * 3, "the filtered triangles", 0));
+    unsigned* voff = M.scan; unsigned* toff = M.scan + wv;
+    const CcStats init = {0ull, 0x7fffffff, 0u, 0u};
+    HIPCHK(hipMemcpyAsync(M.cc_stats, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(M.scan, 0, (wv + wt) * 4, c->stream));         // (the slot behind the last flag turns into the total)
+    { ProfScope ps(c, "cc_label");
+      k_cc_init<<<nbv, MC_BLOCK, 0, c->stream>>>(nv, M.cc_label, M.cc_area, M.cc_used);
+      k_cc_hook<<<nbt, MC_BLOCK, 0, c->stream>>>(nt, M.tris, M.cc_label, M.cc_used);
+      k_cc_flatten<<<nbv, MC_BLOCK, 0, c->stream>>>(nv, M.cc_label); }
+    HIPCHK(hipGetLastError());
+    { ProfScope ps(c, "cc_area"); k_cc_area<<<(nbt + CC_AREA_ITERS - 1) / CC_AREA_ITERS, MC_BLOCK, 0, c->stream>>>(nt, M.tris, M.verts, M.cc_label, M.cc_area); }
+    HIPCHK(hipGetLastError());
+    { ProfScope ps(c, "cc_keep");
+      k_cc_roots<<<nbv, MC_BLOCK, 0, c->stream>>>(nv, M.cc_label, M.cc_used, M.cc_area, (double)min_area, largest_only, M.cc_keep, M.cc_stats);
+      if (largest_only) {
+          k_cc_pick<<<nbv, MC_BLOCK, 0, c->stream>>>(nv, M.cc_label, M.cc_used, M.cc_area, M.cc_stats);
+          k_cc_pick_done<<<1, 1, 0, c->stream>>>(M.cc_keep, M.cc_stats);
+      }
+      k_cc_flags<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, M.tris, M.cc_label, M.cc_used, M.cc_keep, voff, toff); }
+    HIPCHK(hipGetLastError());
+    { ProfScope ps(c, "cc_scan"); CHK(mc_scan(c, voff, nv + 1)); CHK(mc_scan(c, toff, nt + 1)); }
+    { ProfScope ps(c, "cc_compact"); k_cc_compact<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, M.verts, M.tris, voff, toff, M.verts2, M.tris2); }
+    HIPCHK(hipGetLastError());
+    CcStats st;
+    unsigned tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&st, M.cc_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&tot[0], voff + nv, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&tot[1], toff + nt, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    M.verts.swap(M.verts2); M.tris.swap(M.tris2);
+    M.nv = (int)tot[0]; M.nt = (int)tot[1];
+    *n_vertices = M.nv; *n_triangles = M.nt; *n_components = (int)st.n_components; *n_kept = (int)st.n_kept;
     return 0;
 }
 

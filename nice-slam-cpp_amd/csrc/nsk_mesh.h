@@ -289,3 +289,210 @@ __global__ __launch_bounds__(256) void k_mc_scan_add(unsigned* __restrict__ d, i
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q < n) d[q] += sums[blockIdx.x];
 }
+
+// ---- seen mask of a lattice (nsk_lattice_seen) -------------------------------------------------------------------------
+// One thread per node, x fastest.  A node is seen by keyframe k when it lies in front of the camera (which looks along -z), projects onto
+// a pixel at least `edge` pixels inside the image, that pixel carries a finite positive depth D, and the node is no farther than
+// D + trunc.  Every operation is an fp32 operation of its own (tests/mesh_cull_checks.py seen_f32 restates them one by one).
+#define SEEN_MAX_K 32               // keyframes per launch: 12 floats each in the kernel arguments
+struct SeenArgs {
+    float w[SEEN_MAX_K][12];        // rows 0..2 of the row-major world-to-camera matrices
+    int K, H, W;
+    float fx, fy, cx, cy;
+    float ilo, ihi, jlo, jhi;       // edge <= i < W - edge, edge <= j < H - edge, as floats (exact: H, W <= 2^24)
+    float trunc;
+    int accumulate;
+};
+
+__global__ __launch_bounds__(256) void k_lattice_seen(McGeom G, SeenArgs A, const float* __restrict__ depth, uint8_t* __restrict__ valid,
+                                                      unsigned long long* __restrict__ count)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const bool live = n < G.nn;
+    bool seen = false;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        const int i = n % G.nx, r = n / G.nx, j = r % G.ny, k = r / G.ny;
+        p[0] = mc_coord(G.o[0], i, G.s[0]); p[1] = mc_coord(G.o[1], j, G.s[1]); p[2] = mc_coord(G.o[2], k, G.s[2]);
+        seen = A.accumulate && valid[n] != 0;
+    }
+    const size_t img = (size_t)A.H * A.W;
+    for (int kf = 0; kf < A.K; ++kf) {
+        if (__all(seen || !live)) break;                    // the whole wave is done
+        if (seen || !live) continue;
+        const float* w = A.w[kf];
+        float c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            c[a] = __fadd_rn(__fadd_rn(__fadd_rn(mc_mul(w[4 * a], p[0]), mc_mul(w[4 * a + 1], p[1])), mc_mul(w[4 * a + 2], p[2])), w[4 * a + 3]);
+        const float d = -c[2];
+        if (!(d > 0.f)) continue;
+        const float u = __fadd_rn(A.cx, __fdiv_rn(mc_mul(A.fx, c[0]), d));
+        const float v = __fsub_rn(A.cy, __fdiv_rn(mc_mul(A.fy, c[1]), d));
+        const float fi = floorf(__fadd_rn(u, 0.5f)), fj = floorf(__fadd_rn(v, 0.5f));
+        if (!(fi >= A.ilo && fi < A.ihi && fj >= A.jlo && fj < A.jhi)) continue;        // (NaN fails; decided before any conversion to int)
+        const float D = depth[(size_t)kf * img + (size_t)(int)fj * A.W + (int)fi];
+        if (!(D > 0.f && D <= 3.402823466e38f)) continue;  // no measurement: 0, negative, NaN, inf
+        seen = d <= __fadd_rn(D, A.trunc);
+    }
+    if (live) valid[n] = seen ? 1 : 0;
+    if (count) {
+        const unsigned long long b = __ballot(live && seen);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+    }
+}
+
+// ---- connected components of the extracted mesh (nsk_mesh_filter) ----------------------------------------------------------
+// Union-find over the vertices: a root is only ever hooked below a SMALLER index (compare-and-swap on the root's own slot), so the links
+// never form a cycle and a component's final root is its smallest vertex index whatever order the hooks ran in.  find() halves the path it
+// walks; the halving stores race with other walkers, but every value ever stored in a slot is an ancestor of that vertex.
+__device__ __forceinline__ int cc_load(const int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ __forceinline__ int cc_find(int* __restrict__ parent, int x)
+{
+    for (;;) {
+        const int q = cc_load(parent + x);
+        if (q == x) return x;
+        const int g = cc_load(parent + q);
+        if (g != q) __atomic_store_n(parent + x, g, __ATOMIC_RELAXED);
+        x = g;
+    }
+}
+__device__ __forceinline__ void cc_union(int* __restrict__ parent, int a, int b)
+{
+    for (;;) {
+        a = cc_find(parent, a); b = cc_find(parent, b);
+        if (a == b) return;
+        const int lo = a < b ? a : b, hi = a < b ? b : a;
+        if (atomicCAS(parent + hi, hi, lo) == hi) return;  // hi was still a root: hooked.  Otherwise somebody hooked it first: walk on
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cc_init(int nv, int* __restrict__ parent, double* __restrict__ area, uint8_t* __restrict__ used)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v < nv) { parent[v] = v; area[v] = 0.0; used[v] = 0; }
+}
+__global__ __launch_bounds__(256) void k_cc_hook(int nt, const int* __restrict__ tris, int* __restrict__ parent, uint8_t* __restrict__ used)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    const int a = tris[3 * (size_t)t], b = tris[3 * (size_t)t + 1], c = tris[3 * (size_t)t + 2];
+    used[a] = 1; used[b] = 1; used[c] = 1;
+    cc_union(parent, a, b);
+    cc_union(parent, a, c);
+}
+// (after every hook has landed) each vertex points at its root
+__global__ __launch_bounds__(256) void k_cc_flatten(int nv, int* __restrict__ parent)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    int r = v;
+    for (int q = cc_load(parent + r); q != r; q = cc_load(parent + r)) r = q;
+    __atomic_store_n(parent + v, r, __ATOMIC_RELAXED);
+}
+// triangle areas 0.5 |(v1 - v0) x (v2 - v0)| in fp32, summed per component in fp64.  A workgroup walks CC_AREA_ITERS * 256 consecutive
+// triangles; while the triangles of a wave stay in one component (the usual case: triangles are ordered by cell) every lane sums in a
+// register, and the wave adds once when the component changes or the walk ends; a wave that holds several components adds once per
+// component -- a component of millions of triangles receives some thousand atomic adds on its one address, not one per triangle
+#define CC_AREA_ITERS 32
+__device__ __forceinline__ void cc_area_flush(double* __restrict__ area, int run, double acc)
+{
+    if (run < 0) return;                                    // (wave-uniform)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(area + run, acc);
+}
+__global__ __launch_bounds__(256) void k_cc_area(int nt, const int* __restrict__ tris, const float* __restrict__ verts, const int* __restrict__ label,
+                                                 double* __restrict__ area)
+{
+    int run = -1;                                           // the component the wave is summing for (wave-uniform), -1: none
+    double acc = 0.0;
+    for (int it = 0; it < CC_AREA_ITERS; ++it) {
+        const long long tl = ((long long)blockIdx.x * CC_AREA_ITERS + it) * 256 + threadIdx.x;
+        const bool live = tl < nt;
+        const int t = (int)tl;
+        int l = -1;
+        double a = 0.0;
+        if (live) {
+            const int i0 = tris[3 * (size_t)t], i1 = tris[3 * (size_t)t + 1], i2 = tris[3 * (size_t)t + 2];
+            l = label[i0];
+            float e[3], f[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const float v0 = verts[3 * (size_t)i0 + q];
+                e[q] = __fsub_rn(verts[3 * (size_t)i1 + q], v0); f[q] = __fsub_rn(verts[3 * (size_t)i2 + q], v0);
+            }
+            const float x = __fsub_rn(mc_mul(e[1], f[2]), mc_mul(e[2], f[1])), y = __fsub_rn(mc_mul(e[2], f[0]), mc_mul(e[0], f[2])),
+                        z = __fsub_rn(mc_mul(e[0], f[1]), mc_mul(e[1], f[0]));
+            a = (double)mc_mul(0.5f, __fsqrt_rn(__fadd_rn(__fadd_rn(mc_mul(x, x), mc_mul(y, y)), mc_mul(z, z))));
+        }
+        const int first = __ffsll((unsigned long long)__ballot(live)) - 1;
+        if (first < 0) break;                               // (wave-uniform: nothing left for this wave)
+        const int l0 = __shfl(l, first, 64);
+        if (__all(!live || l == l0)) {
+            if (l0 != run) { cc_area_flush(area, run, acc); run = l0; acc = 0.0; }
+            acc += a;
+        } else {
+            // several components in one wave (a small one between the triangles of a large one): one add per component, not per lane
+            cc_area_flush(area, run, acc); run = -1; acc = 0.0;
+            unsigned long long pend = __ballot(live);
+            while (pend) {                                  // (wave-uniform)
+                const int lc = __shfl(l, __ffsll(pend) - 1, 64);
+                const bool mine = live && l == lc;
+                cc_area_flush(area, lc, mine ? a : 0.0);
+                pend &= ~(unsigned long long)__ballot(mine);
+            }
+        }
+    }
+    cc_area_flush(area, run, acc);
+}
+struct CcStats { unsigned long long best; int best_label; unsigned n_components, n_kept; };     // best: bits of the largest area (non-negative doubles order like their bits)
+// per root with a triangle: one component.  largest_only: the largest area; else keep = area > min_area
+__global__ __launch_bounds__(256) void k_cc_roots(int nv, const int* __restrict__ label, const uint8_t* __restrict__ used, const double* __restrict__ area,
+                                                  double min_area, int largest_only, uint8_t* __restrict__ keepc, CcStats* __restrict__ S)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    keepc[v] = 0;
+    if (label[v] != v || !used[v]) return;
+    atomicAdd(&S->n_components, 1u);
+    if (largest_only) { atomicMax(&S->best, (unsigned long long)__double_as_longlong(area[v])); return; }
+    if (area[v] > min_area) { keepc[v] = 1; atomicAdd(&S->n_kept, 1u); }
+}
+// largest_only: ties go to the smaller label
+__global__ __launch_bounds__(256) void k_cc_pick(int nv, const int* __restrict__ label, const uint8_t* __restrict__ used, const double* __restrict__ area,
+                                                 CcStats* __restrict__ S)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv || label[v] != v || !used[v]) return;
+    if ((unsigned long long)__double_as_longlong(area[v]) == S->best) atomicMin(&S->best_label, v);
+}
+__global__ __launch_bounds__(256) void k_cc_pick_done(uint8_t* __restrict__ keepc, CcStats* __restrict__ S)
+{
+    if (S->best_label != 0x7fffffff) { keepc[S->best_label] = 1; S->n_kept = 1; }
+}
+// 0 / 1 per vertex and per triangle for the scans (a triangle goes where its component goes; a vertex without a triangle goes nowhere)
+__global__ __launch_bounds__(256) void k_cc_flags(int nv, int nt, const int* __restrict__ tris, const int* __restrict__ label, const uint8_t* __restrict__ used,
+                                                  const uint8_t* __restrict__ keepc, unsigned* __restrict__ vflag, unsigned* __restrict__ tflag)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nv) vflag[q] = used[q] && keepc[label[q]] ? 1u : 0u;
+    if (q < nt) tflag[q] = keepc[label[tris[3 * (size_t)q]]] ? 1u : 0u;
+}
+// voff / toff: the exclusive scans of the flags, one slot more than elements (the last is the total)
+__global__ __launch_bounds__(256) void k_cc_compact(int nv, int nt, const float* __restrict__ verts, const int* __restrict__ tris,
+                                                    const unsigned* __restrict__ voff, const unsigned* __restrict__ toff,
+                                                    float* __restrict__ verts2, int* __restrict__ tris2)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nv) {
+        const unsigned d = voff[q];
+        if (voff[q + 1] != d)
+            for (int a = 0; a < 3; ++a) verts2[3 * (size_t)d + a] = verts[3 * (size_t)q + a];
+    }
+    if (q < nt) {
+        const unsigned d = toff[q];
+        if (toff[q + 1] != d)
+            for (int a = 0; a < 3; ++a) tris2[3 * (size_t)d + a] = (int)voff[tris[3 * (size_t)q + a]];
+    }
+}

@@ -50,6 +50,7 @@ class Mapper {
     std::vector<float> last_losses;        // loss of every iteration of the last optimize_map call (downloaded once, after the loop)
     int n_keyframes() const { return (int)keyframe_vector.size(); }
     torch::Tensor keyframe_est_c2w(int k) const { return keyframe_vector.at((size_t)k).est_c2w; }      // (bundle adjustment rewrites these, :467-489)
+    torch::Tensor keyframe_gt_depth(int k) const { return keyframe_vector.at((size_t)k).depth; }       // (run() keeps the measured depth image there) with keyframe_est_c2w: what Mesher::get_clean_mesh takes
     std::vector<float> last_overlap;       // overlap fraction of keyframes [0, n-1) in that call (empty if not ranked)
     std::vector<int> last_window;          // keyframe indices of the last optimize_map call (-1 = current frame)
     double last_iter_us = 0.0;             // mean wall time of one iteration of the last optimize_map loop (stream-synchronised at its end)

@@ -5,8 +5,10 @@
 //                              (extent + 2 padding) / (resolution - 1): `resolution` counts NODES, not cells, on the longest and the
 //                              shortest axis alike (cells are not cubes unless the bound is);
 //   meshing.level_set (0)      the occupancy level of the surface (inside = occupancy above it);
-// and leaves clean_mesh (frustum-hull culling), mesh_coarse_level, get_largest_components, remove_small_geometry_threshold and the
-// render_ray_query colouring to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
+//   meshing.remove_small_geometry_threshold (0.2), meshing.get_largest_components (false)   get_clean_mesh only: components of the mesh
+//                              with less surface than the threshold (m^2) are dropped, or all but the largest;
+// and leaves clean_mesh_bound_scale (upstream's convex hull of a TSDF fusion: get_clean_mesh culls per node with the union of the
+// keyframes' depth-truncated frusta instead), mesh_coarse_level and the render_ray_query colouring to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
 // bound's own faces therefore show up as a shell around the scene, with padding 0 the outermost nodes (which lie ON the open bound) do.
 #pragma once
 #include <cstdint>
@@ -24,6 +26,12 @@ class Mesher {
     // valid: optional uint8 / bool [resolution^3] (z, y, x order), 0 = cells touching the node are skipped.
     void get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, bool color = true,
                   torch::Tensor valid = torch::Tensor());
+    // The mesh of what the keyframes saw: lattice as in get_mesh -> nsk_lattice_seen over the keyframes in batches of at most 16 (depths: host
+    // tensors [H, W] of metric z-depth, 0 / NaN / inf = no measurement; c2ws: [4, 4] camera-to-world, camera looking along -z, inverted in
+    // double) -> nsk_mesh_extract with that mask -> nsk_mesh_filter (remove_small_geometry_threshold / get_largest_components) -> colour
+    // query on the filtered vertices -> PLY.  Lattice, mask and mesh stay on the device.
+    void get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                        const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color = true);
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
     static void write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int n_vertices, const int32_t* triangles, int n_triangles);
     static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& triangles);
@@ -31,5 +39,12 @@ class Mesher {
     int resolution;
     float level_set, padding;
     torch::Tensor bound;
+    float remove_small_geometry_threshold;
+    bool get_largest_components;
+    float seen_trunc = 0.5f;    // a node counts as seen up to this far (m) behind the measured depth: the margin inside which the Mapper's own
+                                // frustum selection lets voxels train (nsk_frustum_mask)
+    int seen_edge = 0;          // pixels ignored along the image border
     int last_vertices = 0, last_triangles = 0;
+    int last_components = 0, last_kept = 0;     // get_clean_mesh: components before the filter, components kept
+    long long last_seen = 0;                    // get_clean_mesh: lattice nodes at least one keyframe saw
 };

@@ -1,6 +1,7 @@
 // nsk_mesher.cpp -- Mesher (include/Mesher.h): lattice evaluation and marching cubes stay on the device; the host writes the PLY.
 #include "Mesher.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +19,8 @@ Mesher::Mesher(YAML::Node ns, torch::Tensor bound_3x2, float padding_) : padding
 {
     resolution = ns["meshing"]["resolution"].IsDefined() ? ns["meshing"]["resolution"].as<int>() : 256;
     level_set = ns["meshing"]["level_set"].IsDefined() ? ns["meshing"]["level_set"].as<float>() : 0.f;
+    remove_small_geometry_threshold = ns["meshing"]["remove_small_geometry_threshold"].IsDefined() ? ns["meshing"]["remove_small_geometry_threshold"].as<float>() : 0.2f;
+    get_largest_components = ns["meshing"]["get_largest_components"].IsDefined() ? ns["meshing"]["get_largest_components"].as<bool>() : false;
     if (resolution < 2) throw std::runtime_error("Mesher: meshing.resolution must be at least 2");
     if (!(padding >= 0.f)) throw std::runtime_error("Mesher: padding must be >= 0");
     bound = bound_3x2.defined() ? bound_3x2.detach().to(torch::kCPU, torch::kFloat32).contiguous().clone()
@@ -35,6 +38,36 @@ struct DevMem {
     DevMem& operator=(const DevMem&) = delete;
 };
 }  // namespace
+
+// the context's mesh (nv vertices, nt triangles) -> host, the colour query on the device vertex buffer, the PLY
+static void write_context_mesh(const std::string& path, bool color, int nv, int nt)
+{
+    std::vector<float> xyz((size_t)nv * 3);
+    std::vector<int32_t> tris((size_t)nt * 3);
+    check(nsk_mesh_download(ctx(), xyz.data(), tris.data()));
+    std::vector<uint8_t> rgb;
+    if (color && nv > 0) {
+        float* d_verts = nullptr; int32_t* d_tris = nullptr;
+        check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
+        DevMem raw((size_t)nv * 4 * sizeof(float));
+        const int chunk = (1 << 26) - 1;
+        for (long long v0 = 0; v0 < nv; v0 += chunk) {
+            const int m = (int)std::min<long long>(chunk, nv - v0);
+            check(nsk_eval_points(ctx(), NSK_COLOR, m, d_verts + 3 * v0, (float*)raw.p + 4 * v0));
+        }
+        check(nsk_sync(ctx()));
+        std::vector<float> h((size_t)nv * 4);
+        if (hipMemcpy(h.data(), raw.p, h.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+        rgb.resize((size_t)nv * 3);
+        for (size_t v = 0; v < (size_t)nv; ++v)
+            for (int k = 0; k < 3; ++k) {
+                float x = h[4 * v + k];
+                x = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;                       // clamp to [0, 1]; NaN -> 0
+                rgb[3 * v + k] = (uint8_t)std::lround(x * 255.f);
+            }
+    }
+    Mesher::write_ply(path, xyz.data(), color ? rgb.data() : nullptr, nv, tris.data(), nt);
+}
 
 void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, bool color, torch::Tensor valid)
 {
@@ -61,32 +94,54 @@ void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::st
     check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
     int nv = 0, nt = 0;
     check(nsk_mesh_extract(ctx(), (const float*)vol.p, dvalid ? (const uint8_t*)dvalid->p : nullptr, n, n, n, origin, step, level_set, &nv, &nt));
-    std::vector<float> xyz((size_t)nv * 3);
-    std::vector<int32_t> tris((size_t)nt * 3);
-    check(nsk_mesh_download(ctx(), xyz.data(), tris.data()));
-    std::vector<uint8_t> rgb;
-    if (color && nv > 0) {
-        float* d_verts = nullptr; int32_t* d_tris = nullptr;
-        check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
-        DevMem raw((size_t)nv * 4 * sizeof(float));
-        const int chunk = (1 << 26) - 1;
-        for (long long v0 = 0; v0 < nv; v0 += chunk) {
-            const int m = (int)std::min<long long>(chunk, nv - v0);
-            check(nsk_eval_points(ctx(), NSK_COLOR, m, d_verts + 3 * v0, (float*)raw.p + 4 * v0));
-        }
-        check(nsk_sync(ctx()));
-        std::vector<float> h((size_t)nv * 4);
-        if (hipMemcpy(h.data(), raw.p, h.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
-        rgb.resize((size_t)nv * 3);
-        for (size_t v = 0; v < (size_t)nv; ++v)
-            for (int k = 0; k < 3; ++k) {
-                float x = h[4 * v + k];
-                x = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;                       // clamp to [0, 1]; NaN -> 0
-                rgb[3 * v + k] = (uint8_t)std::lround(x * 255.f);
-            }
-    }
-    write_ply(path, xyz.data(), color ? rgb.data() : nullptr, nv, tris.data(), nt);
+    write_context_mesh(path, color, nv, nt);
     last_vertices = nv; last_triangles = nt;
+}
+
+void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                            const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color)
+{
+    TORCH_CHECK(depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    nskh::sync_grids(c);
+    decoders.sync_to_device();
+    TORCH_CHECK(bound.numel() == 6, "Mesher: bound must be [3,2]");
+    check(nsk_set_bound(ctx(), bound.data_ptr<float>()));
+    const int n = resolution;
+    float origin[3], step[3];
+    for (int a = 0; a < 3; ++a) {
+        const float lo = bound[a][0].item<float>() - padding, hi = bound[a][1].item<float>() + padding;
+        origin[a] = lo;
+        step[a] = (hi - lo) / (float)(n - 1);
+    }
+    const size_t nodes = (size_t)n * n * n, img = (size_t)H * W;
+    DevMem vol(nodes * sizeof(float)), seen(nodes);
+    check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
+    // the seen mask, streamed: at most 16 depth images on the device at a time
+    const int batch = 16, K = (int)depths.size();
+    DevMem dimg((size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
+    std::vector<float> w2c((size_t)batch * 16);
+    long long n_seen = 0;
+    if (K == 0) check(nsk_lattice_seen(ctx(), origin, step, n, n, n, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, seen_edge, seen_trunc, 0, (uint8_t*)seen.p, &n_seen));
+    for (int k0 = 0; k0 < K; k0 += batch) {
+        const int kb = std::min(batch, K - k0);
+        check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
+        for (int k = 0; k < kb; ++k) {
+            torch::Tensor d = depths[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k0 + k, " is not H x W");
+            if (hipMemcpy((float*)dimg.p + (size_t)k * img, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+            torch::Tensor m = c2ws[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat64).contiguous();
+            TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k0 + k, " is not 4 x 4");
+            torch::Tensor inv = torch::linalg_inv(m.view({4, 4})).to(torch::kFloat32).contiguous();      // inverted in double, rounded once
+            std::memcpy(&w2c[(size_t)k * 16], inv.data_ptr<float>(), 16 * sizeof(float));
+        }
+        check(nsk_lattice_seen(ctx(), origin, step, n, n, n, kb, (const float*)dimg.p, H, W, fx, fy, cx, cy, w2c.data(), seen_edge, seen_trunc, k0 > 0,
+                               (uint8_t*)seen.p, k0 + kb >= K ? &n_seen : nullptr));
+    }
+    int nv = 0, nt = 0, nc = 0, nk = 0;
+    check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)seen.p, n, n, n, origin, step, level_set, &nv, &nt));
+    check(nsk_mesh_filter(ctx(), remove_small_geometry_threshold, get_largest_components ? 1 : 0, &nv, &nt, &nc, &nk));
+    write_context_mesh(path, color, nv, nt);
+    last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen;
 }
 
 void Mesher::write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int nv, const int32_t* tris, int nt)

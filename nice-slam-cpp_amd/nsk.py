@@ -26,6 +26,7 @@ SYMBOLS = (
     "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
+    "nsk_lattice_seen", "nsk_mesh_filter",
 )
 
 
@@ -362,6 +363,52 @@ class Context:
         if nt.value:
             tris.view(-1).copy_(torch.as_tensor(_CudaArray(pt.value, 3 * nt.value, "<i4"), device=dev))
         return verts, tris
+
+    def _mesh_tensors(self, nv, nt):
+        """the context's mesh buffers copied into cuda tensors of their own"""
+        import torch
+        pv, pt = C.c_void_p(), C.c_void_p()
+        _chk(lib().nsk_mesh_buffers(self.h, C.byref(pv), C.byref(pt)))
+        dev = "cuda:%d" % self.device
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        if nv:
+            verts.view(-1).copy_(torch.as_tensor(_CudaArray(pv.value, 3 * nv), device=dev))
+        if nt:
+            tris.view(-1).copy_(torch.as_tensor(_CudaArray(pt.value, 3 * nt, "<i4"), device=dev))
+        return verts, tris
+
+    @_ordered
+    def lattice_seen(self, origin, step, nx, ny, nz, depths, intr, w2c, edge=0, trunc=0.5, valid=None):
+        """the lattice nodes that one of the keyframes saw (nsk_lattice_seen).  depths: float32 cuda tensor [K, H, W] (K may be 0);
+        intr = (fx, fy, cx, cy); w2c: [K, 4, 4] world-to-camera on the host.  valid: uint8 cuda tensor [nz, ny, nx] to OR into
+        (default: a new one).  -> (valid, n_seen)"""
+        import numpy as np
+        import torch
+        assert depths.dim() == 3 and depths.dtype == torch.float32
+        K, H, W = depths.shape
+        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(K, 16))
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
+        acc = valid is not None
+        if acc:
+            assert valid.dtype == torch.uint8 and valid.numel() == int(nx) * int(ny) * int(nz)
+        else:
+            valid = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.uint8, device="cuda:%d" % self.device)
+        fx, fy, cx, cy = [C.c_float(float(x)) for x in intr]
+        n = C.c_longlong(0)
+        _chk(lib().nsk_lattice_seen(self.h, o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), int(K),
+                                    _ptr(depths) if K else None, int(H), int(W), fx, fy, cx, cy, w.ctypes.data_as(C.c_void_p) if K else None,
+                                    int(edge), C.c_float(trunc), int(acc), _ptr(valid), C.byref(n)))
+        return valid, int(n.value)
+
+    @_ordered
+    def filter_mesh(self, min_area=0.0, largest_only=False):
+        """connected components of the mesh of the last extract_mesh, small ones (area <= min_area) or all but the largest dropped in
+        place (nsk_mesh_filter) -> (vertices, triangles, n_components, n_kept), the arrays as cuda tensors of their own"""
+        nv, nt, nc, nk = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _chk(lib().nsk_mesh_filter(self.h, C.c_float(min_area), int(bool(largest_only)), C.byref(nv), C.byref(nt), C.byref(nc), C.byref(nk)))
+        verts, tris = self._mesh_tensors(nv.value, nt.value)
+        return verts, tris, nc.value, nk.value
 
     @_ordered
     def raw2outputs(self, raw, z, rays_d, occupancy=False):
