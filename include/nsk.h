@@ -455,6 +455,52 @@ int nsk_lattice_seen(nsk_ctx* ctx, const float h_origin[3], const float h_step[3
  * fails names its byte count and leaves context and mesh as they were. */
 int nsk_mesh_filter(nsk_ctx* ctx, float min_area, int largest_only, int* n_vertices, int* n_triangles, int* n_components, int* n_kept);
 
+/* ---- whole frames: render a view of the map, compare it with the input frame (upstream Renderer.render_img and the visualiser) ---- */
+/* A VIEW is the pixel set i = W0 + stride * col, j = H0 + stride * row of an H x W image, col < Wv = ceil((W1 - W0) / stride),
+ * row < Hv = ceil((H1 - H0) / stride); the window [H0,H1) x [W0,W1) lies inside the image and stride >= 1 (at most 2^30 view pixels).
+ * View pixel n = row * Wv + col (row-major: upstream's get_rays(...).reshape(-1, 3) order); pix_i is the column and pix_j the row, as
+ * everywhere else here.  The pose is on the device: 12 floats c2w, or with pose_is_cam7 the 7-vector (as in nsk_frame_rays).
+ *
+ * nsk_image_rays: the rays (d_rays_o, d_rays_d [n][3]) and the ground-truth depth (d_gt_depth [n], read from d_depth_img [H][W]; both NULL
+ * or both given) of view pixels [first, first + n), in one launch and without pixel-index arrays.  The arithmetic is that of
+ * nsk_rays_from_pixels (c2w) / nsk_rays_from_camera (7-vector) and nsk_gather_pixels on the explicit index lists: the results are
+ * bit-identical.  mode as in nsk_rays_from_pixels.  The pose matrix is formed once per workgroup. */
+int nsk_image_rays(nsk_ctx* ctx, int first, int n, int H0, int H1, int W0, int W1, int stride, int H, int W, float fx, float fy, float cx,
+                   float cy, const float* d_pose, int pose_is_cam7, int mode, const float* d_depth_img, float* d_rays_o, float* d_rays_d,
+                   float* d_gt_depth);
+/* nsk_render_image: the view rendered into d_rgb [Hv][Wv][3], d_depth [Hv][Wv], d_var [Hv][Wv] (device).  The view is walked in chunks of
+ * chunk_rays pixels (the last one ragged); per chunk one nsk_image_rays launch into context-owned buffers, then the launches of
+ * nsk_render_forward on those rays, the compositing writing straight into the images at the chunk's offset.
+ *   d_depth_img NULL: no ground truth (N_surface = 0, near = 0.01, as nsk_render_forward with d_gt_depth NULL); gt_depth_max is not read;
+ *   gt_depth_max < 0: every chunk is a batch of its own with its own device-computed max(gt_depth) (src/Renderer.cpp:76,93) -- upstream's
+ *       render_img.  The bytes are those of nsk_render_forward called on that chunk's rays, so THE FRAME DEPENDS ON chunk_rays, as it does
+ *       upstream (far = 1.2 max(gt) of the chunk feeds the sample depths of every ray of the chunk, and of the rays without a measurement);
+ *   gt_depth_max >= 0: that value for every chunk; the frame does not depend on the chunking.
+ * chunk_rays * S (S = n_samples (+ n_surface)) must stay below the 2^26 samples of a launch; a larger value is rejected with the largest
+ * allowed one.  Asynchronous on the context's stream, no host synchronisation (unless a buffer has to grow).  Not capturable: the call
+ * grows the workspace to chunk_rays rays (a reallocation makes recorded graphs stale, as for any larger batch).
+ * Other context state: a render shows every ray, so an installed ray mask (nsk_set_ray_mask) is ignored; so is a depth-max batch
+ * (nsk_set_depth_max_batch): it describes another batch, an image chunk's maximum is its own.  A batch registered with nsk_map_prepare
+ * stays registered: the next nsk_map_step gives the loss and the outputs it gives without the render in between, bit for bit (if the
+ * render had to grow the workspace the batch is sampled at its own step, with the same results). */
+int nsk_render_image(nsk_ctx* ctx, int stage, int H0, int H1, int W0, int W1, int stride, int H, int W, float fx, float fy, float cx,
+                     float cy, const float* d_pose, int pose_is_cam7, int mode, const float* d_depth_img, float gt_depth_max,
+                     int chunk_rays, float* d_rgb, float* d_depth, float* d_var);
+/* nsk_image_metrics: residuals of a rendered frame (d_rgb [Hv][Wv][3], d_depth [Hv][Wv]) against the input frame (d_gt_depth, d_gt_color:
+ * same shapes, either may be NULL) and their sums, on the device.
+ *   d_res_depth [Hv][Wv] (or NULL) = gt > 0 ? |gt - d| : 0 (the visualiser's rule: no measurement, no residual);
+ *   d_res_color [Hv][Wv][3] (or NULL) = |gt_c - c|.  A residual image needs its ground truth.
+ * Each difference is one fp32 operation; it is widened to double (squared, for the colour) and summed in fp64.  A pixel whose rendered
+ * depth or colour is not finite is left out of every sum and counted; so is a term that is not finite through the ground truth.
+ *   h_out[0] pixels;  [1] pixels in the depth sum (gt > 0);  [2] sum |gt - d| over them;  [3] colour components in the colour sum;
+ *   [4] sum (gt_c - c)^2 over them;  [5] pixels with a non-finite rendered value;  [6], [7] zero.
+ * Depth L1 = [2] / [1], PSNR = -10 log10([4] / [3]).  Without d_gt_depth [1] = [2] = 0, without d_gt_color [3] = [4] = 0.
+ * No floating-point atomics: lanes add their pixels in index order, waves meet by shuffles, every workgroup writes one row of partial
+ * sums and a second, single-workgroup launch adds the rows in index order -- two runs give the same bytes.  Reading h_out is the call's
+ * one synchronisation. */
+int nsk_image_metrics(nsk_ctx* ctx, int Hv, int Wv, const float* d_rgb, const float* d_depth, const float* d_gt_depth,
+                      const float* d_gt_color, float* d_res_depth, float* d_res_color, double h_out[8]);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

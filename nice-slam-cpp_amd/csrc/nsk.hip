@@ -5,6 +5,7 @@
 #include "nsk_train.h"
 #include "nsk_bf16.h"
 #include "nsk_mesh.h"
+#include "nsk_image.h"
 #include "nsk_buf.h"
 
 #include <dlfcn.h>
@@ -813,6 +814,11 @@ struct nsk_ctx {
         Buf<CcStats> cc_stats;
         Buf<float> verts2; Buf<int> tris2;
     } mesh;
+    // whole-frame rendering (nsk_render_image / nsk_image_metrics): the rays of the chunk being rendered, the metrics' partial rows and results
+    struct Image {
+        Buf<float> ro, rd, gd;                               // [chunk][3], [chunk][3], [chunk]: one group
+        Buf<double> rows;                                    // [IMG_MAX_ROWS][IMG_COLS] + 8 results
+    } img;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -1866,7 +1872,7 @@ static int prep_drop(nsk_ctx* c)
 static size_t stage_bins(nsk_ctx* c, int stage) { return c->grid[stage_key_level(stage)].n / 32 * 8; }
 
 static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax, bool save_masks,
-                        bool sorted = false)
+                        bool sorted = false, const nsk_ctx::DMax* dmax = nullptr)      // dmax: instead of the installed depth-max batch (nsk_render_image: none)
 {
     const int M = N * S;
     const uint8_t* mask = save_masks ? c->ray_mask : nullptr;      // (only the steps that form a loss honour it; a plain render shows every ray)
@@ -1889,7 +1895,7 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
         if (is_this_batch(c->req)) c->req.valid = false;    // registered, but no step came by to carry its sampling: sampled here like any other batch
         c->sorted = sorted;
         if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
-        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.z, c->ws.skey, c->ws.srank, c->ws.offs, c->ws.perm, c->dmax));
+        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.z, c->ws.skey, c->ws.srank, c->ws.offs, c->ws.perm, dmax ? *dmax : c->dmax));
     }
     CHK(launch_decode_fwd_stage(c, stage, M, S, ro, rd, save_masks));
     c->dbg_M = M; c->dbg_S = S;
@@ -2800,6 +2806,116 @@ extern "C" int nsk_prepare_rays(nsk_ctx* c, int nframes, const nsk_frame_rays* f
         { ProfScope ps(c, "prepare_rays"); k_prepare_rays<<<dim3((per + 255) / 256, A.nframes), 256, 0, c->stream>>>(A); }
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+
+// ---- whole frames (nsk_image.h) ------------------------------------------------------------------------------------
+// the view's extents; every argument is checked here, before anything is launched
+static int view_checks(const char* fn, nsk_ctx* c, int H0, int H1, int W0, int W1, int stride, int H, int W, int* Hv, int* Wv)
+{
+    if (!c) return fail("%s: null ctx", fn);
+    if (H < 1 || W < 1) return fail("%s: H, W = %d x %d, the image must have at least one pixel", fn, H, W);
+    if (stride < 1) return fail("%s: stride = %d, must be >= 1", fn, stride);
+    if (H0 < 0 || H1 <= H0 || H1 > H) return fail("%s: window rows H0, H1 = [%d,%d) outside the %d x %d image", fn, H0, H1, H, W);
+    if (W0 < 0 || W1 <= W0 || W1 > W) return fail("%s: window columns W0, W1 = [%d,%d) outside the %d x %d image", fn, W0, W1, H, W);
+    *Hv = (H1 - H0 + stride - 1) / stride; *Wv = (W1 - W0 + stride - 1) / stride;
+    if ((long long)*Hv * *Wv > (1LL << 30)) return fail("%s: the view has %lld pixels (at most 2^30)", fn, (long long)*Hv * *Wv);
+    return 0;
+}
+static int launch_image_rays(nsk_ctx* c, int first, int n, int H0, int W0, int stride, int Wv, int W, float fx, float fy, float cx, float cy,
+                             const float* pose, int cam7, int mode, const float* depth_img, float* ro, float* rd, float* gd)
+{
+    ImgView V;
+    V.H0 = H0; V.W0 = W0; V.stride = stride; V.Wv = Wv; V.W = W; V.first = first; V.n = n; V.mode = mode;
+    V.fx = fx; V.fy = fy; V.cx = cx; V.cy = cy;
+    { ProfScope ps(c, "image_rays"); k_image_rays<<<(n + 255) / 256, 256, 0, c->stream>>>(V, pose, cam7, depth_img, ro, rd, depth_img ? gd : nullptr); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int nsk_image_rays(nsk_ctx* c, int first, int n, int H0, int H1, int W0, int W1, int stride, int H, int W, float fx, float fy,
+                              float cx, float cy, const float* d_pose, int pose_is_cam7, int mode, const float* d_depth_img, float* d_rays_o,
+                              float* d_rays_d, float* d_gt_depth)
+{
+    int Hv, Wv;
+    CHK(view_checks("nsk_image_rays", c, H0, H1, W0, W1, stride, H, W, &Hv, &Wv));
+    if (first < 0 || n < 1 || (long long)first + n > (long long)Hv * Wv)
+        return fail("nsk_image_rays: first, n = %d, %d outside the view's %lld pixels", first, n, (long long)Hv * Wv);
+    if (!d_pose) return fail("nsk_image_rays: d_pose is NULL");
+    if (!d_rays_o || !d_rays_d) return fail("nsk_image_rays: d_rays_o / d_rays_d is NULL");
+    if ((d_depth_img != nullptr) != (d_gt_depth != nullptr)) return fail("nsk_image_rays: d_gt_depth must be given exactly when d_depth_img is");
+    HIPCHK(hipSetDevice(c->device));
+    intr(mode, fx, fy, cx, cy);
+    return launch_image_rays(c, first, n, H0, W0, stride, Wv, W, fx, fy, cx, cy, d_pose, pose_is_cam7, mode, d_depth_img, d_rays_o, d_rays_d, d_gt_depth);
+}
+
+extern "C" int nsk_render_image(nsk_ctx* c, int stage, int H0, int H1, int W0, int W1, int stride, int H, int W, float fx, float fy, float cx,
+                                float cy, const float* d_pose, int pose_is_cam7, int mode, const float* d_depth_img, float gt_depth_max,
+                                int chunk_rays, float* d_rgb, float* d_depth, float* d_var)
+{
+    int Hv, Wv;
+    CHK(view_checks("nsk_render_image", c, H0, H1, W0, W1, stride, H, W, &Hv, &Wv));
+    if (!d_pose) return fail("nsk_render_image: d_pose is NULL");
+    if (!d_rgb || !d_depth || !d_var) return fail("nsk_render_image: d_rgb / d_depth / d_var is NULL");
+    CHK(check_stage(c, stage));
+    const int S = c->R.n_samples + (d_depth_img ? c->R.n_surface : 0);
+    const int chunk_max = (int)(((1LL << 26) - 1) / S);
+    if (chunk_rays < 1 || chunk_rays > chunk_max)
+        return fail("nsk_render_image: chunk_rays = %d, must be 1..%d (%d samples per ray, fewer than 2^26 samples per chunk)", chunk_rays, chunk_max, S);
+    if (c->capturing) return fail("nsk_render_image: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    const int total = Hv * Wv, chunk = std::min(chunk_rays, total);
+    CHK(ensure_ws(c, chunk, chunk * S));
+    nsk_ctx::Image& I = c->img;
+    if ((size_t)chunk > I.gd.cap()) {
+        CHK(grow_begin(c, GROW_NO_CAPTURE));
+        const int r = [&]() -> int {
+            CHK(dev_alloc(I.ro, (size_t)chunk * 3, "the chunk's ray origins")); CHK(dev_alloc(I.rd, (size_t)chunk * 3, "the chunk's ray directions"));
+            CHK(dev_alloc(I.gd, (size_t)chunk, "the chunk's depths"));
+            return 0;
+        }();
+        if (r != 0) { reset_all(I.ro, I.rd, I.gd); return r; }
+    }
+    intr(mode, fx, fy, cx, cy);
+    const nsk_ctx::DMax own;                                // a chunk's maximum is its own: an installed depth-max batch describes another batch
+    const float* gt = d_depth_img ? I.gd.get() : nullptr;
+    for (int first = 0; first < total; first += chunk) {
+        const int n = std::min(chunk, total - first);
+        CHK(launch_image_rays(c, first, n, H0, W0, stride, Wv, W, fx, fy, cx, cy, d_pose, pose_is_cam7, mode, d_depth_img, I.ro, I.rd, I.gd));
+        CHK(forward_core(c, stage, n, S, I.ro, I.rd, gt, gt ? gt_depth_max : -1.f, false, false, &own));
+        CompArgs A;
+        comp_args(c, A, stage, n, S, I.ro, I.rd);
+        A.keep = nullptr;                                   // (mode 0 does not read it: a render shows every ray)
+        A.rgb = d_rgb + 3 * (size_t)first; A.depth = d_depth + first; A.var = d_var + first; A.weights = nullptr; A.mode = 0;
+        { ProfScope ps(c, "composite"); k_composite<<<(n + 3) / 4, 256, 0, c->stream>>>(A); }
+        HIPCHK(hipGetLastError());
+    }
+    account(c, stage, S, 1, false, 0);
+    c->last_bytes *= total; c->last_flops *= total; c->last_samples = (int)std::min<long long>((long long)total * S, 0x7fffffffLL);
+    return 0;
+}
+
+extern "C" int nsk_image_metrics(nsk_ctx* c, int Hv, int Wv, const float* d_rgb, const float* d_depth, const float* d_gt_depth,
+                                 const float* d_gt_color, float* d_res_depth, float* d_res_color, double h_out[8])
+{
+    if (!c) return fail("nsk_image_metrics: null ctx");
+    if (Hv < 1 || Wv < 1 || (long long)Hv * Wv > (1LL << 30)) return fail("nsk_image_metrics: Hv, Wv = %d x %d, need 1 .. 2^30 pixels", Hv, Wv);
+    if (!d_rgb || !d_depth) return fail("nsk_image_metrics: d_rgb / d_depth is NULL");
+    if (!h_out) return fail("nsk_image_metrics: h_out is NULL");
+    if (d_res_depth && !d_gt_depth) return fail("nsk_image_metrics: d_res_depth asked for without d_gt_depth");
+    if (d_res_color && !d_gt_color) return fail("nsk_image_metrics: d_res_color asked for without d_gt_color");
+    if (c->capturing) return fail("nsk_image_metrics: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    const int n = Hv * Wv, nrows = std::min((n + 255) / 256, IMG_MAX_ROWS);
+    CHK(grow(c, c->img.rows, (size_t)IMG_MAX_ROWS * IMG_COLS + 8, "the metrics' partial sums", GROW_NO_CAPTURE));
+    double* rows = c->img.rows;
+    double* out = rows + (size_t)IMG_MAX_ROWS * IMG_COLS;
+    { ProfScope ps(c, "image_metrics");
+      k_image_metrics<<<nrows, 256, 0, c->stream>>>(n, d_rgb, d_depth, d_gt_depth, d_gt_color, d_res_depth, d_res_color, rows);
+      k_image_metrics_sum<<<1, 64, 0, c->stream>>>(nrows, n, rows, out); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, out, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // Same surface as the reference's include/Renderer.h:8-25: constructor, eval_points and render_batch_ray keep their
 // signatures (note rays_d before rays_o).  Every call marshals into include/nsk.h.
 #pragma once
+#include <tuple>
 #include <torch/torch.h>
 #include "models/NICE.h"
 
@@ -11,6 +12,13 @@ class Renderer {
     void render_batch_ray(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor rays_d, torch::Tensor rays_o,
                           std::string stage, torch::Tensor gt_depth, torch::Tensor& rgb_map, torch::Tensor& depth_map,
                           torch::Tensor& depth_var, torch::Tensor& weights);
+    // not in the reference (upstream NICE-SLAM's Renderer.render_img): the whole H x W frame seen from c2w ([3][4] or [4][4]) rendered from
+    // the map in chunks of ray_batch_size pixels, each chunk a batch of its own with its own max(gt_depth) (src/Renderer.cpp:76,93), so the
+    // frame depends on ray_batch_size as it does upstream.  gt_depth [H][W] or an undefined tensor (no ground truth: N_surface = 0).
+    // Returns (depth [H][W], uncertainty [H][W], color [H][W][3]).  Rays are generated on the device (nsk_render_image).
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> render_img(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor c2w,
+                                                                         std::string stage, torch::Tensor gt_depth, int H, int W, float fx,
+                                                                         float fy, float cx, float cy);
     // not in the reference: the scene bound is hard-coded there in five places (src/Renderer.cpp:15 ...)
     void set_bound(torch::Tensor bound_3x2);
     torch::Tensor bound;

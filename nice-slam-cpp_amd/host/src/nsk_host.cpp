@@ -402,6 +402,27 @@ void Renderer::render_batch_ray(c10::Dict<std::string, torch::Tensor> c, NICE de
     depth_var = o_v.download({N}).to(dev); weights = o_w.download({N, S}).to(dev);
 }
 
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> Renderer::render_img(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor c2w,
+                                                                               std::string stage, torch::Tensor gt_depth, int H, int W, float fx,
+                                                                               float fy, float cx, float cy)
+{
+    push_opts();
+    nskh::sync_grids(c);
+    decoders.sync_to_device();
+    TORCH_CHECK(c2w.dim() == 2 && c2w.size(0) >= 3 && c2w.size(1) == 4, "c2w must be [3,4] or [4,4]");
+    const bool has_gt = gt_depth.defined();
+    if (has_gt) TORCH_CHECK(gt_depth.numel() == (int64_t)H * W, "gt_depth must be [H,W]");
+    DevBuf pose, gd, o_rgb, o_d, o_v;
+    pose.upload(c2w.detach().to(torch::kCPU, torch::kFloat32).index({Slice(None, 3), Slice(None, 4)}).reshape({12}));
+    if (has_gt) gd.upload(gt_depth.reshape({-1}));
+    const size_t n = (size_t)H * W;
+    o_rgb.ensure(n * 3); o_d.ensure(n); o_v.ensure(n);
+    check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, pose.p, 0, 0, has_gt ? gd.p : nullptr, -1.f,
+                           ray_batch_size, o_rgb.p, o_d.p, o_v.p));
+    auto dev = c2w.device();
+    return std::make_tuple(o_d.download({H, W}).to(dev), o_v.download({H, W}).to(dev), o_rgb.download({H, W, 3}).to(dev));
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // torchlib/utils.h
 // ---------------------------------------------------------------------------------------------------------

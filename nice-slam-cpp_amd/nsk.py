@@ -27,6 +27,7 @@ SYMBOLS = (
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
+    "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
 )
 
 
@@ -320,6 +321,73 @@ class Context:
         _chk(lib().nsk_render_forward(self.h, _stage(stage), N, _ptr(rays_o), _ptr(rays_d), _ptr(gt_depth),
                                       C.c_float(gt_depth_max), _ptr(rgb), _ptr(depth), _ptr(var), _ptr(w)))
         return rgb, depth, var, w
+
+    # -- whole frames ----------------------------------------------------------------------------------------
+    # Python default of render_image's chunk_rays: the smallest chunk within 3 % of the best frame time at 680 x 1200
+    CHUNK_RAYS = 25600
+
+    @staticmethod
+    def view_shape(HW, window=None, stride=1):
+        """(Hv, Wv) of the view: window = (H0, H1, W0, W1) (default: the whole image), every stride-th pixel"""
+        H0, H1, W0, W1 = window if window is not None else (0, int(HW[0]), 0, int(HW[1]))
+        return (H1 - H0 + stride - 1) // stride, (W1 - W0 + stride - 1) // stride
+
+    @_ordered
+    def image_rays(self, HW, intr, pose, depth_img=None, window=None, stride=1, first=0, n=None, mode=0):
+        """nsk_image_rays: rays (and gathered depth) of view pixels [first, first + n) from pose (cuda tensor: 12 floats c2w or the
+        7-vector) + intrinsics + image size -> (rays_o [n, 3], rays_d [n, 3], gt_depth [n] or None)"""
+        import torch
+        H, W = int(HW[0]), int(HW[1])
+        H0, H1, W0, W1 = window if window is not None else (0, H, 0, W)
+        if n is None:
+            Hv, Wv = self.view_shape(HW, window, max(int(stride), 1))
+            n = Hv * Wv - first
+        dev = pose.device
+        ro = torch.empty(max(n, 0), 3, device=dev); rd = torch.empty(max(n, 0), 3, device=dev)
+        gd = torch.empty(max(n, 0), device=dev) if depth_img is not None else None
+        fx, fy, cx, cy = intr
+        _chk(lib().nsk_image_rays(self.h, int(first), int(n), int(H0), int(H1), int(W0), int(W1), int(stride), H, W, C.c_float(fx), C.c_float(fy),
+                                  C.c_float(cx), C.c_float(cy), _ptr(pose), 1 if pose.numel() == 7 else 0, int(mode), _ptr(depth_img),
+                                  _ptr(ro), _ptr(rd), _ptr(gd)))
+        return ro, rd, gd
+
+    @_ordered
+    def render_image(self, stage, HW, intr, pose, depth_img=None, window=None, stride=1, gt_depth_max=-1.0, chunk_rays=None, mode=0):
+        """nsk_render_image: the view rendered from the map -> (rgb [Hv, Wv, 3], depth [Hv, Wv], var [Hv, Wv]) cuda tensors.
+        gt_depth_max < 0: every chunk of chunk_rays pixels is a batch of its own with its own max(gt_depth), as upstream's render_img
+        (the frame then depends on chunk_rays); >= 0: that value for every chunk.  depth_img None: no ground truth."""
+        import torch
+        H, W = int(HW[0]), int(HW[1])
+        H0, H1, W0, W1 = window if window is not None else (0, H, 0, W)
+        Hv, Wv = self.view_shape(HW, window, max(int(stride), 1))
+        dev = pose.device
+        rgb = torch.empty(max(Hv, 0), max(Wv, 0), 3, device=dev); depth = torch.empty(max(Hv, 0), max(Wv, 0), device=dev); var = torch.empty_like(depth)
+        fx, fy, cx, cy = intr
+        _chk(lib().nsk_render_image(self.h, _stage(stage), int(H0), int(H1), int(W0), int(W1), int(stride), H, W, C.c_float(fx), C.c_float(fy),
+                                    C.c_float(cx), C.c_float(cy), _ptr(pose), 1 if pose.numel() == 7 else 0, int(mode), _ptr(depth_img),
+                                    C.c_float(gt_depth_max), int(self.CHUNK_RAYS if chunk_rays is None else chunk_rays), _ptr(rgb), _ptr(depth), _ptr(var)))
+        return rgb, depth, var
+
+    @_ordered
+    def image_metrics(self, rgb, depth, gt_depth=None, gt_color=None, want_residuals=False):
+        """nsk_image_metrics: residual sums of a rendered frame against the input frame -> dict with the counts and sums of include/nsk.h
+        (pixels, depth_pixels, depth_sum, color_terms, color_sum, nonfinite), h_out (the eight doubles), depth_l1 = depth_sum / depth_pixels
+        and psnr = -10 log10(color_sum / color_terms) formed on the host in double (None without the ground truth or without a term),
+        and with want_residuals res_depth [Hv, Wv] / res_color [Hv, Wv, 3] (cuda tensors; None without the ground truth).  Synchronises."""
+        import math
+        import torch
+        Hv, Wv = depth.shape
+        res_d = torch.empty_like(depth) if want_residuals and gt_depth is not None else None
+        res_c = torch.empty_like(rgb) if want_residuals and gt_color is not None else None
+        h = (C.c_double * 8)()
+        _chk(lib().nsk_image_metrics(self.h, int(Hv), int(Wv), _ptr(rgb), _ptr(depth), _ptr(gt_depth), _ptr(gt_color), _ptr(res_d), _ptr(res_c), h))
+        h = [float(x) for x in h]
+        out = dict(h_out=h, pixels=int(h[0]), depth_pixels=int(h[1]), depth_sum=h[2], color_terms=int(h[3]), color_sum=h[4], nonfinite=int(h[5]))
+        out["depth_l1"] = h[2] / h[1] if h[1] > 0 else None
+        out["psnr"] = (-10.0 * math.log10(h[4] / h[3]) if h[4] > 0 else math.inf) if h[3] > 0 else None
+        if want_residuals:
+            out["res_depth"], out["res_color"] = res_d, res_c
+        return out
 
     @_ordered
     def eval_points(self, stage, pts):
