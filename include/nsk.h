@@ -392,6 +392,19 @@ int nsk_allreduce_grads(nsk_ctx* ctx, void* nccl_comm);
  * 0 = automatic), each slab below the 2^26 samples of a launch: a small kernel writes the slab's points (12 B / node), the decoders'
  * forward launches of nsk_eval_points run on them, a finish kernel writes the scalars.  Values equal nsk_eval_points' bit for bit. */
 int nsk_eval_lattice(nsk_ctx* ctx, int stage, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, float* d_volume);
+/* The same at the nodes a validity mask keeps (d_valid: one byte per node on the device, laid out as d_volume; any non-zero byte counts as
+ * set, as in nsk_lattice_seen and nsk_mesh_extract).  A set node receives exactly the bits nsk_eval_lattice writes there (the "100 outside
+ * the bound" rule included; stage 3 gives the fine stage's occupancy); every other node receives the bits of `fill`, whatever they are
+ * (NaN payloads, -0.0).  Every node of d_volume is written.  nsk_mesh_extract with the same d_valid never uses the volume at an unset node
+ * (a cell is processed only when its eight corners are valid), so its mesh is the same bytes as from the dense volume, at the decoding
+ * cost of the set nodes alone.  The set nodes are counted per 256-node workgroup, the counts scanned (the multi-launch scan of
+ * nsk_mesh_extract: no atomics) and ranked into an ascending list of 32-bit node indices (4 B per set node; the unset nodes are filled in
+ * that pass); the slabs of nsk_eval_lattice (same size rule and "lattice_slab" key, applied to the list) then run over the list: a
+ * points kernel reads idx[m], the decoders' forward launches run, a finish kernel scatters to d_volume[idx[m]].  The count comes to the
+ * host between the two passes: the call's one synchronisation.  With no set node no decoder is launched.  n_evaluated (may be NULL)
+ * receives the number of set nodes.  At most 2^28 nodes per call (32-bit counts).  Not while a graph is being captured. */
+int nsk_eval_lattice_masked(nsk_ctx* ctx, int stage, const float h_origin[3], const float h_step[3], int nx, int ny, int nz,
+                            const uint8_t* d_valid, float fill, float* d_volume, long long* n_evaluated);
 
 /* Marching cubes on the device over a volume laid out as above (at least 2 nodes per axis, at most 2^28 nodes; steps > 0).
  *   - a node is INSIDE when value > level (occupancy grows into the solid);

@@ -801,6 +801,7 @@ struct nsk_ctx {
     // mesh extraction (nsk_eval_lattice / nsk_mesh_extract): slab points, per-node scratch, the table's device copy, the last mesh
     struct Mesh {
         Buf<float> lat_pts;                                  // [slab][3] points of the lattice slab being evaluated
+        Buf<unsigned> lat_idx, lat_scan;                     // nsk_eval_lattice_masked: [set nodes] ascending node indices; the workgroup counts' scan words
         int slab = 0;                                        // nsk_set_tuning "lattice_slab": nodes per slab (0 = automatic)
         Buf<uint8_t> cellcase; Buf<int> emap;                // [nodes], [nodes][3]: one group
         Buf<unsigned> scan;
@@ -2034,6 +2035,66 @@ static int mc_scan(nsk_ctx* c, unsigned* d, int n)
     CHK(mc_scan(c, sums, nb));
     k_mc_scan_add<<<nb, MC_BLOCK, 0, c->stream>>>(d, n, sums);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// nsk_eval_lattice at the nodes a mask keeps: count, scan and compact the set nodes into an ascending index list (the other nodes receive
+// `fill` in the compaction pass), then the slabs of nsk_eval_lattice walk that list instead of the lattice
+extern "C" int nsk_eval_lattice_masked(nsk_ctx* c, int stage, const float* o, const float* s, int nx, int ny, int nz, const uint8_t* valid, float fill,
+                                       float* vol, long long* n_evaluated)
+{
+    CHK(lattice_checks("nsk_eval_lattice_masked", c, o, s, nx, ny, nz, 1));
+    if (!valid) return fail("nsk_eval_lattice_masked: d_valid is NULL (nsk_eval_lattice evaluates every node)");
+    if (!vol) return fail("nsk_eval_lattice_masked: d_volume is NULL");
+    if (stage < 0 || stage > 3) return fail("bad stage %d", stage);
+    const int st = stage == NSK_COLOR ? NSK_FINE : stage;
+    CHK(check_stage(c, st));
+    const long long total = (long long)nx * ny * nz;
+    if (total > MC_MAX_NODES) return fail("nsk_eval_lattice_masked: %lld nodes, at most %lld per call", total, (long long)MC_MAX_NODES);
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Mesh& M = c->mesh;
+    if (n_evaluated) *n_evaluated = 0;
+    const int nn = (int)total, nb = (nn + MC_BLOCK - 1) / MC_BLOCK;
+    const size_t words = mc_scan_words((size_t)nb + 1);
+    CHK(grow(c, M.lat_scan, words, "the lattice mask's scan scratch", 0));
+    unsigned* boff = M.lat_scan;
+    unsigned fill_bits;
+    memcpy(&fill_bits, &fill, 4);
+    unsigned n_set = 0;
+    { ProfScope ps(c, "lattice_compact");
+      HIPCHK(hipMemsetAsync(boff, 0, words * 4, c->stream));            // (the slot behind the last workgroup count turns into the total)
+      k_lattice_flags<<<nb, MC_BLOCK, 0, c->stream>>>(nn, valid, boff);
+      HIPCHK(hipGetLastError());
+      CHK(mc_scan(c, boff, nb + 1));
+      HIPCHK(hipMemcpyAsync(&n_set, boff + nb, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      CHK(grow(c, M.lat_idx, (size_t)n_set, "the set nodes' indices", 0));
+      k_lattice_compact<<<nb, MC_BLOCK, 0, c->stream>>>(nn, valid, boff, n_set, fill_bits, M.lat_idx, reinterpret_cast<unsigned*>(vol));
+      HIPCHK(hipGetLastError()); }
+    if (n_evaluated) *n_evaluated = (long long)n_set;
+    if (n_set == 0) return 0;                                           // (no decoder launch, the workspace stays as it is)
+    long long slab = M.slab > 0 ? M.slab : std::max(c->ws.capM, 1 << 21);
+    slab = std::min(std::min(slab, (long long)n_set), (1LL << 26) - 1);
+    CHK(ensure_ws(c, 1, (int)slab));
+    CHK(grow(c, M.lat_pts, (size_t)slab * 3, "the lattice slab's points", 0));
+    McGeom G;
+    G.nx = nx; G.ny = ny; G.nz = nz; G.nn = nn; G.level = 0.f;
+    for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
+    float* pts = M.lat_pts;
+    for (long long m0 = 0; m0 < (long long)n_set; m0 += slab) {
+        const int cnt = (int)std::min(slab, (long long)n_set - m0);
+        const unsigned* idx = M.lat_idx.get() + m0;
+        { ProfScope ps(c, "lattice_points_idx"); k_lattice_points_idx<<<(cnt + 255) / 256, 256, 0, c->stream>>>(G, idx, cnt, pts); }
+        HIPCHK(hipGetLastError());
+        for (int q = 0; q < 3; ++q) {
+            const int w = STAGE_DEC[st][q];
+            if (w < 0) break;
+            CHK(launch_decode_fwd(c, w, cnt, 1, nullptr, nullptr, pts, false));
+        }
+        { ProfScope ps(c, "lattice_finish_idx");
+          k_lattice_finish_idx<<<(cnt + 255) / 256, 256, 0, c->stream>>>(cnt, pts, c->d_bound, st == 0 ? c->ws.occ[0] : c->ws.occ[1], st >= 2 ? c->ws.occ[2] : nullptr, idx, vol); }
+        HIPCHK(hipGetLastError());
+    }
     return 0;
 }
 

@@ -290,6 +290,53 @@ __global__ __launch_bounds__(256) void k_mc_scan_add(unsigned* __restrict__ d, i
     if (q < n) d[q] += sums[blockIdx.x];
 }
 
+// ---- lattice evaluation at the nodes a mask keeps (nsk_eval_lattice_masked) -----------------------------------------------
+// The set nodes (any non-zero byte) go into an ascending list of node indices, the decoders run on that list, the rest receives `fill`.
+// Count per workgroup -> mc_scan over the counts -> rank inside the workgroup: the list's order does not depend on scheduling.
+__global__ __launch_bounds__(256) void k_lattice_flags(int nn, const uint8_t* __restrict__ valid, unsigned* __restrict__ bsum)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    unsigned total;
+    mc_block_scan(n < nn && valid[n] != 0 ? 1u : 0u, &total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+// recomputes the flags; set node: idx[rank] = n (rank < n_set by construction: the guard only matters when the caller's mask changed
+// between the two passes); unset node: the volume receives the bits of `fill` here, so no later pass visits it
+__global__ __launch_bounds__(256) void k_lattice_compact(int nn, const uint8_t* __restrict__ valid, const unsigned* __restrict__ boff, unsigned n_set,
+                                                         unsigned fill_bits, unsigned* __restrict__ idx, unsigned* __restrict__ vol_bits)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const bool live = n < nn, set = live && valid[n] != 0;
+    unsigned total;
+    const unsigned rank = boff[blockIdx.x] + mc_block_scan(set ? 1u : 0u, &total);
+    if (set) { if (rank < n_set) idx[rank] = (unsigned)n; }
+    else if (live) vol_bits[n] = fill_bits;
+}
+// k_lattice_points for the listed nodes idx[0 .. cnt): the same products and sums, so the same bits
+__global__ __launch_bounds__(256) void k_lattice_points_idx(McGeom G, const unsigned* __restrict__ idx, int cnt, float* __restrict__ pts)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= cnt) return;
+    const int n = (int)idx[m], r = n / G.nx;
+    const int i = n % G.nx, j = r % G.ny, k = r / G.ny;
+    pts[3 * (size_t)m] = mc_coord(G.o[0], i, G.s[0]);
+    pts[3 * (size_t)m + 1] = mc_coord(G.o[1], j, G.s[1]);
+    pts[3 * (size_t)m + 2] = mc_coord(G.o[2], k, G.s[2]);
+}
+// k_lattice_finish scattered to the listed nodes (ascending indices: near-coalesced runs)
+__global__ __launch_bounds__(256) void k_lattice_finish_idx(int cnt, const float* __restrict__ pts, const float* __restrict__ bound6,
+                                                            const float* __restrict__ occ_a, const float* __restrict__ occ_b,
+                                                            const unsigned* __restrict__ idx, float* __restrict__ vol)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= cnt) return;
+    const float px = pts[3 * (size_t)m], py = pts[3 * (size_t)m + 1], pz = pts[3 * (size_t)m + 2];
+    const bool inb = px < bound6[1] && px > bound6[0] && py < bound6[3] && py > bound6[2] && pz < bound6[5] && pz > bound6[4];
+    float occ = occ_a[m];
+    if (occ_b) occ = occ_b[m] + occ;
+    vol[idx[m]] = inb ? occ : 100.f;
+}
+
 // ---- seen mask of a lattice (nsk_lattice_seen) -------------------------------------------------------------------------
 // One thread per node, x fastest.  A node is seen by keyframe k when it lies in front of the camera (which looks along -z), projects onto
 // a pixel at least `edge` pixels inside the image, that pixel carries a finite positive depth D, and the node is no farther than

@@ -23,13 +23,15 @@ class Mesher {
     Mesher(YAML::Node ns_config, torch::Tensor bound_3x2 = torch::Tensor(), float padding = 0.f);
     void set_bound(torch::Tensor bound_3x2);
     // nsk_eval_lattice (fine) -> nsk_mesh_extract -> (color) nsk_eval_points (color) on the device vertex buffer, rgb clamped to [0, 1] -> PLY.
-    // valid: optional uint8 / bool [resolution^3] (z, y, x order), 0 = cells touching the node are skipped.
+    // valid: optional uint8 / bool [resolution^3] (z, y, x order), 0 = cells touching the node are skipped; the lattice is then evaluated at
+    // the set nodes only (nsk_eval_lattice_masked, fill 100), which leaves the mesh unchanged.
     void get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, bool color = true,
                   torch::Tensor valid = torch::Tensor());
-    // The mesh of what the keyframes saw: lattice as in get_mesh -> nsk_lattice_seen over the keyframes in batches of at most 16 (depths: host
+    // The mesh of what the keyframes saw: nsk_lattice_seen on the lattice of get_mesh over the keyframes in batches of at most 16 (depths: host
     // tensors [H, W] of metric z-depth, 0 / NaN / inf = no measurement; c2ws: [4, 4] camera-to-world, camera looking along -z, inverted in
-    // double) -> nsk_mesh_extract with that mask -> nsk_mesh_filter (remove_small_geometry_threshold / get_largest_components) -> colour
-    // query on the filtered vertices -> PLY.  Lattice, mask and mesh stay on the device.
+    // double) -> nsk_eval_lattice_masked (fine) at the seen nodes, 100 elsewhere -> nsk_mesh_extract with that mask -> nsk_mesh_filter
+    // (remove_small_geometry_threshold / get_largest_components) -> colour query on the filtered vertices -> PLY.  Lattice, mask and mesh
+    // stay on the device.
     void get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
                         const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color = true);
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
@@ -47,4 +49,5 @@ class Mesher {
     int last_vertices = 0, last_triangles = 0;
     int last_components = 0, last_kept = 0;     // get_clean_mesh: components before the filter, components kept
     long long last_seen = 0;                    // get_clean_mesh: lattice nodes at least one keyframe saw
+    long long last_evaluated = 0;               // lattice nodes the decoders ran on (get_mesh without valid: all of them)
 };

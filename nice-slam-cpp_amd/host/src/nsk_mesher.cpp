@@ -91,11 +91,13 @@ void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::st
         dvalid.reset(new DevMem(nodes));
         if (hipMemcpy(dvalid->p, h.data_ptr<uint8_t>(), nodes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
     }
-    check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
+    long long n_eval = (long long)nodes;
+    if (dvalid) check(nsk_eval_lattice_masked(ctx(), NSK_FINE, origin, step, n, n, n, (const uint8_t*)dvalid->p, 100.f, (float*)vol.p, &n_eval));
+    else check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
     int nv = 0, nt = 0;
     check(nsk_mesh_extract(ctx(), (const float*)vol.p, dvalid ? (const uint8_t*)dvalid->p : nullptr, n, n, n, origin, step, level_set, &nv, &nt));
     write_context_mesh(path, color, nv, nt);
-    last_vertices = nv; last_triangles = nt;
+    last_vertices = nv; last_triangles = nt; last_evaluated = n_eval;
 }
 
 void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
@@ -115,7 +117,6 @@ void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<s
     }
     const size_t nodes = (size_t)n * n * n, img = (size_t)H * W;
     DevMem vol(nodes * sizeof(float)), seen(nodes);
-    check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
     // the seen mask, streamed: at most 16 depth images on the device at a time
     const int batch = 16, K = (int)depths.size();
     DevMem dimg((size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
@@ -137,11 +138,14 @@ void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<s
         check(nsk_lattice_seen(ctx(), origin, step, n, n, n, kb, (const float*)dimg.p, H, W, fx, fy, cx, cy, w2c.data(), seen_edge, seen_trunc, k0 > 0,
                                (uint8_t*)seen.p, k0 + kb >= K ? &n_seen : nullptr));
     }
+    // the decoders run at the seen nodes only: a cell with an unseen corner is not processed, so the extraction never uses the rest
+    long long n_eval = 0;
+    check(nsk_eval_lattice_masked(ctx(), NSK_FINE, origin, step, n, n, n, (const uint8_t*)seen.p, 100.f, (float*)vol.p, &n_eval));
     int nv = 0, nt = 0, nc = 0, nk = 0;
     check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)seen.p, n, n, n, origin, step, level_set, &nv, &nt));
     check(nsk_mesh_filter(ctx(), remove_small_geometry_threshold, get_largest_components ? 1 : 0, &nv, &nt, &nc, &nk));
     write_context_mesh(path, color, nv, nt);
-    last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen;
+    last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen; last_evaluated = n_eval;
 }
 
 void Mesher::write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int nv, const int32_t* tris, int nt)

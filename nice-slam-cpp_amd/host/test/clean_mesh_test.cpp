@@ -55,8 +55,9 @@ int main(int argc, char** argv)
         for (int64_t k = 0; k < depths.size(0); ++k) { dv.push_back(depths[k]); cv.push_back(c2ws[k]); }
         const float* in = intr.data_ptr<float>();
         mesher.get_clean_mesh(dir + "clean_mesh.ply", decoders, c, dv, cv, (int)depths.size(1), (int)depths.size(2), in[0], in[1], in[2], in[3], std::atoi(argv[3]) != 0);
-        std::printf("clean_mesh_test ok: %d vertices, %d triangles, %d components, %d kept, %lld seen\n", mesher.last_vertices, mesher.last_triangles,
-                    mesher.last_components, mesher.last_kept, mesher.last_seen);
+        std::printf("clean_mesh_test ok: %d vertices, %d triangles, %d components, %d kept, %lld seen, %lld evaluated of %lld nodes\n", mesher.last_vertices,
+                    mesher.last_triangles, mesher.last_components, mesher.last_kept, mesher.last_seen, mesher.last_evaluated,
+                    (long long)mesher.resolution * mesher.resolution * mesher.resolution);
         return 0;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "clean_mesh_test failed: %s\n", e.what());

@@ -25,7 +25,7 @@ SYMBOLS = (
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
     "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
-    "nsk_eval_lattice", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
+    "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
 )
@@ -60,6 +60,9 @@ def lib():
         L.nsk_decoder_param_count.argtypes = [C.c_int]
         L.nsk_stream.restype = C.c_void_p
         L.nsk_stream.argtypes = [C.c_void_p]
+        L.nsk_eval_lattice_masked.restype = C.c_int
+        L.nsk_eval_lattice_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                              C.c_void_p, C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
 
@@ -127,6 +130,7 @@ class Context:
         import torch
         self.h = C.c_void_p()
         self.device = int(device)
+        self.last_evaluated = None              # nodes the last eval_lattice with a mask decoded
         lib()
         if torch.cuda.is_available():
             self.tstream = stream if stream is not None else torch.cuda.Stream(self.device)
@@ -398,13 +402,31 @@ class Context:
         return raw
 
     @_ordered
-    def eval_lattice(self, stage, origin, step, nx, ny, nz):
-        """occupancy at the nodes origin + (i, j, k) * step -> float32 cuda tensor [nz, ny, nx] (nsk_eval_lattice)"""
+    def eval_lattice(self, stage, origin, step, nx, ny, nz, valid=None, fill=100.0, out=None):
+        """occupancy at the nodes origin + (i, j, k) * step -> float32 cuda tensor [nz, ny, nx] (nsk_eval_lattice).
+        valid: uint8 / bool cuda tensor of nz * ny * nx elements: only the nodes with a non-zero byte are decoded, the others receive the bits
+        of `fill` (a numpy float32 keeps its NaN payload) (nsk_eval_lattice_masked); the number of decoded nodes is left in
+        self.last_evaluated (None after a call without a mask).  out: a contiguous float32 cuda tensor of nz * ny * nx elements to write into
+        instead of a new one."""
         import numpy as np
         import torch
         o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
-        vol = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.float32, device="cuda:%d" % self.device)
-        _chk(lib().nsk_eval_lattice(self.h, _stage(stage), o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), _ptr(vol)))
+        nodes = int(nx) * int(ny) * int(nz)
+        if out is None:
+            vol = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.float32, device="cuda:%d" % self.device)
+        else:
+            assert out.dtype == torch.float32 and out.numel() == nodes
+            vol = out
+        if valid is None:
+            self.last_evaluated = None
+            _chk(lib().nsk_eval_lattice(self.h, _stage(stage), o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), _ptr(vol)))
+            return vol
+        assert valid.dtype in (torch.uint8, torch.bool) and valid.numel() == nodes
+        n = C.c_longlong(0)
+        f = C.c_float.from_buffer_copy(np.float32(fill).tobytes())            # (the bits as they are: a conversion may quieten or drop a NaN's payload)
+        _chk(lib().nsk_eval_lattice_masked(self.h, _stage(stage), o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz),
+                                           _ptr(valid), f, _ptr(vol), C.byref(n)))
+        self.last_evaluated = int(n.value)
         return vol
 
     @_ordered

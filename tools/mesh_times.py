@@ -1,7 +1,8 @@
 """times of the scene-mesh path on the reference bound: python tools/mesh_times.py [resolutions ...] (default 128 256 384)
 HIP events around every launch group (nsk_profile_begin / _end), 5 warm-ups, 20 repeats, medians in ms.  Per resolution: lattice evaluation
 (fine stage), each extraction pass with the bytes it must move and the time those bytes take at 8 TB/s, the seen mask over K = 16 synthetic
-keyframes (1 B per node + K H W 4 B), the component filter (12 B per vertex + 24 B per triangle read and written), the colour query on the vertices.
+keyframes (1 B per node + K H W 4 B), the lattice evaluation at the set nodes of that mask and of an all-ones mask (nsk_eval_lattice_masked,
+same process and context as the dense row, with their ratios to it and the seen fraction), the component filter (12 B per vertex + 24 B per triangle read and written), the colour query on the vertices.
 For 256 also what the same volume costs without nsk_eval_lattice: points built on the host, uploaded, nsk_eval_points in chunks, raw
 downloaded (host clock around synchronised work, 5 repeats)."""
 import os, sys, time
@@ -46,6 +47,15 @@ for n in res:
     nv, nt = verts.shape[0], tris.shape[0]
     sn, _ = medians(lambda: out.__setitem__("seen", ctx.lattice_seen(origin, step, n, n, n, kdepth, (KFX, KFX, KW / 2 - 0.5, KH / 2 - 0.5), kw2c, 0, 0.5)))
     valid, n_seen = out["seen"]
+    # the masked evaluation against the dense one above: under the seen mask (what get_clean_mesh pays) and under all ones (the pure overhead
+    # of counting, compacting and scattering); the dense call once more afterwards, so that a drift of the box over the run shows
+    ones = torch.ones_like(valid)
+    msk, _ = medians(lambda: out.__setitem__("mvol", ctx.eval_lattice("fine", origin, step, n, n, n, valid=valid)))
+    same_seen = bool((out["mvol"].view(torch.int32)[valid != 0] == vol.view(torch.int32)[valid != 0]).all()) and bool((out["mvol"][valid == 0] == 100.0).all())
+    one, _ = medians(lambda: out.__setitem__("mvol", ctx.eval_lattice("fine", origin, step, n, n, n, valid=ones)))
+    same_ones = bool((out["mvol"].view(torch.int32) == vol.view(torch.int32)).all())
+    lat2, _ = medians(lambda: ctx.eval_lattice("fine", origin, step, n, n, n))
+    del ones
 
     def culled():
         ctx.extract_mesh(vol, origin, step, 0.0, valid)
@@ -68,6 +78,11 @@ for n in res:
     print("extraction kernels %.3f ms (the call also synchronises twice and reads 8 bytes back)" % sum(ext.values()))
     must_seen = nodes * 1 + KF * KH * KW * 4
     print("seen mask (K = %d, %d x %d): %d of %d nodes seen, %.3f ms   %7.1f MB   %.3f ms at 8 TB/s" % (KF, KH, KW, n_seen, nodes, sn["lattice_seen"], must_seen / 1e6, 1e3 * must_seen / HBM))
+    t_lat, t_lat2 = sum(lat.values()), sum(lat2.values())
+    for name, t, same in (("seen mask (fraction %.3f)" % (n_seen / nodes), msk, same_seen), ("all-ones mask", one, same_ones)):
+        print("lattice evaluation, %s: %.3f ms = %.3f of dense (lattice_compact %.3f ms, same bits: %s)  %s" % (
+            name, sum(t.values()), sum(t.values()) / t_lat, t["lattice_compact"], same, {k: round(v, 3) for k, v in t.items()}))
+    print("lattice evaluation, dense again after them: %.3f ms (%.3f of the first)" % (t_lat2, t_lat2 / t_lat))
     must_flt = mv.shape[0] * 12 + mt.shape[0] * 24
     fk = {k: v for k, v in flt.items() if k.startswith("cc_")}
     print("filter of the culled mesh (%d vertices, %d triangles, %d components -> %d kept, %d vertices, %d triangles): %.3f ms   %7.1f MB   %.3f ms at 8 TB/s  %s" % (
