@@ -114,7 +114,9 @@ int nsk_set_sort_mode(nsk_ctx* ctx, int mode);
  *                      barrier (round 3's form) instead of by the backward launch's workgroups;
  *   "no_piggyback" 1:  a batch registered with nsk_map_prepare is sampled by launches of its own at the start of its step;
  *   "no_occ_role" 1 | 2: the forward's middle and fine decoders never | always as one workgroup role (default: where the split predicts
- *                      the shorter launch; same results either way). */
+ *                      the shorter launch; same results either way);
+ *   "no_dead_skip" 1:  the backward's frozen roles run every tile even where an optimiser mask discards all it scatters (see nsk_set_mask);
+ *   "dead_tile_pct" p: what a skipped tile counts for in the backward's workgroup split, in percent of a tile that runs (default 12). */
 int nsk_set_tuning(nsk_ctx* ctx, const char* key, int value);
 
 /* Scene bound [[x0,x1],[y0,y1],[z0,z1]]; the reference hard-codes it in five places
@@ -136,14 +138,17 @@ int nsk_grid_upload(nsk_ctx* ctx, int level, const float* h_czyx, int C, int Z, 
 int nsk_grid_download(nsk_ctx* ctx, int level, float* h_czyx);
 int nsk_grid_grad_download(nsk_ctx* ctx, int level, float* h_czyx);
 /* frustum feature selection (src/Mapper.cpp:254-290,333-350): h_mask_zyx[Z*Y*X] != 0 marks voxels that are
- * optimiser parameters; NULL = all voxels.  Gradients of unmarked voxels are discarded. */
+ * optimiser parameters; NULL = all voxels.  Gradients of unmarked voxels are discarded: nsk_grid_grad_download returns zeros for them,
+ * nsk_adam_step and nsk_grad_pack never read them, and in the raw slab (nsk_grad_slab) their entries are UNSPECIFIED -- whatever partial
+ * sums the scatter left there.  A frozen decoder's backward (no NSK_GRAD_RAYS) does not even run a 16-sample tile none of whose samples
+ * touches a marked voxel of its level, so those entries differ from build to build and with nsk_set_tuning("no_dead_skip", 1). */
 int nsk_set_mask(nsk_ctx* ctx, int level, const uint8_t* h_mask_zyx);
 
 /* Mapper::get_mask_from_c2w (src/Mapper.cpp:42-130, intended semantics): builds the frustum mask of `level` on the device from
  * a depth image (d_depth [H][W], device) and the current pose h_c2w (16 floats, row-major [4][4]) and installs it like
  * nsk_set_mask; h_mask_out [Z*Y*X] (host, may be NULL) receives a copy.  A voxel is kept if its centre projects inside the image
  * with 0 <= depth_along_-z <= sampled_depth + 0.5 (zero depths count as the maximum sampled depth) or lies within 0.5 m of the
- * camera centre; grid_coarse keeps every voxel. */
+ * camera centre; grid_coarse keeps every voxel.  Unmarked voxels' gradients: as for nsk_set_mask. */
 int nsk_frustum_mask(nsk_ctx* ctx, int level, const float* d_depth, int H, int W, float fx, float fy, float cx, float cy,
                      const float h_c2w[16], uint8_t* h_mask_out);
 
@@ -365,7 +370,7 @@ int nsk_zero_grads(nsk_ctx* ctx);
  * buffer so that a mapping step needs exactly one all-reduce.  The decoder gradients of a step
  * are summed into the slab lazily (inside nsk_adam_step when nobody looks earlier): nsk_grad_slab, nsk_allreduce_grads and
  * nsk_decoder_grad_download complete that sum first, so call nsk_grad_slab after nsk_map_step, every step, before reading
- * or exchanging the slab yourself. */
+ * or exchanging the slab yourself.  Entries of voxels an optimiser mask leaves unmarked are unspecified (nsk_set_mask). */
 int nsk_grad_slab(nsk_ctx* ctx, float** d_ptr, size_t* n_floats);
 /* The exchange in compact form.  Every rank holds the same optimiser masks (nsk_set_mask / nsk_frustum_mask), and Adam discards the
  * gradient of an unmarked voxel, so only marked voxels need to travel: nsk_grad_pack gathers, into one contiguous buffer, the marked
@@ -533,6 +538,12 @@ int nsk_debug_relu_bits(nsk_ctx* ctx, int which, int M, uint8_t* h_bits);
  * the sigma whose relu the compositing takes, include/torchlib/utils.h:160), 3 the colour decoder's output [M][4], 4 d loss / d raw [M][4], 5 z [M]. */
 int nsk_debug_fetch(nsk_ctx* ctx, int what, int M, float* h_out);
 int nsk_debug_preact(nsk_ctx* ctx, int which, int N, const float* d_rays_o, const float* d_rays_d, float* d_preact);
+/* nsk_debug_live_tiles: the dead-tile skip (nsk_set_mask) of the last step's backward, after a synchronise.  h_counts[0..2]: the 16-sample tiles the
+ * frozen role of the middle / fine / colour level ran (-1: the level had no frozen role; every tile where nothing was skipped), h_counts[3]: 1 if
+ * a role was skipping; h_counts[4..6]: the workgroups the launch gave the role of each level (frozen or trainable; 0: none, or one launch per
+ * decoder), h_counts[7]: the tiles of the batch -- h_counts has 8 entries.  h_perm [M] (may be NULL): the sample in each tile slot; h_bytes [M] (may be NULL): the slots' liveness bytes -- bit 0
+ * middle, 1 fine, 2 colour: the sample's cell at that level has a marked corner voxel (7 everywhere when the step wrote none). */
+int nsk_debug_live_tiles(nsk_ctx* ctx, int M, int* h_counts, int32_t* h_perm, uint8_t* h_bytes);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,23 @@ __global__ __launch_bounds__(1024) void k_mask_index(int nvox, const uint8_t* __
     if (threadIdx.x == 0) *count = base;
 }
 
+// Per-cell liveness of a masked level, once per mask: a cell (named by its lower corner voxel, as tri_setup's i0) is live when any of its eight
+// corner voxels is marked.  The corners are tri_setup's: the neighbour along an axis clamped into the grid, so a cell on an upper face sees only
+// the voxels a sample in it can reach.  The backward skips tiles of samples whose cells are all dead (decode_bwd_body<.., SKIP>).
+__global__ __launch_bounds__(256) void k_cell_live(int X, int Y, int Z, const uint8_t* __restrict__ mask, uint8_t* __restrict__ live)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= X * Y * Z) return;
+    const int ix = v % X, iy = (v / X) % Y, iz = v / (X * Y);
+    unsigned on = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int jx = min(ix + (c & 1), X - 1), jy = min(iy + ((c >> 1) & 1), Y - 1), jz = min(iz + (c >> 2), Z - 1);
+        on |= mask[(jz * Y + jy) * X + jx];
+    }
+    live[v] = on ? 1 : 0;
+}
+
 // the whole packed exchange buffer in ONE launch each way (it was one launch per level plus two copies: eleven small operations per
 // step around the all-reduce): segments = grid levels (32 floats per listed voxel), trainable decoders and the loss scalars (plain runs)
 struct XSeg { const int* idx; int n4; float* slab; float* buf; int blk_end;       // n4 = float4 count of the segment; idx != nullptr: voxel list, 8 float4 per voxel
@@ -707,6 +724,7 @@ struct GridState {
     Buf<uint8_t> mask;
     size_t g_off = 0;            // offset in the gradient slab
     Buf<int> midx; int nmask = 0; bool midx_dirty = true;      // ascending list of the marked voxels (packed gradient exchange)
+    Buf<uint8_t> live; bool live_dirty = true;                 // per cell: any corner voxel marked (k_cell_live); rebuilt like midx when the mask changed
 };
 struct DecState {
     int n = 0;                                    // parameter count; set once the one-time setup is complete (0 = never uploaded)
@@ -739,6 +757,8 @@ struct Workspace {
     // second set of the sampling outputs: nsk_map_prepare fills it on the side stream while the current step runs; a step that finds its
     // batch prepared swaps the buffers above with these
     Buf<float> z_alt; Buf<int> perm_alt, skey_alt, srank_alt, offs_alt;
+    // liveness bytes (LiveArgs): by sample as k_sample writes them, by slot as k_sort_place re-orders them (ray order: the samples' are the slots')
+    Buf<uint8_t> lsamp, lslot, lsamp_alt, lslot_alt;
 };
 struct nsk_ctx {
     int device = 0;
@@ -781,6 +801,17 @@ struct nsk_ctx {
     int tune_frozen_cost_rays = 0;          // > 0: the same for launches with ray gradients (bundle adjustment: the frozen roles also carry g_e and d/dp)
     int tune_frozen_mid_pct = 100;          // the middle decoder's frozen tile against the fine one's, in percent (its level has 8x the samples per voxel: more same-line atomics)
     int tune_no_frozen_kernel = 0;          // 1: launches without a trainable role also go through k_decode_bwd_multi (experiments, tests)
+    // ---- dead-tile skip of the frozen roles under optimiser masks (decode_bwd_body<.., SKIP>)
+    int tune_no_dead_skip = 0;              // 1: every tile runs (A/B runs, tests)
+    int tune_dead_tile_pct = 12;            // what a skipped tile costs in the workgroup split, in percent of a tile that runs (its staged loads and the loop)
+    int live_epoch = 0;                     // bumped whenever a mask or a masked level changes: liveness bytes written before are stale
+    bool live_ok = false;                   // the primary sampling set holds liveness bytes for the current step (forward_core)
+    Buf<int> live_cnt;                      // device: tiles run by [middle, fine, colour] + the publishing ticket
+    int* live_host = nullptr; int* live_host_dev = nullptr;      // host memory the last counting workgroup writes [3 counts, tag]; never waited for
+    int live_tag = 1;                       // names the current (stage, batch size, flags, masks) of the counts: a step reads only counts of its own kind
+    int live_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    int dbg_wgs[3] = {0, 0, 0}, dbg_ntasks = 0;      // the last backward's split: workgroups of the role of each level (frozen or trainable), its tile count
+    int dbg_live[3] = {-1, -1, -1}; bool dbg_counted[3] = {false, false, false};      // the last backward: tiles per level (-1 no frozen role), which of them the device counts
     const uint8_t* ray_mask = nullptr;      // nsk_set_ray_mask
     // nsk_set_depth_max_batch: the batch whose max(gt_depth) the sampling uses when gt_depth_max < 0 (a ray shard of a larger batch: N > 1)
     struct DMax { const float* gt = nullptr; const uint8_t* keep = nullptr; int n = 0; } dmax;
@@ -791,7 +822,8 @@ struct nsk_ctx {
     // Adam + place): `req` is a registered batch nothing has been launched for yet, `prep` the batch whose outputs sit (or are being built) in the
     // workspace's second set; done: bit 0 sampled, 1 offsets scanned, 2 placed
     struct Prep { bool valid = false; int stage = 0, N = 0, S = 0; const float* ro = nullptr; const float* rd = nullptr; const float* gt = nullptr;
-                  float gtmax = 0.f; const uint8_t* mask = nullptr; bool sorted = false; int done = 0; RParams R; DMax dmax; } prep, req;
+                  float gtmax = 0.f; const uint8_t* mask = nullptr; bool sorted = false; int done = 0; RParams R; DMax dmax;
+                  bool live = false; int live_epoch = 0; } prep, req;      // live: its sampling wrote liveness bytes, under the masks of live_epoch
     int tune_no_piggyback = 0;              // 1: a prepared batch is sampled by launches of its own at the start of its step (experiments, tests)
     int pend_w = -1, pend_nb = 0;           // decoder whose per-workgroup gradient slabs are not yet summed into the slab (flush_pending)
     int dbg_M = 0, dbg_S = 0;               // sample count / samples per ray of the last forward_core (nsk_debug_relu_bits, nsk_debug_preact)
@@ -882,6 +914,7 @@ nsk_ctx::~nsk_ctx()
     invalidate_graphs(this);
     for (auto& r : prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     if (own_stream && stream) hipStreamDestroy(stream);
+    if (live_host) hipHostFree(live_host);
 }
 
 // ---- growing a buffer ---------------------------------------------------------------------------------------------
@@ -959,6 +992,11 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     HIPCHK(hipMemcpy(c->d_bound, b, sizeof(b), hipMemcpyHostToDevice));
     CHK(dev_alloc(c->scal, 16, "the scalars"));
     HIPCHK(hipMemset(c->scal, 0, 16 * sizeof(float)));
+    CHK(dev_alloc(c->live_cnt, 4, "the live-tile counters"));
+    HIPCHK(hipMemset(c->live_cnt, 0, 4 * sizeof(int)));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->live_host), 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->live_host, 0, 16 * sizeof(int));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->live_host_dev), c->live_host, 0));
     // dynamic LDS limits
     CHK(set_lds(k_decode_fwd<0>, fwd_img_floats(0) * 4)); CHK(set_lds(k_decode_fwd<1>, fwd_img_floats(1) * 4));
     CHK(set_lds(k_decode_fwd<2>, fwd_img_floats(2) * 4)); CHK(set_lds(k_decode_fwd<3>, fwd_img_floats(3) * 4));
@@ -1039,6 +1077,8 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "no_occ_role")) { c->tune_no_occ_role = value; return 0; }
     if (!strcmp(key, "fwd_color_cost")) { c->tune_fwd_color_cost = value; return 0; }
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
+    if (!strcmp(key, "no_dead_skip")) { c->tune_no_dead_skip = value; return 0; }
+    if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune_dead_tile_pct = value; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     return fail("nsk_set_tuning: unknown key '%s'", key);
@@ -1105,7 +1145,7 @@ static int grid_upload(nsk_ctx* c, GridState& G, const float* h, int C, int Z, i
         CHK(dev_alloc(G.v, n, "a grid level")); CHK(dev_alloc(G.m, n, "a grid level's first moment")); CHK(dev_alloc(G.s, n, "a grid level's second moment"));
     }
     if (G.Z != Z || G.Y != Y || G.X != X) { if (G.mask) { CHK(grow_begin(c, GROW_STALE_GRAPHS)); G.mask.reset(); } }
-    G.C = C; G.Z = Z; G.Y = Y; G.X = X; G.n = n; G.midx_dirty = true;
+    G.C = C; G.Z = Z; G.Y = Y; G.X = X; G.n = n; G.midx_dirty = true; G.live_dirty = true; ++c->live_epoch;
     std::vector<float> t(n);
     for (int ch = 0; ch < 32; ++ch)
         for (size_t v = 0; v < nvox; ++v) t[v * 32 + ch] = h[(size_t)ch * nvox + v];
@@ -1172,7 +1212,7 @@ extern "C" int nsk_set_mask(nsk_ctx* c, int level, const uint8_t* h_mask)
     if (c->capturing) return fail("nsk_set_mask: not while a graph is being captured");
     HIPCHK(hipStreamSynchronize(c->stream));
     size_t nvox = G.n / 32;
-    G.midx_dirty = true;
+    G.midx_dirty = true; G.live_dirty = true; ++c->live_epoch;
     // A captured step holds the level's voxel list as kernel arguments (its pointer, its length and the block ranges derived from it:
     // k_adam_multi, k_xchg_multi): new mask CONTENTS make every recorded graph wrong, not only a new allocation.
     invalidate_graphs(c);
@@ -1447,6 +1487,7 @@ static int ensure_ws(nsk_ctx* c, int N, int M)
         CHK(dev_alloc(w.dec_slabs, slabs, "the decoder gradient slabs"));
         HIPCHK(hipMemsetAsync(w.dec_slabs, 0, slabs * 4, c->stream));
         CHK(dev_alloc(w.perm, m, "the cell sort")); CHK(dev_alloc(w.skey, m, "the cell sort")); CHK(dev_alloc(w.srank, m, "the cell sort"));
+        CHK(dev_alloc(w.lsamp, m, "the liveness bytes")); CHK(dev_alloc(w.lslot, m, "the liveness bytes"));
         return 0;
     }();
     if (r != 0) { w = Workspace(); return r; }
@@ -1587,12 +1628,16 @@ static int launch_decode_bwd(nsk_ctx* c, int w, int M, int S, const float* ro, c
 }
 
 // split num_cu workgroups over roles in proportion to their cost per task (every role gets at least one)
-static void split_wgs(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8)
+// tasks (optional): per role, the tiles it is expected to RUN (a frozen role under an optimiser mask skips its dead tiles: backward_core), in
+// place of ntasks; the cap on a role's workgroups stays with ntasks, the tiles it walks
+static void split_wgs(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8, const int* tasks = nullptr)
 {
-    int cap = std::max(1, (ntasks + waves - 1) / waves), tot = 0, used = 0;
-    for (int r = 0; r < n; ++r) tot += cost[r];
+    int cap = std::max(1, (ntasks + waves - 1) / waves), used = 0;
+    double tot = 0;
+    auto load = [&](int r) { return (double)cost[r] * (tasks ? std::max(1, tasks[r]) : ntasks); };
+    for (int r = 0; r < n; ++r) tot += load(r);
     for (int r = 0; r < n; ++r) {
-        int k = std::max(1, (int)((double)num_cu * cost[r] / tot));
+        int k = std::max(1, (int)((double)num_cu * load(r) / tot));
         k = std::min(k, cap);
         used += k;
         wg_end[r] = used;
@@ -1602,14 +1647,14 @@ static void split_wgs(int num_cu, int ntasks, int n, const int* cost, int* wg_en
 // Cost-proportional shares, then single workgroups moved from the role that would suffer least to the role that finishes last while
 // the modelled makespan (whole tiles per wave x cost) falls: a role's time is a step function of its workgroups, and the
 // proportional split alone left the forward 3-5 % behind the best split whenever a role sat just past a step (K3, K4 shard).
-static void split_wgs_balanced(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8)
+static void split_wgs_balanced(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8, const int* tasks = nullptr)
 {
-    split_wgs(num_cu, ntasks, n, cost, wg_end, waves);
+    split_wgs(num_cu, ntasks, n, cost, wg_end, waves, tasks);
     int w[4];
     for (int r = 0; r < n; ++r) w[r] = wg_end[r] - (r ? wg_end[r - 1] : 0);
     int used = wg_end[n - 1];
     const int cap = std::max(1, (ntasks + waves - 1) / waves);
-    auto t_of = [&](int r, int wr) { return (long)((ntasks + waves * wr - 1) / (waves * wr)) * cost[r]; };
+    auto t_of = [&](int r, int wr) { return (long)(((tasks ? tasks[r] : ntasks) + waves * wr - 1) / (waves * wr)) * cost[r]; };
     for (int r = 0; used < num_cu && r < 8 * n; ++r) {      // hand out what the rounding left, to whoever finishes last
         int worst = 0;
         for (int q = 1; q < n; ++q) if (t_of(q, w[q]) > t_of(worst, w[worst])) worst = q;
@@ -1639,11 +1684,12 @@ static void split_wgs_balanced(int num_cu, int ntasks, int n, const int* cost, i
 // lockstep), so its time is ceil(groups / workgroups) iterations -- a step function -- while a frozen role's time falls
 // smoothly with its workgroups.  Pick the trainable role's share by minimising the modelled makespan instead of in
 // proportion to cost (1024 rays: 3 iterations with the proportional 191 workgroups, 2 with 192).
-static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int train_role, int* wg_end)
+static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int train_role, int* wg_end, const int* tasks = nullptr)
 {
     const int groups = std::max(1, (ntasks + 7) / 8);
-    int fsum = 0;
-    for (int r = 0; r < n; ++r) if (r != train_role) fsum += cost[r];
+    // a frozen role's share of the workgroups the trainable role leaves: in proportion to cost x the tiles it runs
+    long fload[3] = {0, 0, 0}, fsum = 0;
+    for (int r = 0; r < n; ++r) if (r != train_role) { fload[r] = (long)cost[r] * std::max(1, tasks ? tasks[r] : ntasks); fsum += fload[r]; }
     // For every iteration count the role could run, give it the FEWEST workgroups that reach it: more would not shorten it (its time is
     // a step function) and would starve the frozen roles (1250 rays: 3 iterations need 157 workgroups; the 190 a cost-proportional
     // split hands it left the frozen roles as the kernel's tail, 120 us against 94 us).
@@ -1656,8 +1702,8 @@ static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int 
         const int rest = num_cu - wt;
         for (int r = 0; r < n; ++r) {
             if (r == train_role) continue;
-            const int wr = std::max(1, (int)((long)rest * cost[r] / std::max(1, fsum)));
-            t = std::max(t, (long)((ntasks + 8 * wr - 1) / (8 * wr)) * cost[r]);
+            const int wr = std::max(1, (int)((long)rest * fload[r] / std::max(1L, fsum)));
+            t = std::max(t, (long)(((tasks ? tasks[r] : ntasks) + 8 * wr - 1) / (8 * wr)) * cost[r]);
         }
         if (best < 0 || t < best) { best = t; best_wt = wt; }
         if ((long)iters * cost[train_role] > best) break;          // more iterations only get slower from here
@@ -1665,7 +1711,7 @@ static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int 
     const int rest = num_cu - best_wt;
     int used = 0;
     for (int r = 0; r < n; ++r) {
-        int k = r == train_role ? best_wt : std::max(1, (int)((long)rest * cost[r] / std::max(1, fsum)));
+        int k = r == train_role ? best_wt : std::max(1, (int)((long)rest * fload[r] / std::max(1L, fsum)));
         k = std::min(k, std::max(1, (ntasks + 7) / 8));
         used += k;
         wg_end[r] = used;
@@ -1673,12 +1719,12 @@ static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int 
 }
 
 // predicted time of a split in the cost units of its roles: every wave of a role walks ceil(tiles / waves) tiles
-static long split_makespan(int ntasks, int n, const int* cost, const int* wg_end, int waves = 8)
+static long split_makespan(int ntasks, int n, const int* cost, const int* wg_end, int waves = 8, const int* tasks = nullptr)
 {
     long t = 0;
     for (int r = 0; r < n; ++r) {
         const int w = std::max(1, wg_end[r] - (r ? wg_end[r - 1] : 0));
-        t = std::max(t, (long)((ntasks + waves * w - 1) / (waves * w)) * cost[r]);
+        t = std::max(t, (long)(((tasks ? tasks[r] : ntasks) + waves * w - 1) / (waves * w)) * cost[r]);
     }
     return t;
 }
@@ -1793,8 +1839,52 @@ static int stage_key_level(int stage)
     for (int q = 0; q < 3; ++q) if (STAGE_DEC[stage][q] >= 0) key_level = STAGE_DEC[stage][q];      // the finest level the stage reads
     return key_level;
 }
+// ---- liveness bytes for the backward's dead-tile skip -------------------------------------------------------------------------------------
+// A step that forms a loss writes them with its sampling when a level its decoders read carries an optimiser mask; no mask, the deterministic
+// mode or nsk_set_tuning("no_dead_skip", 1): none are written and the backward runs every tile through the body it always had.
+static bool live_wanted(nsk_ctx* c, int stage, bool save_masks)
+{
+    if (!save_masks || c->tune_no_dead_skip || c->deterministic) return false;
+    for (int q = 0; q < 3; ++q) { const int w = STAGE_DEC[stage][q]; if (w >= 1 && c->grid[w].mask) return true; }
+    return false;
+}
+static int ensure_live(nsk_ctx* c, int l)
+{
+    GridState& G = c->grid[l];
+    if (!G.mask || !G.live_dirty) return 0;
+    if (c->capturing) return fail("graph capture: a mask changed since the last eager step (run the step once after installing masks, then capture)");
+    const size_t nvox = G.n / 32;
+    CHK(grow(c, G.live, nvox, "the live-cell table", GROW_STALE_GRAPHS));
+    k_cell_live<<<(int)((nvox + 255) / 256), 256, 0, c->stream>>>(G.X, G.Y, G.Z, G.mask, G.live);
+    HIPCHK(hipGetLastError());
+    G.live_dirty = false;
+    return 0;
+}
+static int ensure_live_stage(nsk_ctx* c, int stage)
+{
+    for (int q = 0; q < 3; ++q) { const int w = STAGE_DEC[stage][q]; if (w >= 1) CHK(ensure_live(c, w)); }
+    return 0;
+}
+static void live_args(nsk_ctx* c, LiveArgs& L, int stage, uint8_t* out)
+{
+    memset(&L, 0, sizeof(L));
+    L.out = out;
+    if (!out) return;
+    const int key = stage_key_level(stage);
+    const GridState& KG = c->grid[key];
+    for (int q = 0; q < 3; ++q) {
+        const int w = STAGE_DEC[stage][q];
+        if (w < 1) continue;
+        const GridState& G = c->grid[w];
+        if (!G.mask || G.live_dirty) continue;       // no mask on the level: its bit is always set
+        const int k = w - 1;
+        L.lv[k] = G.live; L.X[k] = G.X; L.Y[k] = G.Y; L.Z[k] = G.Z;
+        L.src[k] = (w == key || (G.X == KG.X && G.Y == KG.Y && G.Z == KG.Z)) ? 0 : ((w == 1 && stage >= 2) ? 1 : 2);
+    }
+}
+
 static void samp_args(nsk_ctx* c, SampArgs& A, const RParams& R, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax,
-                      const float* gmax_dev, const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, const nsk_ctx::DMax& dm)
+                      const float* gmax_dev, const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, const nsk_ctx::DMax& dm, uint8_t* lsamp = nullptr)
 {
     const GridState& KG = c->grid[stage_key_level(stage)];
     const GridState* PG = stage >= 2 ? &c->grid[1] : nullptr;      // parent level whose cells order the samples inside a key cell (k_sample)
@@ -1804,6 +1894,7 @@ static void samp_args(nsk_ctx* c, SampArgs& A, const RParams& R, int stage, int 
     A.kX = KG.X; A.kY = KG.Y; A.kZ = KG.Z; A.pX = PG ? PG->X : 0; A.pY = PG ? PG->Y : 0; A.pZ = PG ? PG->Z : 0; A.ncell2 = (int)((bins / 8 + 1) / 2);
     A.skey = sorted ? skey : nullptr; A.srank = srank; A.hist = c->ws.hist();
     if (dm.n > 0) { A.mx_gt = dm.gt; A.mx_keep = dm.keep; A.mx_n = dm.n; } else { A.mx_gt = gt; A.mx_keep = mask; A.mx_n = N; }
+    live_args(c, A.L, stage, lsamp);
 }
 // halves: 256-cell chunks per workgroup (1: k_sort_scan, 2: the role inside k_decode_bwd_multi)
 static ScanArgs scan_args(nsk_ctx* c, int stage, int* offs, int halves)
@@ -1813,9 +1904,10 @@ static ScanArgs scan_args(nsk_ctx* c, int stage, int* offs, int halves)
     A.nblocks = (int)((bins + 2048 * (size_t)halves - 1) / (2048 * (size_t)halves));
     return A;
 }
-static PlaceArgs place_args(int M, const int* skey, const int* srank, const int* offs, int* perm)
+static PlaceArgs place_args(int M, const int* skey, const int* srank, const int* offs, int* perm, const uint8_t* lsamp = nullptr, uint8_t* lslot = nullptr)
 {
     PlaceArgs A; A.M = M; A.skey = skey; A.srank = srank; A.offs = offs; A.perm = perm; A.nblocks = (M + 255) / 256;
+    A.live_in = lsamp; A.live_out = lsamp ? lslot : nullptr;
     return A;
 }
 // the batch maximum of gt_depth has to come from a launch of its own (k_sample's waves take it themselves for smaller batches)
@@ -1823,7 +1915,8 @@ static bool needs_depth_max(const float* gt, float gtmax, int N, const nsk_ctx::
 
 // sampling (+ cell sort) of one batch into the given output set by launches of its own; `done`: stages that have already run (nsk_ctx::Prep)
 static int launch_sampling(nsk_ctx* c, const RParams& R, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax,
-                           const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, int* offs, int* perm, const nsk_ctx::DMax& dm, int done = 0)
+                           const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, int* offs, int* perm, const nsk_ctx::DMax& dm, int done = 0,
+                           uint8_t* lsamp = nullptr, uint8_t* lslot = nullptr)      // lsamp: also the liveness bytes (live_wanted), by sample and, sorted, by slot
 {
     const int M = N * S;
     hipStream_t st = c->stream;
@@ -1837,13 +1930,13 @@ static int launch_sampling(nsk_ctx* c, const RParams& R, int stage, int N, int S
         }
         ProfScope ps(c, "sample");
         SampArgs A;
-        samp_args(c, A, R, stage, N, S, ro, rd, gt, gtmax, gmax_dev, mask, sorted, z, skey, srank, dm);
+        samp_args(c, A, R, stage, N, S, ro, rd, gt, gtmax, gmax_dev, mask, sorted, z, skey, srank, dm, lsamp);
         k_sample<<<(N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS, 64 * NSK_SAMPLE_RAYS, 0, st>>>(A);
     }
     if (sorted && (done & 6) != 6) {
         ProfScope ps(c, "cell_sort");
         if (!(done & 2)) { const ScanArgs A = scan_args(c, stage, offs, 1); k_sort_scan<<<A.nblocks, 256, 0, st>>>(A); }
-        if (!(done & 4)) { const PlaceArgs A = place_args(M, skey, srank, offs, perm); k_sort_place<<<A.nblocks, 256, 0, st>>>(A); }
+        if (!(done & 4)) { const PlaceArgs A = place_args(M, skey, srank, offs, perm, lsamp, lslot); k_sort_place<<<A.nblocks, 256, 0, st>>>(A); }
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1857,7 +1950,12 @@ static int prep_finish(nsk_ctx* c)
     const int all = P.sorted ? 7 : 1;
     if ((P.done & all) == all) return 0;
     Workspace& w = c->ws;
-    CHK(launch_sampling(c, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, P.mask, P.sorted, w.z_alt, w.skey_alt, w.srank_alt, w.offs_alt, w.perm_alt, P.dmax, P.done));
+    if (!(P.done & 1)) {            // not sampled yet: under the masks of now
+        P.live = live_wanted(c, P.stage, true); P.live_epoch = c->live_epoch;
+        if (P.live) CHK(ensure_live_stage(c, P.stage));
+    }
+    CHK(launch_sampling(c, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, P.mask, P.sorted, w.z_alt, w.skey_alt, w.srank_alt, w.offs_alt, w.perm_alt, P.dmax, P.done,
+                        P.live ? w.lsamp_alt.get() : nullptr, w.lslot_alt));
     P.done = all;
     return 0;
 }
@@ -1877,8 +1975,9 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
 {
     const int M = N * S;
     const uint8_t* mask = save_masks ? c->ray_mask : nullptr;      // (only the steps that form a loss honour it; a plain render shows every ray)
+    const bool want_live = live_wanted(c, stage, save_masks);
     auto is_this_batch = [&](const nsk_ctx::Prep& X) {
-        return X.valid && save_masks && !c->capturing && X.stage == stage && X.N == N && X.S == S && X.ro == ro && X.rd == rd && X.gt == gt && X.gtmax == gtmax &&
+        return X.valid && save_masks && (!(X.done & 1) || (X.live == want_live && (!X.live || X.live_epoch == c->live_epoch))) && !c->capturing && X.stage == stage && X.N == N && X.S == S && X.ro == ro && X.rd == rd && X.gt == gt && X.gtmax == gtmax &&
                X.mask == mask && X.sorted == sorted && memcmp(&X.R, &c->R, sizeof(RParams)) == 0 &&
                X.dmax.gt == c->dmax.gt && X.dmax.keep == c->dmax.keep && X.dmax.n == c->dmax.n;
     };
@@ -1889,14 +1988,19 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
         Workspace& w = c->ws;
         w.z.swap(w.z_alt); w.perm.swap(w.perm_alt); w.skey.swap(w.skey_alt); w.srank.swap(w.srank_alt);
         w.offs.swap(w.offs_alt);                            // (both sets are kept at the same capacities: ensure_alt)
+        w.lsamp.swap(w.lsamp_alt); w.lslot.swap(w.lslot_alt);
         c->ws_flip ^= 1;
         P.valid = false;
         c->sorted = sorted;
+        c->live_ok = P.live;
     } else {
         if (is_this_batch(c->req)) c->req.valid = false;    // registered, but no step came by to carry its sampling: sampled here like any other batch
         c->sorted = sorted;
         if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
-        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.z, c->ws.skey, c->ws.srank, c->ws.offs, c->ws.perm, dmax ? *dmax : c->dmax));
+        if (want_live) CHK(ensure_live_stage(c, stage));
+        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.z, c->ws.skey, c->ws.srank, c->ws.offs, c->ws.perm, dmax ? *dmax : c->dmax, 0,
+                            want_live ? c->ws.lsamp.get() : nullptr, c->ws.lslot));
+        c->live_ok = want_live;
     }
     CHK(launch_decode_fwd_stage(c, stage, M, S, ro, rd, save_masks));
     c->dbg_M = M; c->dbg_S = S;
@@ -2315,6 +2419,8 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     const bool rays = (flags & NSK_GRAD_RAYS) != 0;
     const bool grids = (flags & NSK_GRAD_GRIDS) != 0;
     const int M = N * S;
+    for (int k = 0; k < 3; ++k) { c->dbg_live[k] = -1; c->dbg_counted[k] = false; c->dbg_wgs[k] = 0; }      // (nsk_debug_live_tiles: this backward's, whichever way it leaves)
+    c->dbg_ntasks = (M + 15) / 16;
     CHK(flush_pending(c));                      // gradients accumulate across calls: the slabs are about to be overwritten
     MultiArgs MA;
     memset(&MA, 0, sizeof(MA));
@@ -2355,6 +2461,7 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     if ((n == 0 || train_role == -2 || separate) && d_loss) { ProfScope ps(c, "loss_sum"); k_sum<<<1, 1024, 0, c->stream>>>(N, c->ws.ray_loss, d_loss); }
     if (n == 0) return 0;
     if (train_role == -2 || separate) {      // rare configuration (several trainable decoders share one slab buffer): one launch each
+        for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = c->dbg_ntasks;
         for (int r = 0; r < n; ++r)
             CHK(launch_decode_bwd(c, MA.which[r], M, S, ro, rd, MA.train[r] != 0, rays, flags, g_ro, g_rd));
         return 0;
@@ -2364,8 +2471,39 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     // gradients the frozen bodies need 160 VGPRs (the Tracker: 600 tiles, latency-bound either way) and stay in k_decode_bwd_multi
     const bool full = c->bwd_mode == 0;                 // every chain on the fp32 MFMA: k_decode_bwd_multi_full, nothing rides
     const bool frozen_only = train_role == -1 && !rays && !c->tune_no_frozen_kernel && !full;
-    if (train_role >= 0 && n > 1) split_wgs_train(c->num_cu, (M + 15) / 16, n, cost, train_role, MA.wg_end);
-    else split_wgs_balanced(c->num_cu, (M + 15) / 16, n, cost, MA.wg_end, frozen_only ? NSK_FROZEN_NW : 8);
+    // Dead-tile skip: a frozen role whose level carries an optimiser mask walks the slots' liveness bytes (forward_core) and runs only the tiles
+    // with a sample that reaches a marked voxel.  Never with ray gradients (d/dp flows through every sample), the Tracker's launch or the
+    // full-width chains.  The roles count what they ran; the count of an EARLIER step of the same kind (whatever has arrived in live_host: nobody
+    // waits for it) tells the split how long the frozen roles really are -- the first step of a kind assumes every tile runs.
+    const int ntasks = (M + 15) / 16;
+    int tasks[3] = {ntasks, ntasks, ntasks};
+    bool counted[3] = {false, false, false};
+    for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = ntasks;
+    if (c->live_ok && grids && !rays && !full && !dyn_resid && !c->tune_no_dead_skip) {
+        const int key[8] = {stage, M, (int)(flags & 0xffu), c->sorted ? 1 : 0, c->live_epoch, n, train_role, frozen_only ? 1 : 0};
+        if (memcmp(key, c->live_key, sizeof(key)) != 0) { memcpy(c->live_key, key, sizeof(key)); ++c->live_tag; }
+        const volatile int* h = c->live_host;
+        const bool fresh = h[3] == c->live_tag;
+        for (int r = 0; r < n; ++r) {
+            const int w = MA.which[r];
+            if (MA.train[r] || w < 1 || !c->grid[w].mask || c->grid[w].live_dirty) continue;
+            DecArgs& A = MA.a[r];
+            A.live = c->sorted ? c->ws.lslot : c->ws.lsamp; A.live_bit = 1u << (w - 1); A.live_cnt = c->live_cnt + (w - 1);
+            counted[r] = true; c->dbg_counted[w - 1] = true;
+            if (fresh) {
+                const int lv = std::max(0, std::min(ntasks, (int)h[w - 1]));
+                tasks[r] = lv + (int)((long)(ntasks - lv) * c->tune_dead_tile_pct / 100);
+            }
+        }
+    }
+    if (train_role >= 0 && n > 1) split_wgs_train(c->num_cu, ntasks, n, cost, train_role, MA.wg_end, tasks);
+    else split_wgs_balanced(c->num_cu, ntasks, n, cost, MA.wg_end, frozen_only ? NSK_FROZEN_NW : 8, tasks);
+    for (int r = 0; r < n; ++r) {
+        const int wgs = MA.wg_end[r] - (r ? MA.wg_end[r - 1] : 0);
+        if (counted[r]) MA.live_wgs += wgs;
+        if (MA.which[r] >= 1) c->dbg_wgs[MA.which[r] - 1] = wgs;
+    }
+    MA.live_cnt = c->live_cnt; MA.live_out = c->live_host_dev; MA.live_tag = c->live_tag;
     const int extra = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
     if (d_loss) { MA.sum_src = c->ws.ray_loss; MA.sum_dst = d_loss; MA.sum_n = N; }
     // the prepared batch's cell-sort offsets ride behind the roles (nsk_map_prepare): short workgroups that wait for nothing of this launch
@@ -2433,9 +2571,10 @@ static int ensure_alt(nsk_ctx* c, bool need_offs)
     const int r = [&]() -> int {
         CHK(grow(c, w.z_alt, m, "the second sampling set", 0)); CHK(grow(c, w.perm_alt, m, "the second sampling set", 0));
         CHK(grow(c, w.skey_alt, m, "the second sampling set", 0)); CHK(grow(c, w.srank_alt, m, "the second sampling set", 0));
+        CHK(grow(c, w.lsamp_alt, m, "the second sampling set", 0)); CHK(grow(c, w.lslot_alt, m, "the second sampling set", 0));
         return 0;
     }();
-    if (r != 0) { reset_all(w.z_alt, w.perm_alt, w.skey_alt, w.srank_alt); return r; }
+    if (r != 0) { reset_all(w.z_alt, w.perm_alt, w.skey_alt, w.srank_alt, w.lsamp_alt, w.lslot_alt); return r; }
     if (need_offs) CHK(grow(c, w.offs_alt, w.offs.cap(), "the second sampling set's offsets", 0));
     return 0;
 }
@@ -2494,7 +2633,10 @@ extern "C" int nsk_map_step(nsk_ctx* c, int stage, int N, const float* ro, const
     if (ride) {          // the next batch's sampling behind this batch's compositing, one launch (k_composite_sample)
         nsk_ctx::Prep& P = c->prep;
         SampArgs SA;
-        samp_args(c, SA, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, nullptr, P.mask, P.sorted, c->ws.z_alt, c->ws.skey_alt, c->ws.srank_alt, P.dmax);
+        P.live = live_wanted(c, P.stage, true); P.live_epoch = c->live_epoch;
+        if (P.live) CHK(ensure_live_stage(c, P.stage));
+        samp_args(c, SA, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, nullptr, P.mask, P.sorted, c->ws.z_alt, c->ws.skey_alt, c->ws.srank_alt, P.dmax,
+                  P.live ? c->ws.lsamp_alt.get() : nullptr);
         const int cb = (N + 7) / 8, sb = (P.N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS;
         { ProfScope ps(c, "composite"); k_composite_sample<<<cb + sb, 512, 0, c->stream>>>(A, SA, cb); }
         P.done |= 1;
@@ -2646,6 +2788,29 @@ extern "C" int nsk_debug_fetch(nsk_ctx* c, int what, int M, float* h_out)
     HIPCHK(hipMemcpy(h_out, src, (size_t)M * ((what == 3 || what == 4) ? 16 : 4), hipMemcpyDeviceToHost));
     return 0;
 }
+// the dead-tile skip of the last step's backward, after a synchronise: tiles run per level, the slot order and the slots' liveness bytes
+extern "C" int nsk_debug_live_tiles(nsk_ctx* c, int M, int* h_counts, int32_t* h_perm, uint8_t* h_bytes)
+{
+    if (!c || !h_counts) return fail("nsk_debug_live_tiles: null argument");
+    if (M < 1 || M != c->dbg_M || M > c->ws.capM) return fail("nsk_debug_live_tiles: M = %d is not the last step's sample count (%d)", M, c->dbg_M);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const volatile int* h = c->live_host;
+    bool any = false;
+    for (int k = 0; k < 3; ++k) { h_counts[k] = c->dbg_counted[k] ? (int)h[k] : c->dbg_live[k]; any = any || c->dbg_counted[k]; }
+    h_counts[3] = any ? 1 : 0;
+    for (int k = 0; k < 3; ++k) h_counts[4 + k] = c->dbg_wgs[k];
+    h_counts[7] = c->dbg_ntasks;
+    if (h_perm) {
+        if (c->sorted) HIPCHK(hipMemcpy(h_perm, c->ws.perm, (size_t)M * 4, hipMemcpyDeviceToHost));
+        else for (int m = 0; m < M; ++m) h_perm[m] = m;
+    }
+    if (h_bytes) {
+        if (c->live_ok) HIPCHK(hipMemcpy(h_bytes, c->sorted ? c->ws.lslot : c->ws.lsamp, (size_t)M, hipMemcpyDeviceToHost));
+        else memset(h_bytes, 7, (size_t)M);
+    }
+    return 0;
+}
 // the ReLU inputs of decoder `which` over the samples of the last step (same rays), by the forward body of the current matmul mode
 extern "C" int nsk_debug_preact(nsk_ctx* c, int which, int N, const float* ro, const float* rd, float* d_out /*[M][5][32] device*/)
 {
@@ -2673,8 +2838,8 @@ extern "C" int nsk_frustum_mask(nsk_ctx* c, int level, const float* d_depth, int
     if (!G.n) return fail("nsk_frustum_mask: grid level %d not uploaded", level);
     HIPCHK(hipSetDevice(c->device));
     const size_t nvox = G.n / 32;
-    G.midx_dirty = true;
     if (c->capturing) return fail("nsk_frustum_mask: not while a graph is being captured");
+    G.midx_dirty = true; G.live_dirty = true; ++c->live_epoch;
     bool live = false;
     for (auto& R : c->graphs) live = live || !R.stale;
     if (live) { HIPCHK(hipStreamSynchronize(c->stream)); invalidate_graphs(c); }      // new mask contents: see nsk_set_mask
@@ -3062,7 +3227,7 @@ extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b
     {   // the prepared batch's cell-sort placement rides behind the segments (nsk_map_prepare)
         nsk_ctx::Prep& P = c->prep;
         if (AA.n && P.valid && P.sorted && (P.done & 7) == 3 && !c->capturing && !c->tune_no_piggyback) {
-            AA.place = place_args(P.N * P.S, c->ws.skey_alt, c->ws.srank_alt, c->ws.offs_alt, c->ws.perm_alt);
+            AA.place = place_args(P.N * P.S, c->ws.skey_alt, c->ws.srank_alt, c->ws.offs_alt, c->ws.perm_alt, P.live ? c->ws.lsamp_alt.get() : nullptr, c->ws.lslot_alt);
             AA.adam_blocks = blocks; place_wgs = AA.place.nblocks;
             P.done |= 4;
         }

@@ -159,11 +159,17 @@ __device__ __forceinline__ int cell_index(int GX, int GY, int GZ, const float* b
 #define NSK_SAMPLE_RAYS 8           // rays (waves) per workgroup of k_sample (16: 19.6 us at 5000 rays, 8: 18.1, 4: 20.9; 1000 rays: 11.5 / 10.6 / 12.3)
 #endif
 #define NSK_SAMPLE_TABLE 2048       // slots of its cell table (>= 2 x NSK_SAMPLE_RAYS x 64 keeps probing short)
+// Liveness of a sample under the optimiser masks (nsk_set_mask / nsk_frustum_mask): bit k of its byte says that the cell it falls in at level
+// k + 1 (middle, fine, colour) has at least one marked corner voxel, i.e. that the sample's feature gradient at that level reaches a voxel the
+// optimiser reads.  cell_live[level] is built once per mask (k_cell_live); a level without a mask has no table and its bit is always set.
+// src: where the level's cell index comes from -- 0 the sort key's cell (same grid shape), 1 the key's parent cell, 2 computed here.
+struct LiveArgs { uint8_t* out; const uint8_t* lv[3]; int src[3]; int X[3], Y[3], Z[3]; };
 struct SampArgs {
     RParams R; int N, S;
     const float* rays_o; const float* rays_d; const float* gt_depth; float gtmax_host; const float* gtmax_dev; const uint8_t* keep;
     float* z_out; int kX, kY, kZ, pX, pY, pZ, ncell2; int* skey; int* srank; int* hist;
     const float* mx_gt; const uint8_t* mx_keep; int mx_n;      // what the batch maximum of gt_depth runs over: the call's own rays, or the whole batch a shard belongs to (nsk_set_depth_max_batch)
+    LiveArgs L;               // optional (L.out != nullptr): one liveness byte per sample for the backward's dead-tile skip
 };
 // (a body, so that the sampling of the NEXT batch can ride in the composite launch of the current step: k_composite_sample, nsk_map_prepare)
 __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
@@ -258,15 +264,20 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         z = sh2[wave][lane];
     }
     if (active && lane < S) z_out[(size_t)n * S + lane] = z;
-    if (!skey) return;                                                      // uniform over the launch
+    uint8_t* __restrict__ live_out = P.L.out;
+    if (!skey && !live_out) return;                                         // uniform over the launch
     // ---- cell keys and ranks for the cell sort -----------------------------------------------------------------------------
-    if (bid == 0 && threadIdx.x == 0) hist[-1] = 0;                 // the bump cursor of k_sort_scan (one int in front of the histogram)
-    for (int i = threadIdx.x; i < NSK_SAMPLE_TABLE; i += 64 * NSK_SAMPLE_RAYS) { tkey[i] = -1; tcnt[i] = 0; }
-    if (threadIdx.x == 0) nlist = 0;
+    if (skey) {
+        if (bid == 0 && threadIdx.x == 0) hist[-1] = 0;             // the bump cursor of k_sort_scan (one int in front of the histogram)
+        for (int i = threadIdx.x; i < NSK_SAMPLE_TABLE; i += 64 * NSK_SAMPLE_RAYS) { tkey[i] = -1; tcnt[i] = 0; }
+        if (threadIdx.x == 0) nlist = 0;
+    }
     int cell = -1;
     if (active && lane < S) {
         const float px = add_rn(ox, mul_rn(dx, z)), py = add_rn(oy, mul_rn(dy, z)), pz = add_rn(oz, mul_rn(dz, z));   // = sample_finish
-        cell = cell_index(kX, kY, kZ, R.bound, px, py, pz) * 8;
+        const int kc = cell_index(kX, kY, kZ, R.bound, px, py, pz);
+        cell = kc * 8;
+        int pcell = kc;
         // The coarser level read beside the key level (grid_middle under grid_fine / grid_color) does not nest in it: grid_sample's
         // align_corners scaling puts its cell faces INSIDE key cells, so the samples of one key cell fall into up to 2 x 2 x 2 parent
         // cells.  Three parity bits of the parent cell order them inside the key cell; without them they alternate at random and
@@ -275,8 +286,24 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
             const int pc = cell_index(pX, pY, pZ, R.bound, px, py, pz);
             const int ix = pc % pX, iy = (pc / pX) % pY, iz = pc / (pX * pY);
             cell += (ix & 1) | ((iy & 1) << 1) | ((iz & 1) << 2);
+            pcell = pc;
+        }
+        if (live_out) {                 // the cells are those tri_setup finds in the decoders: the same point, the same operation sequence
+            unsigned b = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const uint8_t* __restrict__ lv = P.L.lv[k];
+                unsigned on = 1u;
+                if (lv) {
+                    const int ci = P.L.src[k] == 0 ? kc : (P.L.src[k] == 1 ? pcell : cell_index(P.L.X[k], P.L.Y[k], P.L.Z[k], R.bound, px, py, pz));
+                    on = lv[ci] ? 1u : 0u;
+                }
+                b |= on << k;
+            }
+            live_out[(size_t)n * S + lane] = (uint8_t)b;
         }
     }
+    if (!skey) return;
     // A ray crosses a cell once, so equal cells are consecutive lanes: one histogram add per run, made by its first lane.  The
     // runs of the workgroup's rays are first merged in an LDS table (rays of one frame all start in the cells around the camera,
     // and a thousand adds on one 64-byte line take 25 us: same-line atomics serialise at the memory side), then every
@@ -358,11 +385,16 @@ __device__ __forceinline__ void sort_scan_body(const ScanArgs& P, int bid)
 }
 __global__ __launch_bounds__(256) void k_sort_scan(ScanArgs P) { sort_scan_body<1>(P, blockIdx.x); }
 
-struct PlaceArgs { int M; const int* skey; const int* srank; const int* offs; int* perm; int nblocks; };
+struct PlaceArgs { int M; const int* skey; const int* srank; const int* offs; int* perm; int nblocks;
+                   const uint8_t* live_in; uint8_t* live_out; };      // optional: the samples' liveness bytes (LiveArgs) go to their slots
 __device__ __forceinline__ void sort_place_body(const PlaceArgs& P, int bid)
 {
     const int m = bid * blockDim.x + threadIdx.x;
-    if (m < P.M) P.perm[P.offs[P.skey[m]] + P.srank[m]] = m;
+    if (m < P.M) {
+        const int slot = P.offs[P.skey[m]] + P.srank[m];
+        P.perm[slot] = m;
+        if (P.live_out) P.live_out[slot] = P.live_in[m];
+    }
 }
 __global__ void k_sort_place(PlaceArgs P) { sort_place_body(P, blockIdx.x); }
 
@@ -835,6 +867,9 @@ struct DecArgs {
     float* dump;              // test aid (nsk_debug_preact): ReLU inputs [M][5][32] by sample, or nullptr
     const float* dyn_resid;   // k_decode_bwd_track: per-ray |gt - depth| [dyn_n] (+inf: ray masked) -- the Tracker's median mask is applied HERE (see lower_median_x10)
     int dyn_n;
+    // dead-tile skip of a frozen role (decode_bwd_body<.., SKIP>): one liveness byte per tile SLOT (LiveArgs), this role's bit in it, and where the
+    // role counts the tiles it ran; live == nullptr: every tile runs, through the body without any of this
+    const uint8_t* live; unsigned live_bit; int* live_cnt;
 };
 
 // ray of sample mm = mm / S without the generic division (~25 vector instructions): umulhi by ceil(2^32 / S), exact for mm < 2^32 / S
@@ -982,6 +1017,9 @@ __global__ __launch_bounds__(512) void k_decode_fwd(DecArgs A) { decode_fwd_body
 // one launch for all decoders of a stage: workgroups [wg_end[r-1], wg_end[r]) serve decoder which[r]
 struct MultiArgs {
     DecArgs a[3]; int which[3]; int train[3]; int wg_end[3]; int n;
+    // dead-tile skip: live_cnt = device counters [middle, fine, colour, ticket]; the last of the live_wgs counting workgroups to finish hands the
+    // launch's counts and its tag to live_out (host memory the device can write) and clears the counters for the next launch
+    int* live_cnt; volatile int* live_out; int live_wgs, live_tag;
     const float* sum_src; float* sum_dst; int sum_n;      // optional: one extra workgroup sums the per-ray losses (saves a launch)
     ScanArgs scan;                                        // optional (scan.nblocks > 0): the NEXT batch's cell-sort offsets ride behind the roles (nsk_map_prepare)
     const float* dyn_seed; float* dyn_thr_out;            // k_decode_bwd_track's last workgroup: the compositing's own d/d rays_d term [N][3], 10 x median (scalar)
@@ -1458,10 +1496,14 @@ __device__ __forceinline__ void image_commit(f4* __restrict__ dst, const ImgRegs
 }
 
 // ------------------------------------------------------------------------------------------------------
-template <int WHICH, bool RAYS, int NW = 8, bool FULL = false, bool DYN = false>      // FULL: the chain on the fp32 MFMA whatever RAYS says (nsk_set_backward_mode 0)
+// SKIP: with an optimiser mask on this role's level, a tile none of whose samples touches a marked voxel is not run at all: everything it would
+// scatter lands on voxels whose gradient nobody reads (include/nsk.h: "gradients of unmarked voxels are discarded").  Only for launches that
+// want nothing but grid gradients from a frozen role: ray gradients (d/dp) flow through every sample whatever the voxel mask says.
+template <int WHICH, bool RAYS, int NW = 8, bool FULL = false, bool DYN = false, bool SKIP = false>      // FULL: the chain on the fp32 MFMA whatever RAYS says (nsk_set_backward_mode 0)
 __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int nb)          // DYN: the Tracker's median mask is found and applied here (composite mode 5)
 {
     static_assert(!DYN || RAYS, "the deferred median mask belongs to the Tracker's ray-gradient launch");
+    static_assert(!SKIP || (!RAYS && !FULL && !DYN), "dead tiles are skipped only where grid gradients are all a frozen role is asked for");
     constexpr bool XYZ = WHICH != 0;
     constexpr int OD = WHICH == 3 ? 4 : 1;
     constexpr bool NEED_E = XYZ && RAYS;
@@ -1503,10 +1545,53 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
     const int nw = nb * NW, wg = bid * NW + wave;
     const int tsh = tile_shift(ntasks, nw);
     const int kmax = tiles_per_wave(ntasks, nw, tsh);
+    // SKIP: a dead tile must cost nothing -- a first form looked at each tile's bytes in turn and still staged its loads: every dead tile was a
+    // dependent memory round trip (index -> sample), and at two waves per SIMD a wave hid none of it (K3: the launch got 3 us LONGER).  So the
+    // wave reads the liveness of 64 of its tiles at once -- lane l the sixteen bytes of its l-th tile, one 16-byte load, one ballot -- and walks
+    // the set bits of that scalar mask: the pipeline below (this tile, the next one's loads, the index two ahead) runs over LIVE tiles only.
+    // (Never in the deterministic mode: its waves meet at barriers in every round.)
+    typedef unsigned int lu4 __attribute__((ext_vector_type(4)));
+    unsigned long long lmask = 0; int lblk = 0, ran = 0;
+    auto live_load = [&](int kb) {                     // the bytes of tile kb + lane of this wave (clamped into the array)
+        const int t = min(tile_of(kb + lane, wg, nw, tsh), ntasks - 1);
+        return ld32<lu4>(A.live, (unsigned)t * 16u);
+    };
+    auto live_ballot = [&](const lu4& w, int kb) {
+        const int t = tile_of(kb + lane, wg, nw, tsh);
+        const int nv = A.M - t * 16;                    // valid slots of the tile (the last one may be ragged; its missing slots hold nothing)
+        const unsigned bits = A.live_bit * 0x01010101u;
+        bool lv = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int left = nv - 4 * q;
+            const unsigned keep = left >= 4 ? 0xffffffffu : (left <= 0 ? 0u : ((1u << (8 * left)) - 1u));
+            lv = lv || (w[q] & bits & keep) != 0u;
+        }
+        return (unsigned long long)__builtin_amdgcn_ballot_w64(lv && t < ntasks);
+    };
+    auto next_live = [&](int k) {                       // the wave's next live tile after round k, or kmax; called with rising k only
+        ++k;
+        while (k < kmax) {
+            if ((k >> 6) != lblk) { lblk = k >> 6; lmask = live_ballot(live_load(lblk << 6), lblk << 6); }
+            const unsigned long long rest = lmask >> (k & 63);
+            if (rest) return min(k + (int)__builtin_ctzll(rest), kmax);
+            k = (k | 63) + 1;
+        }
+        return kmax;
+    };
+    int kfirst = 0, k1 = 1;
     {
-        const int mm0 = slot_sample(A, slot_of(tile_of(0, wg, nw, tsh)));
+        lu4 lw0;
+        if constexpr (SKIP) lw0 = live_load(0);
+        int mm0 = 0;
+        if constexpr (!SKIP) mm0 = slot_sample(A, slot_of(tile_of(0, wg, nw, tsh)));
         image_issue<64 * NW>(img_regs, img_src, IMG_F / 4);
-        stage(tile_of(0, wg, nw, tsh), mm0, nx);
+        if constexpr (SKIP) {
+            lmask = live_ballot(lw0, 0);
+            kfirst = next_live(-1);
+            mm0 = slot_sample(A, slot_of(tile_of(kfirst, wg, nw, tsh)));
+        }
+        stage(tile_of(kfirst, wg, nw, tsh), mm0, nx);
         if constexpr (DYN) {
             constexpr int PER = (NSK_MEDIAN_FUSED_MAX + 64 * NW - 1) / (64 * NW);
             float rv[PER];
@@ -1522,13 +1607,17 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
             __syncthreads();
         }
     }
-    int mm_next = slot_sample(A, slot_of(tile_of(1, wg, nw, tsh)));
+    if constexpr (SKIP) k1 = next_live(kfirst);
+    int mm_next = slot_sample(A, slot_of(tile_of(k1, wg, nw, tsh)));
     const bool det = (A.flags & 0x8000u) != 0;      // deterministic debug mode: every wave walks all kmax rounds (they meet at barriers)
-    for (int k = 0; k < kmax; ++k) {
+    int k2 = 2;
+    for (int k = kfirst; k < kmax; k = k1, k1 = k2) {      // !SKIP: k, k1 = k + 1, k2 = k + 2 as ever; SKIP: this wave's next live tiles
         const int task = tile_of(k, wg, nw, tsh);
-        if (task >= ntasks && !det) break;
+        if constexpr (!SKIP) { if (task >= ntasks && !det) break; }
         asm volatile("" ::: "memory");      // keep the LDS fragment reads inside the loop (LICM would hoist + spill them)
         const bool valid = task * 16 + j < A.M;
+        k2 = k1 + 1;
+        if constexpr (SKIP) { k2 = next_live(k1); ++ran; }      // a live tile runs whole, its dead lanes included, as ever
         const int mm = nx.mm;
         float px, py, pz;
         sample_finish(A, nx.r, px, py, pz);
@@ -1547,8 +1636,8 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         float unscale = 1.f;
         if constexpr (B16) unscale = chain_scale<OD>(gout);
         const unsigned long long mask = nx.mask;
-        stage(tile_of(k + 1, wg, nw, tsh), mm_next, nx);
-        mm_next = slot_sample(A, slot_of(tile_of(k + 2, wg, nw, tsh)));
+        stage(tile_of(k1, wg, nw, tsh), mm_next, nx);
+        mm_next = slot_sample(A, slot_of(tile_of(k2, wg, nw, tsh)));
         f4 xcos[6];
         if constexpr (NEED_E) { f4 e[6]; embed<true>(Bm, g, px, py, pz, e, xcos); }
         f4 gh[2];                                                // g_h4 = Wo^T g_out
@@ -1667,6 +1756,36 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
             } else scatter_tile(A.grid, T, gc, lane, valid, scratch);
         }
     }
+    if constexpr (SKIP) {       // the tiles this role ran: the waves' counts meet in LDS (wave 0's scatter scratch, free once the waves are through), one global add per workgroup
+        int* cnt = reinterpret_cast<int*>(smf + IMG_F);
+        if (threadIdx.x == 0) *cnt = 0;
+        __syncthreads();
+        if (lane == 0 && ran) atomicAdd(cnt, ran);
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(A.live_cnt, *cnt);
+    }
+}
+
+// after the roles' bodies (thread 0 of a counting workgroup, behind its own add above): the last counting workgroup of the launch publishes the counts
+__device__ __forceinline__ void live_publish(const MultiArgs& MA)
+{
+    if (threadIdx.x != 0) return;
+    __threadfence();
+    if (atomicAdd(MA.live_cnt + 3, 1) != MA.live_wgs - 1) return;
+    __threadfence();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) MA.live_out[k] = atomicExch(MA.live_cnt + k, 0);
+    atomicExch(MA.live_cnt + 3, 0);
+    __threadfence_system();
+    MA.live_out[3] = MA.live_tag;
+    __threadfence_system();
+}
+// a frozen role of a launch without ray gradients: the skipping body where the role has liveness bytes, else the body as it always was
+template <int WHICH, int NW>
+__device__ __forceinline__ void decode_bwd_frozen_role(const MultiArgs& MA, int r, int bid, int nb)
+{
+    if (MA.a[r].live) { decode_bwd_body<WHICH, false, NW, false, false, true>(MA.a[r], bid, nb); live_publish(MA); }
+    else decode_bwd_body<WHICH, false, NW>(MA.a[r], bid, nb);
 }
 
 template <int WHICH, bool RAYS>
@@ -1685,11 +1804,12 @@ __global__ __launch_bounds__(64 * NSK_FROZEN_NW) void k_decode_bwd_frozen(MultiA
     while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;
     const int b0 = r == 0 ? 0 : MA.wg_end[r - 1];
     const int bid = blockIdx.x - b0, nb = MA.wg_end[r] - b0;
+    static_assert(!RAYS, "the frozen kernel serves launches without ray gradients");
     switch (MA.which[r]) {
     case 0: decode_bwd_body<0, RAYS, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
-    case 1: decode_bwd_body<1, RAYS, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
-    case 2: decode_bwd_body<2, RAYS, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
-    default: decode_bwd_body<3, RAYS, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
+    case 1: decode_bwd_frozen_role<1, NSK_FROZEN_NW>(MA, r, bid, nb); break;
+    case 2: decode_bwd_frozen_role<2, NSK_FROZEN_NW>(MA, r, bid, nb); break;
+    default: decode_bwd_frozen_role<3, NSK_FROZEN_NW>(MA, r, bid, nb); break;
     }
 }
 

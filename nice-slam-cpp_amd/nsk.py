@@ -23,7 +23,7 @@ SYMBOLS = (
     "nsk_track_step", "nsk_loss_map", "nsk_loss_track", "nsk_rays_from_pixels", "nsk_rays_backward",
     "nsk_camera_from_tensor", "nsk_camera_backward", "nsk_inside_filter", "nsk_adam_vector", "nsk_adam_step",
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
-    "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch",
+    "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch", "nsk_debug_live_tiles",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
@@ -759,6 +759,13 @@ class Context:
         out = np.zeros((M, 4) if code in (3, 4) else (M,), np.float32)
         _chk(lib().nsk_debug_fetch(self.h, code, int(M), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def debug_live_tiles(self, M):
+        """the dead-tile skip of the last step's backward (include/nsk.h): (counts [8] int32, perm [M] int32, bytes [M] uint8)"""
+        import numpy as np
+        counts, perm, lb = np.zeros(8, np.int32), np.zeros(M, np.int32), np.zeros(M, np.uint8)
+        _chk(lib().nsk_debug_live_tiles(self.h, int(M), counts.ctypes.data_as(C.c_void_p), perm.ctypes.data_as(C.c_void_p), lb.ctypes.data_as(C.c_void_p)))
+        return counts, perm, lb
 
     @_ordered
     def debug_preact(self, which, rays_o, rays_d, M):
