@@ -519,6 +519,41 @@ int nsk_render_image(nsk_ctx* ctx, int stage, int H0, int H1, int W0, int W1, in
 int nsk_image_metrics(nsk_ctx* ctx, int Hv, int Wv, const float* d_rgb, const float* d_depth, const float* d_gt_depth,
                       const float* d_gt_color, float* d_res_depth, float* d_res_color, double h_out[8]);
 
+/* ---- reconstruction metrics: accuracy, completion, completion ratio (upstream src/tools/eval_recon.py) ----------------------- */
+/* nsk_mesh_sample: n area-weighted surface samples of a triangle mesh (d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3]).
+ *   Area: A_t = 0.5 |(b - a) x (c - a)|, formed in double from the float32 vertices.  A triangle whose area is not finite or not positive,
+ *     or that has an index outside [0, n_vertices), has area 0: it is counted in *h_degenerate and never chosen.
+ *   Cumulative area: the inclusive fp64 scan of A_t in triangle order (lanes by shuffles, waves, workgroups and runs of workgroups each in
+ *     index order: one fixed association, two calls give the same bytes).  *h_area = its last entry.
+ *   Sample s: u_k = (hash_u32(seed, s, k) >> 8) 2^-24 for k = 0, 1, 2 (the counter hash of nsk_sample_pixels);
+ *     triangle = the first t with cum[t] > (double)u_0 cum[last], by binary search;
+ *     r = sqrt(u_1) correctly rounded in fp32, w_a = 1 - r, w_b = r (1 - u_2), w_c = r u_2, p = (w_a a + w_b b) + w_c c per component,
+ *     every product and sum an fp32 operation of its own.
+ *   d_points [n][3]; d_tri [n] (or NULL) the chosen triangles.  n = 0 is valid.  n_triangles = 0 or a total area of 0 is an error.
+ * Synchronises once (the total area and the count come back to the host before the samples are drawn). */
+int nsk_mesh_sample(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles,
+                    unsigned long long seed, int n, float* d_points, int32_t* d_tri, double* h_area, int* h_degenerate);
+/* nsk_cloud_nearest: for every query point the distance to the nearest target point and (d_index, or NULL) that target.
+ *   d_dist[q] = sqrt(min_t d2(q, t)), d2 = (dx dx + dy dy) + dz dz with dx = q_x - t_x (y, z alike), each operation rounded on its own in
+ *   fp32, the square root correctly rounded; d_index[q] = the LOWEST t that attains the minimum of d2.  These are the bits of a brute-force
+ *   evaluation over all targets; the grid below only decides which targets are looked at.
+ *   A target with a non-finite component is left out and counted in *h_target_skipped (or NULL).  A query with a non-finite component gets
+ *   NaN and -1.  Without a finite target every distance is +inf and every index -1.  n_target = 0 is an error; n_query = 0 is valid.
+ * Search: a uniform grid of cubic cells over the box of the finite targets (device reduction -> cells and histogram -> exclusive scan ->
+ * placement with the original indices), about one cell per target and never more than 2^22; an axis shorter than the cell edge has one
+ * cell.  Memory O(n_target + n_query + cells), owned by the context and reused.  A query walks shells of cells of growing Chebyshev radius
+ * around its own (unclamped) cell and stops when its best d2 is strictly below fl(m m), m = the smallest fp32 distance from the query to
+ * a plane of the searched block that still has cells behind it, or when the block covers the grid.  The grid's planes are fp32 numbers
+ * and a target's cell is defined by comparisons with them, so the bound holds for d2 as evaluated, not only in real arithmetic.
+ * Synchronises once (the box and the skipped count come back to the host; the grid is sized from them). */
+int nsk_cloud_nearest(nsk_ctx* ctx, const float* d_query, int n_query, const float* d_target, int n_target, float* d_dist,
+                      int32_t* d_index, int* h_target_skipped);
+/* nsk_cloud_stats: h_out[0] the sum of the finite distances, each widened to double;  [1] their number;  [2] the number of finite
+ * distances with d < threshold (strict);  [3] the largest finite distance (0 without one).  No floating-point atomics: lanes add in index
+ * order, waves meet by shuffles, one row per workgroup, a single-workgroup launch adds the rows in index order -- two runs give the same
+ * bytes.  Reading h_out is the call's one synchronisation.  n = 0 gives zeros. */
+int nsk_cloud_stats(nsk_ctx* ctx, const float* d_dist, int n, float threshold, double h_out[4]);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

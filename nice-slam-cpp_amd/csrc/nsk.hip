@@ -6,6 +6,7 @@
 #include "nsk_bf16.h"
 #include "nsk_mesh.h"
 #include "nsk_image.h"
+#include "nsk_cloud.h"
 #include "nsk_buf.h"
 
 #include <dlfcn.h>
@@ -852,6 +853,17 @@ struct nsk_ctx {
         Buf<float> ro, rd, gd;                               // [chunk][3], [chunk][3], [chunk]: one group
         Buf<double> rows;                                    // [IMG_MAX_ROWS][IMG_COLS] + 8 results
     } img;
+    // reconstruction metrics (nsk_mesh_sample / nsk_cloud_nearest / nsk_cloud_stats): scratch that grows to the largest call and stays
+    struct Cloud {
+        Buf<double> cum, bsum;                               // [triangles] cumulative areas, [workgroups] their totals
+        Buf<unsigned> degenerate;
+        Buf<float> box;                                      // [CLOUD_MAX_ROWS][8] partial boxes + the 8 results
+        Buf<unsigned> tcell, start, cursor; Buf<float4> sorted;      // targets: [n] cells, [cells + 1 + scan levels], [cells], [n] in cell order
+        Buf<unsigned> qcell, qstart, qcursor, qperm;         // queries in cell order (the same grid)
+        Buf<double> rows;                                    // [CLOUD_MAX_ROWS][4] partial sums + the 4 results
+        int cells_x4 = 4;                                    // nsk_set_tuning "cloud_cells_x4": grid cells aimed at per finite target, in quarters
+        int query_mode = 0;                                  // nsk_set_tuning "cloud_query_mode": bit 0 a wave per query; + 2 queries always in input order, + 4 always in cell order (neither: by size)
+    } cloud;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -1081,6 +1093,8 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune_dead_tile_pct = value; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
+    if (!strcmp(key, "cloud_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: cloud_cells_x4 must be 1 .. 256"); c->cloud.cells_x4 = value; return 0; }
+    if (!strcmp(key, "cloud_query_mode")) { if (value < 0 || value > 5) return fail("nsk_set_tuning: cloud_query_mode must be 0 .. 5"); c->cloud.query_mode = value; return 0; }
     return fail("nsk_set_tuning: unknown key '%s'", key);
 }
 
@@ -3141,6 +3155,172 @@ extern "C" int nsk_image_metrics(nsk_ctx* c, int Hv, int Wv, const float* d_rgb,
       k_image_metrics_sum<<<1, 64, 0, c->stream>>>(nrows, n, rows, out); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_out, out, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- reconstruction metrics (nsk_cloud.h) -----------------------------------------------------------------------------------------
+extern "C" int nsk_mesh_sample(nsk_ctx* c, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles,
+                               unsigned long long seed, int n, float* d_points, int32_t* d_tri, double* h_area, int* h_degenerate)
+{
+    if (!c) return fail("nsk_mesh_sample: null ctx");
+    if (n_triangles < 0 || n_vertices < 0 || n < 0) return fail("nsk_mesh_sample: negative count");
+    if (n_triangles == 0) return fail("nsk_mesh_sample: the mesh has no triangle");
+    if (!d_vertices || !d_triangles) return fail("nsk_mesh_sample: d_vertices / d_triangles is NULL");
+    if (n > 0 && !d_points) return fail("nsk_mesh_sample: d_points is NULL");
+    if (c->capturing) return fail("nsk_mesh_sample: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Cloud& K = c->cloud;
+    const int nb = (int)(((long long)n_triangles + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+    CHK(grow(c, K.cum, (size_t)n_triangles, "the cumulative triangle areas", GROW_NO_CAPTURE));
+    CHK(grow(c, K.bsum, (size_t)nb, "the area sums of the workgroups", GROW_NO_CAPTURE));
+    CHK(grow(c, K.degenerate, 16, "the degenerate-triangle count", GROW_NO_CAPTURE));
+    double total = 0.0; unsigned degenerate = 0;
+    { ProfScope ps(c, "mesh_area");
+      HIPCHK(hipMemsetAsync(K.degenerate, 0, 4, c->stream));
+      k_tri_area<<<nb, CLOUD_BLOCK, 0, c->stream>>>(n_vertices, n_triangles, d_vertices, d_triangles, K.cum, K.bsum, K.degenerate);
+      k_tri_area_sums<<<1, CLOUD_BLOCK, 0, c->stream>>>(nb, K.bsum);
+      k_tri_area_add<<<nb, CLOUD_BLOCK, 0, c->stream>>>(n_triangles, K.cum, K.bsum);
+      HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemcpyAsync(&total, K.cum.get() + (n_triangles - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&degenerate, K.degenerate, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_area) *h_area = total;
+    if (h_degenerate) *h_degenerate = (int)degenerate;
+    if (!(total > 0.0)) return fail("nsk_mesh_sample: the mesh has no area (%u of %d triangles degenerate)", degenerate, n_triangles);
+    if (n == 0) return 0;
+    { ProfScope ps(c, "mesh_sample");
+      k_mesh_sample<<<(n + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_BLOCK, 0, c->stream>>>(seed, n, n_triangles, K.cum, d_vertices, d_triangles, d_points, d_tri);
+      HIPCHK(hipGetLastError()); }
+    return 0;
+}
+
+// The grid of nsk_cloud_nearest from the box of the finite targets: cubic cells, about cells_x4 / 4 of them per target, at most 2^22.
+// An axis shorter than the edge (zero extent included) gets one cell, and the edge is found again from the other axes.
+static CloudGrid cloud_grid(const float* box, unsigned nfinite, int cells_x4)
+{
+    CloudGrid G;
+    G.nfinite = (int)nfinite;
+    for (int a = 0; a < 3; ++a) { G.lo[a] = nfinite ? box[a] : 0.f; G.dim[a] = 1; }
+    G.h = 1.f; G.inv_h = 1.f;
+    if (!nfinite) return G;
+    double ext[3], big = 0.0;
+    bool on[3];
+    for (int a = 0; a < 3; ++a) {
+        ext[a] = (double)box[3 + a] - (double)box[a]; on[a] = ext[a] > 0.0;
+        big = std::max(big, std::max(std::fabs((double)box[a]), std::fabs((double)box[3 + a])));
+    }
+    const double want = std::min((double)CLOUD_MAX_CELLS, std::max(1.0, (double)nfinite * cells_x4 / 4.0));
+    double h = 1.0;
+    for (;;) {
+        int k = 0; double logv = 0.0;
+        for (int a = 0; a < 3; ++a) if (on[a]) { ++k; logv += std::log(ext[a]); }
+        if (k == 0) return G;                                  // every target at one point: one cell
+        h = std::exp((logv - std::log(want)) / k);
+        bool dropped = false;
+        for (int a = 0; a < 3; ++a) if (on[a] && ext[a] < h) { on[a] = false; dropped = true; }
+        if (!dropped) break;
+    }
+    h = std::max(h, std::max(big * 9.5367431640625e-7, 1e-30));        // 8 ulp of the largest coordinate: the planes lo + k h stay distinct
+    h = std::min(h, 1e37);
+    for (;;) {
+        double cells = 1.0;
+        for (int a = 0; a < 3; ++a) { G.dim[a] = on[a] ? (int)std::min(std::floor(ext[a] / h) + 1.0, (double)CLOUD_MAX_CELLS) : 1; cells *= G.dim[a]; }
+        if (cells <= (double)CLOUD_MAX_CELLS) break;
+        h *= 1.25;
+    }
+    G.h = (float)h; G.inv_h = 1.f / G.h;
+    return G;
+}
+
+extern "C" int nsk_cloud_nearest(nsk_ctx* c, const float* d_query, int n_query, const float* d_target, int n_target, float* d_dist,
+                                 int32_t* d_index, int* h_target_skipped)
+{
+    if (!c) return fail("nsk_cloud_nearest: null ctx");
+    if (n_query < 0 || n_target < 0) return fail("nsk_cloud_nearest: negative count");
+    if (n_target == 0) return fail("nsk_cloud_nearest: no target");
+    if (!d_target) return fail("nsk_cloud_nearest: d_target is NULL");
+    if (n_query > 0 && (!d_query || !d_dist)) return fail("nsk_cloud_nearest: d_query / d_dist is NULL");
+    if (c->capturing) return fail("nsk_cloud_nearest: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Cloud& K = c->cloud;
+    // pass 1: the box
+    const int nrows = (int)std::min<long long>(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
+    CHK(grow(c, K.box, (size_t)CLOUD_MAX_ROWS * 8 + 8, "the partial boxes", GROW_NO_CAPTURE));
+    float* box_out = K.box.get() + (size_t)CLOUD_MAX_ROWS * 8;
+    float box[8];
+    { ProfScope ps(c, "cloud_box");
+      k_cloud_box<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n_target, d_target, K.box);
+      k_cloud_box_sum<<<1, 64, 0, c->stream>>>(nrows, K.box, box_out);
+      HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemcpyAsync(box, box_out, sizeof(box), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    unsigned nfinite; memcpy(&nfinite, &box[6], 4);
+    if (h_target_skipped) *h_target_skipped = (int)((unsigned)n_target - nfinite);
+    if (n_query == 0) return 0;
+    const CloudGrid G = cloud_grid(box, nfinite, K.cells_x4);
+    const size_t cells = (size_t)G.dim[0] * G.dim[1] * G.dim[2], words = mc_scan_words(cells + 1);
+    // queries in cell order: the ordering passes cost more than they save below about half a million queries
+    const bool ordered = nfinite > 0 && ((K.query_mode & 4) || (!(K.query_mode & 2) && n_query >= CLOUD_ORDER_MIN));
+    const int tb = (int)(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK), qb = (int)(((long long)n_query + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+    if (nfinite) {
+        CHK(grow(c, K.tcell, (size_t)n_target, "the targets' cells", GROW_NO_CAPTURE));
+        CHK(grow(c, K.sorted, (size_t)n_target, "the targets in cell order", GROW_NO_CAPTURE));
+        CHK(grow(c, K.start, words, "the cells' first targets", GROW_NO_CAPTURE));
+        CHK(grow(c, K.cursor, cells, "the cells' placement cursors", GROW_NO_CAPTURE));
+        ProfScope ps(c, "cloud_grid");
+        HIPCHK(hipMemsetAsync(K.start, 0, words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(K.cursor, 0, cells * 4, c->stream));
+        k_cloud_cells<<<tb, CLOUD_BLOCK, 0, c->stream>>>(G, n_target, d_target, 0, K.tcell, K.start);           // pass 2
+        HIPCHK(hipGetLastError());
+        CHK(mc_scan(c, K.start, (int)cells + 1));                                                              // pass 3
+        k_cloud_place<<<tb, CLOUD_BLOCK, 0, c->stream>>>(n_target, d_target, K.tcell, K.start, K.cursor, K.sorted, nullptr);      // pass 4
+        HIPCHK(hipGetLastError());
+    }
+    if (ordered) {
+        CHK(grow(c, K.qcell, (size_t)n_query, "the queries' cells", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qperm, (size_t)n_query, "the queries in cell order", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qstart, words, "the cells' first queries", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qcursor, cells, "the cells' query cursors", GROW_NO_CAPTURE));
+        ProfScope ps(c, "cloud_order");
+        HIPCHK(hipMemsetAsync(K.qstart, 0, words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(K.qcursor, 0, cells * 4, c->stream));
+        k_cloud_cells<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, 1, K.qcell, K.qstart);
+        HIPCHK(hipGetLastError());
+        CHK(mc_scan(c, K.qstart, (int)cells + 1));
+        k_cloud_place<<<qb, CLOUD_BLOCK, 0, c->stream>>>(n_query, d_query, K.qcell, K.qstart, K.qcursor, nullptr, K.qperm);
+        HIPCHK(hipGetLastError());
+    }
+    { ProfScope ps(c, "cloud_query");
+      const unsigned* qperm = ordered ? K.qperm.get() : nullptr;
+      if (K.query_mode & 1) {
+          const long long wg = ((long long)n_query * 64 + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
+          k_cloud_query<64><<<(unsigned)wg, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
+      } else
+          k_cloud_query<1><<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
+      HIPCHK(hipGetLastError()); }
+    return 0;
+}
+
+extern "C" int nsk_cloud_stats(nsk_ctx* c, const float* d_dist, int n, float threshold, double h_out[4])
+{
+    if (!c) return fail("nsk_cloud_stats: null ctx");
+    if (n < 0) return fail("nsk_cloud_stats: negative count");
+    if (!h_out) return fail("nsk_cloud_stats: h_out is NULL");
+    if (n > 0 && !d_dist) return fail("nsk_cloud_stats: d_dist is NULL");
+    if (c->capturing) return fail("nsk_cloud_stats: not while a graph is being captured");
+    for (int k = 0; k < 4; ++k) h_out[k] = 0.0;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const int nrows = (int)std::min<long long>(((long long)n + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
+    CHK(grow(c, c->cloud.rows, (size_t)CLOUD_MAX_ROWS * 4 + 4, "the distance sums of the workgroups", GROW_NO_CAPTURE));
+    double* rows = c->cloud.rows;
+    double* out = rows + (size_t)CLOUD_MAX_ROWS * 4;
+    { ProfScope ps(c, "cloud_stats");
+      k_cloud_stats<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n, d_dist, threshold, rows);
+      k_cloud_stats_sum<<<1, 64, 0, c->stream>>>(nrows, rows, out); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, out, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -18,6 +18,15 @@
 #include <yaml-cpp/yaml.h>
 #include "models/NICE.h"
 
+// upstream's three 3D numbers of a reconstruction against a ground-truth mesh (src/tools/eval_recon.py) and what went into them
+struct ReconMetrics {
+    double accuracy_cm = 0, completion_cm = 0, completion_ratio_pct = 0;      // mean rec -> gt, mean gt -> rec, share of gt samples below the threshold
+    double accuracy_max_cm = 0, completion_max_cm = 0;
+    double rec_area = 0, gt_area = 0;                                         // m^2, degenerate triangles left out
+    int rec_degenerate = 0, gt_degenerate = 0;                                // triangles without an area or with an index out of range
+    int rec_skipped = 0, gt_skipped = 0;                                      // samples with a non-finite coordinate left out of the targets
+};
+
 class Mesher {
   public:
     Mesher(YAML::Node ns_config, torch::Tensor bound_3x2 = torch::Tensor(), float padding = 0.f);
@@ -37,6 +46,19 @@ class Mesher {
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
     static void write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int n_vertices, const int32_t* triangles, int n_triangles);
     static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& triangles);
+    // Any PLY mesh, read by its header: format ascii or binary_little_endian; the vertex element's x, y, z found by name among scalar
+    // properties of any type, number and order and converted to float; the face element's first list property with any count and index
+    // type, polygons of more than three corners fan-triangulated (0, k, k + 1), faces of fewer than three dropped; every other element and
+    // property skipped.  Throws std::runtime_error carrying the path: big-endian, a malformed header, a truncated file, an index out of range.
+    static void read_ply_mesh(const std::string& path, std::vector<float>& xyz, std::vector<int32_t>& triangles);
+    // Accuracy / completion / completion ratio on the device: n_points area-weighted samples of each mesh (nsk_mesh_sample with seed and
+    // seed + 1), exact nearest distances both ways (nsk_cloud_nearest), the sums (nsk_cloud_stats).  Coordinates in metres; the meshes
+    // are taken as they are (no alignment, no culling).  A static function: it needs no map, only the process's context.
+    static ReconMetrics eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n_points = 200000, float threshold = 0.05f,
+                                   unsigned long long seed = 0);
+    static ReconMetrics eval_recon(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles, const float* gt_xyz,
+                                   int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles, int n_points = 200000,
+                                   float threshold = 0.05f, unsigned long long seed = 0);
 
     int resolution;
     float level_set, padding;

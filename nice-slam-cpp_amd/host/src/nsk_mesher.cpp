@@ -4,8 +4,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <sstream>
 
 #include <hip/hip_runtime_api.h>
@@ -208,4 +210,190 @@ void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vec
         if (buf[t * 13] != 3) throw std::runtime_error("Mesher: " + path + " has a face that is not a triangle");
         std::memcpy(&tris[3 * t], &buf[t * 13 + 1], 12);
     }
+}
+
+// ---- any PLY mesh ------------------------------------------------------------------------------------------------------------------
+namespace {
+struct PlyProp { std::string name; int type = -1, count_type = -1; bool list = false; };       // types: index into PLY_TYPES
+struct PlyElem { std::string name; long long count = 0; std::vector<PlyProp> props; };
+const struct { const char* a; const char* b; int size; } PLY_TYPES[] = {
+    {"char", "int8", 1}, {"uchar", "uint8", 1}, {"short", "int16", 2}, {"ushort", "uint16", 2},
+    {"int", "int32", 4}, {"uint", "uint32", 4}, {"float", "float32", 4}, {"double", "float64", 8}};
+int ply_type(const std::string& w)
+{
+    for (int k = 0; k < 8; ++k) if (w == PLY_TYPES[k].a || w == PLY_TYPES[k].b) return k;
+    return -1;
+}
+// one scalar of type t from the body
+struct PlyBody {
+    const std::string& path; const char* p; const char* end; bool ascii;
+    [[noreturn]] void truncated() const { throw std::runtime_error("Mesher: " + path + " is truncated"); }
+    double next(int t)
+    {
+        if (ascii) {
+            while (p < end && (*p == ' ' || *p == '\n' || *p == '\r' || *p == '\t')) ++p;
+            if (p >= end) truncated();
+            const char* q = p;
+            while (q < end && !(*q == ' ' || *q == '\n' || *q == '\r' || *q == '\t')) ++q;
+            const std::string tok(p, q);
+            p = q;
+            char* e = nullptr;
+            const double v = std::strtod(tok.c_str(), &e);
+            if (e == tok.c_str() || *e) throw std::runtime_error("Mesher: " + path + " has '" + tok + "' where a number belongs");
+            return v;
+        }
+        const int n = PLY_TYPES[t].size;
+        if (end - p < n) truncated();
+        double v = 0;
+        switch (t) {
+            case 0: { int8_t x; std::memcpy(&x, p, 1); v = x; break; }
+            case 1: { uint8_t x; std::memcpy(&x, p, 1); v = x; break; }
+            case 2: { int16_t x; std::memcpy(&x, p, 2); v = x; break; }
+            case 3: { uint16_t x; std::memcpy(&x, p, 2); v = x; break; }
+            case 4: { int32_t x; std::memcpy(&x, p, 4); v = x; break; }
+            case 5: { uint32_t x; std::memcpy(&x, p, 4); v = x; break; }
+            case 6: { float x; std::memcpy(&x, p, 4); v = x; break; }
+            default: { double x; std::memcpy(&x, p, 8); v = x; break; }
+        }
+        p += n;
+        return v;
+    }
+};
+}  // namespace
+
+void Mesher::read_ply_mesh(const std::string& path, std::vector<float>& xyz, std::vector<int32_t>& tris)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("Mesher: cannot open " + path);
+    const std::string all((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    auto bad = [&](const std::string& why) { return std::runtime_error("Mesher: " + path + ": " + why); };
+    // the header, line by line
+    size_t pos = 0;
+    bool first = true, ended = false, ascii = false, have_format = false;
+    std::vector<PlyElem> elems;
+    while (pos < all.size()) {
+        size_t nl = all.find('\n', pos);
+        if (nl == std::string::npos) break;
+        std::string line = all.substr(pos, nl - pos);
+        pos = nl + 1;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (first) { if (line != "ply") throw bad("not a PLY file"); first = false; continue; }
+        if (line == "end_header") { ended = true; break; }
+        std::istringstream ls(line);
+        std::string w; ls >> w;
+        if (w == "format") {
+            std::string fmt; ls >> fmt;
+            if (fmt == "ascii") ascii = true;
+            else if (fmt == "binary_little_endian") ascii = false;
+            else if (fmt == "binary_big_endian") throw bad("big-endian PLY files are not read");
+            else throw bad("unknown format '" + fmt + "'");
+            have_format = true;
+        } else if (w == "element") {
+            PlyElem e; ls >> e.name >> e.count;
+            if (!ls || e.count < 0) throw bad("malformed element line '" + line + "'");
+            elems.push_back(e);
+        } else if (w == "property") {
+            if (elems.empty()) throw bad("a property before any element");
+            PlyProp p; std::string t; ls >> t;
+            if (t == "list") { std::string ct, it; ls >> ct >> it >> p.name; p.list = true; p.count_type = ply_type(ct); p.type = ply_type(it); }
+            else { ls >> p.name; p.type = ply_type(t); }
+            if (!ls || p.type < 0 || (p.list && (p.count_type < 0 || p.count_type > 5))) throw bad("malformed property line '" + line + "'");
+            elems.back().props.push_back(p);
+        }       // comment, obj_info: skipped
+    }
+    if (first || !ended) throw bad(first ? "not a PLY file" : "the header does not end (truncated)");
+    if (!have_format) throw bad("no format line");
+    const PlyElem* ve = nullptr; const PlyElem* fe = nullptr;
+    for (const PlyElem& e : elems) { if (e.name == "vertex") ve = &e; else if (e.name == "face") fe = &e; }
+    if (!ve) throw bad("no vertex element");
+    int ix[3] = {-1, -1, -1};
+    for (size_t k = 0; k < ve->props.size(); ++k)
+        for (int a = 0; a < 3; ++a)
+            if (!ve->props[k].list && ve->props[k].name == std::string(1, (char)('x' + a)) && ix[a] < 0) ix[a] = (int)k;
+    if (ix[0] < 0 || ix[1] < 0 || ix[2] < 0) throw bad("the vertex element has no scalar x, y, z");
+    if (ve->count > 0x7fffffffLL) throw bad("more than 2^31 - 1 vertices");
+    int flist = -1;
+    if (fe) for (size_t k = 0; k < fe->props.size() && flist < 0; ++k) if (fe->props[k].list) flist = (int)k;
+    xyz.assign((size_t)ve->count * 3, 0.f);
+    tris.clear();
+    PlyBody B{path, all.data() + pos, all.data() + all.size(), ascii};
+    bool seen_vertices = false;
+    std::vector<long long> poly;
+    for (const PlyElem& e : elems) {
+        const bool is_v = &e == ve, is_f = &e == fe && flist >= 0;
+        if (is_f && !seen_vertices) throw bad("the face element comes before the vertex element");
+        for (long long r = 0; r < e.count; ++r)
+            for (size_t k = 0; k < e.props.size(); ++k) {
+                const PlyProp& p = e.props[k];
+                if (!p.list) {
+                    const double v = B.next(p.type);
+                    if (is_v) for (int a = 0; a < 3; ++a) if (ix[a] == (int)k) xyz[3 * (size_t)r + a] = (float)v;
+                    continue;
+                }
+                const double cnt = B.next(p.count_type);
+                if (!(cnt >= 0) || cnt != std::floor(cnt)) throw bad("a list with a count that is no whole number");
+                const long long m = (long long)cnt;
+                const bool take = is_f && (int)k == flist;
+                poly.clear();
+                for (long long q = 0; q < m; ++q) {
+                    const double v = B.next(p.type);
+                    if (!take) continue;
+                    if (!(v >= 0 && v < (double)ve->count) || v != std::floor(v))
+                        throw bad("face " + std::to_string(r) + " has an index outside the " + std::to_string(ve->count) + " vertices");
+                    poly.push_back((long long)v);
+                }
+                for (size_t q = 1; take && q + 1 < poly.size(); ++q) {
+                    tris.push_back((int32_t)poly[0]); tris.push_back((int32_t)poly[q]); tris.push_back((int32_t)poly[q + 1]);
+                }
+            }
+        if (is_v) seen_vertices = true;
+    }
+}
+
+// ---- reconstruction metrics ----------------------------------------------------------------------------------------------------------
+ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
+                                const int32_t* gt_tris, int gt_nt, int n, float threshold, unsigned long long seed)
+{
+    if (n < 1) throw std::runtime_error("Mesher::eval_recon: n_points must be at least 1");
+    if (rec_nt < 1 || gt_nt < 1) throw std::runtime_error("Mesher::eval_recon: a mesh without a triangle");
+    auto up = [](DevMem& d, const void* h, size_t bytes) {
+        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+    };
+    ReconMetrics M;
+    DevMem rec_pts((size_t)n * 3 * sizeof(float)), gt_pts((size_t)n * 3 * sizeof(float)), dist((size_t)n * sizeof(float));
+    {   // the meshes leave the device again as soon as their samples are drawn
+        DevMem v((size_t)rec_nv * 3 * sizeof(float)), t((size_t)rec_nt * 3 * sizeof(int32_t));
+        up(v, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(t, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
+        check(nsk_mesh_sample(ctx(), (const float*)v.p, rec_nv, (const int32_t*)t.p, rec_nt, seed, n, (float*)rec_pts.p, nullptr, &M.rec_area, &M.rec_degenerate));
+        check(nsk_sync(ctx()));
+    }
+    {
+        DevMem v((size_t)gt_nv * 3 * sizeof(float)), t((size_t)gt_nt * 3 * sizeof(int32_t));
+        up(v, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(t, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
+        check(nsk_mesh_sample(ctx(), (const float*)v.p, gt_nv, (const int32_t*)t.p, gt_nt, seed + 1, n, (float*)gt_pts.p, nullptr, &M.gt_area, &M.gt_degenerate));
+        check(nsk_sync(ctx()));
+    }
+    double a[4], c[4];
+    check(nsk_cloud_nearest(ctx(), (const float*)rec_pts.p, n, (const float*)gt_pts.p, n, (float*)dist.p, nullptr, &M.gt_skipped));
+    check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
+    check(nsk_cloud_nearest(ctx(), (const float*)gt_pts.p, n, (const float*)rec_pts.p, n, (float*)dist.p, nullptr, &M.rec_skipped));
+    check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
+    const double nan = std::nan("");
+    M.accuracy_cm = a[1] > 0 ? 100.0 * a[0] / a[1] : nan;
+    M.completion_cm = c[1] > 0 ? 100.0 * c[0] / c[1] : nan;
+    M.completion_ratio_pct = c[1] > 0 ? 100.0 * c[2] / c[1] : nan;
+    M.accuracy_max_cm = 100.0 * a[3]; M.completion_max_cm = 100.0 * c[3];
+    return M;
+}
+
+ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n, float threshold, unsigned long long seed)
+{
+    std::vector<float> rv, gv;
+    std::vector<int32_t> rt, gt;
+    read_ply_mesh(rec_ply, rv, rt);
+    read_ply_mesh(gt_ply, gv, gt);
+    if (rt.empty()) throw std::runtime_error("Mesher::eval_recon: " + rec_ply + " has no triangle");
+    if (gt.empty()) throw std::runtime_error("Mesher::eval_recon: " + gt_ply + " has no triangle");
+    return eval_recon(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(), (int)(gt.size() / 3),
+                      n, threshold, seed);
 }

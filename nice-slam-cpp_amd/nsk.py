@@ -28,6 +28,7 @@ SYMBOLS = (
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
+    "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
 )
 
 
@@ -63,6 +64,13 @@ def lib():
         L.nsk_eval_lattice_masked.restype = C.c_int
         L.nsk_eval_lattice_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
                                               C.c_void_p, C.POINTER(C.c_longlong)]
+        L.nsk_mesh_sample.restype = C.c_int
+        L.nsk_mesh_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.nsk_cloud_nearest.restype = C.c_int
+        L.nsk_cloud_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.nsk_cloud_stats.restype = C.c_int
+        L.nsk_cloud_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -392,6 +400,67 @@ class Context:
         if want_residuals:
             out["res_depth"], out["res_color"] = res_d, res_c
         return out
+
+    @_ordered
+    def sample_mesh(self, verts, tris, n, seed, want_tri=False):
+        """nsk_mesh_sample: n area-weighted surface samples of the mesh (verts [nv, 3] float32, tris [nt, 3] int32, cuda tensors) ->
+        points [n, 3] float32 (and with want_tri the chosen triangles [n] int32).  The total area and the number of degenerate triangles
+        are left in self.last_area / self.last_degenerate.  Synchronises."""
+        import torch
+        assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        n = int(n)
+        pts = torch.empty((n, 3), dtype=torch.float32, device=verts.device)
+        tri = torch.empty((n,), dtype=torch.int32, device=verts.device) if want_tri else None
+        area, deg = C.c_double(0.0), C.c_int(0)
+        self.last_area = self.last_degenerate = None
+        _chk(lib().nsk_mesh_sample(self.h, _ptr(verts), int(verts.shape[0]), _ptr(tris), int(tris.shape[0]), int(seed) & 0xFFFFFFFFFFFFFFFF, n,
+                                   _ptr(pts) if n else None, _ptr(tri) if n else None, C.byref(area), C.byref(deg)))
+        self.last_area, self.last_degenerate = float(area.value), int(deg.value)
+        return (pts, tri) if want_tri else pts
+
+    @_ordered
+    def cloud_nearest(self, query, target, want_index=False):
+        """nsk_cloud_nearest: the exact fp32 distance from every query point [nq, 3] to its nearest target point [nt, 3] -> dist [nq]
+        (and with want_index the lowest nearest target's index [nq] int32).  The number of non-finite targets left out is in
+        self.last_skipped.  Synchronises."""
+        import torch
+        assert query.dtype == torch.float32 and target.dtype == torch.float32 and query.shape[-1] == 3 and target.shape[-1] == 3
+        nq = int(query.shape[0])
+        dist = torch.empty((nq,), dtype=torch.float32, device=query.device)
+        idx = torch.empty((nq,), dtype=torch.int32, device=query.device) if want_index else None
+        sk = C.c_int(0)
+        _chk(lib().nsk_cloud_nearest(self.h, _ptr(query) if nq else None, nq, _ptr(target), int(target.shape[0]), _ptr(dist) if nq else None,
+                                     _ptr(idx) if nq else None, C.byref(sk)))
+        self.last_skipped = int(sk.value)
+        return (dist, idx) if want_index else dist
+
+    @_ordered
+    def cloud_stats(self, dist, threshold):
+        """nsk_cloud_stats -> dict(sum, count, below, max) over the finite entries of dist (below: d < threshold, strict).  Synchronises."""
+        h = (C.c_double * 4)()
+        n = int(dist.numel())
+        _chk(lib().nsk_cloud_stats(self.h, _ptr(dist) if n else None, n, C.c_float(threshold), h))
+        return dict(sum=float(h[0]), count=int(h[1]), below=int(h[2]), max=float(h[3]))
+
+    def recon_metrics(self, rec_verts, rec_tris, gt_verts, gt_tris, n=200000, threshold=0.05, seed=0):
+        """upstream's three 3D numbers of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors (what extract_mesh /
+        filter_mesh return goes in directly): n samples of each surface (seed, seed + 1), nearest distances both ways, the means in cm and
+        the share of gt samples with a rec sample closer than threshold in %.  Coordinates are taken to be metres."""
+        rec = self.sample_mesh(rec_verts, rec_tris, n, seed)
+        rec_area, rec_deg = self.last_area, self.last_degenerate
+        gt = self.sample_mesh(gt_verts, gt_tris, n, seed + 1)
+        gt_area, gt_deg = self.last_area, self.last_degenerate
+        acc = self.cloud_stats(self.cloud_nearest(rec, gt), threshold)
+        gt_skipped = self.last_skipped
+        comp = self.cloud_stats(self.cloud_nearest(gt, rec), threshold)
+        rec_skipped = self.last_skipped
+        nan = float("nan")
+        return dict(accuracy_cm=100.0 * acc["sum"] / acc["count"] if acc["count"] else nan,
+                    completion_cm=100.0 * comp["sum"] / comp["count"] if comp["count"] else nan,
+                    completion_ratio_pct=100.0 * comp["below"] / comp["count"] if comp["count"] else nan,
+                    accuracy_max_cm=100.0 * acc["max"], completion_max_cm=100.0 * comp["max"],
+                    rec_area=rec_area, gt_area=gt_area, rec_degenerate=rec_deg, gt_degenerate=gt_deg,
+                    rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold))
 
     @_ordered
     def eval_points(self, stage, pts):
