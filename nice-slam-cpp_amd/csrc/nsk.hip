@@ -8,6 +8,7 @@
 #include "nsk_image.h"
 #include "nsk_cloud.h"
 #include "nsk_buf.h"
+#include "nsk_split.h"
 
 #include <dlfcn.h>
 #include <cstdarg>
@@ -793,18 +794,14 @@ struct nsk_ctx {
     bool touched[NSK_NUM_GROUPS] = {false, false, false, false, false, false};
     bool deterministic = false;             // debug: bit-reproducible gradients (see nsk_set_tuning in include/nsk.h)
     bool roctx = false;                     // roctx ranges around every profiled launch group (libroctx64, loaded on demand)
-    int tune_fwd_occ_cost = 0, tune_no_occ_role = 0;         // the merged middle + fine role of the forward: its cost against the colour role's (0 = 460); 1 = never merged, 2 = always
-    int tune_fwd_fine_cost = 0, tune_fwd_color_cost = 0;     // experiments: forward role costs (nsk_set_tuning "fwd_fine_cost" / "fwd_color_cost")
+    SplitTune tune;                         // the cost model of the workgroup splits (nsk_split.h)
+    int tune_no_occ_role = 0;               // the merged middle + fine role of the forward: 1 = never merged, 2 = always
     bool median_fused_pending = false;
     int tune_no_deferred_median = 0;        // 1: the threshold inside the compositing launch (grid barrier) even where the backward could find it (round 3's form)
     int tune_no_fused_median = 0;           // 1: the Tracker's median threshold in its own launch even where the fused form applies (experiments, tests)
-    int tune_frozen_cost = 0;               // > 0: overrides the frozen-role cost of the backward's workgroup split (nsk_set_tuning; experiments)
-    int tune_frozen_cost_rays = 0;          // > 0: the same for launches with ray gradients (bundle adjustment: the frozen roles also carry g_e and d/dp)
-    int tune_frozen_mid_pct = 100;          // the middle decoder's frozen tile against the fine one's, in percent (its level has 8x the samples per voxel: more same-line atomics)
     int tune_no_frozen_kernel = 0;          // 1: launches without a trainable role also go through k_decode_bwd_multi (experiments, tests)
     // ---- dead-tile skip of the frozen roles under optimiser masks (decode_bwd_body<.., SKIP>)
     int tune_no_dead_skip = 0;              // 1: every tile runs (A/B runs, tests)
-    int tune_dead_tile_pct = 12;            // what a skipped tile costs in the workgroup split, in percent of a tile that runs (its staged loads and the loop)
     int live_epoch = 0;                     // bumped whenever a mask or a masked level changes: liveness bytes written before are stale
     bool live_ok = false;                   // the primary sampling set holds liveness bytes for the current step (forward_core)
     Buf<int> live_cnt;                      // device: tiles run by [middle, fine, colour] + the publishing ticket
@@ -1077,20 +1074,20 @@ extern "C" int nsk_set_backward_mode(nsk_ctx* c, int mode)
 extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
 {
     if (!c || !key) return fail("nsk_set_tuning: null argument");
-    if (!strcmp(key, "frozen_cost")) { c->tune_frozen_cost = value; return 0; }
-    if (!strcmp(key, "frozen_cost_rays")) { c->tune_frozen_cost_rays = value; return 0; }
+    if (!strcmp(key, "frozen_cost")) { c->tune.frozen_cost = value; return 0; }
+    if (!strcmp(key, "frozen_cost_rays")) { c->tune.frozen_cost_rays = value; return 0; }
     if (!strcmp(key, "no_frozen_kernel")) { c->tune_no_frozen_kernel = value; return 0; }
     if (!strcmp(key, "no_piggyback")) { c->tune_no_piggyback = value; return 0; }
-    if (!strcmp(key, "frozen_mid_pct")) { if (value < 10 || value > 1000) return fail("nsk_set_tuning: frozen_mid_pct out of range"); c->tune_frozen_mid_pct = value; return 0; }
+    if (!strcmp(key, "frozen_mid_pct")) { if (value < 10 || value > 1000) return fail("nsk_set_tuning: frozen_mid_pct out of range"); c->tune.frozen_mid_pct = value; return 0; }
     if (!strcmp(key, "no_fused_median")) { c->tune_no_fused_median = value; return 0; }
     if (!strcmp(key, "no_deferred_median")) { c->tune_no_deferred_median = value; return 0; }
-    if (!strcmp(key, "fwd_fine_cost")) { c->tune_fwd_fine_cost = value; return 0; }
-    if (!strcmp(key, "fwd_occ_cost")) { c->tune_fwd_occ_cost = value; return 0; }
+    if (!strcmp(key, "fwd_fine_cost")) { c->tune.fwd_fine_cost = value; return 0; }
+    if (!strcmp(key, "fwd_occ_cost")) { c->tune.fwd_occ_cost = value; return 0; }
     if (!strcmp(key, "no_occ_role")) { c->tune_no_occ_role = value; return 0; }
-    if (!strcmp(key, "fwd_color_cost")) { c->tune_fwd_color_cost = value; return 0; }
+    if (!strcmp(key, "fwd_color_cost")) { c->tune.fwd_color_cost = value; return 0; }
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
     if (!strcmp(key, "no_dead_skip")) { c->tune_no_dead_skip = value; return 0; }
-    if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune_dead_tile_pct = value; return 0; }
+    if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune.dead_tile_pct = value; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     if (!strcmp(key, "cloud_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: cloud_cells_x4 must be 1 .. 256"); c->cloud.cells_x4 = value; return 0; }
@@ -1528,11 +1525,6 @@ static int ensure_hist(nsk_ctx* c, size_t bins)
 
 // the forward of a trainable decoder (all but the fine one, see nsk_train.h) also stores its block outputs for the backward
 static bool saves_h(nsk_ctx* c, int w, bool save_masks) { return save_masks && w != 2 && c->dec[w].trainable; }
-static int ensure_hsave(nsk_ctx* c, int w, int M)
-{
-    const size_t tiles = (size_t)(M + 15) / 16 + 1;
-    return grow(c, c->ws.hsave[w], tiles * 10 * 64, "the saved block outputs", GROW_NO_CAPTURE | GROW_STALE_GRAPHS);
-}
 
 static const int STAGE_DEC[4][3] = {{0, -1, -1}, {1, -1, -1}, {1, 2, -1}, {1, 2, 3}};
 
@@ -1573,13 +1565,23 @@ static void fill_args(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* 
     A.out = w == 3 ? c->ws.rgb4 : c->ws.occ[w];
 }
 
-static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, const float* pts, bool save_masks)
+// one decoder of a forward launch: its arguments, the ReLU masks and (trainable, see saves_h) the block outputs kept for the backward
+static int fill_fwd_role(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* ro, const float* rd, const float* pts, bool save_masks)
 {
-    DecArgs A;
     fill_args(c, A, w, M, S, ro, rd, pts);
     A.masks = save_masks ? c->ws.masks[w] : nullptr;
     if (save_masks) c->ws.hsave_M[w] = 0;
-    if (saves_h(c, w, save_masks)) { CHK(ensure_hsave(c, w, M)); A.hsave = c->ws.hsave[w]; c->ws.hsave_M[w] = M; }
+    if (saves_h(c, w, save_masks)) {
+        CHK(grow(c, c->ws.hsave[w], ((size_t)(M + 15) / 16 + 1) * 10 * 64, "the saved block outputs", GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
+        A.hsave = c->ws.hsave[w]; c->ws.hsave_M[w] = M;
+    }
+    return 0;
+}
+
+static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, const float* pts, bool save_masks)
+{
+    DecArgs A;
+    CHK(fill_fwd_role(c, A, w, M, S, ro, rd, pts, save_masks));
     int ntasks = (M + 15) / 16;
     size_t lds = fwd_img_floats(w) * 4;
     int maxwg = c->num_cu;        // persistent: one workgroup per CU balances the 16-sample tasks over SIMDs
@@ -1596,22 +1598,29 @@ static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, c
     return 0;
 }
 
-static int launch_decode_bwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, bool train, bool rays, unsigned flags,
-                             float* g_ro, float* g_rd)
+// one decoder of a backward launch: what every launch form gives it (flags and the Tracker's deferred mask stay with the callers)
+static int fill_bwd_role(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* ro, const float* rd, bool train, bool grids, float* g_ro, float* g_rd)
 {
-    DecArgs A;
     fill_args(c, A, w, M, S, ro, rd, nullptr);
-    A.grid = grid_dev(c, w, (flags & NSK_GRAD_GRIDS) != 0);
+    A.grid = grid_dev(c, w, grids);
     A.masks = c->ws.masks[w];
     A.g_raw = c->ws.g_raw;
     A.g_rays_o = g_ro; A.g_rays_d = g_rd;
     A.g_dec = train ? c->ws.dec_slabs : c->slab + c->dec[w].g_off;
-    A.flags = flags;
     if (w != 0 && (!train || w != 2)) CHK(ensure_bimg16(c, w));      // the chains on fp16 pieces: every frozen MLP decoder, trainable middle / colour
     if (train && w != 2) {
         if (c->ws.hsave_M[w] != M) return fail("backward of trainable decoder %d: its forward must run with the decoder already trainable (block outputs not saved)", w);
         A.hsave = c->ws.hsave[w];
     }
+    return 0;
+}
+
+static int launch_decode_bwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, bool train, bool rays, unsigned flags,
+                             float* g_ro, float* g_rd)
+{
+    DecArgs A;
+    CHK(fill_bwd_role(c, A, w, M, S, ro, rd, train, (flags & NSK_GRAD_GRIDS) != 0, g_ro, g_rd));
+    A.flags = flags;
     int ntasks = (M + 15) / 16;
     size_t lds = bwd_lds_bytes(w, train);
     int grid = std::max(1, std::min((ntasks + 7) / 8, c->num_cu));
@@ -1641,168 +1650,34 @@ static int launch_decode_bwd(nsk_ctx* c, int w, int M, int S, const float* ro, c
     return 0;
 }
 
-// split num_cu workgroups over roles in proportion to their cost per task (every role gets at least one)
-// tasks (optional): per role, the tiles it is expected to RUN (a frozen role under an optimiser mask skips its dead tiles: backward_core), in
-// place of ntasks; the cap on a role's workgroups stays with ntasks, the tiles it walks
-static void split_wgs(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8, const int* tasks = nullptr)
-{
-    int cap = std::max(1, (ntasks + waves - 1) / waves), used = 0;
-    double tot = 0;
-    auto load = [&](int r) { return (double)cost[r] * (tasks ? std::max(1, tasks[r]) : ntasks); };
-    for (int r = 0; r < n; ++r) tot += load(r);
-    for (int r = 0; r < n; ++r) {
-        int k = std::max(1, (int)((double)num_cu * load(r) / tot));
-        k = std::min(k, cap);
-        used += k;
-        wg_end[r] = used;
-    }
-}
-
-// Cost-proportional shares, then single workgroups moved from the role that would suffer least to the role that finishes last while
-// the modelled makespan (whole tiles per wave x cost) falls: a role's time is a step function of its workgroups, and the
-// proportional split alone left the forward 3-5 % behind the best split whenever a role sat just past a step (K3, K4 shard).
-static void split_wgs_balanced(int num_cu, int ntasks, int n, const int* cost, int* wg_end, int waves = 8, const int* tasks = nullptr)
-{
-    split_wgs(num_cu, ntasks, n, cost, wg_end, waves, tasks);
-    int w[4];
-    for (int r = 0; r < n; ++r) w[r] = wg_end[r] - (r ? wg_end[r - 1] : 0);
-    int used = wg_end[n - 1];
-    const int cap = std::max(1, (ntasks + waves - 1) / waves);
-    auto t_of = [&](int r, int wr) { return (long)(((tasks ? tasks[r] : ntasks) + waves * wr - 1) / (waves * wr)) * cost[r]; };
-    for (int r = 0; used < num_cu && r < 8 * n; ++r) {      // hand out what the rounding left, to whoever finishes last
-        int worst = 0;
-        for (int q = 1; q < n; ++q) if (t_of(q, w[q]) > t_of(worst, w[worst])) worst = q;
-        if (w[worst] >= cap) break;
-        ++w[worst]; ++used;
-    }
-    for (int it = 0; it < 64; ++it) {
-        int worst = 0;
-        for (int q = 1; q < n; ++q) if (t_of(q, w[q]) > t_of(worst, w[worst])) worst = q;
-        const long cur = t_of(worst, w[worst]);
-        if (w[worst] >= cap) break;
-        int donor = -1; long best = cur;
-        for (int q = 0; q < n; ++q) {
-            if (q == worst || w[q] <= 1) continue;
-            long m = std::max(t_of(q, w[q] - 1), t_of(worst, w[worst] + 1));
-            for (int o = 0; o < n; ++o) if (o != q && o != worst) m = std::max(m, t_of(o, w[o]));
-            if (m < best) { best = m; donor = q; }
-        }
-        if (donor < 0) break;
-        --w[donor]; ++w[worst];
-    }
-    int acc = 0;
-    for (int r = 0; r < n; ++r) { acc += w[r]; wg_end[r] = acc; }
-}
-
-// Backward with one trainable role: that role advances in whole iterations (8 tasks per workgroup, all its workgroups in
-// lockstep), so its time is ceil(groups / workgroups) iterations -- a step function -- while a frozen role's time falls
-// smoothly with its workgroups.  Pick the trainable role's share by minimising the modelled makespan instead of in
-// proportion to cost (1024 rays: 3 iterations with the proportional 191 workgroups, 2 with 192).
-static void split_wgs_train(int num_cu, int ntasks, int n, const int* cost, int train_role, int* wg_end, const int* tasks = nullptr)
-{
-    const int groups = std::max(1, (ntasks + 7) / 8);
-    // a frozen role's share of the workgroups the trainable role leaves: in proportion to cost x the tiles it runs
-    long fload[3] = {0, 0, 0}, fsum = 0;
-    for (int r = 0; r < n; ++r) if (r != train_role) { fload[r] = (long)cost[r] * std::max(1, tasks ? tasks[r] : ntasks); fsum += fload[r]; }
-    // For every iteration count the role could run, give it the FEWEST workgroups that reach it: more would not shorten it (its time is
-    // a step function) and would starve the frozen roles (1250 rays: 3 iterations need 157 workgroups; the 190 a cost-proportional
-    // split hands it left the frozen roles as the kernel's tail, 120 us against 94 us).
-    long best = -1; int best_wt = 1;
-    const int wt_max = std::min(groups, num_cu - (n - 1));
-    for (int iters = (groups + wt_max - 1) / wt_max; iters <= groups; ++iters) {
-        const int wt = (groups + iters - 1) / iters;
-        if (wt > wt_max) continue;
-        long t = (long)iters * cost[train_role];
-        const int rest = num_cu - wt;
-        for (int r = 0; r < n; ++r) {
-            if (r == train_role) continue;
-            const int wr = std::max(1, (int)((long)rest * fload[r] / std::max(1L, fsum)));
-            t = std::max(t, (long)(((tasks ? tasks[r] : ntasks) + 8 * wr - 1) / (8 * wr)) * cost[r]);
-        }
-        if (best < 0 || t < best) { best = t; best_wt = wt; }
-        if ((long)iters * cost[train_role] > best) break;          // more iterations only get slower from here
-    }
-    const int rest = num_cu - best_wt;
-    int used = 0;
-    for (int r = 0; r < n; ++r) {
-        int k = r == train_role ? best_wt : std::max(1, (int)((long)rest * fload[r] / std::max(1L, fsum)));
-        k = std::min(k, std::max(1, (ntasks + 7) / 8));
-        used += k;
-        wg_end[r] = used;
-    }
-}
-
-// predicted time of a split in the cost units of its roles: every wave of a role walks ceil(tiles / waves) tiles
-static long split_makespan(int ntasks, int n, const int* cost, const int* wg_end, int waves = 8, const int* tasks = nullptr)
-{
-    long t = 0;
-    for (int r = 0; r < n; ++r) {
-        const int w = std::max(1, wg_end[r] - (r ? wg_end[r - 1] : 0));
-        t = std::max(t, (long)(((tasks ? tasks[r] : ntasks) + waves * w - 1) / (waves * w)) * cost[r]);
-    }
-    return t;
-}
-
 // all decoders of the stage in ONE launch (workgroup roles), or a plain launch when the stage has one decoder
 static int launch_decode_fwd_stage(nsk_ctx* c, int stage, int M, int S, const float* ro, const float* rd, bool save_masks)
 {
     int n = 0;
     for (int q = 0; q < 3; ++q) if (STAGE_DEC[stage][q] >= 0) ++n;
     if (n == 1) return launch_decode_fwd(c, STAGE_DEC[stage][0], M, S, ro, rd, nullptr, save_masks);
-    static const int fcost[4] = {96, 240, 292, 248};      // issue cycles per tile of the roles (coarse fp32; middle 7 560, fine 9 380, colour 7 710 + its block-output stores)
+    const int ntasks = (M + 15) / 16;
     MultiArgs MA;
     memset(&MA, 0, sizeof(MA));
-    // middle + fine as ONE role (decode_fwd_occ_body: the middle level looked up once): frozen occupancy decoders on two-piece operands
-    if (c->matmul_mode == 2 && c->tune_no_occ_role != 1 && STAGE_DEC[stage][0] == 1 && STAGE_DEC[stage][1] == 2 && !saves_h(c, 1, save_masks) && !saves_h(c, 2, save_masks)) {
-        const bool colour = STAGE_DEC[stage][2] == 3;
-        for (int r = 0; r < (colour ? 3 : 2); ++r) {
-            const int w = STAGE_DEC[stage][r];
-            fill_args(c, MA.a[r], w, M, S, ro, rd, nullptr);
-            MA.a[r].masks = save_masks ? c->ws.masks[w] : nullptr;
-            if (save_masks) c->ws.hsave_M[w] = 0;
-            MA.which[r] = w;
-        }
-        if (colour && saves_h(c, 3, save_masks)) { CHK(ensure_hsave(c, 3, M)); MA.a[2].hsave = c->ws.hsave[3]; c->ws.hsave_M[3] = M; }
-        int cost[2] = {c->tune_fwd_occ_cost > 0 ? c->tune_fwd_occ_cost : 460, c->tune_fwd_color_cost > 0 ? c->tune_fwd_color_cost : fcost[3]};
-        MA.n = colour ? 2 : 1;
-        split_wgs_balanced(c->num_cu, (M + 15) / 16, MA.n, cost, MA.wg_end, 8);
-        if (!colour) MA.wg_end[1] = MA.wg_end[0];
-        // A merged tile is two decoders long, so small batches quantise worse (K2: 3 000 tiles on 256 workgroups -- forward 37.7 us as three roles,
-        // 40.2 as two): take the form whose split predicts the shorter launch.  (tune_no_occ_role 2: always merged)
-        bool merged = true;
-        if (c->tune_no_occ_role != 2) {
-            int cost3[3], wg3[3], n3 = colour ? 3 : 2;
-            for (int r = 0; r < n3; ++r) {
-                const int w = STAGE_DEC[stage][r];
-                cost3[r] = (w == 2 && c->tune_fwd_fine_cost > 0) ? c->tune_fwd_fine_cost : ((w == 3 && c->tune_fwd_color_cost > 0) ? c->tune_fwd_color_cost : fcost[w]);
-            }
-            split_wgs_balanced(c->num_cu, (M + 15) / 16, n3, cost3, wg3, 8);
-            merged = split_makespan((M + 15) / 16, MA.n, cost, MA.wg_end) <= split_makespan((M + 15) / 16, n3, cost3, wg3);
-        }
-        if (merged) {
-            size_t lds_occ = ((size_t)c->dec[1].fimg16_f + (size_t)c->dec[2].fimg16_f) * 4;
-            if (colour) lds_occ = std::max(lds_occ, (size_t)c->dec[3].fimg16_f * 4);
-            ProfScope ps(c, "decode_fwd_multi");
-            k_decode_fwd_multi_occ<8><<<MA.wg_end[MA.n - 1], 512, lds_occ, c->stream>>>(MA);
-            HIPCHK(hipGetLastError());
-            return 0;
-        }
-        memset(&MA, 0, sizeof(MA));
-    }
-    int cost[3]; size_t lds = 0;
+    size_t lds = 0;
     for (int r = 0; r < n; ++r) {
-        int w = STAGE_DEC[stage][r];
-        fill_args(c, MA.a[r], w, M, S, ro, rd, nullptr);
-        MA.a[r].masks = save_masks ? c->ws.masks[w] : nullptr;
-        if (save_masks) c->ws.hsave_M[w] = 0;
-        if (saves_h(c, w, save_masks)) { CHK(ensure_hsave(c, w, M)); MA.a[r].hsave = c->ws.hsave[w]; c->ws.hsave_M[w] = M; }
-        MA.which[r] = w; cost[r] = (w == 2 && c->tune_fwd_fine_cost > 0) ? c->tune_fwd_fine_cost : ((w == 3 && c->tune_fwd_color_cost > 0) ? c->tune_fwd_color_cost : fcost[w]);
+        const int w = STAGE_DEC[stage][r];
+        CHK(fill_fwd_role(c, MA.a[r], w, M, S, ro, rd, nullptr, save_masks));
+        MA.which[r] = w;
         lds = std::max(lds, fwd_img_floats(w) * 4);
     }
-    MA.n = n;
-    split_wgs_balanced(c->num_cu, (M + 15) / 16, n, cost, MA.wg_end, 8);
+    // middle + fine as ONE role (decode_fwd_occ_body: the middle level looked up once): frozen occupancy decoders on two-piece operands, neither
+    // keeping block outputs (the merged body stores none); which form runs, and its split: plan_fwd (nsk_split.h)
+    const bool can_merge = c->matmul_mode == 2 && STAGE_DEC[stage][0] == 1 && STAGE_DEC[stage][1] == 2 && !saves_h(c, 1, save_masks) && !saves_h(c, 2, save_masks);
+    const FwdPlan P = plan_fwd(c->num_cu, ntasks, STAGE_DEC[stage][2] == 3, c->tune, can_merge ? c->tune_no_occ_role : 1);
+    MA.n = P.n;
+    memcpy(MA.wg_end, P.wg_end, sizeof(P.wg_end));
     ProfScope ps(c, "decode_fwd_multi");
-    if (c->matmul_mode != 0) {
+    if (P.merged) {
+        size_t lds_occ = ((size_t)c->dec[1].fimg16_f + (size_t)c->dec[2].fimg16_f) * 4;
+        if (n == 3) lds_occ = std::max(lds_occ, (size_t)c->dec[3].fimg16_f * 4);
+        k_decode_fwd_multi_occ<8><<<MA.wg_end[MA.n - 1], 512, lds_occ, c->stream>>>(MA);
+    } else if (c->matmul_mode != 0) {
         size_t lds16 = 0;
         for (int r = 0; r < n; ++r) lds16 = std::max(lds16, MA.which[r] == 0 ? fwd_img_floats(0) * 4 : (size_t)c->dec[MA.which[r]].fimg16_f * 4);
         if (c->matmul_mode == 2) k_decode_fwd_multi_bf16<8, 2><<<MA.wg_end[n - 1], 512, lds16, c->stream>>>(MA);
@@ -2426,56 +2301,111 @@ static int flush_pending(nsk_ctx* c)
     return 0;
 }
 
-// dyn_resid: the Tracker's deferred median mask (composite mode 5 wrote the residuals there and the seeds to ws.tmp_rgb): k_decode_bwd_track
-static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, unsigned flags, float* g_ro, float* g_rd,
-                         float* d_loss = nullptr, const float* dyn_resid = nullptr)
+// The steps of backward_core.  BwdRoles: the launch's roles in launch order (colour, fine, middle) and their costs in the split; train_role -2:
+// more than one trainable decoder, or the fine one (its body is not part of k_decode_bwd_multi) -> separate launches
+struct BwdRoles { int n = 0, cost[3] = {0, 0, 0}, train_role = -1; size_t lds = 0; };
+
+// collect: every decoder of the stage that has a gradient to compute becomes a role of MA; marks the parameter groups the launch writes
+static int collect_bwd_roles(nsk_ctx* c, MultiArgs& MA, BwdRoles& R, int stage, int N, int S, const float* ro, const float* rd, unsigned flags,
+                             float* g_ro, float* g_rd, const float* dyn_resid)
 {
-    const bool rays = (flags & NSK_GRAD_RAYS) != 0;
-    const bool grids = (flags & NSK_GRAD_GRIDS) != 0;
-    const int M = N * S;
-    for (int k = 0; k < 3; ++k) { c->dbg_live[k] = -1; c->dbg_counted[k] = false; c->dbg_wgs[k] = 0; }      // (nsk_debug_live_tiles: this backward's, whichever way it leaves)
-    c->dbg_ntasks = (M + 15) / 16;
-    CHK(flush_pending(c));                      // gradients accumulate across calls: the slabs are about to be overwritten
-    MultiArgs MA;
-    memset(&MA, 0, sizeof(MA));
-    int n = 0, cost[3], train_role = -1; size_t lds = 0;
+    const bool rays = (flags & NSK_GRAD_RAYS) != 0, grids = (flags & NSK_GRAD_GRIDS) != 0;
     for (int q = 2; q >= 0; --q) {
         int w = STAGE_DEC[stage][q];
         if (w < 0) continue;
         bool train = (flags & NSK_GRAD_DECODERS) && c->dec[w].trainable;
         if (!train && !grids && !rays) continue;
-        DecArgs& A = MA.a[n];
-        fill_args(c, A, w, M, S, ro, rd, nullptr);
-        A.grid = grid_dev(c, w, grids);
-        A.masks = c->ws.masks[w];
-        A.g_raw = c->ws.g_raw;
-        A.g_rays_o = g_ro; A.g_rays_d = g_rd;
+        DecArgs& A = MA.a[R.n];
+        CHK(fill_bwd_role(c, A, w, N * S, S, ro, rd, train, grids, g_ro, g_rd));
         A.dyn_resid = dyn_resid; A.dyn_n = N;
-        A.g_dec = train ? c->ws.dec_slabs : c->slab + c->dec[w].g_off;
         A.flags = flags & 0xffu;
-        if (w != 0 && (!train || w != 2)) CHK(ensure_bimg16(c, w));
-        if (train && w != 2) {
-            if (c->ws.hsave_M[w] != M) return fail("backward of trainable decoder %d: its forward must run with the decoder already trainable (block outputs not saved)", w);
-            A.hsave = c->ws.hsave[w];
-        }
-        MA.which[n] = w; MA.train[n] = train ? 1 : 0;
-        // relative cost of one tile of a frozen role against one 8-tile iteration of the trainable role (= 1000)
-        const int frozen_cost = rays ? (c->tune_frozen_cost_rays > 0 ? c->tune_frozen_cost_rays : 330) : (c->tune_frozen_cost > 0 ? c->tune_frozen_cost : 205);
-        cost[n] = train ? 1000 : (w == 1 ? frozen_cost * c->tune_frozen_mid_pct / 100 : frozen_cost);
-        lds = std::max(lds, bwd_lds_bytes(w, train));
-        if (train) train_role = (train_role == -1 && w != 2) ? n : -2;     // -2: more than one trainable decoder, or the fine one (its
-                                                                            // body is not part of k_decode_bwd_multi) -> separate launches below
+        MA.which[R.n] = w; MA.train[R.n] = train ? 1 : 0;
+        R.cost[R.n] = bwd_role_cost(train, w, rays, c->tune);
+        R.lds = std::max(R.lds, bwd_lds_bytes(w, train));
+        if (train) R.train_role = (R.train_role == -1 && w != 2) ? R.n : -2;
         if (train) c->touched[NSK_GROUP_DECODERS] = true;
         if (grids) c->touched[NSK_GROUP_COARSE + w] = true;
-        ++n;
+        ++R.n;
     }
+    return 0;
+}
+
+// Dead-tile skip: a frozen role whose level carries an optimiser mask walks the slots' liveness bytes (forward_core) and runs only the tiles
+// with a sample that reaches a marked voxel.  Never with ray gradients (d/dp flows through every sample), the Tracker's launch or the
+// full-width chains (`eligible`).  The roles count what they ran (counted[]); the count of an EARLIER step of the same kind (whatever has arrived
+// in live_host: nobody waits for it) tells the split how long the frozen roles really are (tasks[]) -- the first step of a kind assumes every
+// tile runs.
+static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, int stage, int M, unsigned flags, bool eligible, bool frozen_only,
+                         int* tasks, bool* counted)
+{
+    const int ntasks = (M + 15) / 16;
+    for (int r = 0; r < 3; ++r) { tasks[r] = ntasks; counted[r] = false; }
+    if (!c->live_ok || !eligible || c->tune_no_dead_skip) return;
+    const int key[8] = {stage, M, (int)(flags & 0xffu), c->sorted ? 1 : 0, c->live_epoch, R.n, R.train_role, frozen_only ? 1 : 0};
+    if (memcmp(key, c->live_key, sizeof(key)) != 0) { memcpy(c->live_key, key, sizeof(key)); ++c->live_tag; }
+    const volatile int* h = c->live_host;
+    const bool fresh = h[3] == c->live_tag;
+    for (int r = 0; r < R.n; ++r) {
+        const int w = MA.which[r];
+        if (MA.train[r] || w < 1 || !c->grid[w].mask || c->grid[w].live_dirty) continue;
+        DecArgs& A = MA.a[r];
+        A.live = c->sorted ? c->ws.lslot : c->ws.lsamp; A.live_bit = 1u << (w - 1); A.live_cnt = c->live_cnt + (w - 1);
+        counted[r] = true; c->dbg_counted[w - 1] = true;
+        if (fresh) tasks[r] = dead_skip_tasks(ntasks, (int)h[w - 1], c->tune);
+    }
+}
+
+// the prepared batch's cell-sort offsets ride behind the roles (nsk_map_prepare): short workgroups that wait for nothing of this launch
+static int attach_prep_scan(nsk_ctx* c, MultiArgs& MA, bool may_ride, int waves4)
+{
+    nsk_ctx::Prep& P = c->prep;
+    if (!(P.valid && P.sorted && (P.done & 3) == 1 && may_ride && !c->capturing && !c->tune_no_piggyback)) return 0;
+    MA.scan = scan_args(c, P.stage, c->ws.offs_alt, waves4);
+    P.done |= 2;
+    return MA.scan.nblocks;
+}
+
+// scan_wgs: of attach_prep_scan; extra: the workgroup that sums the per-ray losses
+static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool rays, bool full, bool frozen_only, bool track, int scan_wgs, int extra)
+{
+    const int n = R.n; const size_t lds = R.lds;
+    ProfScope ps(c, "decode_bwd_multi");
+    if (track) {
+        MA.dyn_seed = c->ws.tmp_rgb; MA.dyn_thr_out = c->scal + 1;
+        k_decode_bwd_track<<<MA.wg_end[n - 1] + 1, 512, lds + NSK_DYN_LDS_BYTES, c->stream>>>(MA);
+    } else if (full) {
+        size_t ldsf = 0;
+        for (int r = 0; r < n; ++r) ldsf = std::max(ldsf, bwd_img_floats(MA.which[r]) * 4 + (MA.train[r] ? PN_FLOATS(2) * 4 : 8 * 3840));
+        if (rays) k_decode_bwd_multi_full<true><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
+        else k_decode_bwd_multi_full<false><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
+    } else if (frozen_only) {
+        const size_t lds16 = lds - 8 * 3840 + (size_t)NSK_FROZEN_NW * 3840;      // image + one scatter scratch per wave
+        k_decode_bwd_frozen<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
+    } else if (rays) k_decode_bwd_multi<true><<<MA.wg_end[n - 1] + extra, 512, lds, c->stream>>>(MA);
+    else k_decode_bwd_multi<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA);
+}
+
+// dyn_resid: the Tracker's deferred median mask (composite mode 5 wrote the residuals there and the seeds to ws.tmp_rgb): k_decode_bwd_track
+static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, unsigned flags, float* g_ro, float* g_rd,
+                         float* d_loss = nullptr, const float* dyn_resid = nullptr)
+{
+    const bool rays = (flags & NSK_GRAD_RAYS) != 0, grids = (flags & NSK_GRAD_GRIDS) != 0;
+    const int M = N * S, ntasks = (M + 15) / 16;
+    for (int k = 0; k < 3; ++k) { c->dbg_live[k] = -1; c->dbg_counted[k] = false; c->dbg_wgs[k] = 0; }      // (nsk_debug_live_tiles: this backward's, whichever way it leaves)
+    c->dbg_ntasks = ntasks;
+    CHK(flush_pending(c));                      // gradients accumulate across calls: the slabs are about to be overwritten
+    MultiArgs MA;
+    memset(&MA, 0, sizeof(MA));
+    BwdRoles R;
+    CHK(collect_bwd_roles(c, MA, R, stage, N, S, ro, rd, flags, g_ro, g_rd, dyn_resid));
+    const int n = R.n, train_role = R.train_role;
     if (dyn_resid && (train_role != -1 || !rays || c->deterministic || c->bwd_mode == 0 || n == 0 || N > NSK_MEDIAN_FUSED_MAX))
         return fail("backward_core: the deferred median mask needs the Tracker's launch (frozen decoders, ray gradients)");      // the caller checked the same
     const int separate = c->deterministic ? 1 : 0;      // debug mode: one launch per decoder, in a fixed order
     if ((n == 0 || train_role == -2 || separate) && d_loss) { ProfScope ps(c, "loss_sum"); k_sum<<<1, 1024, 0, c->stream>>>(N, c->ws.ray_loss, d_loss); }
     if (n == 0) return 0;
+    for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = ntasks;      // until a role counts fewer
     if (train_role == -2 || separate) {      // rare configuration (several trainable decoders share one slab buffer): one launch each
-        for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = c->dbg_ntasks;
         for (int r = 0; r < n; ++r)
             CHK(launch_decode_bwd(c, MA.which[r], M, S, ro, rd, MA.train[r] != 0, rays, flags, g_ro, g_rd));
         return 0;
@@ -2485,76 +2415,20 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     // gradients the frozen bodies need 160 VGPRs (the Tracker: 600 tiles, latency-bound either way) and stay in k_decode_bwd_multi
     const bool full = c->bwd_mode == 0;                 // every chain on the fp32 MFMA: k_decode_bwd_multi_full, nothing rides
     const bool frozen_only = train_role == -1 && !rays && !c->tune_no_frozen_kernel && !full;
-    // Dead-tile skip: a frozen role whose level carries an optimiser mask walks the slots' liveness bytes (forward_core) and runs only the tiles
-    // with a sample that reaches a marked voxel.  Never with ray gradients (d/dp flows through every sample), the Tracker's launch or the
-    // full-width chains.  The roles count what they ran; the count of an EARLIER step of the same kind (whatever has arrived in live_host: nobody
-    // waits for it) tells the split how long the frozen roles really are -- the first step of a kind assumes every tile runs.
-    const int ntasks = (M + 15) / 16;
-    int tasks[3] = {ntasks, ntasks, ntasks};
-    bool counted[3] = {false, false, false};
-    for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = ntasks;
-    if (c->live_ok && grids && !rays && !full && !dyn_resid && !c->tune_no_dead_skip) {
-        const int key[8] = {stage, M, (int)(flags & 0xffu), c->sorted ? 1 : 0, c->live_epoch, n, train_role, frozen_only ? 1 : 0};
-        if (memcmp(key, c->live_key, sizeof(key)) != 0) { memcpy(c->live_key, key, sizeof(key)); ++c->live_tag; }
-        const volatile int* h = c->live_host;
-        const bool fresh = h[3] == c->live_tag;
-        for (int r = 0; r < n; ++r) {
-            const int w = MA.which[r];
-            if (MA.train[r] || w < 1 || !c->grid[w].mask || c->grid[w].live_dirty) continue;
-            DecArgs& A = MA.a[r];
-            A.live = c->sorted ? c->ws.lslot : c->ws.lsamp; A.live_bit = 1u << (w - 1); A.live_cnt = c->live_cnt + (w - 1);
-            counted[r] = true; c->dbg_counted[w - 1] = true;
-            if (fresh) {
-                const int lv = std::max(0, std::min(ntasks, (int)h[w - 1]));
-                tasks[r] = lv + (int)((long)(ntasks - lv) * c->tune_dead_tile_pct / 100);
-            }
-        }
-    }
-    if (train_role >= 0 && n > 1) split_wgs_train(c->num_cu, ntasks, n, cost, train_role, MA.wg_end, tasks);
-    else split_wgs_balanced(c->num_cu, ntasks, n, cost, MA.wg_end, frozen_only ? NSK_FROZEN_NW : 8, tasks);
+    int tasks[3]; bool counted[3];
+    bwd_liveness(c, MA, R, stage, M, flags, grids && !rays && !full && !dyn_resid, frozen_only, tasks, counted);
+    plan_bwd(c->num_cu, ntasks, n, R.cost, train_role, frozen_only ? NSK_FROZEN_NW : 8, tasks, MA.wg_end);
     for (int r = 0; r < n; ++r) {
-        const int wgs = MA.wg_end[r] - (r ? MA.wg_end[r - 1] : 0);
-        if (counted[r]) MA.live_wgs += wgs;
-        if (MA.which[r] >= 1) c->dbg_wgs[MA.which[r] - 1] = wgs;
+        if (counted[r]) MA.live_wgs += role_wgs(MA.wg_end, r);
+        if (MA.which[r] >= 1) c->dbg_wgs[MA.which[r] - 1] = role_wgs(MA.wg_end, r);
     }
     MA.live_cnt = c->live_cnt; MA.live_out = c->live_host_dev; MA.live_tag = c->live_tag;
     const int extra = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
     if (d_loss) { MA.sum_src = c->ws.ray_loss; MA.sum_dst = d_loss; MA.sum_n = N; }
-    // the prepared batch's cell-sort offsets ride behind the roles (nsk_map_prepare): short workgroups that wait for nothing of this launch
-    int scan_wgs = 0;
-    {
-        nsk_ctx::Prep& P = c->prep;
-        if (P.valid && P.sorted && (P.done & 3) == 1 && !rays && !full && !c->capturing && !c->tune_no_piggyback) {
-            MA.scan = scan_args(c, P.stage, c->ws.offs_alt, frozen_only ? NSK_FROZEN_NW / 4 : 2);
-            scan_wgs = MA.scan.nblocks;
-            P.done |= 2;
-        }
-    }
-    {
-        ProfScope ps(c, "decode_bwd_multi");
-        if (dyn_resid) {
-            MA.dyn_seed = c->ws.tmp_rgb; MA.dyn_thr_out = c->scal + 1;
-            k_decode_bwd_track<<<MA.wg_end[n - 1] + 1, 512, lds + NSK_DYN_LDS_BYTES, c->stream>>>(MA);
-        } else if (full) {
-            size_t ldsf = 0;
-            for (int r = 0; r < n; ++r) {
-                const int w = MA.which[r];
-                ldsf = std::max(ldsf, MA.train[r] ? (bwd_img_floats(w) + PN_FLOATS(2)) * 4 : bwd_img_floats(w) * 4 + 8 * 3840);
-            }
-            if (rays) k_decode_bwd_multi_full<true><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
-            else k_decode_bwd_multi_full<false><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
-        } else if (frozen_only) {
-            const size_t lds16 = lds - 8 * 3840 + (size_t)NSK_FROZEN_NW * 3840;      // image + one scatter scratch per wave
-            k_decode_bwd_frozen<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
-        } else if (rays) k_decode_bwd_multi<true><<<MA.wg_end[n - 1] + extra, 512, lds, c->stream>>>(MA);
-        else k_decode_bwd_multi<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA);
-    }
+    const int scan_wgs = attach_prep_scan(c, MA, !rays && !full, frozen_only ? NSK_FROZEN_NW / 4 : 2);
+    launch_bwd_roles(c, MA, R, rays, full, frozen_only, dyn_resid != nullptr, scan_wgs, extra);
     HIPCHK(hipGetLastError());
-    if (train_role >= 0) {
-        int w = MA.which[train_role];
-        int nb = MA.wg_end[train_role] - (train_role == 0 ? 0 : MA.wg_end[train_role - 1]);
-        c->pend_w = w; c->pend_nb = nb;          // summed by k_adam_multi, or by flush_pending when someone reads the slab first
-    }
+    if (train_role >= 0) { c->pend_w = MA.which[train_role]; c->pend_nb = role_wgs(MA.wg_end, train_role); }      // summed by k_adam_multi, or by flush_pending when someone reads the slab first
     return 0;
 }
 

@@ -1,0 +1,178 @@
+// The workgroup-split planner of the decoder launches (csrc/nsk_split.h) on the CPU: no torch, no HIP.  tests/test_split_cpu.py runs it.
+//   split_test <table>   the literal cases below, then every row of the recorded table (tests/golden/wg_splits.txt) recomputed and compared
+//   split_test --dump    prints the sweep in the table's format (how the table was recorded: see the table's header)
+// Row: <fn> <num_cu> <ntasks> <n> <waves> <train_role>  c0 c1 c2  t0 t1 t2 | w0 w1 w2 <makespan>      fn: S split_wgs, B split_wgs_balanced,
+// T split_wgs_train; t0 = -1: no tasks; unused columns 0; w: workgroups per role; makespan: split_makespan of that split (same waves and tasks)
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "nsk_split.h"
+
+static const int NUM_CU = 256;
+static int failures = 0;
+
+struct Row { char fn; int num_cu, ntasks, n, waves, train_role, cost[3], tasks[3], w[3]; long makespan; };
+
+static void compute(Row& R)
+{
+    int wg_end[3] = {0, 0, 0};
+    const int* tasks = R.tasks[0] < 0 ? nullptr : R.tasks;
+    if (R.fn == 'S') split_wgs(R.num_cu, R.ntasks, R.n, R.cost, wg_end, R.waves, tasks);
+    else if (R.fn == 'B') split_wgs_balanced(R.num_cu, R.ntasks, R.n, R.cost, wg_end, R.waves, tasks);
+    else split_wgs_train(R.num_cu, R.ntasks, R.n, R.cost, R.train_role, wg_end, tasks);
+    for (int r = 0; r < 3; ++r) R.w[r] = r < R.n ? role_wgs(wg_end, r) : 0;
+    R.makespan = split_makespan(R.ntasks, R.n, R.cost, wg_end, R.waves, tasks);
+}
+
+static void print_row(FILE* f, const Row& R)
+{
+    fprintf(f, "%c %d %d %d %d %d  %d %d %d  %d %d %d | %d %d %d %ld\n", R.fn, R.num_cu, R.ntasks, R.n, R.waves, R.train_role, R.cost[0], R.cost[1],
+            R.cost[2], R.tasks[0], R.tasks[1], R.tasks[2], R.w[0], R.w[1], R.w[2], R.makespan);
+}
+
+// every role has a workgroup and none more than the tiles it walks fill (wg_end increasing follows from the first)
+static bool within_caps(const Row& R)
+{
+    const int cap = std::max(1, (R.ntasks + R.waves - 1) / R.waves);
+    for (int r = 0; r < R.n; ++r) if (R.w[r] < 1 || R.w[r] > cap) return false;
+    return true;
+}
+
+static std::vector<int> sweep_tiles()
+{
+    std::vector<int> v;
+    for (int t = 1; t <= 64; ++t) v.push_back(t);
+    for (int p = 7; p <= 20; ++p) for (int d = -1; d <= 1; ++d) v.push_back((1 << p) + d);
+    return v;
+}
+
+static Row make_row(char fn, int ntasks, int n, int waves, int train_role, const int* cost, bool with_tasks)
+{
+    Row R;
+    memset(&R, 0, sizeof(R));
+    R.fn = fn; R.num_cu = NUM_CU; R.ntasks = ntasks; R.n = n; R.waves = waves; R.train_role = train_role;
+    const int part[3] = {ntasks, ntasks * 3 / 10, ntasks / 8};        // a role that runs everything, one that skips most, one that skips nearly all
+    for (int r = 0, f = 1; r < n; ++r) {
+        R.cost[r] = fn == 'T' ? (r == train_role ? 1000 : cost[r]) : cost[r];
+        R.tasks[r] = fn == 'T' ? (r == train_role ? ntasks : part[f++]) : part[r];
+    }
+    if (!with_tasks) { R.tasks[0] = -1; R.tasks[1] = R.tasks[2] = 0; }
+    return R;
+}
+
+static int dump()
+{
+    static const int fwd[3] = {240, 292, 248}, frozen[3] = {205, 205, 205};
+    long rows = 0, bad = 0;
+    for (int ntasks : sweep_tiles())
+        for (int n = 1; n <= 3; ++n)
+            for (int tk = 0; tk < 2; ++tk) {
+                std::vector<Row> v;
+                for (int waves = 8; waves <= 16; waves += 8) {
+                    v.push_back(make_row('S', ntasks, n, waves, -1, waves == 8 ? fwd : frozen, tk));
+                    v.push_back(make_row('B', ntasks, n, waves, -1, fwd, tk));
+                    v.push_back(make_row('B', ntasks, n, waves, -1, frozen, tk));
+                }
+                for (int tr = 0; tr < n; ++tr) v.push_back(make_row('T', ntasks, n, 8, tr, frozen, tk));
+                for (Row& R : v) { compute(R); print_row(stdout, R); ++rows; if (!within_caps(R)) { ++bad; fprintf(stderr, "caps: "); print_row(stderr, R); } }
+            }
+    fprintf(stderr, "%ld rows, %ld outside [1, cap]\n", rows, bad);
+    return 0;
+}
+
+static void expect(const char* what, char fn, int ntasks, int n, int waves, int train_role, const int* cost, const int* tasks, const int* want, long want_makespan = -1)
+{
+    Row R;
+    memset(&R, 0, sizeof(R));
+    R.fn = fn; R.num_cu = NUM_CU; R.ntasks = ntasks; R.n = n; R.waves = waves; R.train_role = train_role; R.tasks[0] = -1;
+    for (int r = 0; r < n; ++r) { R.cost[r] = cost[r]; if (tasks) R.tasks[r] = tasks[r]; }
+    compute(R);
+    bool ok = want_makespan < 0 || R.makespan == want_makespan;
+    for (int r = 0; r < n; ++r) ok = ok && R.w[r] == want[r];
+    if (!ok) { ++failures; fprintf(stderr, "FAIL %s: got ", what); print_row(stderr, R); }
+}
+
+static void literal_cases()
+{
+    // the backward of the colour stage: roles {colour trainable, fine, middle}, 48 samples per ray -> 3 tiles per ray
+    const int ctrain[3] = {1000, 205, 205};
+    const int t64[3] = {24, 24, 24}, t1000[3] = {188, 34, 34}, t1024[3] = {192, 32, 32}, t1250[3] = {157, 49, 49}, t5000[3] = {171, 42, 42};
+    expect("train 64 rays", 'T', 192, 3, 8, 0, ctrain, nullptr, t64);
+    expect("train 1000 rays", 'T', 3000, 3, 8, 0, ctrain, nullptr, t1000);
+    expect("train 1024 rays (2 iterations need 192 workgroups)", 'T', 3072, 3, 8, 0, ctrain, nullptr, t1024);
+    expect("train 1250 rays (3 iterations need 157 workgroups)", 'T', 3750, 3, 8, 0, ctrain, nullptr, t1250);
+    expect("train 5000 rays", 'T', 15000, 3, 8, 0, ctrain, nullptr, t5000);
+    const int live[3] = {3072, 900, 400}, tlive[3] = {192, 44, 19};
+    expect("train 1024 rays, live counts", 'T', 3072, 3, 8, 0, ctrain, live, tlive);
+    // two frozen roles on the 16-wave kernel
+    const int fr[2] = {205, 205}, f192[2] = {12, 12}, f128[2] = {128, 128};
+    expect("frozen 192 tiles", 'B', 192, 2, 16, -1, fr, nullptr, f192);
+    expect("frozen 3072 tiles", 'B', 3072, 2, 16, -1, fr, nullptr, f128);
+    expect("frozen 15000 tiles", 'B', 15000, 2, 16, -1, fr, nullptr, f128);
+    // the forward's three roles
+    const int fw[3] = {240, 292, 248}, one[3] = {1, 1, 1}, w3000[3] = {78, 95, 83}, w15000[3] = {79, 95, 82};
+    expect("forward 1 tile", 'B', 1, 3, 8, -1, fw, nullptr, one, 292);
+    expect("forward 7 tiles", 'B', 7, 3, 8, -1, fw, nullptr, one, 292);
+    expect("forward 3000 tiles", 'B', 3000, 3, 8, -1, fw, nullptr, w3000, 1240);
+    expect("forward 15000 tiles", 'B', 15000, 3, 8, -1, fw, nullptr, w15000, 5840);
+    const int mg[2] = {460, 248}, wm[2] = {167, 89};
+    expect("forward merged 3000 tiles", 'B', 3000, 2, 8, -1, mg, nullptr, wm, 1380);
+    expect("one role, one tile", 'B', 1, 1, 8, -1, fw, nullptr, one);
+
+    // the forward's choice: 3 000 tiles predict 1 380 merged against 1 240 as three roles (K2) -> three roles, with their split
+    const SplitTune T;
+    FwdPlan P = plan_fwd(NUM_CU, 3000, true, T, 0);
+    if (P.merged || P.n != 3 || P.wg_end[0] != 78 || P.wg_end[1] != 78 + 95 || P.wg_end[2] != 78 + 95 + 83) { ++failures; fprintf(stderr, "FAIL plan_fwd 3000 tiles\n"); }
+    P = plan_fwd(NUM_CU, 3000, true, T, 2);
+    if (!P.merged || P.n != 2 || P.wg_end[0] != 167 || P.wg_end[1] != 167 + 89) { ++failures; fprintf(stderr, "FAIL plan_fwd 3000 tiles, always merged\n"); }
+    P = plan_fwd(NUM_CU, 3000, false, T, 2);
+    if (!P.merged || P.n != 1 || P.wg_end[1] != P.wg_end[0]) { ++failures; fprintf(stderr, "FAIL plan_fwd without colour\n"); }
+    // the cost model's built-in values and the keys that override them
+    SplitTune U;
+    bool ok = fwd_role_cost(0, U) == 96 && fwd_role_cost(1, U) == 240 && fwd_role_cost(2, U) == 292 && fwd_role_cost(3, U) == 248 && fwd_occ_role_cost(U) == 460;
+    ok = ok && bwd_role_cost(true, 3, false, U) == 1000 && bwd_role_cost(false, 2, false, U) == 205 && bwd_role_cost(false, 1, true, U) == 330;
+    ok = ok && dead_skip_tasks(3072, 900, U) == 900 + (3072 - 900) * 12 / 100 && dead_skip_tasks(100, 500, U) == 100 && dead_skip_tasks(100, -3, U) == 12;
+    U.fwd_fine_cost = 300; U.fwd_color_cost = 250; U.fwd_occ_cost = 470; U.frozen_cost = 220; U.frozen_cost_rays = 340; U.frozen_mid_pct = 150; U.dead_tile_pct = 0;
+    ok = ok && fwd_role_cost(1, U) == 240 && fwd_role_cost(2, U) == 300 && fwd_role_cost(3, U) == 250 && fwd_occ_role_cost(U) == 470;
+    ok = ok && bwd_role_cost(false, 2, false, U) == 220 && bwd_role_cost(false, 1, false, U) == 330 && bwd_role_cost(false, 3, true, U) == 340 && dead_skip_tasks(100, 40, U) == 40;
+    if (!ok) { ++failures; fprintf(stderr, "FAIL cost model\n"); }
+    // the backward's choice: one trainable role among several -> the iteration-count split; alone, or none -> the balanced one on the given waves
+    int a[3], b[3];
+    plan_bwd(NUM_CU, 3072, 3, ctrain, 0, 8, nullptr, a); split_wgs_train(NUM_CU, 3072, 3, ctrain, 0, b);
+    ok = !memcmp(a, b, sizeof(a));
+    plan_bwd(NUM_CU, 3072, 2, fr, -1, 16, nullptr, a); split_wgs_balanced(NUM_CU, 3072, 2, fr, b, 16);
+    ok = ok && !memcmp(a, b, 2 * sizeof(int));
+    plan_bwd(NUM_CU, 3072, 1, ctrain, 0, 8, nullptr, a); split_wgs_balanced(NUM_CU, 3072, 1, ctrain, b, 8);
+    ok = ok && a[0] == b[0];
+    if (!ok) { ++failures; fprintf(stderr, "FAIL plan_bwd\n"); }
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 2 && !strcmp(argv[1], "--dump")) return dump();
+    if (argc != 2) { fprintf(stderr, "usage: split_test <table> | --dump\n"); return 2; }
+    literal_cases();
+    FILE* f = fopen(argv[1], "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    char line[256];
+    long rows = 0;
+    while (fgets(line, sizeof(line), f)) {
+        if (line[0] == '#' || line[0] == '\n') continue;
+        Row W, R;
+        memset(&W, 0, sizeof(W));
+        if (sscanf(line, "%c %d %d %d %d %d %d %d %d %d %d %d | %d %d %d %ld", &W.fn, &W.num_cu, &W.ntasks, &W.n, &W.waves, &W.train_role, &W.cost[0], &W.cost[1],
+                   &W.cost[2], &W.tasks[0], &W.tasks[1], &W.tasks[2], &W.w[0], &W.w[1], &W.w[2], &W.makespan) != 16 ||
+            !strchr("SBT", W.fn) || W.n < 1 || W.n > 3 || W.ntasks < 1 || W.waves < 1 || W.num_cu < 3 || (W.fn == 'T' && (W.train_role < 0 || W.train_role >= W.n))) {
+            fprintf(stderr, "bad row: %s", line); fclose(f); return 2;
+        }
+        R = W;
+        compute(R);
+        ++rows;
+        if (memcmp(R.w, W.w, sizeof(R.w)) != 0 || R.makespan != W.makespan) { if (++failures < 20) { fprintf(stderr, "FAIL table: want %sgot  ", line); print_row(stderr, R); } }
+        else if (!within_caps(R)) { if (++failures < 20) { fprintf(stderr, "FAIL caps: "); print_row(stderr, R); } }
+    }
+    fclose(f);
+    printf("split_test: %ld rows, %d failures\n", rows, failures);
+    return failures ? 1 : 0;
+}

@@ -1,0 +1,19 @@
+"""The workgroup-split planner of the decoder launches (csrc/nsk_split.h) without a GPU: host/test/split_test.cpp, built by a plain host compiler
+under AddressSanitizer + UBSan, checks the worked examples of the planner's comments and recomputes every row of tests/golden/wg_splits.txt,
+the splits recorded from the functions as they stood inside nsk.hip."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "nice-slam-cpp_amd", "host")
+TABLE = os.path.join(ROOT, "tests", "golden", "wg_splits.txt")
+
+
+def test_the_split_planner_reproduces_its_recorded_table():
+    subprocess.check_call(["make", "-s", "-C", HOST, "split_test"])
+    r = subprocess.run([os.path.join(HOST, "split_test"), TABLE], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1"))
+    with open(TABLE) as f:
+        rows = sum(1 for line in f if line.strip() and not line.startswith("#"))
+    assert rows > 5000                # (the sweep in the table's header)
+    assert r.returncode == 0 and "split_test: %d rows, 0 failures" % rows in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]

@@ -1,6 +1,7 @@
 """What the dead-tile skip does to a workload's backward, on the GPU: the tiles the frozen roles ran (nsk_debug_live_tiles, to be compared with
 tools/live_tiles.py), the workgroup split the launch chose and the launch's time, with the skip, without it (no_dead_skip), and -- `cost` --
-with every tile dead against every tile live, which is what a skipped tile costs in the split (nsk_set_tuning "dead_tile_pct").
+with every tile dead against every tile live, which is what a skipped tile costs in the split (nsk_set_tuning "dead_tile_pct"; the split
+itself is csrc/nsk_split.h, and tests/test_split_cpu.py shows what it gives for a tile count without a GPU).
 usage: [NSK_LIB=<lib>] python tools/live_split.py [K3 K3:fine K2 K4 cost]"""
 import os
 import sys
