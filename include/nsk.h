@@ -108,6 +108,8 @@ int nsk_set_sort_mode(nsk_ctx* ctx, int mode);
  *                      not covered);
  *   "roctx" 1:         roctxRangePush/Pop around every launch group (names as in nsk_profile_end) for rocprofv3 --marker-trace;
  *   "frozen_cost" n:   relative cost of a frozen decoder's tile in the backward's workgroup split (0 = built-in value);
+ *                      this and the other cost keys of the splits ("frozen_cost_rays", "fwd_fine_cost", "fwd_occ_cost", "fwd_color_cost")
+ *                      take 0 .. 1 000 000, anything else is refused;
  *   "no_fused_median" 1: nsk_track_step computes the Tracker's median threshold in a launch of its own (composite, median, composite)
  *                      even where a fused form applies;
  *   "no_deferred_median" 1: with ray gradients and frozen decoders the threshold is found inside the compositing launch behind a grid
@@ -570,7 +572,8 @@ int nsk_profile_end(nsk_ctx* ctx, char* buf, size_t buf_bytes);
  * current matmul mode (N, rays = those of the last step). */
 int nsk_debug_relu_bits(nsk_ctx* ctx, int which, int M, uint8_t* h_bits);
 /* nsk_debug_fetch: a per-sample array of the last step's workspace, to the host: what = 0..2 the occupancy output of decoder 0..2 [M] (their sum is
- * the sigma whose relu the compositing takes, include/torchlib/utils.h:160), 3 the colour decoder's output [M][4], 4 d loss / d raw [M][4], 5 z [M]. */
+ * the sigma whose relu the compositing takes, include/torchlib/utils.h:160), 3 the colour decoder's output [M][4], 4 d loss / d raw [M][4], 5 z [M],
+ * 6 the 10 x median threshold the last nsk_track_step with handle_dynamic applied (one float). */
 int nsk_debug_fetch(nsk_ctx* ctx, int what, int M, float* h_out);
 int nsk_debug_preact(nsk_ctx* ctx, int which, int N, const float* d_rays_o, const float* d_rays_d, float* d_preact);
 /* nsk_debug_live_tiles: the dead-tile skip (nsk_set_mask) of the last step's backward, after a synchronise.  h_counts[0..2]: the 16-sample tiles the
@@ -579,6 +582,29 @@ int nsk_debug_preact(nsk_ctx* ctx, int which, int N, const float* d_rays_o, cons
  * decoder), h_counts[7]: the tiles of the batch -- h_counts has 8 entries.  h_perm [M] (may be NULL): the sample in each tile slot; h_bytes [M] (may be NULL): the slots' liveness bytes -- bit 0
  * middle, 1 fine, 2 colour: the sample's cell at that level has a marked corner voxel (7 everywhere when the step wrote none). */
 int nsk_debug_live_tiles(nsk_ctx* ctx, int M, int* h_counts, int32_t* h_perm, uint8_t* h_bytes);
+/* nsk_debug_last_split: how the last forward decoder launch (dir 0) or the last backward (dir 1) of the context divided its workgroups, after a
+ * synchronise.  Recorded on the host where the launch's role ranges are filled; launches nothing.  h_out has NSK_SPLIT_INTS entries:
+ *   [0]      the form, one of NSK_SPLIT_* below (0: no such launch yet, or the backward had no gradient to compute)
+ *   [1]      n, the roles of the launch (separate launches: the decoders launched one after the other)
+ *   [2..4]   which[r]: the decoder of role r (0 coarse .. 3 colour); the merged middle + fine role of NSK_SPLIT_FWD_MERGED reports 1
+ *   [5..7]   train[r]: 1 if role r is the trainable body (forward: 0)
+ *   [8..10]  the workgroups of role r (single decoder / separate launches: the grid of each launch)
+ *   [11]     the workgroups of the prepared batch's cell-sort scan riding behind the roles (nsk_map_prepare)
+ *   [12]     1 if a workgroup behind those summed the per-ray losses (the Tracker's launch: its last workgroup did)
+ *   [13]     the 16-sample tiles of the batch
+ *   [14]     the workgroups of the launch, riders included
+ *   [15]     1 if the last workgroup found the Tracker's median threshold (NSK_SPLIT_BWD_TRACK) */
+#define NSK_SPLIT_INTS 16
+#define NSK_SPLIT_FWD_SINGLE 1       /* one decoder: k_decode_fwd */
+#define NSK_SPLIT_FWD_MULTI 2        /* a role per decoder, fp32 MFMA */
+#define NSK_SPLIT_FWD_MULTI_SPLIT 3  /* a role per decoder, split-precision operands (matmul modes 1 and 2) */
+#define NSK_SPLIT_FWD_MERGED 4       /* middle + fine as one role (+ colour) */
+#define NSK_SPLIT_BWD_SEPARATE 1     /* one launch per decoder */
+#define NSK_SPLIT_BWD_MULTI 2        /* k_decode_bwd_multi */
+#define NSK_SPLIT_BWD_MULTI_FULL 3   /* k_decode_bwd_multi_full (nsk_set_backward_mode 0) */
+#define NSK_SPLIT_BWD_FROZEN 4       /* k_decode_bwd_frozen */
+#define NSK_SPLIT_BWD_TRACK 5        /* k_decode_bwd_track */
+int nsk_debug_last_split(nsk_ctx* ctx, int dir, int* h_out);
 
 #ifdef __cplusplus
 }

@@ -824,6 +824,7 @@ struct nsk_ctx {
                   bool live = false; int live_epoch = 0; } prep, req;      // live: its sampling wrote liveness bytes, under the masks of live_epoch
     int tune_no_piggyback = 0;              // 1: a prepared batch is sampled by launches of its own at the start of its step (experiments, tests)
     int pend_w = -1, pend_nb = 0;           // decoder whose per-workgroup gradient slabs are not yet summed into the slab (flush_pending)
+    int dbg_split[2][NSK_SPLIT_INTS] = {{0}, {0}};      // nsk_debug_last_split: the last forward decoder launch / the last backward, recorded where wg_end is filled
     int dbg_M = 0, dbg_S = 0;               // sample count / samples per ray of the last forward_core (nsk_debug_relu_bits, nsk_debug_preact)
     int bwd_mode = 2;                       // decoder backward chains: 2 fp16 2-piece split (default), 0 fp32 MFMA (nsk_set_backward_mode: a measuring stick)
     int matmul_mode = 2;                    // decoder forward: 0 fp32 MFMA, 1 bf16 3-piece split, 2 fp16 2-piece split (nsk_bf16.h)
@@ -1074,17 +1075,17 @@ extern "C" int nsk_set_backward_mode(nsk_ctx* c, int mode)
 extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
 {
     if (!c || !key) return fail("nsk_set_tuning: null argument");
-    if (!strcmp(key, "frozen_cost")) { c->tune.frozen_cost = value; return 0; }
-    if (!strcmp(key, "frozen_cost_rays")) { c->tune.frozen_cost_rays = value; return 0; }
+    if (!strcmp(key, "frozen_cost")) { if (value < 0 || value > 1000000) return fail("nsk_set_tuning: frozen_cost out of range"); c->tune.frozen_cost = value; return 0; }
+    if (!strcmp(key, "frozen_cost_rays")) { if (value < 0 || value > 1000000) return fail("nsk_set_tuning: frozen_cost_rays out of range"); c->tune.frozen_cost_rays = value; return 0; }
     if (!strcmp(key, "no_frozen_kernel")) { c->tune_no_frozen_kernel = value; return 0; }
     if (!strcmp(key, "no_piggyback")) { c->tune_no_piggyback = value; return 0; }
     if (!strcmp(key, "frozen_mid_pct")) { if (value < 10 || value > 1000) return fail("nsk_set_tuning: frozen_mid_pct out of range"); c->tune.frozen_mid_pct = value; return 0; }
     if (!strcmp(key, "no_fused_median")) { c->tune_no_fused_median = value; return 0; }
     if (!strcmp(key, "no_deferred_median")) { c->tune_no_deferred_median = value; return 0; }
-    if (!strcmp(key, "fwd_fine_cost")) { c->tune.fwd_fine_cost = value; return 0; }
-    if (!strcmp(key, "fwd_occ_cost")) { c->tune.fwd_occ_cost = value; return 0; }
+    if (!strcmp(key, "fwd_fine_cost")) { if (value < 0 || value > 1000000) return fail("nsk_set_tuning: fwd_fine_cost out of range"); c->tune.fwd_fine_cost = value; return 0; }
+    if (!strcmp(key, "fwd_occ_cost")) { if (value < 0 || value > 1000000) return fail("nsk_set_tuning: fwd_occ_cost out of range"); c->tune.fwd_occ_cost = value; return 0; }
     if (!strcmp(key, "no_occ_role")) { c->tune_no_occ_role = value; return 0; }
-    if (!strcmp(key, "fwd_color_cost")) { c->tune.fwd_color_cost = value; return 0; }
+    if (!strcmp(key, "fwd_color_cost")) { if (value < 0 || value > 1000000) return fail("nsk_set_tuning: fwd_color_cost out of range"); c->tune.fwd_color_cost = value; return 0; }
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
     if (!strcmp(key, "no_dead_skip")) { c->tune_no_dead_skip = value; return 0; }
     if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune.dead_tile_pct = value; return 0; }
@@ -1578,6 +1579,17 @@ static int fill_fwd_role(nsk_ctx* c, DecArgs& A, int w, int M, int S, const floa
     return 0;
 }
 
+// nsk_debug_last_split: what the launch that is about to go out looks like (dir 0 forward, 1 backward; layout: include/nsk.h)
+static void record_split(nsk_ctx* c, int dir, int form, int n, const int* which, const int* train, const int* wg_end, int scan_wgs, int loss_wg,
+                         int ntasks, int grid)
+{
+    int* d = c->dbg_split[dir];
+    memset(d, 0, sizeof(c->dbg_split[dir]));
+    d[0] = form; d[1] = n;
+    for (int r = 0; r < n && r < 3; ++r) { d[2 + r] = which[r]; d[5 + r] = train ? train[r] : 0; d[8 + r] = wg_end ? role_wgs(wg_end, r) : grid; }
+    d[11] = scan_wgs; d[12] = loss_wg; d[13] = ntasks; d[14] = grid;
+}
+
 static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, const float* rd, const float* pts, bool save_masks)
 {
     DecArgs A;
@@ -1587,6 +1599,7 @@ static int launch_decode_fwd(nsk_ctx* c, int w, int M, int S, const float* ro, c
     int maxwg = c->num_cu;        // persistent: one workgroup per CU balances the 16-sample tasks over SIMDs
     int grid = std::max(1, std::min((ntasks + 7) / 8, maxwg));
     static const char* names[4] = {"decode_fwd_coarse", "decode_fwd_middle", "decode_fwd_fine", "decode_fwd_color"};
+    record_split(c, 0, NSK_SPLIT_FWD_SINGLE, 1, &w, nullptr, nullptr, 0, 0, ntasks, grid);
     ProfScope ps(c, names[w]);
     switch (w) {
     case 0: k_decode_fwd<0><<<grid, 512, lds, c->stream>>>(A); break;
@@ -1672,6 +1685,11 @@ static int launch_decode_fwd_stage(nsk_ctx* c, int stage, int M, int S, const fl
     const FwdPlan P = plan_fwd(c->num_cu, ntasks, STAGE_DEC[stage][2] == 3, c->tune, can_merge ? c->tune_no_occ_role : 1);
     MA.n = P.n;
     memcpy(MA.wg_end, P.wg_end, sizeof(P.wg_end));
+    {
+        const int merged_which[2] = {1, 3};      // the merged role reports as the middle decoder's
+        record_split(c, 0, P.merged ? NSK_SPLIT_FWD_MERGED : (c->matmul_mode != 0 ? NSK_SPLIT_FWD_MULTI_SPLIT : NSK_SPLIT_FWD_MULTI), P.n,
+                     P.merged ? merged_which : MA.which, nullptr, MA.wg_end, 0, 0, ntasks, MA.wg_end[P.n - 1]);
+    }
     ProfScope ps(c, "decode_fwd_multi");
     if (P.merged) {
         size_t lds_occ = ((size_t)c->dec[1].fimg16_f + (size_t)c->dec[2].fimg16_f) * 4;
@@ -2403,9 +2421,11 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
         return fail("backward_core: the deferred median mask needs the Tracker's launch (frozen decoders, ray gradients)");      // the caller checked the same
     const int separate = c->deterministic ? 1 : 0;      // debug mode: one launch per decoder, in a fixed order
     if ((n == 0 || train_role == -2 || separate) && d_loss) { ProfScope ps(c, "loss_sum"); k_sum<<<1, 1024, 0, c->stream>>>(N, c->ws.ray_loss, d_loss); }
+    memset(c->dbg_split[1], 0, sizeof(c->dbg_split[1]));
     if (n == 0) return 0;
     for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = ntasks;      // until a role counts fewer
     if (train_role == -2 || separate) {      // rare configuration (several trainable decoders share one slab buffer): one launch each
+        record_split(c, 1, NSK_SPLIT_BWD_SEPARATE, n, MA.which, MA.train, nullptr, 0, 0, ntasks, c->deterministic ? 1 : std::max(1, std::min((ntasks + 7) / 8, c->num_cu)));
         for (int r = 0; r < n; ++r)
             CHK(launch_decode_bwd(c, MA.which[r], M, S, ro, rd, MA.train[r] != 0, rays, flags, g_ro, g_rd));
         return 0;
@@ -2426,6 +2446,13 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     const int extra = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
     if (d_loss) { MA.sum_src = c->ws.ray_loss; MA.sum_dst = d_loss; MA.sum_n = N; }
     const int scan_wgs = attach_prep_scan(c, MA, !rays && !full, frozen_only ? NSK_FROZEN_NW / 4 : 2);
+    {
+        const bool track = dyn_resid != nullptr;
+        const int form = track ? NSK_SPLIT_BWD_TRACK : (full ? NSK_SPLIT_BWD_MULTI_FULL : (frozen_only ? NSK_SPLIT_BWD_FROZEN : NSK_SPLIT_BWD_MULTI));
+        const int riders = track ? 1 : scan_wgs + extra;      // (the Tracker's one rider finds the median and sums the loss; launch_bwd_roles adds the same)
+        record_split(c, 1, form, n, MA.which, MA.train, MA.wg_end, track ? 0 : scan_wgs, track ? (d_loss ? 1 : 0) : extra, ntasks, MA.wg_end[n - 1] + riders);
+        c->dbg_split[1][15] = track ? 1 : 0;
+    }
     launch_bwd_roles(c, MA, R, rays, full, frozen_only, dyn_resid != nullptr, scan_wgs, extra);
     HIPCHK(hipGetLastError());
     if (train_role >= 0) { c->pend_w = MA.which[train_role]; c->pend_nb = role_wgs(MA.wg_end, train_role); }      // summed by k_adam_multi, or by flush_pending when someone reads the slab first
@@ -2669,10 +2696,11 @@ extern "C" int nsk_debug_fetch(nsk_ctx* c, int what, int M, float* h_out)
 {
     if (!c || !h_out) return fail("nsk_debug_fetch: null argument");
     if (M < 1 || M != c->dbg_M || M > c->ws.capM) return fail("nsk_debug_fetch: M = %d is not the last step's sample count (%d)", M, c->dbg_M);
-    const float* src = what >= 0 && what <= 2 ? c->ws.occ[what] : (what == 3 ? c->ws.rgb4 : (what == 4 ? c->ws.g_raw : (what == 5 ? c->ws.z : nullptr)));
-    if (!src) return fail("nsk_debug_fetch: what = 0..5");
+    const float* src = what >= 0 && what <= 2 ? c->ws.occ[what] : (what == 3 ? c->ws.rgb4 : (what == 4 ? c->ws.g_raw : (what == 5 ? c->ws.z : (what == 6 ? c->scal + 1 : nullptr))));
+    if (!src) return fail("nsk_debug_fetch: what = 0..6");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (what == 6) { HIPCHK(hipMemcpy(h_out, src, 4, hipMemcpyDeviceToHost)); return 0; }      // the Tracker's threshold: one float
     HIPCHK(hipMemcpy(h_out, src, (size_t)M * ((what == 3 || what == 4) ? 16 : 4), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2697,6 +2725,16 @@ extern "C" int nsk_debug_live_tiles(nsk_ctx* c, int M, int* h_counts, int32_t* h
         if (c->live_ok) HIPCHK(hipMemcpy(h_bytes, c->sorted ? c->ws.lslot : c->ws.lsamp, (size_t)M, hipMemcpyDeviceToHost));
         else memset(h_bytes, 7, (size_t)M);
     }
+    return 0;
+}
+// the workgroup split of the last forward decoder launch (dir 0) or the last backward (dir 1), as the host recorded it; launches nothing
+extern "C" int nsk_debug_last_split(nsk_ctx* c, int dir, int* h_out)
+{
+    if (!c || !h_out) return fail("nsk_debug_last_split: null argument");
+    if (dir != 0 && dir != 1) return fail("nsk_debug_last_split: dir = 0 (forward) or 1 (backward)");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(h_out, c->dbg_split[dir], sizeof(c->dbg_split[dir]));
     return 0;
 }
 // the ReLU inputs of decoder `which` over the samples of the last step (same rays), by the forward body of the current matmul mode

@@ -1,5 +1,6 @@
 // The workgroup-split planner of the decoder launches (csrc/nsk_split.h) on the CPU: no torch, no HIP.  tests/test_split_cpu.py runs it.
-//   split_test <table>   the literal cases below, then every row of the recorded table (tests/golden/wg_splits.txt) recomputed and compared
+//   split_test <table>   the literal cases below, then every row of the recorded table (tests/golden/wg_splits.txt) recomputed and compared,
+//                        then the planner swept at the extremes of its tuning keys (knob_sweep: properties, nothing recorded)
 //   split_test --dump    prints the sweep in the table's format (how the table was recorded: see the table's header)
 // Row: <fn> <num_cu> <ntasks> <n> <waves> <train_role>  c0 c1 c2  t0 t1 t2 | w0 w1 w2 <makespan>      fn: S split_wgs, B split_wgs_balanced,
 // T split_wgs_train; t0 = -1: no tasks; unused columns 0; w: workgroups per role; makespan: split_makespan of that split (same waves and tasks)
@@ -148,6 +149,68 @@ static void literal_cases()
     if (!ok) { ++failures; fprintf(stderr, "FAIL plan_bwd\n"); }
 }
 
+// The planner at the extremes of its nsk_set_tuning keys, through the entry points the launches use (plan_fwd, plan_bwd with bwd_role_cost and
+// dead_skip_tasks): properties only, nothing recorded.  Every role in [1, cap], wg_end strictly increasing, and the trainable role within the
+// num_cu - (n - 1) rows its per-workgroup gradient slabs have.
+static long knob_sweep()
+{
+    long plans = 0;
+    auto bad = [&](const char* what, int num_cu, int ntasks, int n, const int* wg_end) {
+        if (++failures < 20) fprintf(stderr, "FAIL knob sweep %s: num_cu %d tiles %d n %d -> ends %d %d %d\n", what, num_cu, ntasks, n, wg_end[0], n > 1 ? wg_end[1] : 0, n > 2 ? wg_end[2] : 0);
+    };
+    auto check = [&](const char* what, int num_cu, int ntasks, int n, int waves, int train_role, const int* wg_end) {
+        ++plans;
+        const int cap = std::max(1, (ntasks + waves - 1) / waves);
+        for (int r = 0; r < n; ++r) {
+            const int w = role_wgs(wg_end, r);
+            if (w < 1 || w > cap || (r == train_role && w > num_cu - (n - 1))) { bad(what, num_cu, ntasks, n, wg_end); return; }      // (w >= 1 for every r: strictly increasing)
+        }
+    };
+    std::vector<int> tiles;
+    for (int t = 1; t <= 200; ++t) tiles.push_back(t);
+    for (int t = 203; t <= 3000; t += 7) tiles.push_back(t);
+    tiles.push_back(999); tiles.push_back(3000);
+    static const int costs[3] = {0, 1, 100000}, pcts[3] = {10, 100, 1000}, dead[3] = {-1, 0, 100};      // dead -1: no live counts (tasks = nullptr)
+    static const int cus[2] = {256, 104};
+    for (int num_cu : cus)
+        for (int ntasks : tiles) {
+            // backward: roles in launch order (colour, fine, middle), or (fine, middle)
+            for (int n = 2; n <= 3; ++n)
+                for (int form = 0; form < 5; ++form) {        // 0 frozen kernel (16 waves), 1 frozen roles in the multi kernel, 2 frozen with ray gradients, 3 trainable, 4 trainable with ray gradients
+                    const bool rays = form == 2 || form == 4;
+                    const int train_role = form >= 3 ? 0 : -1, waves = form == 0 ? 16 : 8;
+                    for (int fc : costs) for (int pct : pcts) for (int dp : dead) {
+                        SplitTune T;
+                        T.frozen_cost = fc; T.frozen_cost_rays = fc; T.frozen_mid_pct = pct; if (dp >= 0) T.dead_tile_pct = dp;
+                        int cost[3], tasks[3], wg_end[3] = {0, 0, 0};
+                        for (int r = 0; r < n; ++r) {
+                            const int w = n == 3 ? 3 - r : 2 - r;
+                            cost[r] = bwd_role_cost(r == train_role, w, rays, T);
+                            tasks[r] = r == train_role ? ntasks : dead_skip_tasks(ntasks, r == n - 1 ? ntasks / 8 : ntasks * 3 / 10, T);
+                        }
+                        plan_bwd(num_cu, ntasks, n, cost, train_role, waves, dp >= 0 && !rays ? tasks : nullptr, wg_end);
+                        check("plan_bwd", num_cu, ntasks, n, waves, train_role, wg_end);
+                    }
+                }
+            // forward: the three keys at default / 1 / 100000, with and without the colour role, every no_occ_role
+            for (int fo : costs) for (int ff : costs) for (int fcl : costs)
+                for (int colour = 0; colour < 2; ++colour)
+                    for (int nor = 0; nor <= 2; ++nor) {
+                        SplitTune T;
+                        T.fwd_occ_cost = fo; T.fwd_fine_cost = ff; T.fwd_color_cost = fcl;
+                        const FwdPlan P = plan_fwd(num_cu, ntasks, colour != 0, T, nor);
+                        const int want_n = P.merged ? (colour ? 2 : 1) : (colour ? 3 : 2);
+                        if (P.n != want_n || (nor == 1 && P.merged) || (nor == 2 && !P.merged)) bad("plan_fwd form", num_cu, ntasks, P.n, P.wg_end);
+                        check("plan_fwd", num_cu, ntasks, P.n, 8, -1, P.wg_end);
+                    }
+        }
+    // the costs at the top of the range nsk_set_tuning accepts: the middle role's cost stays an int (1 000 000 x 1000 / 100 < 2^31)
+    SplitTune T;
+    T.frozen_cost = T.frozen_cost_rays = 1000000; T.frozen_mid_pct = 1000;
+    if (bwd_role_cost(false, 1, false, T) != 10000000 || bwd_role_cost(false, 1, true, T) != 10000000) { ++failures; fprintf(stderr, "FAIL knob sweep: cost at the top of the range\n"); }
+    return plans;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 2 && !strcmp(argv[1], "--dump")) return dump();
@@ -173,6 +236,9 @@ int main(int argc, char** argv)
         else if (!within_caps(R)) { if (++failures < 20) { fprintf(stderr, "FAIL caps: "); print_row(stderr, R); } }
     }
     fclose(f);
+    const int table_failures = failures;
+    const long plans = knob_sweep();
+    printf("split_test: knob sweep %ld plans, %d failures\n", plans, failures - table_failures);
     printf("split_test: %ld rows, %d failures\n", rows, failures);
     return failures ? 1 : 0;
 }

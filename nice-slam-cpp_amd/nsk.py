@@ -23,7 +23,7 @@ SYMBOLS = (
     "nsk_track_step", "nsk_loss_map", "nsk_loss_track", "nsk_rays_from_pixels", "nsk_rays_backward",
     "nsk_camera_from_tensor", "nsk_camera_backward", "nsk_inside_filter", "nsk_adam_vector", "nsk_adam_step",
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
-    "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch", "nsk_debug_live_tiles",
+    "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch", "nsk_debug_live_tiles", "nsk_debug_last_split",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
@@ -822,10 +822,11 @@ class Context:
         return out.astype(bool)
 
     def debug_fetch(self, what, M):
-        """per-sample array of the last step's workspace: "occ0".."occ2" [M], "rgb4" [M, 4], "g_raw" [M, 4], "z" [M]"""
+        """per-sample array of the last step's workspace: "occ0".."occ2" [M], "rgb4" [M, 4], "g_raw" [M, 4], "z" [M],
+        "median_thr" [1] (the Tracker's 10 x median threshold)"""
         import numpy as np
-        code = {"occ0": 0, "occ1": 1, "occ2": 2, "rgb4": 3, "g_raw": 4, "z": 5}[what]
-        out = np.zeros((M, 4) if code in (3, 4) else (M,), np.float32)
+        code = {"occ0": 0, "occ1": 1, "occ2": 2, "rgb4": 3, "g_raw": 4, "z": 5, "median_thr": 6}[what]
+        out = np.zeros((M, 4) if code in (3, 4) else ((1,) if code == 6 else (M,)), np.float32)
         _chk(lib().nsk_debug_fetch(self.h, code, int(M), out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -835,6 +836,18 @@ class Context:
         counts, perm, lb = np.zeros(8, np.int32), np.zeros(M, np.int32), np.zeros(M, np.uint8)
         _chk(lib().nsk_debug_live_tiles(self.h, int(M), counts.ctypes.data_as(C.c_void_p), perm.ctypes.data_as(C.c_void_p), lb.ctypes.data_as(C.c_void_p)))
         return counts, perm, lb
+
+    FWD_FORMS = (None, "single", "multi", "multi_split", "merged")
+    BWD_FORMS = (None, "separate", "multi", "multi_full", "frozen", "track")
+
+    def debug_last_split(self, backward=False):
+        """the workgroup split of the last forward decoder launch (or the last backward), as recorded on the host (include/nsk.h): dict with
+        form (a name of FWD_FORMS / BWD_FORMS; None: no launch), n, which, train, wgs (tuples of n), scan_wgs, loss_wg, tiles, grid, median_wg"""
+        h = (C.c_int * 16)()
+        _chk(lib().nsk_debug_last_split(self.h, 1 if backward else 0, h))
+        n = int(h[1])
+        return dict(form=(self.BWD_FORMS if backward else self.FWD_FORMS)[h[0]], n=n, which=tuple(h[2:2 + n]), train=tuple(h[5:5 + n]),
+                    wgs=tuple(h[8:8 + n]), scan_wgs=int(h[11]), loss_wg=int(h[12]), tiles=int(h[13]), grid=int(h[14]), median_wg=int(h[15]))
 
     @_ordered
     def debug_preact(self, which, rays_o, rays_d, M):

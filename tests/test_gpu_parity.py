@@ -13,6 +13,7 @@ import local_parity as LP
 import scenes
 from gpu_util import cu, make_ctx, stage_levels
 from scenes import rel_l2
+from split_checks import assert_gradients as _assert_gradients      # (shared with tests/test_gpu_split.py)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -180,22 +181,6 @@ def _backward_case(stage, with_gt, occupancy, oracle32, oracle64, trainable, n_r
     out["rays_d"] = (g_rd.cpu().numpy(), ref["g_rays_d"], ref64["g_rays_d"])
     out["_kept"] = float(keep.mean())
     return out, ctx, sc
-
-
-def _assert_gradients(out, what):
-    """filtered rays (no ReLU input within 2e-5 of zero): strictly within 1e-4 of the fp32 oracle, no escape.  All rays: within 1e-2,
-    and within 1e-4 or within 2x of the fp32 oracle's own distance to the fp64 oracle.  A ReLU input within rounding of zero falls
-    on either side of the kink and switches one unit of one sample; the fp32 oracle differs from the fp64 one by such flips
-    (2e-4 .. 1e-3 of a gradient in these scenes), and the HIP path has proportionally more of them: its sin/cos is accurate to
-    1.4e-7 absolute (library sinf: 0.5 ulp), which puts its pre-activations ~1e-6 from the fp64 ones instead of ~3e-7."""
-    kept = out.pop("_kept")
-    for k, (got, ref, ref64) in out.items():
-        e, e64, eo = rel_l2(got, ref), rel_l2(got, ref64), rel_l2(ref, ref64)
-        msg = "%s %s (%.0f %% of the rays): hip-vs-f32 %.2e hip-vs-f64 %.2e f32-vs-f64 %.2e" % (what, k, 100 * kept, e, e64, eo)
-        if what == "filtered":
-            assert e < TOL, msg
-        else:
-            assert e < 100 * TOL and (e < TOL or e64 < 2 * eo + TOL), msg
 
 
 @pytest.mark.parametrize("stage", ["coarse", "middle", "fine", "color"])

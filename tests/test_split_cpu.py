@@ -1,6 +1,9 @@
 """The workgroup-split planner of the decoder launches (csrc/nsk_split.h) without a GPU: host/test/split_test.cpp, built by a plain host compiler
 under AddressSanitizer + UBSan, checks the worked examples of the planner's comments and recomputes every row of tests/golden/wg_splits.txt,
-the splits recorded from the functions as they stood inside nsk.hip."""
+the splits recorded from the functions as they stood inside nsk.hip; then it sweeps plan_fwd / plan_bwd at the extremes of the tuning keys (costs 1 and
+100 000, frozen_mid_pct 10 and 1000, dead_tile_pct 0 and 100; 1 .. 3000 tiles, both wave counts) and asserts properties: every role in [1, cap],
+the role ranges strictly increasing, the trainable role within its num_cu - (n - 1) gradient slabs."""
+import re
 import os
 import subprocess
 
@@ -17,3 +20,5 @@ def test_the_split_planner_reproduces_its_recorded_table():
         rows = sum(1 for line in f if line.strip() and not line.startswith("#"))
     assert rows > 5000                # (the sweep in the table's header)
     assert r.returncode == 0 and "split_test: %d rows, 0 failures" % rows in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+    m = re.search(r"split_test: knob sweep (\d+) plans, 0 failures", r.stdout)
+    assert m and int(m.group(1)) > 100000, r.stdout[-1500:] + r.stderr[-3000:]
