@@ -556,6 +556,66 @@ int nsk_cloud_nearest(nsk_ctx* ctx, const float* d_query, int n_query, const flo
  * bytes.  Reading h_out is the call's one synchronisation.  n = 0 gives zeros. */
 int nsk_cloud_stats(nsk_ctx* ctx, const float* d_dist, int n, float threshold, double h_out[4]);
 
+/* ---- reconstruction depth L1: depth views of a mesh (upstream src/tools/eval_recon.py calc_2d_metric) -------------------------- */
+/* nsk_mesh_depth: depth images of a triangle mesh (d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3] int32, device) from
+ * V views: h_w2c [V][16] row-major world-to-camera on the host, the camera looking along -z, as in nsk_lattice_seen.  d_depth [V][H][W]
+ * float32 on the device receives the depth along -z of the nearest surface, 0 where nothing is hit (the background value of upstream's
+ * renderer, and what nsk_image_metrics reads as "no measurement").  H W <= 2^24, so pixel indices are exact in fp32.  n_triangles = 0 is
+ * valid and gives zeros; V = 0 is valid.  Every operation below is an fp32 operation of its own (no FMA).
+ *   Camera space, vertex p, a = 0..2:  c_a = ((w[4a] p0 + w[4a+1] p1) + w[4a+2] p2) + w[4a+3];   d = -c_2.
+ *   Left out: a triangle with an index outside [0, n_vertices) is left out of every view and counted once in *h_skipped (may be NULL);
+ *     a triangle with a camera-space component that is not finite in a view is left out of that view.
+ *   Pixel (column i, row j): the ray through the camera centre is (x, y, -1), x = (i - cx) / fx, y = -((j - cy) / fy).
+ *   Edge values, with n(p, q) = p x q, n_x = (p_y q_z) - (p_z q_y), n_y = (p_z q_x) - (p_x q_z), n_z = (p_x q_y) - (p_y q_x):
+ *     E(p, q) = (x n_x + y n_y) - n_z;   U = E(b, c), V = E(c, a), W = E(a, b) for the camera-space vertices a, b, c.
+ *     The pixel is inside when U >= 0, V >= 0 and W >= 0, or U <= 0, V <= 0 and W <= 0: both faces are drawn.  Two triangles that share
+ *     an edge evaluate its value as exact negatives of each other, so a welded surface has no cracks and needs no fill convention: a
+ *     pixel on the edge is taken by both and the minimum decides.
+ *   Depth, from the plane through a (not from the edge values, which lose distance / size of their digits):
+ *     e1 = b - a, e2 = c - a, n = e1 x e2 (as above);   t = ((a_x n_x + a_y n_y) + a_z n_z) / ((x n_x + y n_y) - n_z).
+ *     The hit counts when t is finite and t > 0; t is the depth along -z.
+ *   The pixel box is part of the rule, not an acceleration: only its pixels are tested.
+ *     all three d <= 0: the triangle is behind the camera and has no pixel;
+ *     all three d > 0: u_k = cx + (fx c_0) / d, v_k = cy - (fy c_1) / d as in nsk_lattice_seen; if all six are finite and below 2^20 in
+ *       magnitude the box is the columns floor(min u) - 1 .. floor(max u) + 2 and the rows floor(min v) - 1 .. floor(max v) + 2, clamped
+ *       to the image (an empty box has no pixel);
+ *     every other case (a triangle across the camera plane, a projection out of range): the whole image.  Such a triangle is drawn
+ *       correctly by the rule as it stands; there is no clipping step.
+ *   Result per pixel and view: the minimum t over the triangles that hit it; its bits do not depend on the order of execution.
+ * One thread per triangle loads its vertices once and loops over the views of a launch (32 views' matrices ride in the kernel arguments;
+ * longer lists go in several launches).  The image itself is the depth buffer: the uint32 bits of t, +inf at first, lowered by an atomic
+ * minimum (behind a plain load that skips it when the stored value is already smaller); a finish pass turns +inf into 0.  A (view,
+ * triangle) pair whose box has more than raster_inline_max pixels goes to a context-owned queue (one atomic cursor, raster_queue_cap
+ * entries of 24 B) that a second kernel walks with a wave per entry, 64 pixels at a time; when the queue is full the thread walks the box
+ * itself.  nsk_set_tuning "raster_inline_max", "raster_queue_cap", "raster_load_first" (0: the bare atomic) are test and sweep aids: every
+ * setting gives the same bytes.  Asynchronous on the context's stream; asking for *h_skipped is the call's only synchronisation.  An
+ * allocation that fails names its byte count and leaves the context usable.  Not while a graph is being captured. */
+int nsk_mesh_depth(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles, int V,
+                   const float* h_w2c, int H, int W, float fx, float fy, float cx, float cy, float* d_depth, int* h_skipped);
+/* nsk_depth_pair_stats: per-view sums over two depth stacks d_a, d_b [V][n_pix] (device) -> h_out [V][4] doubles:
+ *   [0] the sum of |a - b| over all pixels, each difference one fp32 operation widened to double (upstream's np.abs(gt - ours).mean()
+ *       numerator: the background zeros are part of it);   [1] the number of pixels with a > 0 and b > 0;
+ *   [2] the sum of |a - b| over the pixels of [1];   [3] the number of pixels with a > 0.
+ * A term that is not finite is left out of its sums.  No floating-point atomics: lanes add in index order, waves meet by shuffles, one
+ * row per workgroup (at most 64 per view, a function of n_pix alone), a second launch adds each view's rows in index order -- two runs
+ * give the same bytes.  All views go in one call; reading h_out is its one synchronisation.  n_pix <= 2^24, V <= 2^20; V = 0 is valid. */
+int nsk_depth_pair_stats(nsk_ctx* ctx, const float* d_a, const float* d_b, int V, int n_pix, double* h_out);
+/* nsk_depth_views: the V random views inside a mesh's box that Depth L1 is taken over, as h_w2c [V][16] for nsk_mesh_depth.
+ *   The box: the minimum and maximum of the vertices with finite coordinates (the reduction of nsk_cloud_nearest), written to
+ *   h_box = {lo x y z, hi x y z}.  With d_vertices NULL the box is read from h_box instead, and the call needs neither context nor device.
+ *   View k, every operation a double operation of its own (no FMA), lo / hi widened from float32:
+ *     u_m = (hash_u32(seed, k, m) >> 8) 2^-24, m = 0..5 (the counter hash of nsk_sample_pixels);   ext = hi - lo, ctr = 0.5 (lo + hi);
+ *     origin_a = ctr_a + (u_a - 0.5) (shrink ext_a): uniform in the box scaled by shrink about its centre;
+ *     target_a = lo_a + u_{3+a} ext_a: uniform in the box;   f = target - origin, then f = f / sqrt((f_0 f_0 + f_1 f_1) + f_2 f_2);
+ *     upstream's viewmatrix with up = (0, 0, -1):  s = up x f = (f_1, -f_0, 0) / sqrt(f_1 f_1 + f_0 f_0);   v = f x s, each component
+ *     (f_y s_z) - (f_z s_y) and so on, then v = v / sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2);
+ *     upstream's camera looks along +z with y down, this project's along -z with y up: camera-to-world has the columns s, -v, -f, origin;
+ *     inverted as a rigid motion: row a of world-to-camera is r_a = s, -v, -f and its fourth entry -((r_a0 o_0 + r_a1 o_1) + r_a2 o_2);
+ *     each of the twelve rounded once to float32; the last row is 0 0 0 1.
+ *   A view whose direction is parallel to up, or whose target is its origin, has NaN entries: nsk_mesh_depth then draws nothing for it. */
+int nsk_depth_views(nsk_ctx* ctx, const float* d_vertices, int n_vertices, float h_box[6], unsigned long long seed, double shrink, int V,
+                    float* h_w2c);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

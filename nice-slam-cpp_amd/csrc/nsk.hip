@@ -7,6 +7,7 @@
 #include "nsk_mesh.h"
 #include "nsk_image.h"
 #include "nsk_cloud.h"
+#include "nsk_raster.h"
 #include "nsk_buf.h"
 #include "nsk_split.h"
 
@@ -862,6 +863,15 @@ struct nsk_ctx {
         int cells_x4 = 4;                                    // nsk_set_tuning "cloud_cells_x4": grid cells aimed at per finite target, in quarters
         int query_mode = 0;                                  // nsk_set_tuning "cloud_query_mode": bit 0 a wave per query; + 2 queries always in input order, + 4 always in cell order (neither: by size)
     } cloud;
+    // mesh depth views (nsk_mesh_depth / nsk_depth_pair_stats): the queue of large pixel boxes, its cursor and the skipped count, the sums
+    struct Raster {
+        Buf<RasterJob> queue;                                // [queue_cap] (view, triangle, box) entries of the launch in flight
+        Buf<unsigned> counters;                              // [0] the queue's cursor, [1] triangles with an index out of range
+        Buf<double> rows;                                    // [V][RASTER_STAT_ROWS][4] partial sums, then the [V][4] results
+        int inline_max = 64;                                 // nsk_set_tuning "raster_inline_max": a box of more pixels is queued
+        int queue_cap = 1 << 18;                             // nsk_set_tuning "raster_queue_cap": entries (24 B each)
+        int load_first = 1;                                  // nsk_set_tuning "raster_load_first": a plain load in front of the atomic minimum
+    } raster;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -1093,6 +1103,9 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     if (!strcmp(key, "cloud_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: cloud_cells_x4 must be 1 .. 256"); c->cloud.cells_x4 = value; return 0; }
     if (!strcmp(key, "cloud_query_mode")) { if (value < 0 || value > 5) return fail("nsk_set_tuning: cloud_query_mode must be 0 .. 5"); c->cloud.query_mode = value; return 0; }
+    if (!strcmp(key, "raster_inline_max")) { if (value < 0) return fail("nsk_set_tuning: raster_inline_max must be >= 0"); c->raster.inline_max = value; return 0; }
+    if (!strcmp(key, "raster_queue_cap")) { if (value < 1 || value > (1 << 24)) return fail("nsk_set_tuning: raster_queue_cap must be 1 .. 2^24"); c->raster.queue_cap = value; return 0; }
+    if (!strcmp(key, "raster_load_first")) { if (value < 0 || value > 1) return fail("nsk_set_tuning: raster_load_first must be 0 or 1"); c->raster.load_first = value; return 0; }
     return fail("nsk_set_tuning: unknown key '%s'", key);
 }
 
@@ -3234,6 +3247,155 @@ extern "C" int nsk_cloud_stats(nsk_ctx* c, const float* d_dist, int n, float thr
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_out, out, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- depth views of a mesh (nsk_raster.h) -----------------------------------------------------------------------------------------
+extern "C" int nsk_mesh_depth(nsk_ctx* c, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles, int V,
+                              const float* h_w2c, int H, int W, float fx, float fy, float cx, float cy, float* d_depth, int* h_skipped)
+{
+    if (!c) return fail("nsk_mesh_depth: null ctx");
+    if (n_vertices < 0 || n_triangles < 0 || V < 0) return fail("nsk_mesh_depth: negative count");
+    if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) return fail("nsk_mesh_depth: image %d x %d, need 1 .. 2^24 pixels", H, W);
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy)) return fail("nsk_mesh_depth: intrinsics are not finite");
+    if (n_triangles > 0 && (!d_triangles || (n_vertices > 0 && !d_vertices))) return fail("nsk_mesh_depth: d_vertices / d_triangles is NULL");
+    if (V > 0 && (!d_depth || !h_w2c)) return fail("nsk_mesh_depth: d_depth / h_w2c is NULL with V = %d", V);
+    if (c->capturing) return fail("nsk_mesh_depth: not while a graph is being captured");
+    if (h_skipped) *h_skipped = 0;
+    if (V == 0 && !(h_skipped && n_triangles > 0)) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Raster& R = c->raster;
+    const size_t img = (size_t)H * W, total = img * (size_t)V;
+    unsigned* bits = reinterpret_cast<unsigned*>(d_depth);
+    if (total) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)bits, (int)RASTER_INF_BITS, total, c->stream));
+    if (n_triangles > 0) {
+        CHK(grow(c, R.queue, (size_t)R.queue_cap, "the rasteriser's queue", GROW_NO_CAPTURE));
+        CHK(grow(c, R.counters, 16, "the rasteriser's counters", GROW_NO_CAPTURE));
+        if (h_skipped) HIPCHK(hipMemsetAsync(R.counters.get() + 1, 0, 4, c->stream));
+        RasterArgs A;
+        memset(&A, 0, sizeof(A));
+        A.H = H; A.W = W; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.nv = n_vertices; A.nt = n_triangles;
+        A.inline_max = R.inline_max; A.queue_cap = (unsigned)R.queue_cap; A.load_first = R.load_first;
+        const int nb = (int)(((long long)n_triangles + RASTER_BLOCK - 1) / RASTER_BLOCK);
+        int k0 = 0;
+        do {                                                // (V = 0 still launches once: it counts the skipped triangles)
+            A.K = std::min(V - k0, RASTER_MAX_V);
+            for (int k = 0; k < A.K; ++k) memcpy(A.w[k], h_w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
+            HIPCHK(hipMemsetAsync(R.counters, 0, 4, c->stream));
+            { ProfScope ps(c, "raster_tris");
+              k_raster_tris<<<nb, RASTER_BLOCK, 0, c->stream>>>(A, d_vertices, d_triangles, bits + (size_t)k0 * img, R.queue, R.counters,
+                                                               k0 == 0 && h_skipped ? R.counters.get() + 1 : nullptr); }
+            HIPCHK(hipGetLastError());
+            if (A.K > 0) {
+                ProfScope ps(c, "raster_queue");
+                k_raster_queue<<<RASTER_QUEUE_WG, RASTER_BLOCK, 0, c->stream>>>(A, d_vertices, d_triangles, bits + (size_t)k0 * img, R.queue, R.counters);
+            }
+            HIPCHK(hipGetLastError());
+            k0 += A.K;
+        } while (k0 < V);
+    }
+    if (total) {
+        ProfScope ps(c, "raster_finish");
+        k_raster_finish<<<(unsigned)std::min<size_t>((total + RASTER_BLOCK - 1) / RASTER_BLOCK, 65536), RASTER_BLOCK, 0, c->stream>>>(total, bits);
+        HIPCHK(hipGetLastError());
+    }
+    if (h_skipped && n_triangles > 0) {
+        unsigned cnt = 0;
+        HIPCHK(hipMemcpyAsync(&cnt, R.counters.get() + 1, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *h_skipped = (int)cnt;
+    }
+    return 0;
+}
+
+extern "C" int nsk_depth_pair_stats(nsk_ctx* c, const float* d_a, const float* d_b, int V, int n_pix, double* h_out)
+{
+    if (!c) return fail("nsk_depth_pair_stats: null ctx");
+    if (V < 0 || n_pix < 1 || n_pix > (1 << 24)) return fail("nsk_depth_pair_stats: V = %d, n_pix = %d, need V >= 0 and 1 .. 2^24 pixels", V, n_pix);
+    if (V == 0) return 0;
+    if (V > (1 << 20)) return fail("nsk_depth_pair_stats: V = %d, at most 2^20 views per call", V);
+    if (!d_a || !d_b || !h_out) return fail("nsk_depth_pair_stats: d_a / d_b / h_out is NULL");
+    if (c->capturing) return fail("nsk_depth_pair_stats: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    const int R = std::min((n_pix + RASTER_BLOCK - 1) / RASTER_BLOCK, RASTER_STAT_ROWS);
+    CHK(grow(c, c->raster.rows, (size_t)V * (RASTER_STAT_ROWS + 1) * 4, "the depth sums of the workgroups", GROW_NO_CAPTURE));
+    double* rows = c->raster.rows;
+    double* out = rows + (size_t)V * RASTER_STAT_ROWS * 4;
+    { ProfScope ps(c, "depth_stats");
+      k_depth_pair_stats<<<(unsigned)((size_t)V * R), RASTER_BLOCK, 0, c->stream>>>(n_pix, R, d_a, d_b, rows);
+      k_depth_pair_stats_sum<<<(4 * V + RASTER_BLOCK - 1) / RASTER_BLOCK, RASTER_BLOCK, 0, c->stream>>>(V, R, rows, out); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, out, (size_t)V * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the counter hash of nsk_sample_pixels on the host (hash_u32 of nsk_device.h, which is device code)
+static uint32_t host_hash_u32(unsigned long long seed, uint32_t a, uint32_t b)
+{
+    unsigned long long x = seed ^ (0x9E3779B97F4A7C15ull * ((unsigned long long)a + 1)) ^ (0xC2B2AE3D27D4EB4Full * ((unsigned long long)b + 1));
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
+    return (uint32_t)(x >> 32);
+}
+// one view of the draw stated in include/nsk.h: every operation a double operation of its own, in the order written there
+static void depth_view(const double lo[3], const double ext[3], const double ctr[3], double shrink, unsigned long long seed, uint32_t view,
+                       float* w)
+{
+#pragma clang fp contract(off)
+    double u[6], o[3], f[3];
+    for (int k = 0; k < 6; ++k) u[k] = (double)(host_hash_u32(seed, view, (uint32_t)k) >> 8) * (1.0 / 16777216.0);
+    for (int a = 0; a < 3; ++a) {
+        o[a] = ctr[a] + (u[a] - 0.5) * (shrink * ext[a]);
+        const double target = lo[a] + u[3 + a] * ext[a];
+        f[a] = target - o[a];
+    }
+    const double fl = std::sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+    for (int a = 0; a < 3; ++a) f[a] = f[a] / fl;
+    const double sl = std::sqrt(f[1] * f[1] + f[0] * f[0]);
+    const double s[3] = {f[1] / sl, -f[0] / sl, 0.0};
+    double v[3] = {f[1] * s[2] - f[2] * s[1], f[2] * s[0] - f[0] * s[2], f[0] * s[1] - f[1] * s[0]};
+    const double vl = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    for (int a = 0; a < 3; ++a) v[a] = v[a] / vl;
+    const double rows[3][3] = {{s[0], s[1], s[2]}, {-v[0], -v[1], -v[2]}, {-f[0], -f[1], -f[2]}};
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) w[4 * a + b] = (float)rows[a][b];
+        w[4 * a + 3] = (float)-((rows[a][0] * o[0] + rows[a][1] * o[1]) + rows[a][2] * o[2]);
+    }
+    w[12] = w[13] = w[14] = 0.f; w[15] = 1.f;
+}
+
+extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertices, float h_box[6], unsigned long long seed, double shrink,
+                               int V, float* h_w2c)
+{
+    if (!h_box) return fail("nsk_depth_views: h_box is NULL");
+    if (V < 0 || (V > 0 && !h_w2c)) return fail("nsk_depth_views: V = %d, or h_w2c is NULL", V);
+    if (!std::isfinite(shrink)) return fail("nsk_depth_views: shrink is not finite");
+    if (d_vertices) {
+        if (!c) return fail("nsk_depth_views: null ctx");
+        if (n_vertices < 1) return fail("nsk_depth_views: no vertex");
+        if (c->capturing) return fail("nsk_depth_views: not while a graph is being captured");
+        HIPCHK(hipSetDevice(c->device));
+        nsk_ctx::Cloud& K = c->cloud;
+        const int nrows = (int)std::min<long long>(((long long)n_vertices + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
+        CHK(grow(c, K.box, (size_t)CLOUD_MAX_ROWS * 8 + 8, "the partial boxes", GROW_NO_CAPTURE));
+        float* box_out = K.box.get() + (size_t)CLOUD_MAX_ROWS * 8;
+        float box[8];
+        { ProfScope ps(c, "cloud_box");
+          k_cloud_box<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n_vertices, d_vertices, K.box);
+          k_cloud_box_sum<<<1, 64, 0, c->stream>>>(nrows, K.box, box_out);
+          HIPCHK(hipGetLastError()); }
+        HIPCHK(hipMemcpyAsync(box, box_out, sizeof(box), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        unsigned nfinite; memcpy(&nfinite, &box[6], 4);
+        if (!nfinite) return fail("nsk_depth_views: no vertex with finite coordinates");
+        memcpy(h_box, box, 6 * sizeof(float));
+    }
+    double lo[3], ext[3], ctr[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(h_box[a]) || !std::isfinite(h_box[3 + a])) return fail("nsk_depth_views: the box is not finite");
+        lo[a] = (double)h_box[a]; ext[a] = (double)h_box[3 + a] - lo[a]; ctr[a] = 0.5 * (lo[a] + (double)h_box[3 + a]);
+    }
+    for (int k = 0; k < V; ++k) depth_view(lo, ext, ctr, shrink, seed, (uint32_t)k, h_w2c + 16 * (size_t)k);
     return 0;
 }
 

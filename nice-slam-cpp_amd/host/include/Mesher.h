@@ -27,6 +27,17 @@ struct ReconMetrics {
     int rec_skipped = 0, gt_skipped = 0;                                      // samples with a non-finite coordinate left out of the targets
 };
 
+// upstream's 2D number of a reconstruction, Depth L1 (src/tools/eval_recon.py calc_2d_metric), and what went into it
+struct ReconDepth {
+    double depth_l1_cm = 0;                 // 100 x the mean over the used views of sum |gt - rec| / n_pix (background zeros included, as upstream)
+    double restricted_l1_cm = 0;            // 100 x sum |gt - rec| / count over the pixels of the used views where both meshes are hit
+    int n_views = 0, n_used = 0;            // views drawn; views whose ground-truth cover reaches min_cover
+    int rec_skipped = 0, gt_skipped = 0;    // triangles with an index out of range
+    std::vector<double> view_l1, view_cover;        // per view: sum |gt - rec| / n_pix (m), the share of pixels the ground truth covers
+    std::vector<double> stats;              // [n_views][4]: nsk_depth_pair_stats(gt, rec)
+    std::vector<float> w2c;                 // [n_views][16]: the views (nsk_depth_views)
+};
+
 class Mesher {
   public:
     Mesher(YAML::Node ns_config, torch::Tensor bound_3x2 = torch::Tensor(), float padding = 0.f);
@@ -59,6 +70,16 @@ class Mesher {
     static ReconMetrics eval_recon(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles, const float* gt_xyz,
                                    int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles, int n_points = 200000,
                                    float threshold = 0.05f, unsigned long long seed = 0);
+    // Depth L1 on the device: n_views random views inside the ground truth's box (nsk_depth_views: seed, shrink), both meshes rendered as
+    // H x W depth images with fx = fy = focal, cx = W / 2 - 0.5, cy = H / 2 - 0.5 (nsk_mesh_depth) in batches that keep both stacks below
+    // about 1 GB, the per-view sums (nsk_depth_pair_stats).  A view is used when the ground truth covers at least min_cover of its pixels
+    // (0: every view, upstream's plain mean).  Not done: upstream's rejection of views that see never-observed ground truth, alignment.
+    static ReconDepth eval_recon_depth(const std::string& rec_ply, const std::string& gt_ply, int n_views = 1000, int H = 500, int W = 500,
+                                       float focal = 300.f, unsigned long long seed = 0, double shrink = 0.7, double min_cover = 0.0);
+    static ReconDepth eval_recon_depth(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles,
+                                       const float* gt_xyz, int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles,
+                                       int n_views = 1000, int H = 500, int W = 500, float focal = 300.f, unsigned long long seed = 0,
+                                       double shrink = 0.7, double min_cover = 0.0);
 
     int resolution;
     float level_set, padding;

@@ -397,3 +397,64 @@ ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& g
     return eval_recon(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(), (int)(gt.size() / 3),
                       n, threshold, seed);
 }
+
+// ---- reconstruction depth L1 -----------------------------------------------------------------------------------------------------------
+ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
+                                    const int32_t* gt_tris, int gt_nt, int n_views, int H, int W, float focal, unsigned long long seed,
+                                    double shrink, double min_cover)
+{
+    if (n_views < 1) throw std::runtime_error("Mesher::eval_recon_depth: n_views must be at least 1");
+    if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::eval_recon_depth: the image must have 1 .. 2^24 pixels");
+    if (gt_nv < 1) throw std::runtime_error("Mesher::eval_recon_depth: the ground truth has no vertex");
+    auto up = [](DevMem& d, const void* h, size_t bytes) {
+        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+    };
+    const size_t n_pix = (size_t)H * W;
+    DevMem rv((size_t)rec_nv * 3 * sizeof(float)), rt((size_t)rec_nt * 3 * sizeof(int32_t));
+    DevMem gv((size_t)gt_nv * 3 * sizeof(float)), gtt((size_t)gt_nt * 3 * sizeof(int32_t));
+    up(rv, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(rt, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
+    up(gv, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(gtt, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
+    ReconDepth M;
+    M.n_views = n_views;
+    M.w2c.assign((size_t)n_views * 16, 0.f);
+    M.stats.assign((size_t)n_views * 4, 0.0);
+    float box[6];
+    check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, n_views, M.w2c.data()));
+    int batch = (int)std::max<size_t>(1, ((size_t)1 << 27) / n_pix);          // both stacks together stay below about 1 GB
+    if (batch > 32) batch -= batch % 32;
+    batch = std::min(batch, n_views);
+    DevMem dg((size_t)batch * n_pix * sizeof(float)), dr((size_t)batch * n_pix * sizeof(float));
+    const float cx = (float)(W / 2.0 - 0.5), cy = (float)(H / 2.0 - 0.5);
+    for (int k0 = 0; k0 < n_views; k0 += batch) {
+        const int V = std::min(batch, n_views - k0);
+        const float* w = M.w2c.data() + 16 * (size_t)k0;
+        check(nsk_mesh_depth(ctx(), (const float*)gv.p, gt_nv, (const int32_t*)gtt.p, gt_nt, V, w, H, W, focal, focal, cx, cy, (float*)dg.p,
+                             k0 == 0 ? &M.gt_skipped : nullptr));
+        check(nsk_mesh_depth(ctx(), (const float*)rv.p, rec_nv, (const int32_t*)rt.p, rec_nt, V, w, H, W, focal, focal, cx, cy, (float*)dr.p,
+                             k0 == 0 ? &M.rec_skipped : nullptr));
+        check(nsk_depth_pair_stats(ctx(), (const float*)dg.p, (const float*)dr.p, V, (int)n_pix, M.stats.data() + 4 * (size_t)k0));
+    }
+    M.view_l1.resize((size_t)n_views); M.view_cover.resize((size_t)n_views);
+    double l1 = 0.0, both = 0.0, both_sum = 0.0;
+    for (int k = 0; k < n_views; ++k) {
+        const double* s = &M.stats[4 * (size_t)k];
+        M.view_l1[k] = s[0] / (double)n_pix; M.view_cover[k] = s[3] / (double)n_pix;
+        if (!(M.view_cover[k] >= min_cover)) continue;
+        ++M.n_used; l1 += M.view_l1[k]; both += s[1]; both_sum += s[2];
+    }
+    const double nan = std::nan("");
+    M.depth_l1_cm = M.n_used ? 100.0 * l1 / M.n_used : nan;
+    M.restricted_l1_cm = both > 0 ? 100.0 * both_sum / both : nan;
+    return M;
+}
+
+ReconDepth Mesher::eval_recon_depth(const std::string& rec_ply, const std::string& gt_ply, int n_views, int H, int W, float focal,
+                                    unsigned long long seed, double shrink, double min_cover)
+{
+    std::vector<float> rv, gv;
+    std::vector<int32_t> rt, gt;
+    read_ply_mesh(rec_ply, rv, rt);
+    read_ply_mesh(gt_ply, gv, gt);
+    return eval_recon_depth(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(),
+                            (int)(gt.size() / 3), n_views, H, W, focal, seed, shrink, min_cover);
+}

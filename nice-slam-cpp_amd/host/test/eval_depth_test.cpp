@@ -1,0 +1,27 @@
+// eval_depth_test REC.ply GT.ply N_VIEWS H W FOCAL SEED -- Mesher::eval_recon_depth on two PLY files, one JSON line (tests/test_gpu_raster.py)
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+
+#include "Mesher.h"
+
+int main(int argc, char** argv)
+{
+    if (argc < 3) { std::fprintf(stderr, "usage: %s REC.ply GT.ply [N_VIEWS] [H] [W] [FOCAL] [SEED]\n", argv[0]); return 2; }
+    const int n_views = argc > 3 ? std::atoi(argv[3]) : 1000;
+    const int H = argc > 4 ? std::atoi(argv[4]) : 500, W = argc > 5 ? std::atoi(argv[5]) : 500;
+    const float focal = argc > 6 ? (float)std::atof(argv[6]) : 300.f;
+    const unsigned long long seed = argc > 7 ? std::strtoull(argv[7], nullptr, 10) : 0ull;
+    try {
+        const ReconDepth m = Mesher::eval_recon_depth(argv[1], argv[2], n_views, H, W, focal, seed);
+        std::printf("{\"depth_l1_cm\": %.17g, \"restricted_l1_cm\": %.17g, \"n_views\": %d, \"n_used\": %d, \"rec_skipped\": %d, "
+                    "\"gt_skipped\": %d, \"H\": %d, \"W\": %d, \"focal\": %.9g, \"view0_l1\": %.17g, \"w2c0\": [",
+                    m.depth_l1_cm, m.restricted_l1_cm, m.n_views, m.n_used, m.rec_skipped, m.gt_skipped, H, W, (double)focal, m.view_l1[0]);
+        for (int k = 0; k < 16; ++k) std::printf("%s%.9g", k ? ", " : "", (double)m.w2c[k]);
+        std::printf("]}\n");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "eval_depth_test: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

@@ -29,6 +29,7 @@ SYMBOLS = (
     "nsk_lattice_seen", "nsk_mesh_filter",
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
     "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
+    "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views",
 )
 
 
@@ -71,6 +72,13 @@ def lib():
         L.nsk_cloud_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_cloud_stats.restype = C.c_int
         L.nsk_cloud_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_double)]
+        L.nsk_mesh_depth.restype = C.c_int
+        L.nsk_mesh_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
+        L.nsk_depth_pair_stats.restype = C.c_int
+        L.nsk_depth_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.nsk_depth_views.restype = C.c_int
+        L.nsk_depth_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_ulonglong, C.c_double, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -95,6 +103,16 @@ def mesh_table(case):
     if n < 0:
         raise NskError(lib().nsk_last_error().decode())
     return [(int(buf[3 * t]), int(buf[3 * t + 1]), int(buf[3 * t + 2])) for t in range(n)]
+
+
+def depth_views_from_box(box, n_views, seed=0, shrink=0.7):
+    """nsk_depth_views on a given box (lo x y z, hi x y z): the world-to-camera matrices [n_views, 4, 4] float32; needs no GPU"""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(box, dtype=np.float32).reshape(6))
+    w = np.zeros((int(n_views), 4, 4), np.float32)
+    _chk(lib().nsk_depth_views(None, None, 0, b.ctypes.data_as(C.c_void_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(shrink), int(n_views),
+                               w.ctypes.data_as(C.c_void_p)))
+    return w
 
 
 def _stage(s):
@@ -461,6 +479,84 @@ class Context:
                     accuracy_max_cm=100.0 * acc["max"], completion_max_cm=100.0 * comp["max"],
                     rec_area=rec_area, gt_area=gt_area, rec_degenerate=rec_deg, gt_degenerate=gt_deg,
                     rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold))
+
+    @_ordered
+    def mesh_depth(self, verts, tris, w2c, H, W, fx, fy, cx, cy, want_skipped=False):
+        """nsk_mesh_depth: depth images [V, H, W] float32 (cuda) of the mesh (verts [nv, 3] float32, tris [nt, 3] int32, cuda tensors) from
+        the views w2c [V, 4, 4] (host, world-to-camera, camera looking along -z); 0 where nothing is hit.  Asynchronous unless want_skipped,
+        which leaves the number of triangles with an index out of range in self.last_skipped."""
+        import numpy as np
+        import torch
+        assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        w = np.ascontiguousarray(np.asarray(w2c, dtype=np.float32).reshape(-1, 16))
+        V, nv, nt = int(w.shape[0]), int(verts.shape[0]), int(tris.shape[0])
+        depth = torch.empty((V, int(H), int(W)), dtype=torch.float32, device=verts.device)
+        sk = C.c_int(0)
+        _chk(lib().nsk_mesh_depth(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, V,
+                                  w.ctypes.data_as(C.c_void_p) if V else None, int(H), int(W), C.c_float(fx), C.c_float(fy), C.c_float(cx),
+                                  C.c_float(cy), _ptr(depth) if V else None, C.byref(sk) if want_skipped else None))
+        if want_skipped:
+            self.last_skipped = int(sk.value)
+        return depth
+
+    @_ordered
+    def depth_pair_stats(self, a, b):
+        """nsk_depth_pair_stats of two depth stacks [V, H, W] (or [V, n_pix]) -> numpy [V, 4] float64: sum |a - b|, pixels with a > 0 and
+        b > 0, sum |a - b| over those, pixels with a > 0.  Synchronises."""
+        import numpy as np
+        import torch
+        assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape and a.dim() >= 2
+        V = int(a.shape[0])
+        out = np.zeros((V, 4), np.float64)
+        if V:
+            _chk(lib().nsk_depth_pair_stats(self.h, _ptr(a), _ptr(b), V, int(a[0].numel()), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @_ordered
+    def depth_views(self, verts, n_views, seed=0, shrink=0.7):
+        """nsk_depth_views: n_views random views inside the box of the mesh's vertices -> w2c [n_views, 4, 4] float32 (host); the box is left
+        in self.last_box.  Synchronises."""
+        import numpy as np
+        import torch
+        assert verts.dtype == torch.float32 and verts.shape[-1] == 3
+        box = np.zeros(6, np.float32)
+        w = np.zeros((int(n_views), 4, 4), np.float32)
+        _chk(lib().nsk_depth_views(self.h, _ptr(verts), int(verts.shape[0]), box.ctypes.data_as(C.c_void_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   float(shrink), int(n_views), w.ctypes.data_as(C.c_void_p)))
+        self.last_box = box
+        return w
+
+    def recon_depth_l1(self, rec_verts, rec_tris, gt_verts, gt_tris, n_views=1000, HW=(500, 500), focal=300.0, seed=0, shrink=0.7,
+                       min_cover=0.0):
+        """upstream's Depth L1 of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors: both meshes rendered as
+        depth images from the same n_views random views inside the ground truth's box (depth_views), cx = W / 2 - 0.5, cy = H / 2 - 0.5;
+        depth_l1_cm = 100 x the mean over the used views of sum |gt - rec| / n_pix.  A view is used when the ground truth covers at least
+        min_cover of its pixels (0: every view, upstream's plain mean).  Also: n_used, restricted_l1_cm (the mean over the pixels of the
+        used views where both meshes are hit) and the per-view arrays view_l1 (m), view_cover, stats [n_views, 4], w2c."""
+        import numpy as np
+        H, W = int(HW[0]), int(HW[1])
+        n_pix = H * W
+        w2c = self.depth_views(gt_verts, n_views, seed, shrink)
+        stats = np.zeros((int(n_views), 4), np.float64)
+        batch = max(1, (1 << 27) // n_pix)                 # both stacks together stay below about 1 GB
+        if batch > 32:
+            batch -= batch % 32
+        for k0 in range(0, int(n_views), batch):
+            w = w2c[k0:k0 + batch]
+            gt = self.mesh_depth(gt_verts, gt_tris, w, H, W, focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5)
+            rec = self.mesh_depth(rec_verts, rec_tris, w, H, W, focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5)
+            stats[k0:k0 + batch] = self.depth_pair_stats(gt, rec)
+        view_l1 = stats[:, 0] / n_pix
+        cover = stats[:, 3] / n_pix
+        used = cover >= min_cover
+        n_used, l1, both, both_sum = 0, 0.0, 0.0, 0.0
+        for k in range(int(n_views)):                       # (in view order, as Mesher::eval_recon_depth adds them)
+            if used[k]:
+                n_used += 1; l1 += view_l1[k]; both += stats[k, 1]; both_sum += stats[k, 2]
+        nan = float("nan")
+        return dict(depth_l1_cm=100.0 * l1 / n_used if n_used else nan, n_used=n_used,
+                    restricted_l1_cm=100.0 * both_sum / both if both else nan, view_l1=view_l1, view_cover=cover, stats=stats, w2c=w2c,
+                    n_views=int(n_views), H=H, W=W, focal=float(focal), seed=int(seed), shrink=float(shrink), min_cover=float(min_cover))
 
     @_ordered
     def eval_points(self, stage, pts):
