@@ -556,6 +556,55 @@ int nsk_cloud_nearest(nsk_ctx* ctx, const float* d_query, int n_query, const flo
  * bytes.  Reading h_out is the call's one synchronisation.  n = 0 gives zeros. */
 int nsk_cloud_stats(nsk_ctx* ctx, const float* d_dist, int n, float threshold, double h_out[4]);
 
+/* ---- alignment: point-to-point ICP of the reconstruction onto the ground truth (upstream src/tools/eval_recon.py, align=True: Open3D's
+ * registration_icp with threshold 0.1 m, identity start, 30 iterations, relative fitness / RMSE 1e-6) ------------------------------ */
+/* The rule.
+ *   Transformed source point.  Source S [n_s][3] and target T [n_t][3] are float32 on the device.  The current transform M is a 4x4 of
+ *     doubles on the host, row-major, last row 0 0 0 1 (the last row is not read).  The point is formed in double from the float32 source
+ *     point: s'_a = ((M[a][0] x + M[a][1] y) + M[a][2] z) + M[a][3], every product and sum its own operation (no FMA), and rounded once to
+ *     float32.  A source point with a component that is not finite is its own s', unchanged.  It is always the ORIGINAL source that is
+ *     transformed, by the accumulated M -- never a transformed copy again -- so rounding does not pile up over iterations.
+ *   Correspondence.  The nearest finite target and its distance d exactly as nsk_cloud_nearest defines them for the query s': the same
+ *     bits, the lowest index on ties.  The pair counts when s' is finite and d <= threshold (inclusive, on the fp32 distance).
+ *   Pair sums.  17 doubles over the counting pairs: [0] the count; [1] sum d d, the fp32 d widened to double and squared there;
+ *     [2..4] sum s'; [5..7] sum t; [8..16] sum s'_a t_b, row-major, the float32 values widened and the products in double.
+ *     No floating-point atomics.  Pairs are added by SOURCE INDEX whatever order the queries ran in, in the association of
+ *     nsk_cloud_stats: a lane adds its sources in index order, lanes meet by shuffles, waves in wave order, one row per workgroup, a
+ *     single-workgroup launch adds the rows in index order.  Two runs, and every cloud_query_mode / cloud_cells_x4, give the same bytes.
+ *   Rigid solve (host, double, no scaling: Umeyama / Kabsch; csrc/nsk_rigid.h).  n = [0], mu_s = [2..4] / n, mu_t = [5..7] / n,
+ *     C = sum s' t^T / n - mu_s mu_t^T.  C = U diag(sigma) V^T by a cyclic one-sided Jacobi, sigma descending.
+ *     R = V diag(1, 1, det(V U^T)) U^T, which maps s' onto t;  trans = mu_t - R mu_s;  the update is [R trans; 0 0 0 1].
+ *     rank = the number of sigma above 1e-12 of the largest (a C that is all rounding of its own formation, every sigma below 1e-14 of
+ *     the largest |sum s'_a t_b| / n, has rank 0).  Rank >= 2 determines R.  Rank <= 1 still returns a proper rotation
+ *     (R^T R = I, det +1, finite) and is reported as `degenerate`.  A count of 0 returns the identity.
+ *   The loop (Open3D's, in its order).  1. evaluate the pairs under M_0 (the init, default identity): fitness = count / n_s,
+ *     rmse = sqrt([1] / count) (0 without a pair).  2. solve for the update U from the sums.  3. M <- U M, a 4x4 product in double,
+ *     every product and sum on its own, k ascending.  4. evaluate again.  5. stop when both |fitness - previous| < rel_fitness and
+ *     |rmse - previous| < rel_rmse (converged), or after max_iter updates.  max_iter = 0 is the evaluation alone.  A count of 0 at any
+ *     evaluation stops the loop (not converged) and returns the M that was evaluated.
+ *
+ * nsk_cloud_pair_sums: one evaluation.  h_M NULL: the identity.  d_dist [n_source] / d_index [n_source] (either may be NULL) receive the
+ *   correspondences by source index: NaN / -1 where s' is not finite, +inf / -1 without a finite target.  *h_target_skipped (or NULL) =
+ *   targets with a non-finite component.  n_source = 0 is valid (zeros).  n_target = 0 and a negative threshold are errors that leave
+ *   the context usable.  Synchronises twice: the grid's box, the sums.
+ * nsk_rigid_from_sums: the rigid solve alone.  Host only: no context, no device.  h_U [16] row-major, *h_rank (or NULL) as above.
+ *   A sum that is not finite is an error.
+ * nsk_cloud_icp: the loop.  The targets' grid is built once; every evaluation queries it with the source transformed on load (no
+ *   transformed copy of the source is stored) and costs one synchronisation (the sums).  h_init NULL: the identity.  h_M [16] receives
+ *   the accumulated transform.  h_info: [0] updates applied; [1] fitness and [2] inlier rmse of the last evaluation (of h_M);
+ *   [3] its correspondences; [4] 1 converged, 0 stopped at max_iter or without a pair; [5] targets skipped; [6] sources whose s' is not
+ *   finite; [7] 1 when any solve had rank <= 1.  n_source = 0 is valid and gives the init.  n_target = 0, a negative threshold or a
+ *   negative max_iter are errors that leave the context usable.
+ * nsk_cloud_transform: d_out[p] = the transformed point of d_in[p] by the rule above, n points; d_out == d_in is allowed; a point with a
+ *   non-finite component passes through unchanged.  h_M NULL: the identity.  Asynchronous.
+ * None of the four may be called while a graph is being captured (nsk_rigid_from_sums aside). */
+int nsk_cloud_pair_sums(nsk_ctx* ctx, const float* d_source, int n_source, const float* d_target, int n_target, const double* h_M,
+                        float threshold, double* h_sums, float* d_dist, int32_t* d_index, int* h_target_skipped);
+int nsk_rigid_from_sums(const double* h_sums, double* h_U, int* h_rank);
+int nsk_cloud_icp(nsk_ctx* ctx, const float* d_source, int n_source, const float* d_target, int n_target, float threshold, int max_iter,
+                  double rel_fitness, double rel_rmse, const double* h_init, double* h_M, double* h_info);
+int nsk_cloud_transform(nsk_ctx* ctx, const double* h_M, const float* d_in, int n, float* d_out);
+
 /* ---- reconstruction depth L1: depth views of a mesh (upstream src/tools/eval_recon.py calc_2d_metric) -------------------------- */
 /* nsk_mesh_depth: depth images of a triangle mesh (d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3] int32, device) from
  * V views: h_w2c [V][16] row-major world-to-camera on the host, the camera looking along -z, as in nsk_lattice_seen.  d_depth [V][H][W]

@@ -7,6 +7,8 @@
 #include "nsk_mesh.h"
 #include "nsk_image.h"
 #include "nsk_cloud.h"
+#include "nsk_icp.h"
+#include "nsk_rigid.h"
 #include "nsk_raster.h"
 #include "nsk_buf.h"
 #include "nsk_split.h"
@@ -860,6 +862,8 @@ struct nsk_ctx {
         Buf<unsigned> tcell, start, cursor; Buf<float4> sorted;      // targets: [n] cells, [cells + 1 + scan levels], [cells], [n] in cell order
         Buf<unsigned> qcell, qstart, qcursor, qperm;         // queries in cell order (the same grid)
         Buf<double> rows;                                    // [CLOUD_MAX_ROWS][4] partial sums + the 4 results
+        Buf<double> icp_rows;                                // nsk_cloud_pair_sums / nsk_cloud_icp: [CLOUD_MAX_ROWS][ICP_COLS] partial sums + the results
+        Buf<float> icp_dist; Buf<int> icp_index;             // [sources] the correspondences, when the caller keeps none
         int cells_x4 = 4;                                    // nsk_set_tuning "cloud_cells_x4": grid cells aimed at per finite target, in quarters
         int query_mode = 0;                                  // nsk_set_tuning "cloud_query_mode": bit 0 a wave per query; + 2 queries always in input order, + 4 always in cell order (neither: by size)
     } cloud;
@@ -3158,16 +3162,11 @@ static CloudGrid cloud_grid(const float* box, unsigned nfinite, int cells_x4)
     return G;
 }
 
-extern "C" int nsk_cloud_nearest(nsk_ctx* c, const float* d_query, int n_query, const float* d_target, int n_target, float* d_dist,
-                                 int32_t* d_index, int* h_target_skipped)
+// nsk_cloud_nearest in two halves, so that nsk_cloud_icp builds the targets' grid once and queries it at every evaluation.
+struct CloudBuilt { CloudGrid G; size_t cells = 0, words = 0; unsigned nfinite = 0; };
+// the box (one synchronisation) and, with `place`, the grid: cells -> scan -> placement into c->cloud.start / sorted
+static int cloud_build(nsk_ctx* c, const float* d_target, int n_target, bool place, CloudBuilt& B)
 {
-    if (!c) return fail("nsk_cloud_nearest: null ctx");
-    if (n_query < 0 || n_target < 0) return fail("nsk_cloud_nearest: negative count");
-    if (n_target == 0) return fail("nsk_cloud_nearest: no target");
-    if (!d_target) return fail("nsk_cloud_nearest: d_target is NULL");
-    if (n_query > 0 && (!d_query || !d_dist)) return fail("nsk_cloud_nearest: d_query / d_dist is NULL");
-    if (c->capturing) return fail("nsk_cloud_nearest: not while a graph is being captured");
-    HIPCHK(hipSetDevice(c->device));
     nsk_ctx::Cloud& K = c->cloud;
     // pass 1: the box
     const int nrows = (int)std::min<long long>(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
@@ -3180,51 +3179,79 @@ extern "C" int nsk_cloud_nearest(nsk_ctx* c, const float* d_query, int n_query, 
       HIPCHK(hipGetLastError()); }
     HIPCHK(hipMemcpyAsync(box, box_out, sizeof(box), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    unsigned nfinite; memcpy(&nfinite, &box[6], 4);
-    if (h_target_skipped) *h_target_skipped = (int)((unsigned)n_target - nfinite);
-    if (n_query == 0) return 0;
-    const CloudGrid G = cloud_grid(box, nfinite, K.cells_x4);
-    const size_t cells = (size_t)G.dim[0] * G.dim[1] * G.dim[2], words = mc_scan_words(cells + 1);
-    // queries in cell order: the ordering passes cost more than they save below about half a million queries (DESIGN 7c)
-    const bool ordered = nfinite > 0 && ((K.query_mode & 4) || (!(K.query_mode & 2) && n_query >= CLOUD_ORDER_MIN));
-    const int tb = (int)(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK), qb = (int)(((long long)n_query + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
-    if (nfinite) {
+    memcpy(&B.nfinite, &box[6], 4);
+    if (!place) return 0;
+    B.G = cloud_grid(box, B.nfinite, K.cells_x4);
+    B.cells = (size_t)B.G.dim[0] * B.G.dim[1] * B.G.dim[2]; B.words = mc_scan_words(B.cells + 1);
+    if (B.nfinite) {
+        const int tb = (int)(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
         CHK(grow(c, K.tcell, (size_t)n_target, "the targets' cells", GROW_NO_CAPTURE));
         CHK(grow(c, K.sorted, (size_t)n_target, "the targets in cell order", GROW_NO_CAPTURE));
-        CHK(grow(c, K.start, words, "the cells' first targets", GROW_NO_CAPTURE));
-        CHK(grow(c, K.cursor, cells, "the cells' placement cursors", GROW_NO_CAPTURE));
+        CHK(grow(c, K.start, B.words, "the cells' first targets", GROW_NO_CAPTURE));
+        CHK(grow(c, K.cursor, B.cells, "the cells' placement cursors", GROW_NO_CAPTURE));
         ProfScope ps(c, "cloud_grid");
-        HIPCHK(hipMemsetAsync(K.start, 0, words * 4, c->stream));
-        HIPCHK(hipMemsetAsync(K.cursor, 0, cells * 4, c->stream));
-        k_cloud_cells<<<tb, CLOUD_BLOCK, 0, c->stream>>>(G, n_target, d_target, 0, K.tcell, K.start);           // pass 2
+        HIPCHK(hipMemsetAsync(K.start, 0, B.words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(K.cursor, 0, B.cells * 4, c->stream));
+        k_cloud_cells<<<tb, CLOUD_BLOCK, 0, c->stream>>>(B.G, n_target, d_target, 0, K.tcell, K.start);        // pass 2
         HIPCHK(hipGetLastError());
-        CHK(mc_scan(c, K.start, (int)cells + 1));                                                              // pass 3
+        CHK(mc_scan(c, K.start, (int)B.cells + 1));                                                           // pass 3
         k_cloud_place<<<tb, CLOUD_BLOCK, 0, c->stream>>>(n_target, d_target, K.tcell, K.start, K.cursor, K.sorted, nullptr);      // pass 4
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+// the queries against a built grid; with X they are the sources of an ICP evaluation, transformed on load (nsk_icp.h)
+static int cloud_query(nsk_ctx* c, const CloudBuilt& B, const float* d_query, int n_query, const CloudXform* X, float* d_dist, int32_t* d_index)
+{
+    nsk_ctx::Cloud& K = c->cloud;
+    const CloudGrid& G = B.G;
+    // queries in cell order: the ordering passes cost more than they save below about half a million queries (DESIGN 7c)
+    const bool ordered = B.nfinite > 0 && ((K.query_mode & 4) || (!(K.query_mode & 2) && n_query >= CLOUD_ORDER_MIN));
+    const int qb = (int)(((long long)n_query + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
     if (ordered) {
         CHK(grow(c, K.qcell, (size_t)n_query, "the queries' cells", GROW_NO_CAPTURE));
         CHK(grow(c, K.qperm, (size_t)n_query, "the queries in cell order", GROW_NO_CAPTURE));
-        CHK(grow(c, K.qstart, words, "the cells' first queries", GROW_NO_CAPTURE));
-        CHK(grow(c, K.qcursor, cells, "the cells' query cursors", GROW_NO_CAPTURE));
-        ProfScope ps(c, "cloud_order");
-        HIPCHK(hipMemsetAsync(K.qstart, 0, words * 4, c->stream));
-        HIPCHK(hipMemsetAsync(K.qcursor, 0, cells * 4, c->stream));
-        k_cloud_cells<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, 1, K.qcell, K.qstart);
+        CHK(grow(c, K.qstart, B.words, "the cells' first queries", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qcursor, B.cells, "the cells' query cursors", GROW_NO_CAPTURE));
+        ProfScope ps(c, X ? "icp_order" : "cloud_order");
+        HIPCHK(hipMemsetAsync(K.qstart, 0, B.words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(K.qcursor, 0, B.cells * 4, c->stream));
+        if (X) k_icp_cells<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, *X, n_query, d_query, K.qcell, K.qstart);
+        else k_cloud_cells<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, 1, K.qcell, K.qstart);
         HIPCHK(hipGetLastError());
-        CHK(mc_scan(c, K.qstart, (int)cells + 1));
+        CHK(mc_scan(c, K.qstart, (int)B.cells + 1));
         k_cloud_place<<<qb, CLOUD_BLOCK, 0, c->stream>>>(n_query, d_query, K.qcell, K.qstart, K.qcursor, nullptr, K.qperm);
         HIPCHK(hipGetLastError());
     }
-    { ProfScope ps(c, "cloud_query");
+    { ProfScope ps(c, X ? "icp_query" : "cloud_query");
       const unsigned* qperm = ordered ? K.qperm.get() : nullptr;
       if (K.query_mode & 1) {
           const long long wg = ((long long)n_query * 64 + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
-          k_cloud_query<64><<<(unsigned)wg, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
-      } else
+          if (X) k_icp_query<64><<<(unsigned)wg, CLOUD_BLOCK, 0, c->stream>>>(G, *X, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
+          else k_cloud_query<64><<<(unsigned)wg, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
+      } else if (X)
+          k_icp_query<1><<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, *X, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
+      else
           k_cloud_query<1><<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, qperm, K.start, K.sorted, d_dist, d_index);
       HIPCHK(hipGetLastError()); }
     return 0;
+}
+
+extern "C" int nsk_cloud_nearest(nsk_ctx* c, const float* d_query, int n_query, const float* d_target, int n_target, float* d_dist,
+                                 int32_t* d_index, int* h_target_skipped)
+{
+    if (!c) return fail("nsk_cloud_nearest: null ctx");
+    if (n_query < 0 || n_target < 0) return fail("nsk_cloud_nearest: negative count");
+    if (n_target == 0) return fail("nsk_cloud_nearest: no target");
+    if (!d_target) return fail("nsk_cloud_nearest: d_target is NULL");
+    if (n_query > 0 && (!d_query || !d_dist)) return fail("nsk_cloud_nearest: d_query / d_dist is NULL");
+    if (c->capturing) return fail("nsk_cloud_nearest: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    CloudBuilt B;
+    CHK(cloud_build(c, d_target, n_target, n_query > 0, B));
+    if (h_target_skipped) *h_target_skipped = (int)((unsigned)n_target - B.nfinite);
+    if (n_query == 0) return 0;
+    return cloud_query(c, B, d_query, n_query, nullptr, d_dist, d_index);
 }
 
 extern "C" int nsk_cloud_stats(nsk_ctx* c, const float* d_dist, int n, float threshold, double h_out[4])
@@ -3247,6 +3274,130 @@ extern "C" int nsk_cloud_stats(nsk_ctx* c, const float* d_dist, int n, float thr
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_out, out, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- alignment: point-to-point ICP (nsk_icp.h, nsk_rigid.h) ------------------------------------------------------------------------
+static void cloud_xform_of(const double* h_M, CloudXform& X)
+{
+    double I[16]; nsk_rigid::identity4(I);
+    for (int k = 0; k < 12; ++k) X.m[k] = (h_M ? h_M : I)[k];
+}
+// one evaluation of the pairs under X against a built grid: query, sums, the ICP_COLS doubles back (the evaluation's one synchronisation)
+static int cloud_pair_eval(nsk_ctx* c, const CloudBuilt& B, const float* d_source, int n_source, const float* d_target, const CloudXform& X,
+                           float threshold, float* d_dist, int32_t* d_index, double* h_cols)
+{
+    nsk_ctx::Cloud& K = c->cloud;
+    CHK(cloud_query(c, B, d_source, n_source, &X, d_dist, d_index));
+    const int nrows = (int)std::min<long long>(((long long)n_source + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
+    double* rows = K.icp_rows;
+    double* out = rows + (size_t)CLOUD_MAX_ROWS * ICP_COLS;
+    { ProfScope ps(c, "icp_sums");
+      k_icp_sums<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(X, n_source, d_source, d_dist, d_index, d_target, threshold, rows);
+      k_icp_sums_sum<<<1, 64, 0, c->stream>>>(nrows, rows, out);
+      HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemcpyAsync(h_cols, out, ICP_COLS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+// the arguments both entry points share, the grid (once) and the buffers of an evaluation
+static int cloud_pair_setup(nsk_ctx* c, const char* who, const float* d_source, int n_source, const float* d_target, int n_target, float threshold,
+                            float** d_dist, int32_t** d_index, CloudBuilt& B)
+{
+    if (!c) return fail("%s: null ctx", who);
+    if (n_source < 0 || n_target < 0) return fail("%s: negative count", who);
+    if (n_target == 0) return fail("%s: no target", who);
+    if (!d_target) return fail("%s: d_target is NULL", who);
+    if (n_source > 0 && !d_source) return fail("%s: d_source is NULL", who);
+    if (!(threshold >= 0.f)) return fail("%s: the threshold must not be negative", who);
+    if (c->capturing) return fail("%s: not while a graph is being captured", who);
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Cloud& K = c->cloud;
+    if (n_source > 0) {
+        CHK(grow(c, K.icp_rows, (size_t)CLOUD_MAX_ROWS * ICP_COLS + ICP_COLS, "the pair sums of the workgroups", GROW_NO_CAPTURE));
+        if (!*d_dist) { CHK(grow(c, K.icp_dist, (size_t)n_source, "the correspondences' distances", GROW_NO_CAPTURE)); *d_dist = K.icp_dist; }
+        if (!*d_index) { CHK(grow(c, K.icp_index, (size_t)n_source, "the correspondences", GROW_NO_CAPTURE)); *d_index = K.icp_index; }
+    }
+    return cloud_build(c, d_target, n_target, n_source > 0, B);
+}
+
+extern "C" int nsk_cloud_pair_sums(nsk_ctx* c, const float* d_source, int n_source, const float* d_target, int n_target, const double* h_M,
+                                   float threshold, double* h_sums, float* d_dist, int32_t* d_index, int* h_target_skipped)
+{
+    if (!h_sums) return fail("nsk_cloud_pair_sums: h_sums is NULL");
+    CloudBuilt B;
+    CHK(cloud_pair_setup(c, "nsk_cloud_pair_sums", d_source, n_source, d_target, n_target, threshold, &d_dist, &d_index, B));
+    if (h_target_skipped) *h_target_skipped = (int)((unsigned)n_target - B.nfinite);
+    for (int k = 0; k < 17; ++k) h_sums[k] = 0.0;
+    if (n_source == 0) return 0;
+    CloudXform X; cloud_xform_of(h_M, X);
+    double cols[ICP_COLS];
+    CHK(cloud_pair_eval(c, B, d_source, n_source, d_target, X, threshold, d_dist, d_index, cols));
+    for (int k = 0; k < 17; ++k) h_sums[k] = cols[k];
+    return 0;
+}
+
+extern "C" int nsk_rigid_from_sums(const double* h_sums, double* h_U, int* h_rank)
+{
+    if (!h_sums || !h_U) return fail("nsk_rigid_from_sums: null argument");
+    if (nsk_rigid::from_sums(h_sums, h_U, h_rank) != 0) return fail("nsk_rigid_from_sums: a sum is not finite");
+    return 0;
+}
+
+extern "C" int nsk_cloud_icp(nsk_ctx* c, const float* d_source, int n_source, const float* d_target, int n_target, float threshold, int max_iter,
+                             double rel_fitness, double rel_rmse, const double* h_init, double* h_M, double* h_info)
+{
+    if (!h_M || !h_info) return fail("nsk_cloud_icp: h_M / h_info is NULL");
+    if (max_iter < 0) return fail("nsk_cloud_icp: max_iter must not be negative");
+    float* d_dist = nullptr; int32_t* d_index = nullptr;
+    CloudBuilt B;
+    CHK(cloud_pair_setup(c, "nsk_cloud_icp", d_source, n_source, d_target, n_target, threshold, &d_dist, &d_index, B));
+    double M[16];
+    if (h_init) memcpy(M, h_init, sizeof(M)); else nsk_rigid::identity4(M);
+    M[12] = M[13] = M[14] = 0.0; M[15] = 1.0;
+    for (int k = 0; k < 8; ++k) h_info[k] = 0.0;
+    h_info[5] = (double)((unsigned)n_target - B.nfinite);
+    memcpy(h_M, M, sizeof(M));
+    if (n_source == 0) return 0;
+    double cols[ICP_COLS];
+    CloudXform X; cloud_xform_of(M, X);
+    CHK(cloud_pair_eval(c, B, d_source, n_source, d_target, X, threshold, d_dist, d_index, cols));
+    auto fitness = [&]() { return cols[0] / (double)n_source; };
+    auto rmse = [&]() { return cols[0] > 0 ? std::sqrt(cols[1] / cols[0]) : 0.0; };
+    double fit = fitness(), err = rmse();
+    int updates = 0, converged = 0, degenerate = 0;
+    while (updates < max_iter && cols[0] > 0) {
+        double U[16], next[16];
+        int rank = 0;
+        if (nsk_rigid::from_sums(cols, U, &rank) != 0) return fail("nsk_cloud_icp: a pair sum is not finite");
+        if (rank <= 1) degenerate = 1;
+        nsk_rigid::mul4(U, M, next);
+        memcpy(M, next, sizeof(M));
+        ++updates;
+        cloud_xform_of(M, X);
+        CHK(cloud_pair_eval(c, B, d_source, n_source, d_target, X, threshold, d_dist, d_index, cols));
+        const double f2 = fitness(), e2 = rmse();
+        const bool still = std::fabs(f2 - fit) < rel_fitness && std::fabs(e2 - err) < rel_rmse;
+        fit = f2; err = e2;
+        if (cols[0] > 0 && still) { converged = 1; break; }
+    }
+    memcpy(h_M, M, sizeof(M));
+    h_info[0] = updates; h_info[1] = fit; h_info[2] = err; h_info[3] = cols[0]; h_info[4] = converged; h_info[6] = cols[17]; h_info[7] = degenerate;
+    return 0;
+}
+
+extern "C" int nsk_cloud_transform(nsk_ctx* c, const double* h_M, const float* d_in, int n, float* d_out)
+{
+    if (!c) return fail("nsk_cloud_transform: null ctx");
+    if (n < 0) return fail("nsk_cloud_transform: negative count");
+    if (n == 0) return 0;
+    if (!d_in || !d_out) return fail("nsk_cloud_transform: d_in / d_out is NULL");
+    if (c->capturing) return fail("nsk_cloud_transform: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    CloudXform X; cloud_xform_of(h_M, X);
+    { ProfScope ps(c, "cloud_transform");
+      k_cloud_transform<<<(unsigned)(((long long)n + CLOUD_BLOCK - 1) / CLOUD_BLOCK), CLOUD_BLOCK, 0, c->stream>>>(X, n, d_in, d_out);
+      HIPCHK(hipGetLastError()); }
     return 0;
 }
 

@@ -237,24 +237,11 @@ __device__ __forceinline__ void cloud_try(CloudBest& B, float qx, float qy, floa
 // faces that have cells behind them (subtractions in fp32), monotone rounding gives |q_a - t_a| (as the kernel rounds it) >= m for that
 // axis, and d2 as evaluated >= fl(m m) because the other two squares are not negative and every rounding is monotone.  So the walk ends
 // when best < fl(m m) -- strictly: at equality a lower index could still sit outside -- or when no face has cells behind it.
+// The walk of one finite query q against a grid with at least one target; every lane of the query's LANES returns the same best.
 template <int LANES>
-__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_query(CloudGrid G, int nq, const float* __restrict__ query, const unsigned* __restrict__ qperm,
-                                                            const unsigned* __restrict__ start, const float4* __restrict__ sorted4,
-                                                            float* __restrict__ dist, int* __restrict__ index)
+__device__ __forceinline__ CloudBest cloud_walk(const CloudGrid& G, const float (&q)[3], int lane, const unsigned* __restrict__ start,
+                                                const float4* __restrict__ sorted4)
 {
-    const long long slot = ((long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x) / LANES;
-    const int lane = threadIdx.x % LANES;
-    if (slot >= nq) return;                                     // (LANES = 64: the whole wave leaves)
-    const size_t qi = qperm ? qperm[slot] : (size_t)slot;
-    const float q[3] = {query[3 * qi], query[3 * qi + 1], query[3 * qi + 2]};
-    if (!(cloud_finite(q[0]) && cloud_finite(q[1]) && cloud_finite(q[2]))) {
-        if (lane == 0) { dist[qi] = __builtin_nanf(""); if (index) index[qi] = -1; }
-        return;
-    }
-    if (G.nfinite == 0) {
-        if (lane == 0) { dist[qi] = __builtin_inff(); if (index) index[qi] = -1; }
-        return;
-    }
     int c[3], r = 0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -303,7 +290,35 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_query(CloudGrid G, int nq
         }
         if (m == __builtin_inff() || B.d2 < mul_rn(m, m)) break;   // (m = inf: the block covers the grid)
     }
+    return B;
+}
+// what a query leaves behind: NaN / -1 when it is not finite, +inf / -1 without a finite target, else the walk's best
+template <int LANES>
+__device__ __forceinline__ void cloud_answer(const CloudGrid& G, const float (&q)[3], int lane, const unsigned* __restrict__ start,
+                                             const float4* __restrict__ sorted4, size_t qi, float* __restrict__ dist, int* __restrict__ index)
+{
+    if (!(cloud_finite(q[0]) && cloud_finite(q[1]) && cloud_finite(q[2]))) {
+        if (lane == 0) { dist[qi] = __builtin_nanf(""); if (index) index[qi] = -1; }
+        return;
+    }
+    if (G.nfinite == 0) {
+        if (lane == 0) { dist[qi] = __builtin_inff(); if (index) index[qi] = -1; }
+        return;
+    }
+    const CloudBest B = cloud_walk<LANES>(G, q, lane, start, sorted4);
     if (lane == 0) { dist[qi] = cloud_sqrt_rn(B.d2); if (index) index[qi] = B.idx; }
+}
+template <int LANES>
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_query(CloudGrid G, int nq, const float* __restrict__ query, const unsigned* __restrict__ qperm,
+                                                            const unsigned* __restrict__ start, const float4* __restrict__ sorted4,
+                                                            float* __restrict__ dist, int* __restrict__ index)
+{
+    const long long slot = ((long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x) / LANES;
+    const int lane = threadIdx.x % LANES;
+    if (slot >= nq) return;                                     // (LANES = 64: the whole wave leaves)
+    const size_t qi = qperm ? qperm[slot] : (size_t)slot;
+    const float q[3] = {query[3 * qi], query[3 * qi + 1], query[3 * qi + 2]};
+    cloud_answer<LANES>(G, q, lane, start, sorted4, qi, dist, index);
 }
 
 // ---- the reductions (nsk_cloud_stats) --------------------------------------------------------------------------------------------------

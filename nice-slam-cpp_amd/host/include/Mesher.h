@@ -25,6 +25,9 @@ struct ReconMetrics {
     double rec_area = 0, gt_area = 0;                                         // m^2, degenerate triangles left out
     int rec_degenerate = 0, gt_degenerate = 0;                                // triangles without an area or with an index out of range
     int rec_skipped = 0, gt_skipped = 0;                                      // samples with a non-finite coordinate left out of the targets
+    double transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // align: the reconstruction was measured under this (row-major 4x4)
+    double icp_fitness = 0, icp_rmse = 0;                                     // align: share of rec vertices with a gt vertex within reach, their rmse (m)
+    int icp_iterations = 0;                                                   // align: updates applied
 };
 
 // upstream's 2D number of a reconstruction, Depth L1 (src/tools/eval_recon.py calc_2d_metric), and what went into it
@@ -36,6 +39,17 @@ struct ReconDepth {
     std::vector<double> view_l1, view_cover;        // per view: sum |gt - rec| / n_pix (m), the share of pixels the ground truth covers
     std::vector<double> stats;              // [n_views][4]: nsk_depth_pair_stats(gt, rec)
     std::vector<float> w2c;                 // [n_views][16]: the views (nsk_depth_views)
+    double transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // align: as in ReconMetrics
+    double icp_fitness = 0, icp_rmse = 0;
+    int icp_iterations = 0;
+};
+
+// what Mesher::align_recon found (nsk_cloud_icp's h_M and h_info)
+struct ReconAlign {
+    double transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int iterations = 0, correspondences = 0;
+    double fitness = 0, rmse = 0;
+    bool converged = false, degenerate = false;
 };
 
 class Mesher {
@@ -64,22 +78,29 @@ class Mesher {
     static void read_ply_mesh(const std::string& path, std::vector<float>& xyz, std::vector<int32_t>& triangles);
     // Accuracy / completion / completion ratio on the device: n_points area-weighted samples of each mesh (nsk_mesh_sample with seed and
     // seed + 1), exact nearest distances both ways (nsk_cloud_nearest), the sums (nsk_cloud_stats).  Coordinates in metres; the meshes
-    // are taken as they are (no alignment, no culling).  A static function: it needs no map, only the process's context.
+    // are taken as they are (no culling).  With align the reconstruction's vertices are first registered to the ground truth's
+    // (align_recon) and the transformed mesh is measured.  A static function: it needs no map, only the process's context.
     static ReconMetrics eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n_points = 200000, float threshold = 0.05f,
-                                   unsigned long long seed = 0);
+                                   unsigned long long seed = 0, bool align = false);
     static ReconMetrics eval_recon(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles, const float* gt_xyz,
                                    int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles, int n_points = 200000,
-                                   float threshold = 0.05f, unsigned long long seed = 0);
+                                   float threshold = 0.05f, unsigned long long seed = 0, bool align = false);
+    // upstream's get_align_transformation: point-to-point ICP of the reconstruction's vertices onto the ground truth's from the identity
+    // (nsk_cloud_icp: Open3D's registration_icp, relative fitness / rmse 1e-6).  Host arrays [n][3]; nothing is changed.
+    static ReconAlign align_recon(const float* rec_xyz, int rec_vertices, const float* gt_xyz, int gt_vertices, float threshold = 0.1f,
+                                  int max_iter = 30);
     // Depth L1 on the device: n_views random views inside the ground truth's box (nsk_depth_views: seed, shrink), both meshes rendered as
     // H x W depth images with fx = fy = focal, cx = W / 2 - 0.5, cy = H / 2 - 0.5 (nsk_mesh_depth) in batches that keep both stacks below
     // about 1 GB, the per-view sums (nsk_depth_pair_stats).  A view is used when the ground truth covers at least min_cover of its pixels
-    // (0: every view, upstream's plain mean).  Not done: upstream's rejection of views that see never-observed ground truth, alignment.
+    // (0: every view, upstream's plain mean).  With align the reconstruction is registered first, as in eval_recon.  Not done: upstream's
+    // rejection of views that see never-observed ground truth.
     static ReconDepth eval_recon_depth(const std::string& rec_ply, const std::string& gt_ply, int n_views = 1000, int H = 500, int W = 500,
-                                       float focal = 300.f, unsigned long long seed = 0, double shrink = 0.7, double min_cover = 0.0);
+                                       float focal = 300.f, unsigned long long seed = 0, double shrink = 0.7, double min_cover = 0.0,
+                                       bool align = false);
     static ReconDepth eval_recon_depth(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles,
                                        const float* gt_xyz, int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles,
                                        int n_views = 1000, int H = 500, int W = 500, float focal = 300.f, unsigned long long seed = 0,
-                                       double shrink = 0.7, double min_cover = 0.0);
+                                       double shrink = 0.7, double min_cover = 0.0, bool align = false);
 
     int resolution;
     float level_set, padding;

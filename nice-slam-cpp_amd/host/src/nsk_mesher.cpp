@@ -350,9 +350,31 @@ void Mesher::read_ply_mesh(const std::string& path, std::vector<float>& xyz, std
     }
 }
 
+// ---- alignment -------------------------------------------------------------------------------------------------------------------------
+ReconAlign Mesher::align_recon(const float* rec_xyz, int rec_nv, const float* gt_xyz, int gt_nv, float threshold, int max_iter)
+{
+    if (rec_nv < 1 || gt_nv < 1) throw std::runtime_error("Mesher::align_recon: a mesh without a vertex");
+    DevMem rv((size_t)rec_nv * 3 * sizeof(float)), gv((size_t)gt_nv * 3 * sizeof(float));
+    if (hipMemcpy(rv.p, rec_xyz, (size_t)rec_nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(gv.p, gt_xyz, (size_t)gt_nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        throw std::runtime_error("Mesher: H2D failed");
+    ReconAlign A;
+    double info[8];
+    check(nsk_cloud_icp(ctx(), (const float*)rv.p, rec_nv, (const float*)gv.p, gt_nv, threshold, max_iter, 1e-6, 1e-6, nullptr, A.transform, info));
+    A.iterations = (int)info[0]; A.fitness = info[1]; A.rmse = info[2]; A.correspondences = (int)info[3];
+    A.converged = info[4] != 0.0; A.degenerate = info[7] != 0.0;
+    return A;
+}
+// the fields both results share
+template <class R> static void keep_alignment(R& M, const ReconAlign& A)
+{
+    for (int k = 0; k < 16; ++k) M.transform[k] = A.transform[k];
+    M.icp_fitness = A.fitness; M.icp_rmse = A.rmse; M.icp_iterations = A.iterations;
+}
+
 // ---- reconstruction metrics ----------------------------------------------------------------------------------------------------------
 ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
-                                const int32_t* gt_tris, int gt_nt, int n, float threshold, unsigned long long seed)
+                                const int32_t* gt_tris, int gt_nt, int n, float threshold, unsigned long long seed, bool align)
 {
     if (n < 1) throw std::runtime_error("Mesher::eval_recon: n_points must be at least 1");
     if (rec_nt < 1 || gt_nt < 1) throw std::runtime_error("Mesher::eval_recon: a mesh without a triangle");
@@ -360,10 +382,12 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
         if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
     };
     ReconMetrics M;
+    if (align) keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
     DevMem rec_pts((size_t)n * 3 * sizeof(float)), gt_pts((size_t)n * 3 * sizeof(float)), dist((size_t)n * sizeof(float));
     {   // the meshes leave the device again as soon as their samples are drawn
         DevMem v((size_t)rec_nv * 3 * sizeof(float)), t((size_t)rec_nt * 3 * sizeof(int32_t));
         up(v, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(t, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
+        if (align) check(nsk_cloud_transform(ctx(), M.transform, (const float*)v.p, rec_nv, (float*)v.p));
         check(nsk_mesh_sample(ctx(), (const float*)v.p, rec_nv, (const int32_t*)t.p, rec_nt, seed, n, (float*)rec_pts.p, nullptr, &M.rec_area, &M.rec_degenerate));
         check(nsk_sync(ctx()));
     }
@@ -386,7 +410,7 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
     return M;
 }
 
-ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n, float threshold, unsigned long long seed)
+ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n, float threshold, unsigned long long seed, bool align)
 {
     std::vector<float> rv, gv;
     std::vector<int32_t> rt, gt;
@@ -395,13 +419,13 @@ ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& g
     if (rt.empty()) throw std::runtime_error("Mesher::eval_recon: " + rec_ply + " has no triangle");
     if (gt.empty()) throw std::runtime_error("Mesher::eval_recon: " + gt_ply + " has no triangle");
     return eval_recon(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(), (int)(gt.size() / 3),
-                      n, threshold, seed);
+                      n, threshold, seed, align);
 }
 
 // ---- reconstruction depth L1 -----------------------------------------------------------------------------------------------------------
 ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
                                     const int32_t* gt_tris, int gt_nt, int n_views, int H, int W, float focal, unsigned long long seed,
-                                    double shrink, double min_cover)
+                                    double shrink, double min_cover, bool align)
 {
     if (n_views < 1) throw std::runtime_error("Mesher::eval_recon_depth: n_views must be at least 1");
     if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::eval_recon_depth: the image must have 1 .. 2^24 pixels");
@@ -415,6 +439,10 @@ ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int3
     up(rv, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(rt, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
     up(gv, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(gtt, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
     ReconDepth M;
+    if (align) {
+        keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
+        check(nsk_cloud_transform(ctx(), M.transform, (const float*)rv.p, rec_nv, (float*)rv.p));
+    }
     M.n_views = n_views;
     M.w2c.assign((size_t)n_views * 16, 0.f);
     M.stats.assign((size_t)n_views * 4, 0.0);
@@ -449,12 +477,12 @@ ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int3
 }
 
 ReconDepth Mesher::eval_recon_depth(const std::string& rec_ply, const std::string& gt_ply, int n_views, int H, int W, float focal,
-                                    unsigned long long seed, double shrink, double min_cover)
+                                    unsigned long long seed, double shrink, double min_cover, bool align)
 {
     std::vector<float> rv, gv;
     std::vector<int32_t> rt, gt;
     read_ply_mesh(rec_ply, rv, rt);
     read_ply_mesh(gt_ply, gv, gt);
     return eval_recon_depth(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(),
-                            (int)(gt.size() / 3), n_views, H, W, focal, seed, shrink, min_cover);
+                            (int)(gt.size() / 3), n_views, H, W, focal, seed, shrink, min_cover, align);
 }

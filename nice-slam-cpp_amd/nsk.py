@@ -29,6 +29,7 @@ SYMBOLS = (
     "nsk_lattice_seen", "nsk_mesh_filter",
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
     "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
+    "nsk_cloud_pair_sums", "nsk_rigid_from_sums", "nsk_cloud_icp", "nsk_cloud_transform",
     "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views",
 )
 
@@ -72,6 +73,16 @@ def lib():
         L.nsk_cloud_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_cloud_stats.restype = C.c_int
         L.nsk_cloud_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_double)]
+        PD = C.POINTER(C.c_double)
+        L.nsk_cloud_pair_sums.restype = C.c_int
+        L.nsk_cloud_pair_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, PD, C.c_float, PD, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int)]
+        L.nsk_rigid_from_sums.restype = C.c_int
+        L.nsk_rigid_from_sums.argtypes = [PD, PD, C.POINTER(C.c_int)]
+        L.nsk_cloud_icp.restype = C.c_int
+        L.nsk_cloud_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, PD, PD, PD]
+        L.nsk_cloud_transform.restype = C.c_int
+        L.nsk_cloud_transform.argtypes = [C.c_void_p, PD, C.c_void_p, C.c_int, C.c_void_p]
         L.nsk_mesh_depth.restype = C.c_int
         L.nsk_mesh_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                      C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
@@ -113,6 +124,25 @@ def depth_views_from_box(box, n_views, seed=0, shrink=0.7):
     _chk(lib().nsk_depth_views(None, None, 0, b.ctypes.data_as(C.c_void_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(shrink), int(n_views),
                                w.ctypes.data_as(C.c_void_p)))
     return w
+
+
+def rigid_from_sums(sums):
+    """nsk_rigid_from_sums: the rigid update [4, 4] float64 that best maps s' onto t from the 17 pair sums, and the numerical rank of the
+    covariance (include/nsk.h: the rigid solve); needs no GPU"""
+    import numpy as np
+    h = (C.c_double * 17)(*[float(x) for x in np.asarray(sums, np.float64).reshape(17)])
+    U = (C.c_double * 16)()
+    rank = C.c_int(0)
+    _chk(lib().nsk_rigid_from_sums(h, U, C.byref(rank)))
+    return np.array(U[:], np.float64).reshape(4, 4), int(rank.value)
+
+
+def _mat16(M):
+    """a 4x4 (anything numpy reads) as the 16 doubles of the C ABI, or None"""
+    if M is None:
+        return None
+    import numpy as np
+    return (C.c_double * 16)(*[float(x) for x in np.asarray(M, np.float64).reshape(16)])
 
 
 def _stage(s):
@@ -460,10 +490,78 @@ class Context:
         _chk(lib().nsk_cloud_stats(self.h, _ptr(dist) if n else None, n, C.c_float(threshold), h))
         return dict(sum=float(h[0]), count=int(h[1]), below=int(h[2]), max=float(h[3]))
 
-    def recon_metrics(self, rec_verts, rec_tris, gt_verts, gt_tris, n=200000, threshold=0.05, seed=0):
+    @_ordered
+    def cloud_pair_sums(self, source, target, M=None, threshold=0.1, want_pairs=False):
+        """nsk_cloud_pair_sums: the 17 pair sums (numpy float64) of source [ns, 3] under the 4x4 M (None: the identity) against target
+        [nt, 3]; with want_pairs also the correspondences (dist [ns] float32, index [ns] int32) by source index.  The number of non-finite
+        targets left out is in self.last_skipped.  Synchronises."""
+        import numpy as np
+        import torch
+        assert source.dtype == torch.float32 and target.dtype == torch.float32 and source.shape[-1] == 3 and target.shape[-1] == 3
+        ns = int(source.shape[0])
+        dist = torch.empty((ns,), dtype=torch.float32, device=source.device) if want_pairs else None
+        idx = torch.empty((ns,), dtype=torch.int32, device=source.device) if want_pairs else None
+        h = (C.c_double * 17)()
+        sk = C.c_int(0)
+        _chk(lib().nsk_cloud_pair_sums(self.h, _ptr(source) if ns else None, ns, _ptr(target), int(target.shape[0]), _mat16(M),
+                                       C.c_float(threshold), h, _ptr(dist) if ns else None, _ptr(idx) if ns else None, C.byref(sk)))
+        self.last_skipped = int(sk.value)
+        sums = np.array(h[:], np.float64)
+        return (sums, dist, idx) if want_pairs else sums
+
+    @_ordered
+    def cloud_icp(self, source, target, threshold=0.1, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, init=None):
+        """nsk_cloud_icp: point-to-point ICP of source [ns, 3] onto target [nt, 3] (cuda float32) -> (M [4, 4] float64 numpy, info dict:
+        iterations, fitness, rmse, correspondences, converged, target_skipped, source_nonfinite, degenerate).  Synchronises."""
+        import numpy as np
+        import torch
+        assert source.dtype == torch.float32 and target.dtype == torch.float32 and source.shape[-1] == 3 and target.shape[-1] == 3
+        ns = int(source.shape[0])
+        M = (C.c_double * 16)()
+        info = (C.c_double * 8)()
+        _chk(lib().nsk_cloud_icp(self.h, _ptr(source) if ns else None, ns, _ptr(target), int(target.shape[0]), C.c_float(threshold), int(max_iter),
+                                 float(rel_fitness), float(rel_rmse), _mat16(init), M, info))
+        return np.array(M[:], np.float64).reshape(4, 4), dict(
+            iterations=int(info[0]), fitness=float(info[1]), rmse=float(info[2]), correspondences=int(info[3]), converged=bool(info[4]),
+            target_skipped=int(info[5]), source_nonfinite=int(info[6]), degenerate=bool(info[7]))
+
+    @_ordered
+    def cloud_transform(self, M, points, out=None):
+        """nsk_cloud_transform: points [n, 3] (cuda float32) under the 4x4 M -> a new tensor, or into out (out may be points itself)"""
+        import torch
+        assert points.dtype == torch.float32 and points.shape[-1] == 3
+        if out is None:
+            out = torch.empty_like(points)
+        assert out.dtype == torch.float32 and out.shape == points.shape
+        n = int(points.shape[0])
+        _chk(lib().nsk_cloud_transform(self.h, _mat16(M), _ptr(points) if n else None, n, _ptr(out) if n else None))
+        return out
+
+    def align_mesh(self, rec_verts, gt_verts, threshold=0.1, max_iter=30, n_points=0, rec_tris=None, gt_tris=None, seed=0):
+        """upstream's get_align_transformation: the rigid transform (M [4, 4] float64, info as cloud_icp) that registers the reconstruction
+        to the ground truth by point-to-point ICP from the identity.  n_points = 0 aligns the vertices, as upstream does; n_points > 0
+        aligns that many surface samples of each mesh (seed, seed + 1), for which the triangles must be given."""
+        if n_points > 0:
+            assert rec_tris is not None and gt_tris is not None, "align_mesh: surface samples need the triangles"
+            rec_verts = self.sample_mesh(rec_verts, rec_tris, n_points, seed)
+            gt_verts = self.sample_mesh(gt_verts, gt_tris, n_points, seed + 1)
+        return self.cloud_icp(rec_verts, gt_verts, threshold, max_iter)
+
+    def _aligned(self, rec_verts, gt_verts, threshold, max_iter):
+        M, info = self.align_mesh(rec_verts, gt_verts, threshold, max_iter)
+        return self.cloud_transform(M, rec_verts), dict(transform=M, icp_fitness=info["fitness"], icp_rmse=info["rmse"],
+                                                        icp_iterations=info["iterations"])
+
+    def recon_metrics(self, rec_verts, rec_tris, gt_verts, gt_tris, n=200000, threshold=0.05, seed=0, align=False, align_threshold=0.1,
+                      align_max_iter=30):
         """upstream's three 3D numbers of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors (what extract_mesh /
         filter_mesh return goes in directly): n samples of each surface (seed, seed + 1), nearest distances both ways, the means in cm and
-        the share of gt samples with a rec sample closer than threshold in %.  Coordinates are taken to be metres."""
+        the share of gt samples with a rec sample closer than threshold in %.  Coordinates are taken to be metres.  With align the
+        reconstruction's vertices are first registered to the ground truth's (align_mesh) and the transformed mesh is measured; the
+        result then also holds transform, icp_fitness, icp_rmse and icp_iterations."""
+        extra = {}
+        if align:
+            rec_verts, extra = self._aligned(rec_verts, gt_verts, align_threshold, align_max_iter)
         rec = self.sample_mesh(rec_verts, rec_tris, n, seed)
         rec_area, rec_deg = self.last_area, self.last_degenerate
         gt = self.sample_mesh(gt_verts, gt_tris, n, seed + 1)
@@ -478,7 +576,7 @@ class Context:
                     completion_ratio_pct=100.0 * comp["below"] / comp["count"] if comp["count"] else nan,
                     accuracy_max_cm=100.0 * acc["max"], completion_max_cm=100.0 * comp["max"],
                     rec_area=rec_area, gt_area=gt_area, rec_degenerate=rec_deg, gt_degenerate=gt_deg,
-                    rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold))
+                    rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold), **extra)
 
     @_ordered
     def mesh_depth(self, verts, tris, w2c, H, W, fx, fy, cx, cy, want_skipped=False):
@@ -527,13 +625,18 @@ class Context:
         return w
 
     def recon_depth_l1(self, rec_verts, rec_tris, gt_verts, gt_tris, n_views=1000, HW=(500, 500), focal=300.0, seed=0, shrink=0.7,
-                       min_cover=0.0):
+                       min_cover=0.0, align=False, align_threshold=0.1, align_max_iter=30):
         """upstream's Depth L1 of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors: both meshes rendered as
         depth images from the same n_views random views inside the ground truth's box (depth_views), cx = W / 2 - 0.5, cy = H / 2 - 0.5;
         depth_l1_cm = 100 x the mean over the used views of sum |gt - rec| / n_pix.  A view is used when the ground truth covers at least
         min_cover of its pixels (0: every view, upstream's plain mean).  Also: n_used, restricted_l1_cm (the mean over the pixels of the
-        used views where both meshes are hit) and the per-view arrays view_l1 (m), view_cover, stats [n_views, 4], w2c."""
+        used views where both meshes are hit) and the per-view arrays view_l1 (m), view_cover, stats [n_views, 4], w2c.  With align the
+        reconstruction's vertices are first registered to the ground truth's (align_mesh) and the transformed mesh is rendered; the result
+        then also holds transform, icp_fitness, icp_rmse and icp_iterations."""
         import numpy as np
+        extra = {}
+        if align:
+            rec_verts, extra = self._aligned(rec_verts, gt_verts, align_threshold, align_max_iter)
         H, W = int(HW[0]), int(HW[1])
         n_pix = H * W
         w2c = self.depth_views(gt_verts, n_views, seed, shrink)
@@ -556,7 +659,8 @@ class Context:
         nan = float("nan")
         return dict(depth_l1_cm=100.0 * l1 / n_used if n_used else nan, n_used=n_used,
                     restricted_l1_cm=100.0 * both_sum / both if both else nan, view_l1=view_l1, view_cover=cover, stats=stats, w2c=w2c,
-                    n_views=int(n_views), H=H, W=W, focal=float(focal), seed=int(seed), shrink=float(shrink), min_cover=float(min_cover))
+                    n_views=int(n_views), H=H, W=W, focal=float(focal), seed=int(seed), shrink=float(shrink), min_cover=float(min_cover),
+                    **extra)
 
     @_ordered
     def eval_points(self, stage, pts):
