@@ -10,6 +10,7 @@
 #include "nsk_icp.h"
 #include "nsk_rigid.h"
 #include "nsk_raster.h"
+#include "nsk_reduce.h"
 #include "nsk_buf.h"
 #include "nsk_split.h"
 
@@ -849,29 +850,26 @@ struct nsk_ctx {
         Buf<CcStats> cc_stats;
         Buf<float> verts2; Buf<int> tris2;
     } mesh;
-    // whole-frame rendering (nsk_render_image / nsk_image_metrics): the rays of the chunk being rendered, the metrics' partial rows and results
+    // row reductions (rows_reduce): [groups][rows][columns] partial rows of the call in flight, then its [groups][columns] results
+    Buf<double> rows;
+    // whole-frame rendering (nsk_render_image): the rays of the chunk being rendered
     struct Image {
         Buf<float> ro, rd, gd;                               // [chunk][3], [chunk][3], [chunk]: one group
-        Buf<double> rows;                                    // [IMG_MAX_ROWS][IMG_COLS] + 8 results
     } img;
     // reconstruction metrics (nsk_mesh_sample / nsk_cloud_nearest / nsk_cloud_stats): scratch that grows to the largest call and stays
     struct Cloud {
         Buf<double> cum, bsum;                               // [triangles] cumulative areas, [workgroups] their totals
         Buf<unsigned> degenerate;
-        Buf<float> box;                                      // [CLOUD_MAX_ROWS][8] partial boxes + the 8 results
         Buf<unsigned> tcell, start, cursor; Buf<float4> sorted;      // targets: [n] cells, [cells + 1 + scan levels], [cells], [n] in cell order
         Buf<unsigned> qcell, qstart, qcursor, qperm;         // queries in cell order (the same grid)
-        Buf<double> rows;                                    // [CLOUD_MAX_ROWS][4] partial sums + the 4 results
-        Buf<double> icp_rows;                                // nsk_cloud_pair_sums / nsk_cloud_icp: [CLOUD_MAX_ROWS][ICP_COLS] partial sums + the results
         Buf<float> icp_dist; Buf<int> icp_index;             // [sources] the correspondences, when the caller keeps none
         int cells_x4 = 4;                                    // nsk_set_tuning "cloud_cells_x4": grid cells aimed at per finite target, in quarters
         int query_mode = 0;                                  // nsk_set_tuning "cloud_query_mode": bit 0 a wave per query; + 2 queries always in input order, + 4 always in cell order (neither: by size)
     } cloud;
-    // mesh depth views (nsk_mesh_depth / nsk_depth_pair_stats): the queue of large pixel boxes, its cursor and the skipped count, the sums
+    // mesh depth views (nsk_mesh_depth): the queue of large pixel boxes, its cursor and the skipped count
     struct Raster {
         Buf<RasterJob> queue;                                // [queue_cap] (view, triangle, box) entries of the launch in flight
         Buf<unsigned> counters;                              // [0] the queue's cursor, [1] triangles with an index out of range
-        Buf<double> rows;                                    // [V][RASTER_STAT_ROWS][4] partial sums, then the [V][4] results
         int inline_max = 64;                                 // nsk_set_tuning "raster_inline_max": a box of more pixels is queued
         int queue_cap = 1 << 18;                             // nsk_set_tuning "raster_queue_cap": entries (24 B each)
         int load_first = 1;                                  // nsk_set_tuning "raster_load_first": a plain load in front of the atomic minimum
@@ -967,6 +965,26 @@ static int grow(nsk_ctx* c, Buf<T>& b, size_t n, const char* what, unsigned flag
     if (n <= b.cap()) return 0;
     CHK(grow_begin(c, flags));
     return dev_alloc(b, n, what);
+}
+
+// A row reduction (nsk_reduce.h) of `groups` sets of n elements each: min(ceil(n / block), cap) rows per group -- a function of n alone --
+// in the context's one scratch, launch(nrows, rows) the caller's partial-rows kernel, the finisher, groups * Cols::N doubles back to the
+// host.  Synchronises, so the scratch is free again when it returns.
+template <class Cols, class Launch>
+static int rows_reduce(nsk_ctx* c, const char* name, const char* what, int groups, long long n, int block, int cap, Launch launch, double* h_out)
+{
+    const int nrows = (int)std::min<long long>((n + block - 1) / block, cap);
+    const size_t nout = (size_t)groups * Cols::N;
+    CHK(grow(c, c->rows, (size_t)groups * (cap + 1) * Cols::N, what, GROW_NO_CAPTURE));
+    double* rows = c->rows;
+    double* out = rows + (size_t)nrows * nout;
+    { ProfScope ps(c, name);
+      launch(nrows, rows);
+      k_rows_finish<Cols><<<(unsigned)((nout + 255) / 256), 256, 0, c->stream>>>(groups, nrows, rows, out); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, out, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 extern "C" const char* nsk_last_error(void) { return g_err.c_str(); }
@@ -3075,16 +3093,14 @@ extern "C" int nsk_image_metrics(nsk_ctx* c, int Hv, int Wv, const float* d_rgb,
     if (d_res_color && !d_gt_color) return fail("nsk_image_metrics: d_res_color asked for without d_gt_color");
     if (c->capturing) return fail("nsk_image_metrics: not while a graph is being captured");
     HIPCHK(hipSetDevice(c->device));
-    const int n = Hv * Wv, nrows = std::min((n + 255) / 256, IMG_MAX_ROWS);
-    CHK(grow(c, c->img.rows, (size_t)IMG_MAX_ROWS * IMG_COLS + 8, "the metrics' partial sums", GROW_NO_CAPTURE));
-    double* rows = c->img.rows;
-    double* out = rows + (size_t)IMG_MAX_ROWS * IMG_COLS;
-    { ProfScope ps(c, "image_metrics");
-      k_image_metrics<<<nrows, 256, 0, c->stream>>>(n, d_rgb, d_depth, d_gt_depth, d_gt_color, d_res_depth, d_res_color, rows);
-      k_image_metrics_sum<<<1, 64, 0, c->stream>>>(nrows, n, rows, out); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_out, out, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const int n = Hv * Wv;
+    double cols[IMG_COLS];
+    CHK(rows_reduce<RowSums<IMG_COLS>>(c, "image_metrics", "the metrics' partial sums", 1, n, 256, IMG_MAX_ROWS, [&](int nrows, double* rows) {
+        k_image_metrics<<<nrows, 256, 0, c->stream>>>(n, d_rgb, d_depth, d_gt_depth, d_gt_color, d_res_depth, d_res_color, rows); }, cols));
+    // h_out: 0 pixels, 1 depth pixels, 2 depth sum, 3 colour components, 4 colour sum, 5 non-finite pixels, 6 / 7 spare
+    h_out[0] = (double)n;
+    for (int k = 0; k < 4; ++k) h_out[1 + k] = cols[k];
+    h_out[5] = cols[4]; h_out[6] = h_out[7] = 0.0;
     return 0;
 }
 
@@ -3162,24 +3178,25 @@ static CloudGrid cloud_grid(const float* box, unsigned nfinite, int cells_x4)
     return G;
 }
 
+// the box {min x y z, max x y z} of the finite points and their number (one synchronisation)
+static int cloud_box(nsk_ctx* c, const float* d_pts, int n, float box[6], unsigned& nfinite)
+{
+    double cols[7];
+    CHK(rows_reduce<CloudBoxCols>(c, "cloud_box", "the partial boxes", 1, n, CLOUD_BLOCK, CLOUD_MAX_ROWS, [&](int nrows, double* rows) {
+        k_cloud_box<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n, d_pts, rows); }, cols));
+    for (int k = 0; k < 6; ++k) box[k] = (float)cols[k];     // (floats widened by the kernel: the same floats)
+    nfinite = (unsigned)cols[6];
+    return 0;
+}
+
 // nsk_cloud_nearest in two halves, so that nsk_cloud_icp builds the targets' grid once and queries it at every evaluation.
 struct CloudBuilt { CloudGrid G; size_t cells = 0, words = 0; unsigned nfinite = 0; };
 // the box (one synchronisation) and, with `place`, the grid: cells -> scan -> placement into c->cloud.start / sorted
 static int cloud_build(nsk_ctx* c, const float* d_target, int n_target, bool place, CloudBuilt& B)
 {
     nsk_ctx::Cloud& K = c->cloud;
-    // pass 1: the box
-    const int nrows = (int)std::min<long long>(((long long)n_target + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
-    CHK(grow(c, K.box, (size_t)CLOUD_MAX_ROWS * 8 + 8, "the partial boxes", GROW_NO_CAPTURE));
-    float* box_out = K.box.get() + (size_t)CLOUD_MAX_ROWS * 8;
-    float box[8];
-    { ProfScope ps(c, "cloud_box");
-      k_cloud_box<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n_target, d_target, K.box);
-      k_cloud_box_sum<<<1, 64, 0, c->stream>>>(nrows, K.box, box_out);
-      HIPCHK(hipGetLastError()); }
-    HIPCHK(hipMemcpyAsync(box, box_out, sizeof(box), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(&B.nfinite, &box[6], 4);
+    float box[6];
+    CHK(cloud_box(c, d_target, n_target, box, B.nfinite));                                                     // pass 1
     if (!place) return 0;
     B.G = cloud_grid(box, B.nfinite, K.cells_x4);
     B.cells = (size_t)B.G.dim[0] * B.G.dim[1] * B.G.dim[2]; B.words = mc_scan_words(B.cells + 1);
@@ -3264,17 +3281,8 @@ extern "C" int nsk_cloud_stats(nsk_ctx* c, const float* d_dist, int n, float thr
     for (int k = 0; k < 4; ++k) h_out[k] = 0.0;
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    const int nrows = (int)std::min<long long>(((long long)n + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
-    CHK(grow(c, c->cloud.rows, (size_t)CLOUD_MAX_ROWS * 4 + 4, "the distance sums of the workgroups", GROW_NO_CAPTURE));
-    double* rows = c->cloud.rows;
-    double* out = rows + (size_t)CLOUD_MAX_ROWS * 4;
-    { ProfScope ps(c, "cloud_stats");
-      k_cloud_stats<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n, d_dist, threshold, rows);
-      k_cloud_stats_sum<<<1, 64, 0, c->stream>>>(nrows, rows, out); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_out, out, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return rows_reduce<CloudStatCols>(c, "cloud_stats", "the distance sums of the workgroups", 1, n, CLOUD_BLOCK, CLOUD_MAX_ROWS,
+                                      [&](int nrows, double* rows) { k_cloud_stats<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n, d_dist, threshold, rows); }, h_out);
 }
 
 // ---- alignment: point-to-point ICP (nsk_icp.h, nsk_rigid.h) ------------------------------------------------------------------------
@@ -3287,18 +3295,9 @@ static void cloud_xform_of(const double* h_M, CloudXform& X)
 static int cloud_pair_eval(nsk_ctx* c, const CloudBuilt& B, const float* d_source, int n_source, const float* d_target, const CloudXform& X,
                            float threshold, float* d_dist, int32_t* d_index, double* h_cols)
 {
-    nsk_ctx::Cloud& K = c->cloud;
     CHK(cloud_query(c, B, d_source, n_source, &X, d_dist, d_index));
-    const int nrows = (int)std::min<long long>(((long long)n_source + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
-    double* rows = K.icp_rows;
-    double* out = rows + (size_t)CLOUD_MAX_ROWS * ICP_COLS;
-    { ProfScope ps(c, "icp_sums");
-      k_icp_sums<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(X, n_source, d_source, d_dist, d_index, d_target, threshold, rows);
-      k_icp_sums_sum<<<1, 64, 0, c->stream>>>(nrows, rows, out);
-      HIPCHK(hipGetLastError()); }
-    HIPCHK(hipMemcpyAsync(h_cols, out, ICP_COLS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return rows_reduce<RowSums<ICP_COLS>>(c, "icp_sums", "the pair sums of the workgroups", 1, n_source, CLOUD_BLOCK, CLOUD_MAX_ROWS, [&](int nrows, double* rows) {
+        k_icp_sums<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(X, n_source, d_source, d_dist, d_index, d_target, threshold, rows); }, h_cols);
 }
 // the arguments both entry points share, the grid (once) and the buffers of an evaluation
 static int cloud_pair_setup(nsk_ctx* c, const char* who, const float* d_source, int n_source, const float* d_target, int n_target, float threshold,
@@ -3314,7 +3313,6 @@ static int cloud_pair_setup(nsk_ctx* c, const char* who, const float* d_source, 
     HIPCHK(hipSetDevice(c->device));
     nsk_ctx::Cloud& K = c->cloud;
     if (n_source > 0) {
-        CHK(grow(c, K.icp_rows, (size_t)CLOUD_MAX_ROWS * ICP_COLS + ICP_COLS, "the pair sums of the workgroups", GROW_NO_CAPTURE));
         if (!*d_dist) { CHK(grow(c, K.icp_dist, (size_t)n_source, "the correspondences' distances", GROW_NO_CAPTURE)); *d_dist = K.icp_dist; }
         if (!*d_index) { CHK(grow(c, K.icp_index, (size_t)n_source, "the correspondences", GROW_NO_CAPTURE)); *d_index = K.icp_index; }
     }
@@ -3468,17 +3466,8 @@ extern "C" int nsk_depth_pair_stats(nsk_ctx* c, const float* d_a, const float* d
     if (!d_a || !d_b || !h_out) return fail("nsk_depth_pair_stats: d_a / d_b / h_out is NULL");
     if (c->capturing) return fail("nsk_depth_pair_stats: not while a graph is being captured");
     HIPCHK(hipSetDevice(c->device));
-    const int R = std::min((n_pix + RASTER_BLOCK - 1) / RASTER_BLOCK, RASTER_STAT_ROWS);
-    CHK(grow(c, c->raster.rows, (size_t)V * (RASTER_STAT_ROWS + 1) * 4, "the depth sums of the workgroups", GROW_NO_CAPTURE));
-    double* rows = c->raster.rows;
-    double* out = rows + (size_t)V * RASTER_STAT_ROWS * 4;
-    { ProfScope ps(c, "depth_stats");
-      k_depth_pair_stats<<<(unsigned)((size_t)V * R), RASTER_BLOCK, 0, c->stream>>>(n_pix, R, d_a, d_b, rows);
-      k_depth_pair_stats_sum<<<(4 * V + RASTER_BLOCK - 1) / RASTER_BLOCK, RASTER_BLOCK, 0, c->stream>>>(V, R, rows, out); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_out, out, (size_t)V * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return rows_reduce<RowSums<4>>(c, "depth_stats", "the depth sums of the workgroups", V, n_pix, RASTER_BLOCK, RASTER_STAT_ROWS, [&](int R, double* rows) {
+        k_depth_pair_stats<<<(unsigned)((size_t)V * R), RASTER_BLOCK, 0, c->stream>>>(n_pix, R, d_a, d_b, rows); }, h_out);
 }
 
 // the counter hash of nsk_sample_pixels on the host (hash_u32 of nsk_device.h, which is device code)
@@ -3526,20 +3515,11 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
         if (n_vertices < 1) return fail("nsk_depth_views: no vertex");
         if (c->capturing) return fail("nsk_depth_views: not while a graph is being captured");
         HIPCHK(hipSetDevice(c->device));
-        nsk_ctx::Cloud& K = c->cloud;
-        const int nrows = (int)std::min<long long>(((long long)n_vertices + CLOUD_BLOCK - 1) / CLOUD_BLOCK, CLOUD_MAX_ROWS);
-        CHK(grow(c, K.box, (size_t)CLOUD_MAX_ROWS * 8 + 8, "the partial boxes", GROW_NO_CAPTURE));
-        float* box_out = K.box.get() + (size_t)CLOUD_MAX_ROWS * 8;
-        float box[8];
-        { ProfScope ps(c, "cloud_box");
-          k_cloud_box<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n_vertices, d_vertices, K.box);
-          k_cloud_box_sum<<<1, 64, 0, c->stream>>>(nrows, K.box, box_out);
-          HIPCHK(hipGetLastError()); }
-        HIPCHK(hipMemcpyAsync(box, box_out, sizeof(box), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        unsigned nfinite; memcpy(&nfinite, &box[6], 4);
+        float box[6];
+        unsigned nfinite;
+        CHK(cloud_box(c, d_vertices, n_vertices, box, nfinite));
         if (!nfinite) return fail("nsk_depth_views: no vertex with finite coordinates");
-        memcpy(h_box, box, 6 * sizeof(float));
+        memcpy(h_box, box, sizeof(box));
     }
     double lo[3], ext[3], ctr[3];
     for (int a = 0; a < 3; ++a) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "nsk_reduce.h"
 
 #define CLOUD_BLOCK 256
 #define CLOUD_MAX_CELLS (1 << 22)
@@ -11,28 +12,11 @@
 #define CLOUD_ORDER_MIN (1 << 19)            // queries from which on they are visited in cell order
 #define CLOUD_CELL_CLAMP 268435456.f        // 2^28: an unclamped query cell plus a shell radius stays inside an int
 
-__device__ __forceinline__ bool cloud_finite(float x) { return fabsf(x) < __builtin_inff(); }      // false for NaN and +-inf
 // the correctly rounded fp32 square root: the fp64 root is correctly rounded, and rounding it again to 24 bits cannot differ from rounding
 // the exact root (53 >= 2 * 24 + 2).  (__fsqrt_rn is the native instruction here, 1 ulp.)
 __device__ __forceinline__ float cloud_sqrt_rn(float x) { return (float)sqrt((double)x); }
 
 // ---- mesh sampling ----------------------------------------------------------------------------------------------------------------
-// inclusive scan of one double per thread over the 256 threads of a workgroup (lanes by shuffles, the four waves in wave order)
-__device__ __forceinline__ double cloud_block_scan_f64(double v, double* total)
-{
-    __shared__ double wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const double t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    double base = 0.0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    return base + inc;
-}
-
 // A_t = 0.5 |(b - a) x (c - a)| in double from the float32 vertices; not finite, not positive or an index outside [0, nv): area 0, counted.
 // cum[t] = the inclusive sum inside the workgroup, bsum[workgroup] = its total
 __global__ __launch_bounds__(CLOUD_BLOCK) void k_tri_area(int nv, int nt, const float* __restrict__ verts, const int* __restrict__ tris,
@@ -59,7 +43,7 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_tri_area(int nv, int nt, const 
     const unsigned long long b = __ballot(bad);
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(degenerate, (unsigned)__popcll(b));         // (an integer count: any order, the same number)
     double total;
-    const double inc = cloud_block_scan_f64(area, &total);
+    const double inc = block_scan(area, &total);
     if (t < nt) cum[t] = inc;
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
@@ -139,52 +123,21 @@ __device__ __forceinline__ int cloud_cell_axis(float x, float lo, float h, float
     return g;
 }
 
-// pass 1: box of the finite points and their number.  rows[workgroup] = {min x y z, max x y z, count}; min / max do not depend on the order
-__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_box(int n, const float* __restrict__ pts, float* __restrict__ rows)
+// pass 1: box of the finite points and their number.  rows[workgroup] = {min x y z, max x y z, count}: the extrema widen to double exactly
+struct CloudBoxCols { static constexpr int N = 7; static constexpr RowOp op(int k) { return k < 3 ? ROW_MIN : (k < 6 ? ROW_MAX : ROW_SUM); } };
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_box(int n, const float* __restrict__ pts, double* __restrict__ rows)
 {
-    __shared__ float sh[4][7];
     const float inf = __builtin_inff();
     float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf}, cnt = 0.f;
     for (long long p = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x; p < n; p += (long long)gridDim.x * CLOUD_BLOCK) {
         const float x = pts[3 * (size_t)p], y = pts[3 * (size_t)p + 1], z = pts[3 * (size_t)p + 2];
-        if (!(cloud_finite(x) && cloud_finite(y) && cloud_finite(z))) continue;
+        if (!(finite_f32(x) && finite_f32(y) && finite_f32(z))) continue;
         mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
         mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
         cnt += 1.f;                                             // (a lane sees at most n / 256 < 2^24 points: exact)
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        float* s = sh[threadIdx.x >> 6];
-        s[0] = mn[0]; s[1] = mn[1]; s[2] = mn[2]; s[3] = mx[0]; s[4] = mx[1]; s[5] = mx[2];
-    }
-    // the count as an integer through the ballots of the finite lanes would need the loop's structure; a double sum of exact floats is exact too
-    double c = (double)cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    __shared__ double shc[4];
-    if ((threadIdx.x & 63) == 0) shc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x < 3) rows[(size_t)blockIdx.x * 8 + threadIdx.x] = fminf(fminf(sh[0][threadIdx.x], sh[1][threadIdx.x]), fminf(sh[2][threadIdx.x], sh[3][threadIdx.x]));
-    else if (threadIdx.x < 6) rows[(size_t)blockIdx.x * 8 + threadIdx.x] = fmaxf(fmaxf(sh[0][threadIdx.x], sh[1][threadIdx.x]), fmaxf(sh[2][threadIdx.x], sh[3][threadIdx.x]));
-    else if (threadIdx.x == 6) reinterpret_cast<unsigned*>(rows)[(size_t)blockIdx.x * 8 + 6] = (unsigned)(((shc[0] + shc[1]) + shc[2]) + shc[3]);
-}
-__global__ __launch_bounds__(64) void k_cloud_box_sum(int nrows, const float* __restrict__ rows, float* __restrict__ out)
-{
-    const int k = threadIdx.x;
-    if (k >= 7) return;
-    if (k == 6) {
-        unsigned s = 0;
-        for (int r = 0; r < nrows; ++r) s += reinterpret_cast<const unsigned*>(rows)[(size_t)r * 8 + 6];
-        reinterpret_cast<unsigned*>(out)[6] = s;
-        return;
-    }
-    float v = rows[k];
-    for (int r = 1; r < nrows; ++r) v = k < 3 ? fminf(v, rows[(size_t)r * 8 + k]) : fmaxf(v, rows[(size_t)r * 8 + k]);
-    out[k] = v;
+    const double acc[7] = {(double)mn[0], (double)mn[1], (double)mn[2], (double)mx[0], (double)mx[1], (double)mx[2], (double)cnt};
+    rows_store<CloudBoxCols>(acc, rows + (size_t)blockIdx.x * 7);
 }
 
 // pass 2: the cell of every point (x fastest) and the histogram.  A target with a non-finite component gets no cell
@@ -195,7 +148,7 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_cells(CloudGrid G, int n,
     const long long p = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
     if (p >= n) return;
     const float x = pts[3 * (size_t)p], y = pts[3 * (size_t)p + 1], z = pts[3 * (size_t)p + 2];
-    if (!keep_nonfinite && !(cloud_finite(x) && cloud_finite(y) && cloud_finite(z))) { cell[p] = CLOUD_NO_CELL; return; }
+    if (!keep_nonfinite && !(finite_f32(x) && finite_f32(y) && finite_f32(z))) { cell[p] = CLOUD_NO_CELL; return; }
     const int cx = cloud_cell_axis(x, G.lo[0], G.h, G.inv_h, G.dim[0]), cy = cloud_cell_axis(y, G.lo[1], G.h, G.inv_h, G.dim[1]),
               cz = cloud_cell_axis(z, G.lo[2], G.h, G.inv_h, G.dim[2]);
     const unsigned id = ((unsigned)cz * G.dim[1] + cy) * G.dim[0] + cx;
@@ -242,6 +195,7 @@ template <int LANES>
 __device__ __forceinline__ CloudBest cloud_walk(const CloudGrid& G, const float (&q)[3], int lane, const unsigned* __restrict__ start,
                                                 const float4* __restrict__ sorted4)
 {
+    static_assert(LANES == 1 || LANES == 64, "a thread or a wave per query");
     int c[3], r = 0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -273,13 +227,8 @@ __device__ __forceinline__ CloudBest cloud_walk(const CloudGrid& G, const float 
                     for (unsigned p = start[row + xa] + lane; p < e; p += LANES) cloud_try(B, q[0], q[1], q[2], sorted4[p]);
                 }
             }
-        if (LANES > 1) {
-#pragma unroll
-            for (int o = LANES / 2; o > 0; o >>= 1) {
-                const float od = __shfl_xor(B.d2, o, 64); const int oi = __shfl_xor(B.idx, o, 64);
-                if (od < B.d2 || (od == B.d2 && oi < B.idx)) { B.d2 = od; B.idx = oi; }
-            }
-        }
+        if (LANES > 1)
+            B = wave_all(B, [](CloudBest a, CloudBest b) { return b.d2 < a.d2 || (b.d2 == a.d2 && b.idx < a.idx) ? b : a; });
         float m = __builtin_inff();
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -297,7 +246,7 @@ template <int LANES>
 __device__ __forceinline__ void cloud_answer(const CloudGrid& G, const float (&q)[3], int lane, const unsigned* __restrict__ start,
                                              const float4* __restrict__ sorted4, size_t qi, float* __restrict__ dist, int* __restrict__ index)
 {
-    if (!(cloud_finite(q[0]) && cloud_finite(q[1]) && cloud_finite(q[2]))) {
+    if (!(finite_f32(q[0]) && finite_f32(q[1]) && finite_f32(q[2]))) {
         if (lane == 0) { dist[qi] = __builtin_nanf(""); if (index) index[qi] = -1; }
         return;
     }
@@ -322,38 +271,17 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_query(CloudGrid G, int nq
 }
 
 // ---- the reductions (nsk_cloud_stats) --------------------------------------------------------------------------------------------------
-// per workgroup one row {sum of the finite distances, their number, those below the threshold, the largest}: a lane adds its entries in
-// index order, the lanes of a wave meet by xor shuffles, the waves through LDS in wave order, k_cloud_stats_sum adds the rows in index
-// order; the grid is a function of n alone.  No floating-point atomics
+// per workgroup one row {sum of the finite distances, their number, those below the threshold, the largest}, in the association of nsk_reduce.h
+struct CloudStatCols { static constexpr int N = 4; static constexpr RowOp op(int k) { return k == 3 ? ROW_MAX : ROW_SUM; } };
 __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_stats(int n, const float* __restrict__ dist, float threshold, double* __restrict__ rows)
 {
-    __shared__ double sh[4][4];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (long long p = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x; p < n; p += (long long)gridDim.x * CLOUD_BLOCK) {
         const float d = dist[p];
-        if (!cloud_finite(d)) continue;
+        if (!finite_f32(d)) continue;
         acc[0] += (double)d; acc[1] += 1.0;
         if (d < threshold) acc[2] += 1.0;
         acc[3] = fmax(acc[3], (double)d);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] += __shfl_xor(acc[k], o);
-        acc[3] = fmax(acc[3], __shfl_xor(acc[3], o));
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; ++k) sh[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < 3) rows[(size_t)blockIdx.x * 4 + k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
-    else if (k == 3) rows[(size_t)blockIdx.x * 4 + 3] = fmax(fmax(sh[0][3], sh[1][3]), fmax(sh[2][3], sh[3][3]));
-}
-__global__ __launch_bounds__(64) void k_cloud_stats_sum(int nrows, const double* __restrict__ rows, double* __restrict__ out)
-{
-    const int k = threadIdx.x;
-    if (k >= 4) return;
-    double s = 0.0;
-    for (int r = 0; r < nrows; ++r) s = k < 3 ? s + rows[(size_t)r * 4 + k] : fmax(s, rows[(size_t)r * 4 + 3]);
-    out[k] = s;
+    rows_store<CloudStatCols>(acc, rows + (size_t)blockIdx.x * 4);
 }

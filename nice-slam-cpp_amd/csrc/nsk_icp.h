@@ -17,7 +17,7 @@ struct CloudXform { double m[12]; };
 __device__ __forceinline__ void cloud_xform(const CloudXform& X, float x, float y, float z, float (&out)[3])
 {
 #pragma clang fp contract(off)
-    if (!(cloud_finite(x) && cloud_finite(y) && cloud_finite(z))) { out[0] = x; out[1] = y; out[2] = z; return; }
+    if (!(finite_f32(x) && finite_f32(y) && finite_f32(z))) { out[0] = x; out[1] = y; out[2] = z; return; }
     const double dx = (double)x, dy = (double)y, dz = (double)z;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -68,21 +68,19 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_icp_query(CloudGrid G, CloudXfo
 // The pair sums: source p counts when its transformed point s' is finite and d <= threshold (inclusive, on the fp32 distance; NaN and the
 // +inf of "no finite target" fail it).  Columns: [0] the count, [1] sum d d (the fp32 d widened, squared in double), [2..4] sum s',
 // [5..7] sum t, [8..16] sum s'_a t_b (fp32 values widened, products in double), [17] the sources with s' not finite.  The association is
-// k_cloud_stats': a lane adds its sources in index order, lanes meet by xor shuffles, waves through LDS in wave order, one row per
-// workgroup, k_icp_sums_sum adds the rows in index order; the grid is a function of n alone.  No floating-point atomics
+// that of nsk_reduce.h
 __global__ __launch_bounds__(CLOUD_BLOCK) void k_icp_sums(CloudXform X, int n, const float* __restrict__ src, const float* __restrict__ dist,
                                                          const int* __restrict__ index, const float* __restrict__ target, float threshold,
                                                          double* __restrict__ rows)
 {
 #pragma clang fp contract(off)
-    __shared__ double sh[4][ICP_COLS];
     double acc[ICP_COLS];
 #pragma unroll
     for (int k = 0; k < ICP_COLS; ++k) acc[k] = 0.0;
     for (long long p = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x; p < n; p += (long long)gridDim.x * CLOUD_BLOCK) {
         float s[3];
         cloud_xform(X, src[3 * (size_t)p], src[3 * (size_t)p + 1], src[3 * (size_t)p + 2], s);
-        if (!(cloud_finite(s[0]) && cloud_finite(s[1]) && cloud_finite(s[2]))) { acc[17] += 1.0; continue; }
+        if (!(finite_f32(s[0]) && finite_f32(s[1]) && finite_f32(s[2]))) { acc[17] += 1.0; continue; }
         const float d = dist[p];
         const int j = index[p];
         if (j < 0 || !(d <= threshold)) continue;
@@ -99,24 +97,5 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_icp_sums(CloudXform X, int n, c
             for (int b = 0; b < 3; ++b) acc[8 + 3 * a + b] += sv[a] * tv[b];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < ICP_COLS; ++k) acc[k] += __shfl_xor(acc[k], o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < ICP_COLS; ++k) sh[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < ICP_COLS) rows[(size_t)blockIdx.x * ICP_COLS + k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
-}
-__global__ __launch_bounds__(64) void k_icp_sums_sum(int nrows, const double* __restrict__ rows, double* __restrict__ out)
-{
-    const int k = threadIdx.x;
-    if (k >= ICP_COLS) return;
-    double s = 0.0;
-    for (int r = 0; r < nrows; ++r) s += rows[(size_t)r * ICP_COLS + k];
-    out[k] = s;
+    rows_store<RowSums<ICP_COLS>>(acc, rows + (size_t)blockIdx.x * ICP_COLS);
 }

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "nsk_reduce.h"
 
 // defined in nsk.hip (quad2rotation / get_camera_from_tensor); the same body serves k_rays_from_camera and k_prepare_rays
 __device__ __forceinline__ void camera_matrix(const float* cam, float* c2w);
@@ -53,36 +54,25 @@ __global__ __launch_bounds__(256) void k_image_rays(ImgView V, const float* __re
 
 // ---- metrics ---------------------------------------------------------------------------------------------------------------------
 // Per workgroup one row of IMG_COLS doubles: [0] pixels that take part in the depth sum, [1] their sum |gt - d|, [2] colour components
-// that take part, [3] their sum (gt_c - c)^2, [4] pixels with a non-finite rendered value.  No floating-point atomics anywhere: a lane adds
-// its pixels in index order, the 64 lanes of a wave meet by xor shuffles, the four waves through LDS in wave order, and k_image_metrics_sum
-// adds the rows in index order -- the grid is a function of the pixel count alone, so two runs add in the same order.
+// that take part, [3] their sum (gt_c - c)^2, [4] pixels with a non-finite rendered value.  The association is that of nsk_reduce.h.
 #define IMG_COLS 5
 #define IMG_MAX_ROWS 1024
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ bool img_finite(float x) { return fabsf(x) < __builtin_inff(); }       // false for NaN and +-inf
 
 __global__ __launch_bounds__(256) void k_image_metrics(int n, const float* __restrict__ rgb, const float* __restrict__ depth,
                                                        const float* __restrict__ gt_d, const float* __restrict__ gt_c,
                                                        float* __restrict__ res_d, float* __restrict__ res_c, double* __restrict__ rows)
 {
-    __shared__ double sh[4][IMG_COLS];
     double acc[IMG_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (unsigned p = blockIdx.x * 256 + threadIdx.x; p < (unsigned)n; p += gridDim.x * 256) {      // (n <= 2^30: no wrap)
         const float d = depth[p];
         const float c0 = rgb[3 * (size_t)p], c1 = rgb[3 * (size_t)p + 1], c2 = rgb[3 * (size_t)p + 2];
-        const bool good = img_finite(d) && img_finite(c0) && img_finite(c1) && img_finite(c2);
+        const bool good = finite_f32(d) && finite_f32(c0) && finite_f32(c1) && finite_f32(c2);
         if (!good) acc[4] += 1.0;
         if (gt_d) {
             const float g = gt_d[p];
             const float r = g > 0.f ? fabsf(sub_rn(g, d)) : 0.f;          // the visualiser's rule: no measurement, no residual
             if (res_d) res_d[p] = r;
-            if (good && g > 0.f && img_finite(r)) { acc[0] += 1.0; acc[1] += (double)r; }
+            if (good && g > 0.f && finite_f32(r)) { acc[0] += 1.0; acc[1] += (double)r; }
         }
         if (gt_c) {
             const float c[3] = {c0, c1, c2};
@@ -90,27 +80,9 @@ __global__ __launch_bounds__(256) void k_image_metrics(int n, const float* __res
             for (int a = 0; a < 3; ++a) {
                 const float r = fabsf(sub_rn(gt_c[3 * (size_t)p + a], c[a]));
                 if (res_c) res_c[3 * (size_t)p + a] = r;
-                if (good && img_finite(r)) { acc[2] += 1.0; acc[3] += (double)r * (double)r; }
+                if (good && finite_f32(r)) { acc[2] += 1.0; acc[3] += (double)r * (double)r; }
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < IMG_COLS; ++k) {
-        const double s = wave_sum_f64(acc[k]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < IMG_COLS) rows[(size_t)blockIdx.x * IMG_COLS + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-// one workgroup: lane k adds column k of the rows in index order and writes the call's eight results
-__global__ __launch_bounds__(64) void k_image_metrics_sum(int nrows, int n, const double* __restrict__ rows, double* __restrict__ out)
-{
-    const int k = threadIdx.x;
-    if (k >= 8) return;
-    double s = 0.0;
-    if (k < IMG_COLS) for (int r = 0; r < nrows; ++r) s += rows[(size_t)r * IMG_COLS + k];
-    // h_out: 0 pixels, 1 depth pixels, 2 depth sum, 3 colour components, 4 colour sum, 5 non-finite pixels, 6 / 7 spare
-    const int dst = k < 4 ? k + 1 : (k == 4 ? 5 : (k == 5 ? 0 : k));
-    out[dst] = k < IMG_COLS ? s : (k == 5 ? (double)n : 0.0);
+    rows_store<RowSums<IMG_COLS>>(acc, rows + (size_t)blockIdx.x * IMG_COLS);
 }

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstring>
+#include "nsk_reduce.h"
 
 #define MC_ROW 16                   // table row stride in edge numbers: the largest case has 5 triangles (tests/test_mesh_cpu.py asserts it)
 #define MC_BLOCK 256                // nodes per workgroup of the extraction passes, elements per workgroup of the scan passes
@@ -132,23 +133,6 @@ __global__ __launch_bounds__(256) void k_lattice_finish(int cnt, const float* __
     vol[m] = inb ? occ : 100.f;
 }
 
-// exclusive scan of one value per thread over the 256 threads of a workgroup; *total = the workgroup's sum
-__device__ __forceinline__ unsigned mc_block_scan(unsigned v, unsigned* total)
-{
-    __shared__ unsigned wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    __syncthreads();                        // (a second scan in the same kernel must not overtake the readers of the first)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return base + inc - v;
-}
-
 // (D) per cell: case index (0 for a cell that is not processed: such a cell and the two uniform cases emit nothing) and triangle count
 __global__ __launch_bounds__(256) void k_mc_cells(McGeom G, const float* __restrict__ vol, const uint8_t* __restrict__ valid,
                                                   const uint8_t* __restrict__ ntri, uint8_t* __restrict__ cellcase, unsigned* __restrict__ bsum)
@@ -173,7 +157,7 @@ __global__ __launch_bounds__(256) void k_mc_cells(McGeom G, const float* __restr
         cnt = ntri[code];
     }
     unsigned total;
-    mc_block_scan(cnt, &total);
+    block_scan(cnt, &total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(256) void k_mc_edges(McGeom G, const float* __restr
         flags = mc_edge_flags(G, vol, cellcase, n, i, j, k, v0, v1);
     }
     unsigned total;
-    const unsigned excl = mc_block_scan(__popc(flags), &total);
+    const unsigned cnt = __popc(flags), excl = block_scan(cnt, &total) - cnt;
     if (!EMIT) { if (threadIdx.x == 0) bsum[blockIdx.x] = total; return; }
     if (n >= G.nn) return;
     unsigned id = boff[blockIdx.x] + excl;
@@ -265,7 +249,7 @@ __global__ __launch_bounds__(256) void k_mc_tris(McGeom G, const uint8_t* __rest
     unsigned code = 0, cnt = 0;
     if (n < G.nn) { code = cellcase[n]; cnt = ntri[code]; }
     unsigned total;
-    const unsigned excl = mc_block_scan(cnt, &total);
+    const unsigned excl = block_scan(cnt, &total) - cnt;
     if (!cnt) return;
     const size_t first = (size_t)boff[blockIdx.x] + excl, sy = (size_t)G.nx, sz = (size_t)G.nx * G.ny;
     for (unsigned t = 0; t < 3 * cnt; ++t) {
@@ -280,7 +264,7 @@ __global__ __launch_bounds__(256) void k_mc_scan_block(unsigned* __restrict__ d,
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     unsigned total;
-    const unsigned excl = mc_block_scan(q < n ? d[q] : 0u, &total);
+    const unsigned v = q < n ? d[q] : 0u, excl = block_scan(v, &total) - v;
     if (q < n) d[q] = excl;
     if (sums && threadIdx.x == 0) sums[blockIdx.x] = total;
 }
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(256) void k_lattice_flags(int nn, const uint8_t* __
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     unsigned total;
-    mc_block_scan(n < nn && valid[n] != 0 ? 1u : 0u, &total);
+    block_scan(n < nn && valid[n] != 0 ? 1u : 0u, &total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 // recomputes the flags; set node: idx[rank] = n (rank < n_set by construction: the guard only matters when the caller's mask changed
@@ -308,7 +292,7 @@ __global__ __launch_bounds__(256) void k_lattice_compact(int nn, const uint8_t* 
     const int n = blockIdx.x * 256 + threadIdx.x;
     const bool live = n < nn, set = live && valid[n] != 0;
     unsigned total;
-    const unsigned rank = boff[blockIdx.x] + mc_block_scan(set ? 1u : 0u, &total);
+    const unsigned one = set ? 1u : 0u, rank = boff[blockIdx.x] + (block_scan(one, &total) - one);
     if (set) { if (rank < n_set) idx[rank] = (unsigned)n; }
     else if (live) vol_bits[n] = fill_bits;
 }

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "nsk_device.h"
+#include "nsk_reduce.h"
 
 #define RASTER_MAX_V 32                     // views per launch: 12 floats each in the kernel arguments
 #define RASTER_BLOCK 256
@@ -27,7 +28,6 @@ struct RasterJob { int view, tri, x0, x1, y0, y1; };
 // what a pixel needs of a (triangle, view) pair
 struct RasterSetup { float nbc[3], nca[3], nab[3], n[3], num; };
 
-__device__ __forceinline__ bool raster_finite(float x) { return fabsf(x) < __builtin_inff(); }
 __device__ __forceinline__ void raster_cross(const float* p, const float* q, float* n)
 {
     n[0] = sub_rn(mul_rn(p[1], q[2]), mul_rn(p[2], q[1]));
@@ -46,7 +46,7 @@ __device__ __forceinline__ bool raster_camera(const float* w, const float v[3][3
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             c[k][a] = add_rn(add_rn(add_rn(mul_rn(w[4 * a], v[k][0]), mul_rn(w[4 * a + 1], v[k][1])), mul_rn(w[4 * a + 2], v[k][2])), w[4 * a + 3]);
-            ok = ok && raster_finite(c[k][a]);
+            ok = ok && finite_f32(c[k][a]);
         }
     return ok;
 }
@@ -186,13 +186,11 @@ __global__ __launch_bounds__(RASTER_BLOCK) void k_raster_finish(size_t n, unsign
 }
 
 // ---- per-view sums of two depth stacks (nsk_depth_pair_stats) ---------------------------------------------------------------------------
-// Workgroup (view, r) of R per view writes one row {sum |a - b|, pixels with a > 0 and b > 0, sum |a - b| over those, pixels with a > 0}:
-// a lane adds its pixels in index order, the lanes of a wave meet by xor shuffles, the four waves through LDS in wave order;
-// k_depth_pair_stats_sum adds a view's rows in index order.  R is a function of n_pix alone.  No floating-point atomics.
+// Workgroup (view, r) of R per view writes one row {sum |a - b|, pixels with a > 0 and b > 0, sum |a - b| over those, pixels with a > 0}
+// in the association of nsk_reduce.h, a view being a group of R rows.  R is a function of n_pix alone.
 __global__ __launch_bounds__(RASTER_BLOCK) void k_depth_pair_stats(int n_pix, int R, const float* __restrict__ a, const float* __restrict__ b,
                                                                   double* __restrict__ rows)
 {
-    __shared__ double sh[4][4];
     const size_t view = blockIdx.x / R;
     const int r = blockIdx.x % R;
     const float* pa = a + view * (size_t)n_pix;
@@ -201,29 +199,11 @@ __global__ __launch_bounds__(RASTER_BLOCK) void k_depth_pair_stats(int n_pix, in
     for (int p = r * RASTER_BLOCK + threadIdx.x; p < n_pix; p += R * RASTER_BLOCK) {
         const float x = pa[p], y = pb[p];
         const float d = fabsf(sub_rn(x, y));
-        const bool fin = raster_finite(d), both = x > 0.f && y > 0.f;
+        const bool fin = finite_f32(d), both = x > 0.f && y > 0.f;
         if (fin) acc[0] += (double)d;
         if (both) acc[1] += 1.0;
         if (both && fin) acc[2] += (double)d;
         if (x > 0.f) acc[3] += 1.0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] += __shfl_xor(acc[k], o);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; ++k) sh[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < 4) rows[(size_t)blockIdx.x * 4 + k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
-}
-__global__ __launch_bounds__(RASTER_BLOCK) void k_depth_pair_stats_sum(int V, int R, const double* __restrict__ rows, double* __restrict__ out)
-{
-    const long long g = (long long)blockIdx.x * RASTER_BLOCK + threadIdx.x;
-    if (g >= 4ll * V) return;
-    const size_t view = (size_t)(g >> 2);
-    const int k = (int)(g & 3);
-    double s = 0.0;
-    for (int r = 0; r < R; ++r) s += rows[(view * R + r) * 4 + k];
-    out[g] = s;
+    rows_store<RowSums<4>>(acc, rows + (size_t)blockIdx.x * 4);
 }
