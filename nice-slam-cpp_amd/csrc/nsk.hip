@@ -221,18 +221,6 @@ __global__ __launch_bounds__(256) void k_xchg_multi(XArgs A)
     if (A.gather) *bf = *sl; else *sl = *bf;
 }
 
-struct PackSeg { float* img; const int* idx; const float* P; int n; int blk_end; };
-struct PackArgs { PackSeg s[8]; int n; };
-__global__ void k_pack_multi(PackArgs A)
-{
-    int r = 0;
-    while (r < A.n - 1 && (int)blockIdx.x >= A.s[r].blk_end) ++r;
-    const PackSeg& S = A.s[r];
-    const int b0 = r == 0 ? 0 : A.s[r - 1].blk_end;
-    const int i = (blockIdx.x - b0) * blockDim.x + threadIdx.x;
-    if (i < S.n) { int k = S.idx[i]; S.img[i] = k >= 0 ? S.P[k] : 0.f; }
-}
-
 __global__ void k_adam_scalar(int n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                               float* __restrict__ v, float step_size, float bc2s, float b1, float b2, float eps)
 {
@@ -747,25 +735,35 @@ struct DecState {
     bool loaded = false;
     size_t g_off = 0;
 };
+// One set of sampling outputs: what k_sample, k_sort_scan and k_sort_place leave of one batch for the decoders, the compositing and the backward.
+struct SampleSet {
+    Buf<float> z;                    // [m] sample depths
+    // cell sort of the samples (k_sample keys -> k_sort_scan -> k_sort_place): perm lists the samples cell by cell
+    Buf<int> perm, skey, srank;      // [m]
+    // liveness bytes (LiveArgs): by sample as k_sample writes them, by slot as k_sort_place re-orders them (ray order: the samples' are the slots')
+    Buf<uint8_t> lsamp, lslot;       // [m]
+    Buf<int> offs;                   // [bins of the key level], sized apart from the six above (ensure_hist, ensure_next)
+    size_t cap() const { return z.cap(); }      // m: the six are allocated and released together (alloc_samples)
+    uint8_t* live_out(bool wanted) const { return wanted ? lsamp.get() : nullptr; }      // where a sampling writes liveness bytes, if it is to write any
+    void swap(SampleSet& o) noexcept { z.swap(o.z); perm.swap(o.perm); skey.swap(o.skey); srank.swap(o.srank); lsamp.swap(o.lsamp); lslot.swap(o.lslot); offs.swap(o.offs); }
+};
 struct Workspace {
     int capM = 0, capN = 0;          // the batch (samples, rays) the group below was allocated for; 0 = not allocated
-    Buf<float> z, occ[3], rgb4;
+    // cur: the set the current step's launches read.  next: the set of the batch nsk_map_prepare registered, filled while the current step runs; a
+    // step that finds its batch prepared swaps the two (forward_core).  Both are kept at the same capacities (ensure_next).
+    SampleSet cur, next;
+    Buf<float> occ[3], rgb4;
     Buf<unsigned long long> masks[4];
     Buf<f4> hsave[4];                // block outputs of trainable decoders saved by the forward (save_h)
     int hsave_M[4] = {0, 0, 0, 0};   // sample count of the forward that filled hsave (0 = stale)
     Buf<float> g_raw, ray_loss;
-    Buf<float> tmp_rgb, tmp_depth, tmp_var;
+    Buf<float> tmp_rgb, tmp_depth;
     Buf<float> dec_slabs;            // per-workgroup partial decoder gradients [num_cu][20920]
-    // cell sort of the samples (k_sample keys -> k_sort_scan -> k_sort_place): perm lists the samples cell by cell
-    Buf<int> perm, skey, srank;      // [capM]
-    Buf<int> hist_raw, offs;         // [bins of the key level] (offs.cap() = bins); the histogram is zero between steps
+    Buf<int> hist_raw;               // the cell sort's histogram, one for both sets [bins of the key level] (cur.offs.cap() = bins); zero between steps
     int* hist() const { return hist_raw ? hist_raw.get() + 16 : nullptr; }      // behind one 64-byte line: hist()[-1] is k_sort_scan's cursor
-    // second set of the sampling outputs: nsk_map_prepare fills it on the side stream while the current step runs; a step that finds its
-    // batch prepared swaps the buffers above with these
-    Buf<float> z_alt; Buf<int> perm_alt, skey_alt, srank_alt, offs_alt;
-    // liveness bytes (LiveArgs): by sample as k_sample writes them, by slot as k_sort_place re-orders them (ray order: the samples' are the slots')
-    Buf<uint8_t> lsamp, lslot, lsamp_alt, lslot_alt;
 };
+// how much of a prepared batch's sampling has run (nsk_ctx::Prep): the samples, then -- cell-sorted batches only -- the offsets, then the placement
+enum PrepDone { PREP_NOTHING, PREP_SAMPLED, PREP_SCANNED, PREP_PLACED };
 struct nsk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -792,7 +790,7 @@ struct nsk_ctx {
     struct CapVec { int n; float* p; const float* g; float* m; float* v; float lr, b1, b2, eps; int step; hipGraphNode_t node; float ss, bc2s; };
     std::vector<CapVec> cap_vecs;               // nsk_adam_vector launches seen during the current capture
     int cap_rollback[NSK_NUM_GROUPS] = {0, 0, 0, 0, 0, 0};
-    int ws_flip = 0;                            // parity of the swaps between the workspace's two sampling-output sets (forward_core): a graph records the set that was primary at capture
+    int ws_flip = 0;                            // parity of the swaps between the workspace's two sampling sets (forward_core): a graph records the set that was primary at capture
     struct GraphRec { bool stale = false; int flip = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipGraphNode_t adam_node = nullptr; bool has_adam = false; CapAdam adam; std::vector<CapVec> vecs; };
     std::vector<GraphRec> graphs;
     bool touched[NSK_NUM_GROUPS] = {false, false, false, false, false, false};
@@ -819,12 +817,12 @@ struct nsk_ctx {
     struct DMax { const float* gt = nullptr; const uint8_t* keep = nullptr; int n = 0; } dmax;
     float* xextra = nullptr; size_t xextra_n = 0;      // nsk_grad_extra: a caller-owned vector that travels with the packed exchange
     int sort_mode = -1;                     // -1 automatic (sort_pays), 0 never, 1 always (nsk_set_sort_mode; tests)
-    bool sorted = false;                    // the current step's decoder launches walk the samples in cell-sorted order (ws.perm)
+    bool sorted = false;                    // the current step's decoder launches walk the samples in cell-sorted order (ws.cur.perm)
     // nsk_map_prepare: the sampling (+ cell sort) of the NEXT batch rides in the launches of the current step (composite + sample, backward + scan,
     // Adam + place): `req` is a registered batch nothing has been launched for yet, `prep` the batch whose outputs sit (or are being built) in the
-    // workspace's second set; done: bit 0 sampled, 1 offsets scanned, 2 placed
+    // workspace's `next` set; done: how far its sampling has come (PrepDone: the stages run in this order and none is skipped)
     struct Prep { bool valid = false; int stage = 0, N = 0, S = 0; const float* ro = nullptr; const float* rd = nullptr; const float* gt = nullptr;
-                  float gtmax = 0.f; const uint8_t* mask = nullptr; bool sorted = false; int done = 0; RParams R; DMax dmax;
+                  float gtmax = 0.f; const uint8_t* mask = nullptr; bool sorted = false; PrepDone done = PREP_NOTHING; RParams R; DMax dmax;
                   bool live = false; int live_epoch = 0; } prep, req;      // live: its sampling wrote liveness bytes, under the masks of live_epoch
     int tune_no_piggyback = 0;              // 1: a prepared batch is sampled by launches of its own at the start of its step (experiments, tests)
     int pend_w = -1, pend_nb = 0;           // decoder whose per-workgroup gradient slabs are not yet summed into the slab (flush_pending)
@@ -949,6 +947,19 @@ static int dev_alloc(Buf<T>& b, size_t n, const char* what)
     (void)hipGetLastError();
     return fail("cannot allocate %zu bytes for %s (%s)", n * sizeof(T), what, hipGetErrorString((hipError_t)e));
 }
+// the six per-sample buffers of a sampling set, m elements each; after a failure the set is empty (its offsets are not touched).  what: one name
+// for the whole set in the failure's text, else each buffer is named by its content
+static int alloc_samples(SampleSet& s, size_t m, const char* what = nullptr)
+{
+    const int r = [&]() -> int {
+        CHK(dev_alloc(s.z, m, what ? what : "the sample depths"));
+        CHK(dev_alloc(s.perm, m, what ? what : "the cell sort")); CHK(dev_alloc(s.skey, m, what ? what : "the cell sort")); CHK(dev_alloc(s.srank, m, what ? what : "the cell sort"));
+        CHK(dev_alloc(s.lsamp, m, what ? what : "the liveness bytes")); CHK(dev_alloc(s.lslot, m, what ? what : "the liveness bytes"));
+        return 0;
+    }();
+    if (r != 0) reset_all(s.z, s.perm, s.skey, s.srank, s.lsamp, s.lslot);
+    return r;
+}
 // what has to happen before a buffer that launches (and, per site, recorded graphs) may point into is replaced
 enum { GROW_NO_CAPTURE = 1,         // refuse while a graph is being captured
        GROW_STALE_GRAPHS = 2 };     // the recorded graphs hold this buffer's address
@@ -1050,7 +1061,7 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     CHK(set_lds(k_median_thr, 16384 * 4));
     CHK(set_lds(k_decode_fwd_multi, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_bf16<8>, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_bf16<8, 2>, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_occ<8>, 160 * 1024));
     CHK(set_lds(k_decode_bwd_multi<false>, 160 * 1024 - 256)); CHK(set_lds(k_decode_bwd_multi<true>, 160 * 1024));      // (<false>, frozen: the scan role keeps a few words of static LDS)
-    CHK(set_lds(k_decode_bwd_frozen<false>, 160 * 1024 - 256));
+    CHK(set_lds(k_decode_bwd_frozen, 160 * 1024 - 256));
     CHK(set_lds(k_decode_bwd_track, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<false>, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<true>, 160 * 1024));
     CHK(set_lds(k_decode_fwd_dump<0>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<1>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<2>, 160 * 1024));
     *out = owner.release();
@@ -1521,20 +1532,18 @@ static int ensure_ws(nsk_ctx* c, int N, int M)
     CHK(grow_begin(c, GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
     CHK(prep_drop(c));
     const int capM = std::max(M, w.capM), capN = std::max(N, w.capN);
-    w = Workspace();             // everything, the histogram, the saved block outputs and the second sampling set included
+    w = Workspace();             // everything, the histogram, the saved block outputs and both sampling sets included
     const size_t m = (size_t)capM + 64, n = (size_t)capN + 64, slabs = (size_t)c->num_cu * 20920;
     const int r = [&]() -> int {
-        CHK(dev_alloc(w.z, m, "the sample depths"));
+        CHK(alloc_samples(w.cur, m));
         for (int i = 0; i < 3; ++i) CHK(dev_alloc(w.occ[i], m, "the occupancies"));
         CHK(dev_alloc(w.rgb4, m * 4, "the colours"));
         for (int i = 0; i < 4; ++i) CHK(dev_alloc(w.masks[i], m * 4, "the ReLU bits"));
         CHK(dev_alloc(w.g_raw, m * 4, "the sample gradients"));
         CHK(dev_alloc(w.ray_loss, n, "the ray losses"));
-        CHK(dev_alloc(w.tmp_rgb, n * 3, "the ray colours")); CHK(dev_alloc(w.tmp_depth, n, "the ray depths")); CHK(dev_alloc(w.tmp_var, n, "the ray variances"));
+        CHK(dev_alloc(w.tmp_rgb, n * 3, "the ray colours")); CHK(dev_alloc(w.tmp_depth, n, "the ray depths"));
         CHK(dev_alloc(w.dec_slabs, slabs, "the decoder gradient slabs"));
         HIPCHK(hipMemsetAsync(w.dec_slabs, 0, slabs * 4, c->stream));
-        CHK(dev_alloc(w.perm, m, "the cell sort")); CHK(dev_alloc(w.skey, m, "the cell sort")); CHK(dev_alloc(w.srank, m, "the cell sort"));
-        CHK(dev_alloc(w.lsamp, m, "the liveness bytes")); CHK(dev_alloc(w.lslot, m, "the liveness bytes"));
         return 0;
     }();
     if (r != 0) { w = Workspace(); return r; }
@@ -1546,16 +1555,16 @@ static int ensure_ws(nsk_ctx* c, int N, int M)
 static int ensure_hist(nsk_ctx* c, size_t bins)
 {
     Workspace& w = c->ws;
-    if (bins <= w.offs.cap()) return 0;
+    if (bins <= w.cur.offs.cap()) return 0;
     CHK(grow_begin(c, GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
     c->prep.valid = false; c->req.valid = false;       // (the histogram is replaced: nothing to clean)
     const size_t slots = ((bins / 8 + 1) / 2) * 16 + 16;    // hist_slot() layout (bins = 8 keys per cell) + one 64-byte line in front (Workspace::hist)
     const int r = [&]() -> int {
-        CHK(dev_alloc(w.hist_raw, slots, "the cell histogram")); CHK(dev_alloc(w.offs, bins, "the cell offsets"));
+        CHK(dev_alloc(w.hist_raw, slots, "the cell histogram")); CHK(dev_alloc(w.cur.offs, bins, "the cell offsets"));
         HIPCHK(hipMemsetAsync(w.hist_raw, 0, slots * 4, c->stream));
         return 0;
     }();
-    if (r != 0) reset_all(w.hist_raw, w.offs);
+    if (r != 0) reset_all(w.hist_raw, w.cur.offs);
     return r;
 }
 
@@ -1588,8 +1597,8 @@ static int check_stage(nsk_ctx* c, int stage)
 static void fill_args(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* ro, const float* rd, const float* pts)
 {
     memset(&A, 0, sizeof(A));
-    A.rays_o = ro; A.rays_d = rd; A.z = c->ws.z; A.pts = pts; A.M = M; A.S = S; A.S_magic = S > 1 ? (unsigned)((0x100000000ull + (unsigned)S - 1) / (unsigned)S) : 0u;
-    A.perm = (c->sorted && !pts) ? c->ws.perm : nullptr;
+    A.rays_o = ro; A.rays_d = rd; A.z = c->ws.cur.z; A.pts = pts; A.M = M; A.S = S; A.S_magic = S > 1 ? (unsigned)((0x100000000ull + (unsigned)S - 1) / (unsigned)S) : 0u;
+    A.perm = (c->sorted && !pts) ? c->ws.cur.perm : nullptr;
     memcpy(A.bound, c->R.bound, sizeof(A.bound));
     A.grid = grid_dev(c, w, false);
     if (w == 2) A.grid_mid = grid_dev(c, 1, false);
@@ -1826,43 +1835,43 @@ static void live_args(nsk_ctx* c, LiveArgs& L, int stage, uint8_t* out)
 }
 
 static void samp_args(nsk_ctx* c, SampArgs& A, const RParams& R, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax,
-                      const float* gmax_dev, const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, const nsk_ctx::DMax& dm, uint8_t* lsamp = nullptr)
+                      const float* gmax_dev, const uint8_t* mask, bool sorted, const SampleSet& out, bool live, const nsk_ctx::DMax& dm)      // live: also the liveness bytes (live_wanted)
 {
     const GridState& KG = c->grid[stage_key_level(stage)];
     const GridState* PG = stage >= 2 ? &c->grid[1] : nullptr;      // parent level whose cells order the samples inside a key cell (k_sample)
     const size_t bins = KG.n / 32 * 8;
     memset(&A, 0, sizeof(A));
-    A.R = R; A.N = N; A.S = S; A.rays_o = ro; A.rays_d = rd; A.gt_depth = gt; A.gtmax_host = gtmax; A.gtmax_dev = gmax_dev; A.keep = mask; A.z_out = z;
+    A.R = R; A.N = N; A.S = S; A.rays_o = ro; A.rays_d = rd; A.gt_depth = gt; A.gtmax_host = gtmax; A.gtmax_dev = gmax_dev; A.keep = mask; A.z_out = out.z;
     A.kX = KG.X; A.kY = KG.Y; A.kZ = KG.Z; A.pX = PG ? PG->X : 0; A.pY = PG ? PG->Y : 0; A.pZ = PG ? PG->Z : 0; A.ncell2 = (int)((bins / 8 + 1) / 2);
-    A.skey = sorted ? skey : nullptr; A.srank = srank; A.hist = c->ws.hist();
+    A.skey = sorted ? out.skey.get() : nullptr; A.srank = out.srank; A.hist = c->ws.hist();
     if (dm.n > 0) { A.mx_gt = dm.gt; A.mx_keep = dm.keep; A.mx_n = dm.n; } else { A.mx_gt = gt; A.mx_keep = mask; A.mx_n = N; }
-    live_args(c, A.L, stage, lsamp);
+    live_args(c, A.L, stage, out.live_out(live));
 }
 // halves: 256-cell chunks per workgroup (1: k_sort_scan, 2: the role inside k_decode_bwd_multi)
-static ScanArgs scan_args(nsk_ctx* c, int stage, int* offs, int halves)
+static ScanArgs scan_args(nsk_ctx* c, int stage, const SampleSet& out, int halves)
 {
     const size_t bins = c->grid[stage_key_level(stage)].n / 32 * 8;
-    ScanArgs A; A.nkeys = (int)bins; A.ncell2 = (int)((bins / 8 + 1) / 2); A.hist = c->ws.hist(); A.offs = offs;
+    ScanArgs A; A.nkeys = (int)bins; A.ncell2 = (int)((bins / 8 + 1) / 2); A.hist = c->ws.hist(); A.offs = out.offs;
     A.nblocks = (int)((bins + 2048 * (size_t)halves - 1) / (2048 * (size_t)halves));
     return A;
 }
-static PlaceArgs place_args(int M, const int* skey, const int* srank, const int* offs, int* perm, const uint8_t* lsamp = nullptr, uint8_t* lslot = nullptr)
+static PlaceArgs place_args(int M, const SampleSet& out, bool live)      // live: the sampling wrote liveness bytes; they are re-ordered with the samples
 {
-    PlaceArgs A; A.M = M; A.skey = skey; A.srank = srank; A.offs = offs; A.perm = perm; A.nblocks = (M + 255) / 256;
-    A.live_in = lsamp; A.live_out = lsamp ? lslot : nullptr;
+    PlaceArgs A; A.M = M; A.skey = out.skey; A.srank = out.srank; A.offs = out.offs; A.perm = out.perm; A.nblocks = (M + 255) / 256;
+    A.live_in = out.live_out(live); A.live_out = live ? out.lslot.get() : nullptr;
     return A;
 }
 // the batch maximum of gt_depth has to come from a launch of its own (k_sample's waves take it themselves for smaller batches)
 static bool needs_depth_max(const float* gt, float gtmax, int N, const nsk_ctx::DMax& dm) { return gt && gtmax < 0.f && (dm.n > 0 ? dm.n : N) > 8192; }
 
-// sampling (+ cell sort) of one batch into the given output set by launches of its own; `done`: stages that have already run (nsk_ctx::Prep)
+// sampling (+ cell sort) of one batch into the set `out` by launches of its own; live: also the liveness bytes (live_wanted), by sample and,
+// sorted, by slot; done: what has already run (a prepared batch's riders)
 static int launch_sampling(nsk_ctx* c, const RParams& R, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax,
-                           const uint8_t* mask, bool sorted, float* z, int* skey, int* srank, int* offs, int* perm, const nsk_ctx::DMax& dm, int done = 0,
-                           uint8_t* lsamp = nullptr, uint8_t* lslot = nullptr)      // lsamp: also the liveness bytes (live_wanted), by sample and, sorted, by slot
+                           const uint8_t* mask, bool sorted, const SampleSet& out, bool live, const nsk_ctx::DMax& dm, PrepDone done = PREP_NOTHING)
 {
     const int M = N * S;
     hipStream_t st = c->stream;
-    if (!(done & 1)) {
+    if (done < PREP_SAMPLED) {
         const float* gmax_dev = nullptr;
         if (needs_depth_max(gt, gtmax, N, dm)) {
             ProfScope ps(c, "depth_max");
@@ -1872,16 +1881,100 @@ static int launch_sampling(nsk_ctx* c, const RParams& R, int stage, int N, int S
         }
         ProfScope ps(c, "sample");
         SampArgs A;
-        samp_args(c, A, R, stage, N, S, ro, rd, gt, gtmax, gmax_dev, mask, sorted, z, skey, srank, dm, lsamp);
+        samp_args(c, A, R, stage, N, S, ro, rd, gt, gtmax, gmax_dev, mask, sorted, out, live, dm);
         k_sample<<<(N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS, 64 * NSK_SAMPLE_RAYS, 0, st>>>(A);
     }
-    if (sorted && (done & 6) != 6) {
+    if (sorted && done < PREP_PLACED) {
         ProfScope ps(c, "cell_sort");
-        if (!(done & 2)) { const ScanArgs A = scan_args(c, stage, offs, 1); k_sort_scan<<<A.nblocks, 256, 0, st>>>(A); }
-        if (!(done & 4)) { const PlaceArgs A = place_args(M, skey, srank, offs, perm, lsamp, lslot); k_sort_place<<<A.nblocks, 256, 0, st>>>(A); }
+        if (done < PREP_SCANNED) { const ScanArgs A = scan_args(c, stage, out, 1); k_sort_scan<<<A.nblocks, 256, 0, st>>>(A); }
+        const PlaceArgs A = place_args(M, out, live); k_sort_place<<<A.nblocks, 256, 0, st>>>(A);
     }
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+static size_t stage_bins(nsk_ctx* c, int stage) { return c->grid[stage_key_level(stage)].n / 32 * 8; }
+
+// ---- the life of a prepared batch (nsk_map_prepare) ---------------------------------------------------------------------------------------
+// nsk_map_prepare registers the NEXT batch as c->req and launches nothing.  The nsk_map_step that follows promotes it to c->prep, the batch whose
+// outputs are built in ws.next, and carries its sampling in the composite launch (prep_ride_sample); that step's backward launch carries the
+// offsets of its cell sort (prep_ride_scan), the nsk_adam_step after it the placement (prep_ride_place).  Whatever no launch has carried when the
+// batch's own step arrives -- or when something else needs the cell histogram or ws.next -- runs by launches of its own (prep_finish), or the
+// batch is forgotten and sampled afresh by its step (prep_drop).  Its step then swaps ws.next for ws.cur (forward_core).  No rider goes into a
+// graph capture, and none under nsk_set_tuning("no_piggyback", 1).
+
+// ws.next at the capacities of ws.cur
+static int ensure_next(nsk_ctx* c, bool need_offs)
+{
+    Workspace& w = c->ws;
+    const size_t m = (size_t)w.capM + 64;
+    if (m > w.next.cap()) { CHK(grow_begin(c, 0)); CHK(alloc_samples(w.next, m, "the second sampling set")); }
+    if (need_offs) CHK(grow(c, w.next.offs, w.cur.offs.cap(), "the second sampling set's offsets", 0));
+    return 0;
+}
+
+// a registered batch becomes the prepared one (ws.next is free: the step that was using it has swapped it out); ride: its sampling may go into
+// this step's composite launch
+static int prep_promote(nsk_ctx* c, bool* ride)
+{
+    *ride = false;
+    if (!c->req.valid || c->capturing) return 0;
+    if (c->prep.valid) { const nsk_ctx::Prep keep = c->req; CHK(prep_drop(c)); c->req = keep; }      // an unclaimed set makes room
+    const nsk_ctx::Prep R = c->req;
+    if (R.sorted) CHK(ensure_hist(c, stage_bins(c, R.stage)));
+    CHK(ensure_next(c, R.sorted));
+    c->prep = R; c->prep.done = PREP_NOTHING; c->req.valid = false;
+    *ride = !c->tune_no_piggyback && !needs_depth_max(R.gt, R.gtmax, R.N, R.dmax);
+    return 0;
+}
+
+// whether the prepared batch's sampling writes liveness bytes is decided when it is sampled: under the masks of then
+static int prep_sample_live(nsk_ctx* c, nsk_ctx::Prep& P)
+{
+    P.live = live_wanted(c, P.stage, true); P.live_epoch = c->live_epoch;
+    if (P.live) CHK(ensure_live_stage(c, P.stage));
+    return 0;
+}
+
+// Rider 1, nsk_map_step's composite launch (k_composite_sample): the sampling.  Promotes a registered batch first.  Precondition: that batch was
+// promoted by this very call, so nothing of it has run, and it needs no depth-max launch in front (prep_promote's `ride`).  *wgs: the workgroups
+// to append for SA; 0 = nothing rides.
+static int prep_ride_sample(nsk_ctx* c, SampArgs& SA, int* wgs)
+{
+    bool ride = false;
+    *wgs = 0;
+    CHK(prep_promote(c, &ride));
+    if (!ride) return 0;
+    nsk_ctx::Prep& P = c->prep;
+    CHK(prep_sample_live(c, P));
+    samp_args(c, SA, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, nullptr, P.mask, P.sorted, c->ws.next, P.live, P.dmax);
+    *wgs = (P.N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS;
+    P.done = PREP_SAMPLED;
+    return 0;
+}
+
+// Rider 2, the backward launch (k_decode_bwd_multi<false> / k_decode_bwd_frozen; may_ride: it is one of those): the cell sort's offsets, by short
+// workgroups behind the roles that wait for nothing of the launch.  Precondition: sampled, not scanned.  Returns the workgroups to append for
+// MA.scan; waves4: 256-cell chunks per workgroup.
+static int prep_ride_scan(nsk_ctx* c, MultiArgs& MA, bool may_ride, int waves4)
+{
+    nsk_ctx::Prep& P = c->prep;
+    if (!(P.valid && P.sorted && P.done == PREP_SAMPLED && may_ride && !c->capturing && !c->tune_no_piggyback)) return 0;
+    MA.scan = scan_args(c, P.stage, c->ws.next, waves4);
+    P.done = PREP_SCANNED;
+    return MA.scan.nblocks;
+}
+
+// Rider 3, nsk_adam_step's launch (k_adam_multi, when it has a segment to update): the cell sort's placement behind the segments.
+// Precondition: scanned, not placed.  Returns the workgroups to append for AA.place; adam_blocks: those of the segments.
+static int prep_ride_place(nsk_ctx* c, AdamArgs& AA, int adam_blocks)
+{
+    nsk_ctx::Prep& P = c->prep;
+    if (!(AA.n && P.valid && P.sorted && P.done == PREP_SCANNED && !c->capturing && !c->tune_no_piggyback)) return 0;
+    AA.place = place_args(P.N * P.S, c->ws.next, P.live);
+    AA.adam_blocks = adam_blocks;
+    P.done = PREP_PLACED;
+    return AA.place.nblocks;
 }
 
 // the stages of the prepared batch that have not run yet, by launches of their own (its step has come, or something else needs the histogram)
@@ -1889,15 +1982,10 @@ static int prep_finish(nsk_ctx* c)
 {
     nsk_ctx::Prep& P = c->prep;
     if (!P.valid) return 0;
-    const int all = P.sorted ? 7 : 1;
-    if ((P.done & all) == all) return 0;
-    Workspace& w = c->ws;
-    if (!(P.done & 1)) {            // not sampled yet: under the masks of now
-        P.live = live_wanted(c, P.stage, true); P.live_epoch = c->live_epoch;
-        if (P.live) CHK(ensure_live_stage(c, P.stage));
-    }
-    CHK(launch_sampling(c, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, P.mask, P.sorted, w.z_alt, w.skey_alt, w.srank_alt, w.offs_alt, w.perm_alt, P.dmax, P.done,
-                        P.live ? w.lsamp_alt.get() : nullptr, w.lslot_alt));
+    const PrepDone all = P.sorted ? PREP_PLACED : PREP_SAMPLED;
+    if (P.done >= all) return 0;
+    if (P.done < PREP_SAMPLED) CHK(prep_sample_live(c, P));
+    CHK(launch_sampling(c, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, P.mask, P.sorted, c->ws.next, P.live, P.dmax, P.done));
     P.done = all;
     return 0;
 }
@@ -1905,12 +1993,10 @@ static int prep_finish(nsk_ctx* c)
 static int prep_drop(nsk_ctx* c)
 {
     nsk_ctx::Prep& P = c->prep;
-    if (P.valid && P.sorted && (P.done & 1) && !(P.done & 2)) { const ScanArgs A = scan_args(c, P.stage, c->ws.offs_alt, 1); k_sort_scan<<<A.nblocks, 256, 0, c->stream>>>(A); HIPCHK(hipGetLastError()); }
+    if (P.valid && P.sorted && P.done == PREP_SAMPLED) { const ScanArgs A = scan_args(c, P.stage, c->ws.next, 1); k_sort_scan<<<A.nblocks, 256, 0, c->stream>>>(A); HIPCHK(hipGetLastError()); }
     P.valid = false; c->req.valid = false;
     return 0;
 }
-
-static size_t stage_bins(nsk_ctx* c, int stage) { return c->grid[stage_key_level(stage)].n / 32 * 8; }
 
 static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax, bool save_masks,
                         bool sorted = false, const nsk_ctx::DMax* dmax = nullptr)      // dmax: instead of the installed depth-max batch (nsk_render_image: none)
@@ -1919,7 +2005,7 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
     const uint8_t* mask = save_masks ? c->ray_mask : nullptr;      // (only the steps that form a loss honour it; a plain render shows every ray)
     const bool want_live = live_wanted(c, stage, save_masks);
     auto is_this_batch = [&](const nsk_ctx::Prep& X) {
-        return X.valid && save_masks && (!(X.done & 1) || (X.live == want_live && (!X.live || X.live_epoch == c->live_epoch))) && !c->capturing && X.stage == stage && X.N == N && X.S == S && X.ro == ro && X.rd == rd && X.gt == gt && X.gtmax == gtmax &&
+        return X.valid && save_masks && (X.done < PREP_SAMPLED || (X.live == want_live && (!X.live || X.live_epoch == c->live_epoch))) && !c->capturing && X.stage == stage && X.N == N && X.S == S && X.ro == ro && X.rd == rd && X.gt == gt && X.gtmax == gtmax &&
                X.mask == mask && X.sorted == sorted && memcmp(&X.R, &c->R, sizeof(RParams)) == 0 &&
                X.dmax.gt == c->dmax.gt && X.dmax.keep == c->dmax.keep && X.dmax.n == c->dmax.n;
     };
@@ -1927,10 +2013,7 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
     if (!c->capturing) CHK(prep_finish(c));                 // (also when the set is for another batch: the sampling below needs the cell histogram; nsk_graph_begin has settled it before a capture)
     if (is_this_batch(P)) {
         // this batch was sampled during the previous step (nsk_map_prepare): take its outputs
-        Workspace& w = c->ws;
-        w.z.swap(w.z_alt); w.perm.swap(w.perm_alt); w.skey.swap(w.skey_alt); w.srank.swap(w.srank_alt);
-        w.offs.swap(w.offs_alt);                            // (both sets are kept at the same capacities: ensure_alt)
-        w.lsamp.swap(w.lsamp_alt); w.lslot.swap(w.lslot_alt);
+        c->ws.cur.swap(c->ws.next);                         // (both sets are kept at the same capacities: ensure_next)
         c->ws_flip ^= 1;
         P.valid = false;
         c->sorted = sorted;
@@ -1940,8 +2023,7 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
         c->sorted = sorted;
         if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
         if (want_live) CHK(ensure_live_stage(c, stage));
-        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.z, c->ws.skey, c->ws.srank, c->ws.offs, c->ws.perm, dmax ? *dmax : c->dmax, 0,
-                            want_live ? c->ws.lsamp.get() : nullptr, c->ws.lslot));
+        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, c->ws.cur, want_live, dmax ? *dmax : c->dmax));
         c->live_ok = want_live;
     }
     CHK(launch_decode_fwd_stage(c, stage, M, S, ro, rd, save_masks));
@@ -1952,7 +2034,7 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
 static void comp_args(nsk_ctx* c, CompArgs& A, int stage, int N, int S, const float* ro, const float* rd)
 {
     memset(&A, 0, sizeof(A));
-    A.R = c->R; A.N = N; A.S = S; A.stage = stage; A.rays_o = ro; A.rays_d = rd; A.z = c->ws.z;
+    A.R = c->R; A.N = N; A.S = S; A.stage = stage; A.rays_o = ro; A.rays_d = rd; A.z = c->ws.cur.z;
     A.occ_a = stage == 0 ? c->ws.occ[0] : c->ws.occ[1];
     A.occ_b = stage >= 2 ? c->ws.occ[2] : nullptr;
     A.rgb4 = stage == 3 ? c->ws.rgb4 : nullptr;
@@ -2402,23 +2484,13 @@ static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, int stage
         const int w = MA.which[r];
         if (MA.train[r] || w < 1 || !c->grid[w].mask || c->grid[w].live_dirty) continue;
         DecArgs& A = MA.a[r];
-        A.live = c->sorted ? c->ws.lslot : c->ws.lsamp; A.live_bit = 1u << (w - 1); A.live_cnt = c->live_cnt + (w - 1);
+        A.live = c->sorted ? c->ws.cur.lslot : c->ws.cur.lsamp; A.live_bit = 1u << (w - 1); A.live_cnt = c->live_cnt + (w - 1);
         counted[r] = true; c->dbg_counted[w - 1] = true;
         if (fresh) tasks[r] = dead_skip_tasks(ntasks, (int)h[w - 1], c->tune);
     }
 }
 
-// the prepared batch's cell-sort offsets ride behind the roles (nsk_map_prepare): short workgroups that wait for nothing of this launch
-static int attach_prep_scan(nsk_ctx* c, MultiArgs& MA, bool may_ride, int waves4)
-{
-    nsk_ctx::Prep& P = c->prep;
-    if (!(P.valid && P.sorted && (P.done & 3) == 1 && may_ride && !c->capturing && !c->tune_no_piggyback)) return 0;
-    MA.scan = scan_args(c, P.stage, c->ws.offs_alt, waves4);
-    P.done |= 2;
-    return MA.scan.nblocks;
-}
-
-// scan_wgs: of attach_prep_scan; extra: the workgroup that sums the per-ray losses
+// scan_wgs: of prep_ride_scan; extra: the workgroup that sums the per-ray losses
 static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool rays, bool full, bool frozen_only, bool track, int scan_wgs, int extra)
 {
     const int n = R.n; const size_t lds = R.lds;
@@ -2433,7 +2505,7 @@ static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool 
         else k_decode_bwd_multi_full<false><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
     } else if (frozen_only) {
         const size_t lds16 = lds - 8 * 3840 + (size_t)NSK_FROZEN_NW * 3840;      // image + one scatter scratch per wave
-        k_decode_bwd_frozen<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
+        k_decode_bwd_frozen<<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
     } else if (rays) k_decode_bwd_multi<true><<<MA.wg_end[n - 1] + extra, 512, lds, c->stream>>>(MA);
     else k_decode_bwd_multi<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA);
 }
@@ -2480,7 +2552,7 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     MA.live_cnt = c->live_cnt; MA.live_out = c->live_host_dev; MA.live_tag = c->live_tag;
     const int extra = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
     if (d_loss) { MA.sum_src = c->ws.ray_loss; MA.sum_dst = d_loss; MA.sum_n = N; }
-    const int scan_wgs = attach_prep_scan(c, MA, !rays && !full, frozen_only ? NSK_FROZEN_NW / 4 : 2);
+    const int scan_wgs = prep_ride_scan(c, MA, !rays && !full, frozen_only ? NSK_FROZEN_NW / 4 : 2);
     {
         const bool track = dyn_resid != nullptr;
         const int form = track ? NSK_SPLIT_BWD_TRACK : (full ? NSK_SPLIT_BWD_MULTI_FULL : (frozen_only ? NSK_SPLIT_BWD_FROZEN : NSK_SPLIT_BWD_MULTI));
@@ -2513,22 +2585,6 @@ extern "C" int nsk_render_backward(nsk_ctx* c, int stage, int N, const float* ro
     return 0;
 }
 
-// second set of sampling outputs, kept at the capacities of the first
-static int ensure_alt(nsk_ctx* c, bool need_offs)
-{
-    Workspace& w = c->ws;
-    const size_t m = (size_t)w.capM + 64;
-    const int r = [&]() -> int {
-        CHK(grow(c, w.z_alt, m, "the second sampling set", 0)); CHK(grow(c, w.perm_alt, m, "the second sampling set", 0));
-        CHK(grow(c, w.skey_alt, m, "the second sampling set", 0)); CHK(grow(c, w.srank_alt, m, "the second sampling set", 0));
-        CHK(grow(c, w.lsamp_alt, m, "the second sampling set", 0)); CHK(grow(c, w.lslot_alt, m, "the second sampling set", 0));
-        return 0;
-    }();
-    if (r != 0) { reset_all(w.z_alt, w.perm_alt, w.skey_alt, w.srank_alt, w.lsamp_alt, w.lslot_alt); return r; }
-    if (need_offs) CHK(grow(c, w.offs_alt, w.offs.cap(), "the second sampling set's offsets", 0));
-    return 0;
-}
-
 // Registers the NEXT batch.  Nothing is launched here: the nsk_map_step that follows carries the batch's sampling in its composite launch, its
 // backward launch carries the offsets of the cell sort, the nsk_adam_step after it the placement -- three launches and their dependent round
 // trips (30 us at 5000 rays, 20 us at 1000) leave the front of the next step.  Until round 3 the sampling ran on a side stream beside the
@@ -2542,24 +2598,9 @@ extern "C" int nsk_map_prepare(nsk_ctx* c, int stage, int N, const float* ro, co
     CHK(common_checks(c, stage, N, ro, rd, &S, gt));
     const bool sorted = sort_pays(c, stage, N * S, flags);
     if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
-    CHK(ensure_alt(c, sorted));
+    CHK(ensure_next(c, sorted));
     nsk_ctx::Prep& P = c->req;
-    P.valid = true; P.stage = stage; P.N = N; P.S = S; P.ro = ro; P.rd = rd; P.gt = gt; P.gtmax = gtmax; P.mask = c->ray_mask; P.sorted = sorted; P.done = 0; P.R = c->R; P.dmax = c->dmax;
-    return 0;
-}
-
-// a registered batch becomes the prepared one (the second set is free: the step that was using it has swapped it out); ride: its sampling may
-// go into this step's composite launch
-static int prep_promote(nsk_ctx* c, bool* ride)
-{
-    *ride = false;
-    if (!c->req.valid || c->capturing) return 0;
-    if (c->prep.valid) { const nsk_ctx::Prep keep = c->req; CHK(prep_drop(c)); c->req = keep; }      // an unclaimed set makes room
-    const nsk_ctx::Prep R = c->req;
-    if (R.sorted) CHK(ensure_hist(c, stage_bins(c, R.stage)));
-    CHK(ensure_alt(c, R.sorted));
-    c->prep = R; c->prep.done = 0; c->req.valid = false;
-    *ride = !c->tune_no_piggyback && !needs_depth_max(R.gt, R.gtmax, R.N, R.dmax);
+    P.valid = true; P.stage = stage; P.N = N; P.S = S; P.ro = ro; P.rd = rd; P.gt = gt; P.gtmax = gtmax; P.mask = c->ray_mask; P.sorted = sorted; P.done = PREP_NOTHING; P.R = c->R; P.dmax = c->dmax;
     return 0;
 }
 
@@ -2578,18 +2619,11 @@ extern "C" int nsk_map_step(nsk_ctx* c, int stage, int N, const float* ro, const
     A.mode = 2; A.gt_depth = gt; A.gt_color = gtc; A.w_color = w_color; A.use_color = use_color;
     A.rgb = rgb; A.depth = depth; A.var = var; A.loss = c->ws.ray_loss;
     if (flags & NSK_GRAD_RAYS) { A.g_rays_o = g_ro; A.g_rays_d = g_rd; }
-    bool ride = false;
-    CHK(prep_promote(c, &ride));
-    if (ride) {          // the next batch's sampling behind this batch's compositing, one launch (k_composite_sample)
-        nsk_ctx::Prep& P = c->prep;
-        SampArgs SA;
-        P.live = live_wanted(c, P.stage, true); P.live_epoch = c->live_epoch;
-        if (P.live) CHK(ensure_live_stage(c, P.stage));
-        samp_args(c, SA, P.R, P.stage, P.N, P.S, P.ro, P.rd, P.gt, P.gtmax, nullptr, P.mask, P.sorted, c->ws.z_alt, c->ws.skey_alt, c->ws.srank_alt, P.dmax,
-                  P.live ? c->ws.lsamp_alt.get() : nullptr);
-        const int cb = (N + 7) / 8, sb = (P.N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS;
-        { ProfScope ps(c, "composite"); k_composite_sample<<<cb + sb, 512, 0, c->stream>>>(A, SA, cb); }
-        P.done |= 1;
+    SampArgs SA; int sb = 0;
+    CHK(prep_ride_sample(c, SA, &sb));
+    if (sb) {            // the next batch's sampling behind this batch's compositing, one launch (k_composite_sample)
+        const int cb = (N + 7) / 8;
+        ProfScope ps(c, "composite"); k_composite_sample<<<cb + sb, 512, 0, c->stream>>>(A, SA, cb);
     } else {
         ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A);
     }
@@ -2712,7 +2746,7 @@ extern "C" int nsk_debug_relu_bits(nsk_ctx* c, int which, int M, uint8_t* h_bits
     std::vector<unsigned long long> mk((size_t)M * 4);
     std::vector<int> perm;
     HIPCHK(hipMemcpy(mk.data(), c->ws.masks[which], mk.size() * 8, hipMemcpyDeviceToHost));
-    if (c->sorted) { perm.resize(M); HIPCHK(hipMemcpy(perm.data(), c->ws.perm, (size_t)M * 4, hipMemcpyDeviceToHost)); }
+    if (c->sorted) { perm.resize(M); HIPCHK(hipMemcpy(perm.data(), c->ws.cur.perm, (size_t)M * 4, hipMemcpyDeviceToHost)); }
     for (int slot = 0; slot < M; ++slot) {
         const int m = c->sorted ? perm[slot] : slot;
         if (m < 0 || m >= M) return fail("nsk_debug_relu_bits: perm[%d] = %d out of range", slot, m);
@@ -2731,7 +2765,7 @@ extern "C" int nsk_debug_fetch(nsk_ctx* c, int what, int M, float* h_out)
 {
     if (!c || !h_out) return fail("nsk_debug_fetch: null argument");
     if (M < 1 || M != c->dbg_M || M > c->ws.capM) return fail("nsk_debug_fetch: M = %d is not the last step's sample count (%d)", M, c->dbg_M);
-    const float* src = what >= 0 && what <= 2 ? c->ws.occ[what] : (what == 3 ? c->ws.rgb4 : (what == 4 ? c->ws.g_raw : (what == 5 ? c->ws.z : (what == 6 ? c->scal + 1 : nullptr))));
+    const float* src = what >= 0 && what <= 2 ? c->ws.occ[what] : (what == 3 ? c->ws.rgb4 : (what == 4 ? c->ws.g_raw : (what == 5 ? c->ws.cur.z : (what == 6 ? c->scal + 1 : nullptr))));
     if (!src) return fail("nsk_debug_fetch: what = 0..6");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2753,11 +2787,11 @@ extern "C" int nsk_debug_live_tiles(nsk_ctx* c, int M, int* h_counts, int32_t* h
     for (int k = 0; k < 3; ++k) h_counts[4 + k] = c->dbg_wgs[k];
     h_counts[7] = c->dbg_ntasks;
     if (h_perm) {
-        if (c->sorted) HIPCHK(hipMemcpy(h_perm, c->ws.perm, (size_t)M * 4, hipMemcpyDeviceToHost));
+        if (c->sorted) HIPCHK(hipMemcpy(h_perm, c->ws.cur.perm, (size_t)M * 4, hipMemcpyDeviceToHost));
         else for (int m = 0; m < M; ++m) h_perm[m] = m;
     }
     if (h_bytes) {
-        if (c->live_ok) HIPCHK(hipMemcpy(h_bytes, c->sorted ? c->ws.lslot : c->ws.lsamp, (size_t)M, hipMemcpyDeviceToHost));
+        if (c->live_ok) HIPCHK(hipMemcpy(h_bytes, c->sorted ? c->ws.cur.lslot : c->ws.cur.lsamp, (size_t)M, hipMemcpyDeviceToHost));
         else memset(h_bytes, 7, (size_t)M);
     }
     return 0;
@@ -3561,9 +3595,8 @@ extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b
     if (!c || !lr) return fail("nsk_adam_step: null argument");
     HIPCHK(hipSetDevice(c->device));
     AdamArgs AA; memset(&AA, 0, sizeof(AA));
-    PackArgs PA; memset(&PA, 0, sizeof(PA));
     AA.b1 = b1; AA.b2 = b2; AA.eps = eps;
-    int blocks = 0, pblocks = 0;
+    int blocks = 0;
     int seg_group[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int lv = 0; lv < 4; ++lv) {
         int grp = NSK_GROUP_COARSE + lv;
@@ -3608,17 +3641,8 @@ extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b
         for (int i = 0; i < AA.n; ++i) { ca.group[i] = seg_group[i]; ca.lr[i] = lr[seg_group[i]]; }
         c->cap_adams.push_back(ca);
     }
-    int place_wgs = 0;
-    {   // the prepared batch's cell-sort placement rides behind the segments (nsk_map_prepare)
-        nsk_ctx::Prep& P = c->prep;
-        if (AA.n && P.valid && P.sorted && (P.done & 7) == 3 && !c->capturing && !c->tune_no_piggyback) {
-            AA.place = place_args(P.N * P.S, c->ws.skey_alt, c->ws.srank_alt, c->ws.offs_alt, c->ws.perm_alt, P.live ? c->ws.lsamp_alt.get() : nullptr, c->ws.lslot_alt);
-            AA.adam_blocks = blocks; place_wgs = AA.place.nblocks;
-            P.done |= 4;
-        }
-    }
+    const int place_wgs = prep_ride_place(c, AA, blocks);
     if (AA.n) { ProfScope ps(c, "adam_multi"); k_adam_multi<<<blocks + place_wgs, 256, 0, c->stream>>>(AA); }
-    if (PA.n) { ProfScope ps(c, "pack_images"); k_pack_multi<<<pblocks, 256, 0, c->stream>>>(PA); }
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -191,14 +191,13 @@ __device__ __forceinline__ void decode_fwd_bf16_body(const DecArgs& A, int bid, 
     // trips (z -> p -> gather) leaves the critical path (29 % of wave time was s_waitcnt, profiles/README.md)
     // (with a cell-sorted launch the sample index is itself a load, A.perm: fetched two tiles ahead)
     const int nw = nb * NW, wg = bid * NW + wave;
-    const int tsh = tile_shift(ntasks, nw);
-    const int kmax = tiles_per_wave(ntasks, nw, tsh);
+    const int kmax = tiles_per_wave(ntasks, nw);
     SampleRaw nx;
-    int m = slot_sample(A, tile_of(0, wg, nw, tsh) * 16 + j);
+    int m = slot_sample(A, tile_of(0, wg, nw) * 16 + j);
     sample_load(A, m, nx);
-    int m_next = slot_sample(A, tile_of(1, wg, nw, tsh) * 16 + j);
+    int m_next = slot_sample(A, tile_of(1, wg, nw) * 16 + j);
     for (int k = 0; k < kmax; ++k) {
-        const int task = tile_of(k, wg, nw, tsh);
+        const int task = tile_of(k, wg, nw);
         if (task >= ntasks) break;
         asm volatile("" ::: "memory");
         const int slot = task * 16 + j;
@@ -208,11 +207,11 @@ __device__ __forceinline__ void decode_fwd_bf16_body(const DecArgs& A, int bid, 
         tri_setup(A.grid, A.bound, px, py, pz, T);
         Act<CQ> C;
         GatherRaw R;                                   // the gather's 16 loads are in flight while the embedding is computed
-        tri_gather_issue<true>(A.grid, T, g, R);
+        tri_gather_issue(A.grid, T, g, R);
         sample_load(A, m_next, nx);                    // unconditional (clamped): no branch, no wait here
         const int m_cur = m;
         m = m_next;
-        m_next = slot_sample(A, tile_of(k + 2, wg, nw, tsh) * 16 + j);
+        m_next = slot_sample(A, tile_of(k + 2, wg, nw) * 16 + j);
         f4 dummy[6];
         embed<false>(imgf + I::P_BM, g, px, py, pz, C.xe, dummy);
         asm volatile("" ::: "memory");                 // keep the order: loads, embedding, weighting
@@ -261,14 +260,13 @@ __device__ __forceinline__ void decode_fwd_occ_body(const DecArgs& Am, const Dec
     const h8* img_f = reinterpret_cast<const h8*>(imgf_f);
     const int ntasks = (Af.M + 15) >> 4;
     const int nw = nb * NW, wg = bid * NW + wave;
-    const int tsh = tile_shift(ntasks, nw);
-    const int kmax = tiles_per_wave(ntasks, nw, tsh);
+    const int kmax = tiles_per_wave(ntasks, nw);
     SampleRaw nx;
-    int m = slot_sample(Af, tile_of(0, wg, nw, tsh) * 16 + j);
+    int m = slot_sample(Af, tile_of(0, wg, nw) * 16 + j);
     sample_load(Af, m, nx);
-    int m_next = slot_sample(Af, tile_of(1, wg, nw, tsh) * 16 + j);
+    int m_next = slot_sample(Af, tile_of(1, wg, nw) * 16 + j);
     for (int k = 0; k < kmax; ++k) {
-        const int task = tile_of(k, wg, nw, tsh);
+        const int task = tile_of(k, wg, nw);
         if (task >= ntasks) break;
         asm volatile("" ::: "memory");
         const int slot = task * 16 + j;
@@ -282,7 +280,7 @@ __device__ __forceinline__ void decode_fwd_occ_body(const DecArgs& Am, const Dec
             tri_setup(Am.grid, Am.bound, px, py, pz, T);
             Act<2> C;
             GatherRaw R;
-            tri_gather_issue<true>(Am.grid, T, g, R);
+            tri_gather_issue(Am.grid, T, g, R);
             sample_load(Af, m_next, nx);                   // unconditional (clamped): no branch, no wait here
             embed<false>(imgf_m + IM::P_BM, g, px, py, pz, C.xe, dummy);
             asm volatile("" ::: "memory");                 // keep the order: loads, embedding, weighting
@@ -296,13 +294,13 @@ __device__ __forceinline__ void decode_fwd_occ_body(const DecArgs& Am, const Dec
         }
         const int m_cur = m;
         m = m_next;
-        m_next = slot_sample(Af, tile_of(k + 2, wg, nw, tsh) * 16 + j);
+        m_next = slot_sample(Af, tile_of(k + 2, wg, nw) * 16 + j);
         {
             Tri T;
             tri_setup(Af.grid, Af.bound, px, py, pz, T);
             Act<4> C;
             GatherRaw R;
-            tri_gather_issue<true>(Af.grid, T, g, R);
+            tri_gather_issue(Af.grid, T, g, R);
             embed<false>(imgf_f + IF::P_BM, g, px, py, pz, C.xe, dummy);
             asm volatile("" ::: "memory");
             tri_gather_reduce(T, R, C.xc[0], C.xc[1]);

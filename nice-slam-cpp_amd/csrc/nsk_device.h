@@ -624,14 +624,14 @@ __device__ __forceinline__ float chain_scale(float (&g)[OD])
     return __builtin_ldexpf(1.f, e + 3);
 }
 
-// the same in two steps (loads first, weighting later) so that independent work can sit between them
+// the same in two steps (loads first, weighting later) so that independent work can sit between them; every body that gathers this way takes the
+// 32-bit offset form of voxel_ptr
 struct GatherRaw { f4 a[8], b[8]; };
-template <bool O32 = false>
 __device__ __forceinline__ void tri_gather_issue(const GridD& G, const Tri& T, int g, GatherRaw& R)
 {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const f4* vp = voxel_ptr<O32>(G, T.vox[c], g);
+        const f4* vp = voxel_ptr<true>(G, T.vox[c], g);
         R.a[c] = vp[0]; R.b[c] = vp[4];
     }
 }
@@ -927,13 +927,12 @@ __device__ __forceinline__ int slot_sample(const DecArgs& A, int slot)
     return A.perm ? ld32<int>(A.perm, (unsigned)s * 4u) : s;
 }
 
-// Tile schedule shared by the decoder kernels: wave `wg` of `nw` takes blocks of 2^sh consecutive tiles, dealt round-robin over the
-// waves.  Single tiles (sh = 0) everywhere: dealing keeps the waves' loads equal (tiles in sparsely sampled space cost the scatter
-// one flush per sample, tiles inside a well-sampled cell one per tile; waves that owned a contiguous range of the former ran 100 us
-// behind), and blocks of 4 left up to 13 % of the forward's waves idle at 5000 rays.
-__device__ __forceinline__ int tile_shift(int, int) { return 0; }
-__device__ __forceinline__ int tile_of(int k, int wg, int nw, int sh) { return ((((k >> sh) * nw + wg)) << sh) + (k & ((1 << sh) - 1)); }
-__device__ __forceinline__ int tiles_per_wave(int ntasks, int nw, int sh) { return ((((ntasks + (1 << sh) - 1) >> sh) + nw - 1) / nw) << sh; }
+// Tile schedule shared by the decoder kernels: single tiles dealt round-robin, wave `wg` of `nw` takes tiles wg, wg + nw, ...  Dealing
+// keeps the waves' loads equal (tiles in sparsely sampled space cost the scatter one flush per sample, tiles inside a well-sampled
+// cell one per tile; waves that owned a contiguous range of the former ran 100 us behind), and dealing blocks of 4 consecutive tiles
+// left up to 13 % of the forward's waves idle at 5000 rays.
+__device__ __forceinline__ int tile_of(int k, int wg, int nw) { return k * nw + wg; }
+__device__ __forceinline__ int tiles_per_wave(int ntasks, int nw) { return (ntasks + nw - 1) / nw; }
 
 // The backward of a TRAINABLE decoder needs the block outputs h0..h4 as the X operands of its weight gradients.  The
 // forward stores them (one coalesced KiB per quad and tile) instead of the backward recomputing the MLP: 640 B per sample
@@ -956,10 +955,9 @@ __device__ __forceinline__ void decode_fwd_body(const DecArgs& A, int bid, int n
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
     const float* imgf = reinterpret_cast<const float*>(smem);
     const int ntasks = (A.M + 15) >> 4;
-    const int tsh = tile_shift(ntasks, nb * NW);
-    const int kmax = tiles_per_wave(ntasks, nb * NW, tsh);
+    const int kmax = tiles_per_wave(ntasks, nb * NW);
     for (int k = 0; k < kmax; ++k) {
-        const int task = tile_of(k, bid * NW + wave, nb * NW, tsh);
+        const int task = tile_of(k, bid * NW + wave, nb * NW);
         if (task >= ntasks) break;
         asm volatile("" ::: "memory");      // keep the LDS fragment reads inside the loop (LICM would hoist + spill them)
         const int slot = task * 16 + j;
@@ -1475,8 +1473,10 @@ __device__ __forceinline__ void tri_grad_p(const GridD& G, const Tri& T, int g, 
 // K4 (frozen decoders): backward over 16-sample tiles from the ReLU bits the forward saved:
 // g_out -> chain of transposed products -> g_c (-> run-deduplicated scatter into the grid gradient)
 // [-> g_p for NSK_GRAD_RAYS: embedding and trilinear derivatives].  LDS holds the backward image.
-// Trainable decoders use decode_bwd_train_body (nsk_train.h).
-// The same copy in two halves, so that a body can put the first tile's own loads between them: the image loads are issued, then the
+// Trainable decoders go through decode_bwd_train_any (nsk_train.h): decode_bwd_train_m_body for the middle and colour decoders,
+// decode_bwd_train_body for the coarse and fine ones and for every decoder under nsk_set_backward_mode 0.
+//
+// copy_image_to_lds in two halves, so that a body can put the first tile's own loads between them: the image loads are issued, then the in two halves, so that a body can put the first tile's own loads between them: the image loads are issued, then the
 // sample loads (which wait only for the sample index fetched before the image: loads return in order), then the image is stored.
 // Until round 3 a body copied its image, met at the barrier and only then started the chain index -> sample -> corners: three round
 // trips behind the image's one ("first stage" 9 000 cycles after an image copy of 2 000).
@@ -1543,8 +1543,7 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         S_.mm = mm_;
     };
     const int nw = nb * NW, wg = bid * NW + wave;
-    const int tsh = tile_shift(ntasks, nw);
-    const int kmax = tiles_per_wave(ntasks, nw, tsh);
+    const int kmax = tiles_per_wave(ntasks, nw);
     // SKIP: a dead tile must cost nothing -- a first form looked at each tile's bytes in turn and still staged its loads: every dead tile was a
     // dependent memory round trip (index -> sample), and at two waves per SIMD a wave hid none of it (K3: the launch got 3 us LONGER).  So the
     // wave reads the liveness of 64 of its tiles at once -- lane l the sixteen bytes of its l-th tile, one 16-byte load, one ballot -- and walks
@@ -1553,11 +1552,11 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
     typedef unsigned int lu4 __attribute__((ext_vector_type(4)));
     unsigned long long lmask = 0; int lblk = 0, ran = 0;
     auto live_load = [&](int kb) {                     // the bytes of tile kb + lane of this wave (clamped into the array)
-        const int t = min(tile_of(kb + lane, wg, nw, tsh), ntasks - 1);
+        const int t = min(tile_of(kb + lane, wg, nw), ntasks - 1);
         return ld32<lu4>(A.live, (unsigned)t * 16u);
     };
     auto live_ballot = [&](const lu4& w, int kb) {
-        const int t = tile_of(kb + lane, wg, nw, tsh);
+        const int t = tile_of(kb + lane, wg, nw);
         const int nv = A.M - t * 16;                    // valid slots of the tile (the last one may be ragged; its missing slots hold nothing)
         const unsigned bits = A.live_bit * 0x01010101u;
         bool lv = false;
@@ -1584,14 +1583,14 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         lu4 lw0;
         if constexpr (SKIP) lw0 = live_load(0);
         int mm0 = 0;
-        if constexpr (!SKIP) mm0 = slot_sample(A, slot_of(tile_of(0, wg, nw, tsh)));
+        if constexpr (!SKIP) mm0 = slot_sample(A, slot_of(tile_of(0, wg, nw)));
         image_issue<64 * NW>(img_regs, img_src, IMG_F / 4);
         if constexpr (SKIP) {
             lmask = live_ballot(lw0, 0);
             kfirst = next_live(-1);
-            mm0 = slot_sample(A, slot_of(tile_of(kfirst, wg, nw, tsh)));
+            mm0 = slot_sample(A, slot_of(tile_of(kfirst, wg, nw)));
         }
-        stage(tile_of(kfirst, wg, nw, tsh), mm0, nx);
+        stage(tile_of(kfirst, wg, nw), mm0, nx);
         if constexpr (DYN) {
             constexpr int PER = (NSK_MEDIAN_FUSED_MAX + 64 * NW - 1) / (64 * NW);
             float rv[PER];
@@ -1608,11 +1607,11 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         }
     }
     if constexpr (SKIP) k1 = next_live(kfirst);
-    int mm_next = slot_sample(A, slot_of(tile_of(k1, wg, nw, tsh)));
+    int mm_next = slot_sample(A, slot_of(tile_of(k1, wg, nw)));
     const bool det = (A.flags & 0x8000u) != 0;      // deterministic debug mode: every wave walks all kmax rounds (they meet at barriers)
     int k2 = 2;
     for (int k = kfirst; k < kmax; k = k1, k1 = k2) {      // !SKIP: k, k1 = k + 1, k2 = k + 2 as ever; SKIP: this wave's next live tiles
-        const int task = tile_of(k, wg, nw, tsh);
+        const int task = tile_of(k, wg, nw);
         if constexpr (!SKIP) { if (task >= ntasks && !det) break; }
         asm volatile("" ::: "memory");      // keep the LDS fragment reads inside the loop (LICM would hoist + spill them)
         const bool valid = task * 16 + j < A.M;
@@ -1636,8 +1635,8 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         float unscale = 1.f;
         if constexpr (B16) unscale = chain_scale<OD>(gout);
         const unsigned long long mask = nx.mask;
-        stage(tile_of(k1, wg, nw, tsh), mm_next, nx);
-        mm_next = slot_sample(A, slot_of(tile_of(k2, wg, nw, tsh)));
+        stage(tile_of(k1, wg, nw), mm_next, nx);
+        mm_next = slot_sample(A, slot_of(tile_of(k2, wg, nw)));
         f4 xcos[6];
         if constexpr (NEED_E) { f4 e[6]; embed<true>(Bm, g, px, py, pz, e, xcos); }
         f4 gh[2];                                                // g_h4 = Wo^T g_out
@@ -1795,8 +1794,7 @@ __global__ __launch_bounds__(512) void k_decode_bwd(DecArgs A) { decode_bwd_body
 // trainable body's ~240 and run at two waves per SIMD.  Here a workgroup is 16 waves (four per SIMD: two more tiles' latency chains -- scatter
 // fences, LDS round trips, MFMA dependencies -- to interleave) around one LDS image.
 #define NSK_FROZEN_NW 16
-template <bool RAYS>
-__global__ __launch_bounds__(64 * NSK_FROZEN_NW) void k_decode_bwd_frozen(MultiArgs MA)
+__global__ __launch_bounds__(64 * NSK_FROZEN_NW) void k_decode_bwd_frozen(MultiArgs MA)      // (no ray gradients: those launches are k_decode_bwd_multi<true> / k_decode_bwd_track)
 {
     if (MA.sum_n > 0 && blockIdx.x == gridDim.x - 1) { block_sum(MA.sum_src, MA.sum_n, MA.sum_dst); return; }
     if ((int)blockIdx.x >= MA.wg_end[MA.n - 1]) { sort_scan_body<NSK_FROZEN_NW / 4>(MA.scan, (int)blockIdx.x - MA.wg_end[MA.n - 1]); return; }      // see k_decode_bwd_multi
@@ -1804,9 +1802,8 @@ __global__ __launch_bounds__(64 * NSK_FROZEN_NW) void k_decode_bwd_frozen(MultiA
     while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;
     const int b0 = r == 0 ? 0 : MA.wg_end[r - 1];
     const int bid = blockIdx.x - b0, nb = MA.wg_end[r] - b0;
-    static_assert(!RAYS, "the frozen kernel serves launches without ray gradients");
     switch (MA.which[r]) {
-    case 0: decode_bwd_body<0, RAYS, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
+    case 0: decode_bwd_body<0, false, NSK_FROZEN_NW>(MA.a[r], bid, nb); break;
     case 1: decode_bwd_frozen_role<1, NSK_FROZEN_NW>(MA, r, bid, nb); break;
     case 2: decode_bwd_frozen_role<2, NSK_FROZEN_NW>(MA, r, bid, nb); break;
     default: decode_bwd_frozen_role<3, NSK_FROZEN_NW>(MA, r, bid, nb); break;

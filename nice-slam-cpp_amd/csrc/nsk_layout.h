@@ -11,7 +11,6 @@
 #pragma once
 
 #define NSK_E 93        // GaussianFFT mapping size (reference src/models/MLP.cpp:21)
-#define NSK_EP 96       // padded to 6 quads
 #define NSK_HID 32        // hidden size (reference src/main.cpp:29)
 
 // ---- forward image of MLP (middle / fine / color), CQ = c_dim/16 --------------------------------------

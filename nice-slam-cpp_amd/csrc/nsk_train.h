@@ -193,8 +193,7 @@ __device__ __forceinline__ void pn_put_masked(char* __restrict__ pn, int moff, i
 
 // the tiles of one phase owned by this wave, accumulated over the panel's 128 samples
 template <int NSL>
-__device__ __forceinline__ void pn_tiles(const char* __restrict__ pn, int moff, int RT, int NC, int rowsum, int wave, int lane, f4* acc, int xrow0 = PN_GROWS,
-                                         int grow0 = 0)
+__device__ __forceinline__ void pn_tiles(const char* __restrict__ pn, int moff, int RT, int NC, int rowsum, int wave, int lane, f4* acc, int xrow0 = PN_GROWS)
 {
     const int r = lane & 15, sq = lane >> 4;
     const int ntiles = RT * NC + (rowsum ? RT : 0);
@@ -205,7 +204,7 @@ __device__ __forceinline__ void pn_tiles(const char* __restrict__ pn, int moff, 
             const bool rs = tile >= RT * NC;
             const int rt = rs ? tile - RT * NC : tile / NC;
             const int ch = rs ? 0 : tile % NC;
-            const char* ga = pn + (grow0 + 16 * rt + r) * PN_RB + 16 * sq;
+            const char* ga = pn + (16 * rt + r) * PN_RB + 16 * sq;
             const char* xb = pn + (xrow0 + 16 * ch + r) * PN_RB + 16 * sq;
             f4 d0 = acc[k], d1 = (f4)(0.f);
 #pragma unroll
@@ -264,7 +263,7 @@ __device__ __forceinline__ void pn_flush(float* __restrict__ g_dec, const TrainP
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // (none of these barriers may ever be skipped: the scatter's run table shares LDS with the panel, and a run without them faulted the GPU)
 
-template <int WHICH, bool RAYS, bool FULL = false>      // FULL: the chain's products on the fp32 MFMA (nsk_set_backward_mode 0); the weight-gradient panels keep two bf16 pieces
+template <int WHICH, bool RAYS, bool FULL = false>      // FULL: instantiated for k_decode_bwd_multi_full (nsk_set_backward_mode 0); the weight-gradient panels keep two bf16 pieces
 __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid, int nb)
 {
     constexpr bool XYZ = WHICH != 0;
@@ -274,13 +273,9 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
     // is recomputed here and the backward (transposed) image stays in LDS for the whole kernel.  The fine decoder (64 input
     // features, images too large for LDS beside the panel) keeps the older form: forward recompute, fragments streamed from L2.
     constexpr bool SAVED = WHICH != 2;
-    // H16: the chain's transposed products (g_c, g_h, g_e) on the fp16 matrix cores with 2-piece operands and a per-sample scale
-    // (nsk_device.h: MlpBwdImgH, chain_scale) instead of 240 fp32 MFMAs per tile; the image has the size of the fp32 one.
-    // 90 MFMAs of 16 cycles replace 240 of 32.  First built, it did not shorten the iteration (K3: 27.7 against 27.1 us per 128
-    // samples) because it spilled 59 VGPRs -- loop-invariant per-lane addresses, reloaded from scratch inside the loop, each reload
-    // a vmcnt wait behind the previous iteration's atomics.  Without spills (opaque lane index per iteration, g_e formed after the
-    // chain): 24 us, backward 270 -> 240 us at K3.
-    constexpr bool H16 = XYZ && SAVED && !FULL;
+    // The chain's products here are always fp32 MFMAs on the fp32 image: the middle and colour decoders run their fp16 chain in
+    // decode_bwd_train_m_body (decode_bwd_train_any) and come here only for nsk_set_backward_mode 0.
+    static_assert(FULL || WHICH == 0 || WHICH == 2, "the middle and colour decoders take this body only with FULL");
     typedef MlpFwdImg<CQ> FI;
     typedef TrainPlan<WHICH> PL;
     constexpr PL plan{};
@@ -293,17 +288,14 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
     char* pn = reinterpret_cast<char*>(smf + IMG_F);     // shared panel (plane H; plane M at + PM)
     constexpr int PM = PN_MOFF(CQ);
     float* scratch = smf + IMG_F + wave * 1056;     // per-wave scatter scratch (NSK_SCRATCH_FLOATS <= 1056): the head of plane H, idle between the last phase and phase OUT
-    static_assert(!H16 || MlpBwdImgH::TOTAL_F == BWD_F, "the fp16 backward image takes the fp32 image's place in LDS");
-    copy_image_to_lds<512>(smem, H16 ? reinterpret_cast<const f4*>(A.bimg16) : A.bimg, IMG_F / 4);
+    copy_image_to_lds<512>(smem, A.bimg, IMG_F / 4);
     __syncthreads();
-    const h8* imgh = reinterpret_cast<const h8*>(smem);
     const f4* fimg = A.img;                         // !SAVED only: forward fragments from L2
     const float* fimgf = reinterpret_cast<const float*>(fimg);
     const f4* bimg = SAVED ? smem : A.bimg;
     const float* bimgf = reinterpret_cast<const float*>(bimg);
     const float* Bm = nullptr;                      // embedding matrix [3][96]
     if constexpr (XYZ) Bm = SAVED ? bimgf + MlpBwdImg::P_BM : fimgf + FI::P_BM;
-    static_assert(MlpBwdImgH::P_BM == MlpBwdImg::P_BM && MlpBwdImgH::P_WO == MlpBwdImg::P_WO, "same fp32 tail in both images");
     const float* Bmb = Bm;
     const float* Wo = SAVED ? bimgf + (XYZ ? MlpBwdImg::P_WO : CoarseBwdImg::P_WO) : fimgf + FI::P_WO;
 
@@ -312,14 +304,14 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
     for (int k = 0; k < plan.nslots; ++k) acc[k] = (f4)(0.f);
 
     const int ntasks = (A.M + 15) >> 4;
-    const int iters = tiles_per_wave(ntasks, nb * 8, 0);
+    const int iters = tiles_per_wave(ntasks, nb * 8);
     const bool scat = (A.flags & 1u) && A.grid.g;
     // Everything iteration it+1 reads from global memory (its samples, upstream gradient, gathered features, and the
     // forward image) is fetched at the end of iteration it BEFORE that iteration's scatter: vmcnt retires in order, so a
     // load issued after the atomics would wait for all of them (measured: 13k cycles at the top of an iteration).
     struct Staged { float px, py, pz, zz; int n; bool valid; f4 gr; f4 xc[CQ]; f4 h4[2]; unsigned long long mask; } nx;
-    // single tiles dealt round-robin (tile_of with sh = 0): this role synchronises its 8 waves every iteration and carries nothing over
-    auto task_of = [&](int it_) { return tile_of(it_, bid * 8 + wave, nb * 8, 0); };
+    // single tiles dealt round-robin (tile_of): this role synchronises its 8 waves every iteration and carries nothing over
+    auto task_of = [&](int it_) { return tile_of(it_, bid * 8 + wave, nb * 8); };
     auto slot_of = [&](int it_) { return task_of(it_) * 16 + j; };
     auto stage_a = [&](int it_, int mm, Staged& S_) {  // issue the sample loads (no use, no wait); mm = the slot's sample (perm, fetched an iteration earlier)
         const int task = task_of(it_);
@@ -368,8 +360,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
         f4 go;                                           // G of phase OUT: g_out itself (rows >= OD zero)
 #pragma unroll
         for (int i = 0; i < 4; ++i) go[i] = (4 * g + i) < OD ? gout[(4 * g + i) < OD ? (4 * g + i) : 0] : 0.f;
-        float us = 1.f;                                  // H16: gout becomes a power-of-two multiple of itself, us takes the scale off again
-        if constexpr (H16) us = chain_scale<OD>(gout);
         Act<CQ> C;
         ActC CC;
         f4 xcos[6];
@@ -412,7 +402,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
         f4 ge[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) ge[q] = (f4)(0.f);
-        H2 xa3;
         auto load_h = [&](auto KC) {
             constexpr int k = decltype(KC)::value;
             const f4* src = A.hsave + ((size_t)htask * 10 + 2 * k) * 64 + lane;
@@ -426,15 +415,10 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             // one phase ahead, as it was, every W phase opened with s_waitcnt vmcnt on a load issued ~1000 cycles earlier
             if constexpr (SAVED && l >= 2) load_h(std::integral_constant<int, l - 2>{});
             if constexpr (XYZ) {
-                if constexpr (H16) {        // (the low accumulators join g_c layer by layer: eight registers fewer across the panel phases)
-                    const H2 xg = split_block_h(gh[0], gh[1]);
-                    f4 gl[2] = {(f4)(0.f), (f4)(0.f)};
-                    gemm_h(imgh, MlpBwdImgH::FT(l), lane, xg, gc, gl);
-                    gc[0] += gl[0] * (1.f / NSK_H16_SCALE); gc[1] += gl[1] * (1.f / NSK_H16_SCALE);
-                } else gemm<2, 2>(bimg, MlpBwdImg::FT(l), lane, gh, gc);                 // g_c += fc[l]^T g_h
+                gemm<2, 2>(bimg, MlpBwdImg::FT(l), lane, gh, gc);                 // g_c += fc[l]^T g_h
                 // ---- phase FC_l: G = g_h, X = c ------------------------------------------------------------
-                pn_put(pn, PM, 0, wave, lane, gh[0], us);
-                pn_put(pn, PM, 16, wave, lane, gh[1], us);
+                pn_put(pn, PM, 0, wave, lane, gh[0]);
+                pn_put(pn, PM, 16, wave, lane, gh[1]);
 #pragma unroll
                 for (int q = 0; q < CQ; ++q) pn_put(pn, PM, PN_GROWS + 16 * q, wave, lane, C.xc[q]);
                 lds_barrier();
@@ -447,12 +431,10 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ga[r][i] = ((mask >> (8 * l + 4 * r + i)) & 1ull) ? gh[r][i] : 0.f;
-            H2 xa;
-            if constexpr (H16) xa = split_block_h(ga[0], ga[1]);       // (split again rather than masking g_h's pieces: those would stay live across phase FC)
             // ---- phase W_l: G = g_a, X = layer input ----------------------------------------------------------
             {
-                pn_put(pn, PM, 0, wave, lane, ga[0], us);
-                pn_put(pn, PM, 16, wave, lane, ga[1], us);
+                pn_put(pn, PM, 0, wave, lane, ga[0]);
+                pn_put(pn, PM, 16, wave, lane, ga[1]);
                 if constexpr (XYZ) {
                     if constexpr (l == 0) {
                     } else if constexpr (l == 3) {
@@ -487,17 +469,7 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                     lds_barrier();
                 }
             }
-            if constexpr (H16) {
-                // g_e = W3e^T g_a3 + W0e^T g_a0 is needed only after the chain: layer 3 keeps the pieces of g_a3 (8 registers) instead of
-                // forming its share of g_e (24 registers) three layers early
-                if constexpr (l == 3) xa3 = xa;
-                if constexpr (l == 0) { gemm_e_h(imgh, MlpBwdImgH::W3ET, lane, xa3, ge); gemm_e_h(imgh, MlpBwdImgH::W0ET, lane, xa, ge); }
-                if constexpr (l >= 1) {
-                    f4 ghn[2] = {(f4)(0.f), (f4)(0.f)}, ghl[2] = {(f4)(0.f), (f4)(0.f)};
-                    gemm_h(imgh, MlpBwdImgH::WT(l), lane, xa, ghn, ghl);
-                    gh[0] = ghn[0] + ghl[0] * (1.f / NSK_H16_SCALE); gh[1] = ghn[1] + ghl[1] * (1.f / NSK_H16_SCALE);
-                }
-            } else if constexpr (XYZ) {
+            if constexpr (XYZ) {
                 if constexpr (l == 3) gemm_e(bimg, MlpBwdImg::W3ET, lane, ga, ge);
                 if constexpr (l == 0) gemm_e(bimg, MlpBwdImg::W0ET, lane, ga, ge);
                 if constexpr (l >= 1) {
@@ -522,9 +494,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
         layer(std::integral_constant<int, 1>{});
         layer(std::integral_constant<int, 0>{});
         if (it + 1 < iters) { stage_a(it + 1, mm_next, nx); mm_next = slot_sample(A, slot_of(it + 2)); }
-        if constexpr (H16) {        // take the sample's scale off g_c (g_e keeps it: phase DB and g_p below)
-            gc[0] *= us; gc[1] *= us;
-        }
         float gp[3] = {0.f, 0.f, 0.f};
         asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));     // opaque: forces the recomputation below instead of keeping T / cos live
         tri_setup(A.grid, A.bound, px, py, pz, T);
@@ -537,7 +506,7 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
                 f4 pq;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { int row = 4 * g + i; pq[i] = !valid ? 0.f : (row == 0 ? px : (row == 1 ? py : (row == 2 ? pz : 0.f))); }
-                pn_put(pn, PM, 0, wave, lane, pq, us);          // (H16: g_s below still carries the sample's scale; it comes off on this side of the product)
+                pn_put(pn, PM, 0, wave, lane, pq);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) pn_put(pn, PM, PN_EROWS(CQ) + 16 * q, wave, lane, ge[q]);
                 lds_barrier();
@@ -554,7 +523,6 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { gp[0] += ge[q][i] * b0[i]; gp[1] += ge[q][i] * b1[i]; gp[2] += ge[q][i] * b2[i]; }
                 }
-                if constexpr (H16) { gp[0] *= us; gp[1] *= us; gp[2] *= us; }
             }
         }
         if constexpr (RAYS) {
@@ -618,7 +586,8 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
 // iteration on 13 phases; here the two weight phases of a layer (dFc_l = g_h c^T and dW_l = g_a x^T) share one store -> barrier ->
 // tiles -> barrier sequence, and the grid features c are stored once per iteration.  That needs g_h, g_a, c and the layer input in
 // the panel at the same time (128 rows + 96 rows of e = 224 rows, 121 856 B); the room comes from the e-part fragments
-// (W0e^T, W3e^T: 24 KB), which g_e's two products -- both after the chain now -- read from global memory (L2) instead of LDS.
+// (W0e^T, W3e^T: 24 KB), which have no place of their own in LDS: g_e's two products -- both after the chain now -- read a copy that
+// the workgroup makes once per iteration into panel rows that are idle by then (see eimg in the body).
 //   rows   0..31  G1: g_h (phase OUT: g_out; phase DB: p)         rows  64..95  XC: c (written once per iteration)
 //   rows  32..63  G2: g_a                                          rows  96..127 XH: layer input h_{l-1} (phase OUT: h4)
 //   rows 128..223 E : sin(pB), later g_s                           (the per-wave scatter scratch is plane H of rows 0..124)
@@ -634,8 +603,8 @@ __device__ __forceinline__ void decode_bwd_train_body(const DecArgs& A, int bid,
 #define PM_IMG_F (PM_IMG_FRAG_F + 128 + 288)            // + Wo + B
 #define PM_LDS_BYTES (PM_IMG_F * 4 + PM_ROWS * PN_RB * 2)
 
-// acc[0..5] += W?e^T x with the fragments read from global memory, one 32-row slice (4 fragment loads) at a time
-// the same from an LDS copy of fragment groups W0ET..W3ET+5 (group index relative to W0ET)
+// acc[0..5] += W3e^T x3 + W0e^T x0 from an LDS copy of fragment groups W0ET..W3ET+5 (group index relative to W0ET), one 32-row slice (4 fragment
+// loads) at a time
 __device__ __forceinline__ void gemm_e2_lds(const h8* __restrict__ eimg, int lane, const H2& x3, const H2& x0, f4 (&acc)[6])
 {
     constexpr int G3 = MlpBwdImgH::W3ET - MlpBwdImgH::W0ET;
@@ -669,29 +638,6 @@ __device__ __forceinline__ f4 mfma_bf16_k16(unsigned a01, unsigned a23, unsigned
 {
     typedef unsigned int u2v __attribute__((ext_vector_type(2)));
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4v, (u2v){a01, a23}), __builtin_bit_cast(s4v, (u2v){b01, b23}), c, 0, 0, 0);
-}
-// (the loads of slice a + 1 are issued before the products of slice a: written slice by slice, every slice opened with a wait for an L2
-// round trip -- three of them, ~1 000 cycles each, per tile)
-struct FragE { FragH a30, a31, a00, a01; };
-__device__ __forceinline__ FragE load_frag_e(const h8* __restrict__ gimg, int a, int lane)
-{
-    FragE F;
-    F.a30 = load_frag_h(gimg, MlpBwdImgH::W3ET + 2 * a, lane); F.a31 = load_frag_h(gimg, MlpBwdImgH::W3ET + 2 * a + 1, lane);
-    F.a00 = load_frag_h(gimg, MlpBwdImgH::W0ET + 2 * a, lane); F.a01 = load_frag_h(gimg, MlpBwdImgH::W0ET + 2 * a + 1, lane);
-    return F;
-}
-__device__ __forceinline__ void gemm_e2_global(const h8* __restrict__ gimg, int lane, const H2& x3, const H2& x0, f4 (&acc)[6])
-{
-    FragE F[3];
-    F[0] = load_frag_e(gimg, 0, lane);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (a + 1 < 3) F[a + 1] = load_frag_e(gimg, a + 1, lane);
-        f4 tH[2] = {acc[2 * a], acc[2 * a + 1]}, tL[2] = {(f4)(0.f), (f4)(0.f)};
-        mac_block_h(F[a].a30, F[a].a31, x3, tH, tL);
-        mac_block_h(F[a].a00, F[a].a01, x0, tH, tL);
-        acc[2 * a] = tH[0] + tL[0] * (1.f / NSK_H16_SCALE); acc[2 * a + 1] = tH[1] + tL[1] * (1.f / NSK_H16_SCALE);
-    }
 }
 
 // ---- weight-gradient tiles of the merged-phase body as JOBS (round 3) ------------------------------------------------------------------------
@@ -835,7 +781,7 @@ __device__ __forceinline__ void pn_phase_jobs(const char* __restrict__ pn, int m
     pn_jobs_seq<WHICH, JP.first[PH]>(pn, moff, wave, lane, acc, std::make_integer_sequence<int, JP.first[PH + 1] - JP.first[PH]>{});
 }
 // store the tiles of job JJ (if this wave owns it) into the workgroup's slab, canonical parameter layout
-template <int WHICH, int JJ, bool SKIP_DB = false>
+template <int WHICH, int JJ, bool SKIP_DB>
 __device__ __forceinline__ void pn_job_flush(float* __restrict__ g_dec, int wave, int lane, const f4* acc)
 {
     constexpr JobPlan<WHICH> JP{};
@@ -846,7 +792,6 @@ __device__ __forceinline__ void pn_job_flush(float* __restrict__ g_dec, int wave
     const int x = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int k = 0; k < J.nt; ++k) {
-        constexpr int dummy = 0; (void)dummy;
         const TrainPhase P = plan.p[J.ph[k]];
         if (SKIP_DB && J.ph[k] == TrainPlan<WHICH>::P_DB) continue;       // (mapping steps keep d/dB outside the jobs: see the loop's tail)
         const bool rs = J.ch[k] < 0;
@@ -903,7 +848,7 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
     for (int k = 0; k < JP.nslots; ++k) acc[k] = (f4)(0.f);
 
     const int ntasks = (A.M + 15) >> 4;
-    const int iters = tiles_per_wave(ntasks, nb * 8, 0);
+    const int iters = tiles_per_wave(ntasks, nb * 8);
     const bool scat = (A.flags & 1u) && A.grid.g;
     // Staged: what iteration it + 1 needs, fetched during iteration it in three steps, none of which waits for a load it has just issued:
     //   stage_a   (after the chain)        sample data as loaded (z, ray), upstream gradient, ReLU bits, h4   -- issue only
@@ -912,7 +857,7 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
     // (until round 3 stage_a computed p at once and stage_b reduced its gather at once: ~2 700 + ~5 000 cycles of an iteration spent
     // waiting for round trips to L2 with nothing else to issue -- DESIGN.md section 4.3, round 3)
     struct Staged { SampleRaw r; float px, py, pz; int mm; bool valid; f4 gr; f4 xc[CQ]; f4 h4[2]; unsigned long long mask; } nx;
-    auto task_of = [&](int it_) { return tile_of(it_, bid * 8 + wave, nb * 8, 0); };
+    auto task_of = [&](int it_) { return tile_of(it_, bid * 8 + wave, nb * 8); };
     auto slot_of = [&](int it_) { return task_of(it_) * 16 + j; };
     auto stage_a = [&](int it_, int mm, Staged& S_) {
         const int task = task_of(it_);
@@ -929,7 +874,7 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
     auto stage_b1 = [&](Staged& S_) {
         sample_finish(A, S_.r, S_.px, S_.py, S_.pz);
         tri_setup(A.grid, A.bound, S_.px, S_.py, S_.pz, Tn);
-        tri_gather_issue<true>(A.grid, Tn, g, GR);
+        tri_gather_issue(A.grid, Tn, g, GR);
     };
     auto stage_b2 = [&](Staged& S_) { tri_gather_reduce(Tn, GR, S_.xc[0], S_.xc[1]); };
     int mm_next = 0;
@@ -966,6 +911,12 @@ __device__ __forceinline__ void decode_bwd_train_m_body(const DecArgs& A, int bi
         f4 go;
 #pragma unroll
         for (int i = 0; i < 4; ++i) go[i] = (4 * g + i) < OD ? gout[(4 * g + i) < OD ? (4 * g + i) : 0] : 0.f;
+        // The chain's transposed products (g_c, g_h, g_e) run on the fp16 matrix cores with 2-piece operands and a per-sample scale (nsk_device.h:
+        // MlpBwdImgH, chain_scale): gout becomes a power-of-two multiple of itself, us takes the scale off again.  90 MFMAs of 16 cycles replace
+        // 240 of 32.  First built (in the one-phase-per-weight body, which has since lost it), the fp16 chain did not shorten the iteration (K3:
+        // 27.7 against 27.1 us per 128 samples) because it spilled 59 VGPRs -- loop-invariant per-lane addresses, reloaded from scratch inside the
+        // loop, each reload a vmcnt wait behind the previous iteration's atomics.  Without spills (opaque lane index per iteration, g_e formed
+        // after the chain): 24 us, backward 270 -> 240 us at K3.
         const float us = chain_scale<OD>(gout);
         const unsigned long long mask = nx.mask;
         const int htask = min(task_of(it), ntasks - 1);

@@ -312,6 +312,54 @@ def test_map_prepare_and_graphs_do_not_step_on_each_other(order):
     assert rel_l2(d1, d0) < 1e-4
 
 
+@pytest.mark.parametrize("render", ["before-adam", "after-adam"])
+def test_map_prepare_survives_a_workspace_growth(render):
+    """A prepared batch across a workspace growth: prepare(B), step(A), Adam, step(B), Adam on 64-ray batches, with a 256-ray render -- the
+    first call of that size, so the workspace and both sampling sets are released and allocated anew -- between step(A) and its Adam step
+    (B is sampled and its offsets scanned; the placement has nothing left to ride on) or after that Adam step (B is complete).  The growth
+    drops the batch: B's own step samples it afresh, a `sample` launch of its own in the profile, and losses and parameters are those of the
+    same calls with nothing prepared (up to the order of the gradient sums).  A rider or a swap that kept a pointer into the released set
+    would write into, or read from, freed memory."""
+    sc = scenes.make_scene(11, scenes.SMALL_GRID_SHAPES, grid_std=0.05)
+    B = []
+    for k in range(2):
+        r = scenes.make_rays(90 + k, 64, sc["bound"], n_frames=2)
+        B.append([cu(r[x]) for x in ("rays_o", "rays_d", "gt_depth", "gt_color")] + [float(r["gt_depth"].max())])
+    big = scenes.make_rays(77, 256, sc["bound"], n_frames=2)
+    bro, brd, bgd, bgm = cu(big["rays_o"]), cu(big["rays_d"]), cu(big["gt_depth"]), float(big["gt_depth"].max())
+    out = []
+    for prepare in (False, True):
+        ctx = make_ctx(sc, trainable=["color"])
+        ctx.set_sort_mode(1)
+        loss = torch.zeros(1, device="cuda")
+        losses = []
+        with torch.cuda.stream(ctx.tstream):
+            if prepare:
+                ctx.map_prepare("color", B[1][0], B[1][1], B[1][2], B[1][4], flags=3)
+            ctx.map_step("color", *B[0][:4], B[0][4], 0.2, True, flags=3, loss=loss)
+            losses.append(float(loss))
+            if render == "before-adam":
+                ctx.render_forward("color", bro, brd, bgd, bgm)
+            ctx.adam_step(LR)
+            if render == "after-adam":
+                ctx.render_forward("color", bro, brd, bgd, bgm)
+            ctx.profile_begin()
+            ctx.map_step("color", *B[1][:4], B[1][4], 0.2, True, flags=3, loss=loss)
+            names = set(ctx.profile_end().keys())
+            losses.append(float(loss))
+            ctx.adam_step(LR)
+        ctx.sync()
+        out.append((losses, {k: ctx.grid_download(k) for k in ("middle", "fine", "color")}, ctx.decoder_download("color"), names))
+        ctx.close()
+    (l0, g0, d0, n0), (l1, g1, d1, n1) = out
+    assert "sample" in n0 and "sample" in n1, (n0, n1)                   # dropped by the growth: sampled afresh by its own step
+    assert np.all(np.isfinite(l1)) and np.allclose(l0, l1, rtol=1e-5), (l0, l1)
+    for k in g0:
+        assert np.isfinite(g1[k]).all()
+        assert rel_l2(g1[k] - sc["grids"][k], g0[k] - sc["grids"][k]) < 5e-3, k          # (Adam amplifies last-bit differences of the sums: see test_gpu_configs)
+    assert rel_l2(d1, d0) < 1e-4
+
+
 def test_map_prepare_reads_the_mask_buffer_installed_at_registration():
     """The keep mask of a prepared batch is the BUFFER installed (nsk_set_ray_mask) when nsk_map_prepare was called; its contents are read when
     the batch's sampling runs (inside the current step's composite launch), so it must be a different buffer from the current step's mask and
