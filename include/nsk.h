@@ -664,6 +664,55 @@ int nsk_depth_pair_stats(nsk_ctx* ctx, const float* d_a, const float* d_b, int V
  *   A view whose direction is parallel to up, or whose target is its origin, has NaN entries: nsk_mesh_depth then draws nothing for it. */
 int nsk_depth_views(nsk_ctx* ctx, const float* d_vertices, int n_vertices, float h_box[6], unsigned long long seed, double shrink, int V,
                     float* h_w2c);
+/* nsk_depth_views_range: views first .. first + V - 1 of the stream nsk_depth_views draws from the box h_box (lo x y z, hi x y z), as h_w2c
+ * [V][16]: view first + k reads u_m = (hash_u32(seed, first + k, m) >> 8) 2^-24 and is formed as stated above.  Host only: no context, no
+ * device.  nsk_depth_views is this with first = 0 (after it has found the box).  first >= 0 and first + V <= 2^32 (the hash's counter is
+ * 32 bits wide); V = 0 is valid. */
+int nsk_depth_views_range(const float h_box[6], unsigned long long seed, double shrink, long long first, int V, float* h_w2c);
+
+/* ---- culling a mesh to what a trajectory saw; depth views clear of the unseen (upstream src/tools/cull_mesh.py, and the unseen points that
+ * eval_recon.py's calc_2d_metric rejects views with) ---------------------------------------------------------------------------------- */
+/* nsk_points_seen: the points of a list (d_points [n][3] float32, device) that at least one of K frames saw: d_seen[p] = 1, else 0 (device,
+ * one byte per point).  d_depth [K][H][W] floats on the device or NULL; h_w2c [K][16] row-major world-to-camera on the host; the camera
+ * looks along -z.  Frame k sees the point p by the rule of nsk_lattice_seen, word for word -- every operation an fp32 operation of its own
+ * (no FMA):
+ *   c_a = ((w[4a] p0 + w[4a+1] p1) + w[4a+2] p2) + w[4a+3], a = 0..2;   d = -c_2 > 0;
+ *   u = cx + (fx c_0) / d,  v = cy - (fy c_1) / d;   i = floor(u + 0.5), j = floor(v + 0.5)   (the nearest pixel);
+ *   edge <= i < W - edge and edge <= j < H - edge, decided on the floats (a NaN fails; an edge that leaves no pixel is valid: nothing is seen);
+ *   D = d_depth[k][j][i] is finite and > 0 (a pixel without a measurement sees nothing);   d <= D + eps   (eps takes the place of trunc).
+ * zero_sees != 0 is for depth that was rendered from the mesh itself (nsk_mesh_depth): a pixel with D == 0 (nothing hit, so nothing in
+ * the way) is read as FLT_MAX; NaN and +-inf still see nothing.  d_depth == NULL is the frustum alone: every pixel is read as FLT_MAX.
+ * A point with a component that is not finite is never seen.  accumulate != 0 ORs the old byte in, as in nsk_lattice_seen, so a long
+ * trajectory can be streamed through in batches of a few depth images; K = 0 with accumulate = 0 clears the mask.  n = 0 is valid;
+ * n <= 2^31 - 1.  One thread per point loops over the frames (at most 32 frames' matrices ride in the kernel arguments; longer lists go in
+ * several launches); a wave leaves the loop once all its points are seen.  n_seen (may be NULL) receives the number of set bytes after the
+ * call: asking for it is the call's only synchronisation.  Not while a graph is being captured. */
+int nsk_points_seen(nsk_ctx* ctx, const float* d_points, int n, int K, const float* d_depth, int H, int W, float fx, float fy, float cx,
+                    float cy, const float* h_w2c, int edge, float eps, int zero_sees, int accumulate, uint8_t* d_seen, long long* n_seen);
+/* nsk_mesh_select: the sub-mesh of a mesh the caller owns (d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3] int32, device)
+ * that a per-vertex mask selects (d_seen [n_vertices] bytes, any non-zero byte counts as set): upstream's face_mask = mask[faces].all(axis=1)
+ * followed by remove_unreferenced_vertices.
+ *   A triangle with an index outside [0, n_vertices) belongs to neither part and is counted in *h_skipped (may be NULL).
+ *   part = 0: the triangles whose three vertices are all seen.  part = 1: every other valid triangle (the unseen complement).
+ *   Kept triangles keep their relative order.  A vertex stays when a kept triangle names it; kept vertices keep their relative order.
+ *   Triangles are re-indexed.  d_vertex_src[o] (or NULL) is the input index of output vertex o.
+ * The output buffers (d_out_vertices [n_vertices][3], d_out_triangles [n_triangles][3], d_vertex_src [n_vertices]) are the caller's, sized
+ * for the input (the output cannot be larger), and must not alias the input.  Compaction by the multi-launch scans of nsk_mesh_extract:
+ * no atomic append, so two runs give the same bytes.  An empty result gives zero counts and no error; n_vertices = 0 or n_triangles = 0
+ * is valid.  At most (2^31 - 1) / 3 vertices and triangles.  Synchronises once, for the counts.  Device memory: 4 B per vertex and per
+ * triangle of scan scratch (+ its upper levels); an allocation that fails names its byte count and leaves the context usable.  Not while
+ * a graph is being captured. */
+int nsk_mesh_select(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles, const uint8_t* d_seen,
+                    int part, float* d_out_vertices, int32_t* d_out_triangles, int32_t* d_vertex_src, int* out_vertices, int* out_triangles,
+                    int* h_skipped);
+/* nsk_points_view_counts: h_count[k] = the number of the points (d_points [n][3], device) that view k (h_w2c [V][16], host) has in its
+ * image by the frustum rule of nsk_points_seen (camera space, d > 0, the nearest pixel inside the edge bounds; a point with a component
+ * that is not finite is never counted).  No depth: a hidden point still counts, as upstream's check_proj does.  n <= 2^31 - 1, so the
+ * 32-bit device counters cannot wrap.  One thread per point loops over the launch's 32 views; per view a ballot and a population count,
+ * and one integer atomic add per wave with a non-zero count: integer addition gives the same result whatever the order.  V = 0 and n = 0
+ * are valid.  Reading h_count is the call's one synchronisation.  Not while a graph is being captured. */
+int nsk_points_view_counts(nsk_ctx* ctx, const float* d_points, int n, int V, const float* h_w2c, int H, int W, float fx, float fy, float cx,
+                           float cy, int edge, long long* h_count);
 
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */

@@ -872,6 +872,12 @@ struct nsk_ctx {
         int queue_cap = 1 << 18;                             // nsk_set_tuning "raster_queue_cap": entries (24 B each)
         int load_first = 1;                                  // nsk_set_tuning "raster_load_first": a plain load in front of the atomic minimum
     } raster;
+    // culling (nsk_cull.h): nsk_points_seen's optional count, nsk_points_view_counts' counters, nsk_mesh_select's scan words
+    struct Cull {
+        Buf<unsigned long long> seen_count;
+        Buf<unsigned> view_counts;                           // [V]
+        Buf<unsigned> scan;                                  // vertex flags' scan | triangle flags' scan | the skipped count
+    } cull;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -3538,6 +3544,22 @@ static void depth_view(const double lo[3], const double ext[3], const double ctr
     w[12] = w[13] = w[14] = 0.f; w[15] = 1.f;
 }
 
+// views first .. first + V - 1 of the stream: host only
+extern "C" int nsk_depth_views_range(const float h_box[6], unsigned long long seed, double shrink, long long first, int V, float* h_w2c)
+{
+    if (!h_box) return fail("nsk_depth_views_range: h_box is NULL");
+    if (V < 0 || (V > 0 && !h_w2c)) return fail("nsk_depth_views_range: V = %d, or h_w2c is NULL", V);
+    if (first < 0 || first + (long long)V > (1LL << 32)) return fail("nsk_depth_views_range: views %lld .. %lld, the stream has 2^32", first, first + (long long)V);
+    if (!std::isfinite(shrink)) return fail("nsk_depth_views_range: shrink is not finite");
+    double lo[3], ext[3], ctr[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(h_box[a]) || !std::isfinite(h_box[3 + a])) return fail("nsk_depth_views_range: the box is not finite");
+        lo[a] = (double)h_box[a]; ext[a] = (double)h_box[3 + a] - lo[a]; ctr[a] = 0.5 * (lo[a] + (double)h_box[3 + a]);
+    }
+    for (int k = 0; k < V; ++k) depth_view(lo, ext, ctr, shrink, seed, (uint32_t)(first + k), h_w2c + 16 * (size_t)k);
+    return 0;
+}
+
 extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertices, float h_box[6], unsigned long long seed, double shrink,
                                int V, float* h_w2c)
 {
@@ -3555,14 +3577,13 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
         if (!nfinite) return fail("nsk_depth_views: no vertex with finite coordinates");
         memcpy(h_box, box, sizeof(box));
     }
-    double lo[3], ext[3], ctr[3];
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < 3; ++a)
         if (!std::isfinite(h_box[a]) || !std::isfinite(h_box[3 + a])) return fail("nsk_depth_views: the box is not finite");
-        lo[a] = (double)h_box[a]; ext[a] = (double)h_box[3 + a] - lo[a]; ctr[a] = 0.5 * (lo[a] + (double)h_box[3 + a]);
-    }
-    for (int k = 0; k < V; ++k) depth_view(lo, ext, ctr, shrink, seed, (uint32_t)k, h_w2c + 16 * (size_t)k);
-    return 0;
+    return nsk_depth_views_range(h_box, seed, shrink, 0, V, h_w2c);
 }
+
+// ---- culling to what a trajectory saw (kernels and entry points: nsk_cull.h) ---------------------------------------------------------
+#include "nsk_cull.h"
 
 extern "C" int nsk_inside_filter(nsk_ctx* c, int N, const float* ro, const float* rd, const float* gt, uint8_t* keep)
 {

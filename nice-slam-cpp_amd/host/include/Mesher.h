@@ -39,6 +39,8 @@ struct ReconDepth {
     std::vector<double> view_l1, view_cover;        // per view: sum |gt - rec| / n_pix (m), the share of pixels the ground truth covers
     std::vector<double> stats;              // [n_views][4]: nsk_depth_pair_stats(gt, rec)
     std::vector<float> w2c;                 // [n_views][16]: the views (nsk_depth_views)
+    int candidates_tried = 0;               // with unseen points: candidates of the view stream looked at (n_views is then the accepted number)
+    std::vector<long long> view_index;      // with unseen points: the accepted candidates' indices in the stream
     double transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // align: as in ReconMetrics
     double icp_fitness = 0, icp_rmse = 0;
     int icp_iterations = 0;
@@ -50,6 +52,16 @@ struct ReconAlign {
     int iterations = 0, correspondences = 0;
     double fitness = 0, rmse = 0;
     bool converged = false, degenerate = false;
+};
+
+// what Mesher::cull_mesh returns: the part of a mesh a trajectory saw
+struct CulledMesh {
+    std::vector<float> xyz;                 // [vertices][3]: the vertices a kept triangle names, in their old order
+    std::vector<int32_t> triangles;         // [triangles][3]: the triangles whose three vertices were seen, re-indexed, in their old order
+    std::vector<int32_t> vertex_src;        // [vertices]: the input index of every output vertex
+    std::vector<uint8_t> seen;              // [input vertices]: 1 = at least one frame saw it
+    long long n_seen = 0;                   // set bytes of seen
+    int skipped = 0;                        // triangles with an index out of range (in neither part)
 };
 
 class Mesher {
@@ -78,7 +90,7 @@ class Mesher {
     static void read_ply_mesh(const std::string& path, std::vector<float>& xyz, std::vector<int32_t>& triangles);
     // Accuracy / completion / completion ratio on the device: n_points area-weighted samples of each mesh (nsk_mesh_sample with seed and
     // seed + 1), exact nearest distances both ways (nsk_cloud_nearest), the sums (nsk_cloud_stats).  Coordinates in metres; the meshes
-    // are taken as they are (no culling).  With align the reconstruction's vertices are first registered to the ground truth's
+    // are taken as they are: callers that follow upstream's protocol pass meshes culled by cull_mesh.  With align the reconstruction's vertices are first registered to the ground truth's
     // (align_recon) and the transformed mesh is measured.  A static function: it needs no map, only the process's context.
     static ReconMetrics eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n_points = 200000, float threshold = 0.05f,
                                    unsigned long long seed = 0, bool align = false);
@@ -92,15 +104,35 @@ class Mesher {
     // Depth L1 on the device: n_views random views inside the ground truth's box (nsk_depth_views: seed, shrink), both meshes rendered as
     // H x W depth images with fx = fy = focal, cx = W / 2 - 0.5, cy = H / 2 - 0.5 (nsk_mesh_depth) in batches that keep both stacks below
     // about 1 GB, the per-view sums (nsk_depth_pair_stats).  A view is used when the ground truth covers at least min_cover of its pixels
-    // (0: every view, upstream's plain mean).  With align the reconstruction is registered first, as in eval_recon.  Not done: upstream's
-    // rejection of views that see never-observed ground truth.
+    // (0: every view, upstream's plain mean).  With align the reconstruction is registered first, as in eval_recon.  With unseen_xyz
+    // ([n_unseen][3], host: the never-observed ground truth, unseen_points) the views are the first n_views candidates of the same stream
+    // that have none of those points in their image (nsk_depth_views_range + nsk_points_view_counts in rounds of 32, at most
+    // 16 n_views candidates): upstream's redraw.  n_views of the result is then the number accepted (it may be smaller).
     static ReconDepth eval_recon_depth(const std::string& rec_ply, const std::string& gt_ply, int n_views = 1000, int H = 500, int W = 500,
                                        float focal = 300.f, unsigned long long seed = 0, double shrink = 0.7, double min_cover = 0.0,
                                        bool align = false);
     static ReconDepth eval_recon_depth(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles,
                                        const float* gt_xyz, int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles,
                                        int n_views = 1000, int H = 500, int W = 500, float focal = 300.f, unsigned long long seed = 0,
-                                       double shrink = 0.7, double min_cover = 0.0, bool align = false);
+                                       double shrink = 0.7, double min_cover = 0.0, bool align = false, const float* unseen_xyz = nullptr,
+                                       int n_unseen = 0);
+    // upstream's cull_mesh.py on the device: the part of a mesh the trajectory w2c ([K][16] row-major world-to-camera, host; the camera
+    // looks along -z) saw, per vertex by the rule of nsk_points_seen, then nsk_mesh_select (part 0).
+    //   occlusion "none": the view frusta alone;  "depth": against the sensor depth images depths ([K][H][W], host), a pixel without a
+    //   measurement sees nothing;  "self": every batch of frames is rendered from the mesh itself (nsk_mesh_depth) and tested against that.
+    // At most frames_per_batch frames' images are on the device at a time; the result does not depend on it.  eps (m): how far behind the
+    // depth a vertex still counts as seen; 0.03 is this project's first choice, not upstream's number.
+    static CulledMesh cull_mesh(const float* xyz, int n_vertices, const int32_t* triangles, int n_triangles, const float* w2c, int K, int H, int W,
+                                float fx, float fy, float cx, float cy, const float* depths = nullptr, const std::string& occlusion = "none",
+                                int edge = 0, float eps = 0.03f, int frames_per_batch = 32);
+    // the same from a PLY file (read_ply_mesh) into a PLY file (write_ply, no colours)
+    static CulledMesh cull_mesh(const std::string& in_ply, const std::string& out_ply, const float* w2c, int K, int H, int W, float fx, float fy,
+                                float cx, float cy, const float* depths = nullptr, const std::string& occlusion = "none", int edge = 0,
+                                float eps = 0.03f, int frames_per_batch = 32);
+    // n area-weighted samples [n][3] of the part of the mesh that was not seen (nsk_mesh_select part 1, then nsk_mesh_sample): what
+    // eval_recon_depth takes as unseen_xyz.  Empty when n = 0 or every valid triangle was seen.
+    static std::vector<float> unseen_points(const float* xyz, int n_vertices, const int32_t* triangles, int n_triangles, const uint8_t* seen,
+                                            int n, unsigned long long seed = 0);
 
     int resolution;
     float level_set, padding;

@@ -425,7 +425,7 @@ ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& g
 // ---- reconstruction depth L1 -----------------------------------------------------------------------------------------------------------
 ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
                                     const int32_t* gt_tris, int gt_nt, int n_views, int H, int W, float focal, unsigned long long seed,
-                                    double shrink, double min_cover, bool align)
+                                    double shrink, double min_cover, bool align, const float* unseen_xyz, int n_unseen)
 {
     if (n_views < 1) throw std::runtime_error("Mesher::eval_recon_depth: n_views must be at least 1");
     if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::eval_recon_depth: the image must have 1 .. 2^24 pixels");
@@ -443,16 +443,41 @@ ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int3
         keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
         check(nsk_cloud_transform(ctx(), M.transform, (const float*)rv.p, rec_nv, (float*)rv.p));
     }
-    M.n_views = n_views;
-    M.w2c.assign((size_t)n_views * 16, 0.f);
-    M.stats.assign((size_t)n_views * 4, 0.0);
+    const float cx = (float)(W / 2.0 - 0.5), cy = (float)(H / 2.0 - 0.5);
     float box[6];
-    check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, n_views, M.w2c.data()));
+    if (unseen_xyz && n_unseen > 0) {
+        // upstream's redraw: the first n_views candidates of the stream without an unseen point in their image, counted in rounds
+        const int round = 32, cap_factor = 16;
+        const long long cap = (long long)cap_factor * n_views;
+        DevMem up_((size_t)n_unseen * 3 * sizeof(float));
+        up(up_, unseen_xyz, (size_t)n_unseen * 3 * sizeof(float));
+        check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, 0, nullptr));        // (the box)
+        std::vector<float> w((size_t)round * 16);
+        std::vector<long long> cnt((size_t)round);
+        long long first = 0;
+        while ((int)M.view_index.size() < n_views && first < cap) {
+            const int m = (int)std::min<long long>(round, cap - first);
+            check(nsk_depth_views_range(box, seed, shrink, first, m, w.data()));
+            check(nsk_points_view_counts(ctx(), (const float*)up_.p, n_unseen, m, w.data(), H, W, focal, focal, cx, cy, 0, cnt.data()));
+            for (int k = 0; k < m && (int)M.view_index.size() < n_views; ++k) {
+                if (cnt[(size_t)k] != 0) continue;
+                M.view_index.push_back(first + k);
+                M.w2c.insert(M.w2c.end(), w.begin() + 16 * (size_t)k, w.begin() + 16 * (size_t)(k + 1));
+            }
+            first += m;
+        }
+        M.candidates_tried = (int)M.view_index.size() == n_views ? (int)(M.view_index.back() + 1) : (int)cap;
+        n_views = (int)M.view_index.size();
+    } else {
+        M.w2c.assign((size_t)n_views * 16, 0.f);
+        check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, n_views, M.w2c.data()));
+    }
+    M.n_views = n_views;
+    M.stats.assign((size_t)n_views * 4, 0.0);
     int batch = (int)std::max<size_t>(1, ((size_t)1 << 27) / n_pix);          // both stacks together stay below about 1 GB
     if (batch > 32) batch -= batch % 32;
-    batch = std::min(batch, n_views);
+    batch = std::max(1, std::min(batch, n_views));
     DevMem dg((size_t)batch * n_pix * sizeof(float)), dr((size_t)batch * n_pix * sizeof(float));
-    const float cx = (float)(W / 2.0 - 0.5), cy = (float)(H / 2.0 - 0.5);
     for (int k0 = 0; k0 < n_views; k0 += batch) {
         const int V = std::min(batch, n_views - k0);
         const float* w = M.w2c.data() + 16 * (size_t)k0;
@@ -485,4 +510,83 @@ ReconDepth Mesher::eval_recon_depth(const std::string& rec_ply, const std::strin
     read_ply_mesh(gt_ply, gv, gt);
     return eval_recon_depth(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(),
                             (int)(gt.size() / 3), n_views, H, W, focal, seed, shrink, min_cover, align);
+}
+
+// ---- culling to what a trajectory saw -----------------------------------------------------------------------------------------------------
+CulledMesh Mesher::cull_mesh(const float* xyz, int nv, const int32_t* tris, int nt, const float* w2c, int K, int H, int W, float fx, float fy,
+                             float cx, float cy, const float* depths, const std::string& occlusion, int edge, float eps, int frames_per_batch)
+{
+    const int mode = occlusion == "none" ? 0 : occlusion == "depth" ? 1 : occlusion == "self" ? 2 : -1;
+    if (mode < 0) throw std::runtime_error("Mesher::cull_mesh: occlusion must be none, depth or self, not " + occlusion);
+    if (nv < 0 || nt < 0 || K < 0) throw std::runtime_error("Mesher::cull_mesh: negative count");
+    if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::cull_mesh: the image must have 1 .. 2^24 pixels");
+    if (mode == 1 && K > 0 && !depths) throw std::runtime_error("Mesher::cull_mesh: occlusion depth needs the depth images");
+    auto up = [](DevMem& d, const void* h, size_t bytes) {
+        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+    };
+    auto down = [](void* h, const DevMem& d, size_t bytes) {
+        if (bytes && hipMemcpy(h, d.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+    };
+    const size_t img = (size_t)H * W, vb = (size_t)nv * 3 * sizeof(float), tb = (size_t)nt * 3 * sizeof(int32_t);
+    const int batch = std::max(1, frames_per_batch);
+    DevMem v(vb), t(tb), seen((size_t)nv), ov(vb), ot(tb), src((size_t)nv * sizeof(int32_t));
+    DevMem dimg(mode == 0 ? 0 : (size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
+    up(v, xyz, vb); up(t, tris, tb);
+    CulledMesh R;
+    check(nsk_points_seen(ctx(), (const float*)v.p, nv, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, edge, eps, 0, 0, (uint8_t*)seen.p, nullptr));     // (cleared)
+    for (int k0 = 0; k0 < K; k0 += batch) {
+        const int kb = std::min(batch, K - k0);
+        const float* w = w2c + 16 * (size_t)k0;
+        if (mode == 1) {
+            check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
+            up(dimg, depths + (size_t)k0 * img, (size_t)kb * img * sizeof(float));
+        } else if (mode == 2) {
+            check(nsk_mesh_depth(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, kb, w, H, W, fx, fy, cx, cy, (float*)dimg.p, nullptr));
+        }
+        check(nsk_points_seen(ctx(), (const float*)v.p, nv, kb, mode == 0 ? nullptr : (const float*)dimg.p, H, W, fx, fy, cx, cy, w, edge, eps,
+                              mode == 2 ? 1 : 0, 1, (uint8_t*)seen.p, k0 + kb >= K ? &R.n_seen : nullptr));
+    }
+    int onv = 0, ont = 0;
+    check(nsk_mesh_select(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, (const uint8_t*)seen.p, 0, (float*)ov.p, (int32_t*)ot.p,
+                          (int32_t*)src.p, &onv, &ont, &R.skipped));
+    R.xyz.resize((size_t)onv * 3); R.triangles.resize((size_t)ont * 3); R.vertex_src.resize((size_t)onv); R.seen.resize((size_t)nv);
+    check(nsk_sync(ctx()));
+    down(R.xyz.data(), ov, R.xyz.size() * sizeof(float)); down(R.triangles.data(), ot, R.triangles.size() * sizeof(int32_t));
+    down(R.vertex_src.data(), src, R.vertex_src.size() * sizeof(int32_t)); down(R.seen.data(), seen, R.seen.size());
+    return R;
+}
+
+CulledMesh Mesher::cull_mesh(const std::string& in_ply, const std::string& out_ply, const float* w2c, int K, int H, int W, float fx, float fy,
+                             float cx, float cy, const float* depths, const std::string& occlusion, int edge, float eps, int frames_per_batch)
+{
+    std::vector<float> xyz;
+    std::vector<int32_t> tris;
+    read_ply_mesh(in_ply, xyz, tris);
+    CulledMesh R = cull_mesh(xyz.data(), (int)(xyz.size() / 3), tris.data(), (int)(tris.size() / 3), w2c, K, H, W, fx, fy, cx, cy, depths, occlusion,
+                             edge, eps, frames_per_batch);
+    write_ply(out_ply, R.xyz.data(), nullptr, (int)(R.xyz.size() / 3), R.triangles.data(), (int)(R.triangles.size() / 3));
+    return R;
+}
+
+std::vector<float> Mesher::unseen_points(const float* xyz, int nv, const int32_t* tris, int nt, const uint8_t* seen, int n, unsigned long long seed)
+{
+    std::vector<float> out;
+    if (n < 1 || nt < 1 || nv < 1) return out;
+    auto up = [](DevMem& d, const void* h, size_t bytes) {
+        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+    };
+    const size_t vb = (size_t)nv * 3 * sizeof(float), tb = (size_t)nt * 3 * sizeof(int32_t);
+    DevMem v(vb), t(tb), s((size_t)nv), ov(vb), ot(tb), pts((size_t)n * 3 * sizeof(float));
+    up(v, xyz, vb); up(t, tris, tb); up(s, seen, (size_t)nv);
+    int onv = 0, ont = 0;
+    check(nsk_mesh_select(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, (const uint8_t*)s.p, 1, (float*)ov.p, (int32_t*)ot.p, nullptr, &onv,
+                          &ont, nullptr));
+    if (ont == 0) return out;
+    double area = 0.0;
+    int degenerate = 0;
+    check(nsk_mesh_sample(ctx(), (const float*)ov.p, onv, (const int32_t*)ot.p, ont, seed, n, (float*)pts.p, nullptr, &area, &degenerate));
+    check(nsk_sync(ctx()));
+    out.resize((size_t)n * 3);
+    if (hipMemcpy(out.data(), pts.p, out.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+    return out;
 }

@@ -30,7 +30,8 @@ SYMBOLS = (
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
     "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
     "nsk_cloud_pair_sums", "nsk_rigid_from_sums", "nsk_cloud_icp", "nsk_cloud_transform",
-    "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views",
+    "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views", "nsk_depth_views_range",
+    "nsk_points_seen", "nsk_mesh_select", "nsk_points_view_counts",
 )
 
 
@@ -90,6 +91,17 @@ def lib():
         L.nsk_depth_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.nsk_depth_views.restype = C.c_int
         L.nsk_depth_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_ulonglong, C.c_double, C.c_int, C.c_void_p]
+        L.nsk_depth_views_range.restype = C.c_int
+        L.nsk_depth_views_range.argtypes = [C.c_void_p, C.c_ulonglong, C.c_double, C.c_longlong, C.c_int, C.c_void_p]
+        L.nsk_points_seen.restype = C.c_int
+        L.nsk_points_seen.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.nsk_mesh_select.restype = C.c_int
+        L.nsk_mesh_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.nsk_points_view_counts.restype = C.c_int
+        L.nsk_points_view_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                             C.c_float, C.c_float, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -123,6 +135,17 @@ def depth_views_from_box(box, n_views, seed=0, shrink=0.7):
     w = np.zeros((int(n_views), 4, 4), np.float32)
     _chk(lib().nsk_depth_views(None, None, 0, b.ctypes.data_as(C.c_void_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(shrink), int(n_views),
                                w.ctypes.data_as(C.c_void_p)))
+    return w
+
+
+def depth_views_range(box, first, n_views, seed=0, shrink=0.7):
+    """nsk_depth_views_range: views first .. first + n_views - 1 of the stream depth_views draws from the box (lo x y z, hi x y z) -> w2c
+    [n_views, 4, 4] float32; needs no GPU"""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(box, dtype=np.float32).reshape(6))
+    w = np.zeros((int(n_views), 4, 4), np.float32)
+    _chk(lib().nsk_depth_views_range(b.ctypes.data_as(C.c_void_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(shrink), int(first), int(n_views),
+                                     w.ctypes.data_as(C.c_void_p)))
     return w
 
 
@@ -624,27 +647,170 @@ class Context:
         self.last_box = box
         return w
 
+    # -- culling a mesh to what a trajectory saw; depth views clear of the unseen (nsk_cull.h) ----------------------------------------
+    @_ordered
+    def points_seen(self, points, w2c, intr, HW, depths=None, edge=0, eps=0.03, zero_sees=False, seen=None):
+        """nsk_points_seen: the points [n, 3] (float32 cuda) that one of the K frames saw.  w2c [K, 4, 4] world-to-camera on the host;
+        intr = (fx, fy, cx, cy); HW = (H, W); depths: float32 cuda tensor [K, H, W], or None for the frustum alone; zero_sees: the depth was
+        rendered from the mesh itself (a pixel with depth 0 hides nothing).  seen: uint8 cuda tensor [n] to OR into (default: a new one).
+        -> (seen, n_seen).  Synchronises (the count)."""
+        import numpy as np
+        import torch
+        assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[-1] == 3
+        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(-1, 16))
+        K, n, H, W = int(w.shape[0]), int(points.shape[0]), int(HW[0]), int(HW[1])
+        if depths is not None:
+            assert depths.dtype == torch.float32 and tuple(depths.shape) == (K, H, W)
+        acc = seen is not None
+        if acc:
+            assert seen.dtype == torch.uint8 and seen.numel() == n
+        else:
+            seen = torch.empty((n,), dtype=torch.uint8, device=points.device)
+        fx, fy, cx, cy = [float(x) for x in intr]
+        cnt = C.c_longlong(0)
+        _chk(lib().nsk_points_seen(self.h, _ptr(points) if n else None, n, K, _ptr(depths) if depths is not None and K else None, H, W, fx, fy,
+                                   cx, cy, w.ctypes.data_as(C.c_void_p) if K else None, int(edge), float(eps), int(bool(zero_sees)), int(acc),
+                                   _ptr(seen) if n else None, C.byref(cnt)))
+        return seen, int(cnt.value)
+
+    @_ordered
+    def mesh_select(self, verts, tris, seen, part=0):
+        """nsk_mesh_select: the sub-mesh of (verts [nv, 3] float32, tris [nt, 3] int32, cuda) whose triangles have all three vertices set in
+        seen [nv] uint8 (part 0), or every other valid triangle (part 1: the unseen complement); unreferenced vertices dropped, order kept,
+        triangles re-indexed -> (verts, tris, vertex_src [int32: the input index of every output vertex], skipped [triangles with an index
+        out of range]).  Synchronises."""
+        import torch
+        assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        nv, nt = int(verts.shape[0]), int(tris.shape[0])
+        assert seen.dtype in (torch.uint8, torch.bool) and seen.numel() == nv
+        ov = torch.empty((nv, 3), dtype=torch.float32, device=verts.device)
+        ot = torch.empty((nt, 3), dtype=torch.int32, device=verts.device)
+        src = torch.empty((nv,), dtype=torch.int32, device=verts.device)
+        a, b, sk = C.c_int(0), C.c_int(0), C.c_int(0)
+        _chk(lib().nsk_mesh_select(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, _ptr(seen) if nv else None, int(part),
+                                   _ptr(ov) if nv else None, _ptr(ot) if nt else None, _ptr(src) if nv else None, C.byref(a), C.byref(b),
+                                   C.byref(sk)))
+        return ov[:a.value].clone(), ot[:b.value].clone(), src[:a.value].clone(), int(sk.value)
+
+    @_ordered
+    def points_view_counts(self, points, w2c, HW, intr, edge=0):
+        """nsk_points_view_counts: how many of the points [n, 3] (float32 cuda) each view of w2c [V, 4, 4] (host) has in its image (the frustum
+        alone: a hidden point counts) -> numpy int64 [V].  Synchronises."""
+        import numpy as np
+        import torch
+        assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[-1] == 3
+        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(-1, 16))
+        V, n = int(w.shape[0]), int(points.shape[0])
+        out = np.zeros(V, np.int64)
+        fx, fy, cx, cy = [float(x) for x in intr]
+        _chk(lib().nsk_points_view_counts(self.h, _ptr(points) if n else None, n, V, w.ctypes.data_as(C.c_void_p) if V else None, int(HW[0]),
+                                          int(HW[1]), fx, fy, cx, cy, int(edge), out.ctypes.data_as(C.c_void_p) if V else None))
+        return out
+
+    depth_views_range = staticmethod(depth_views_range)
+
+    def cull_mesh(self, verts, tris, w2c, intr, HW, depths=None, occlusion="none", edge=0, eps=0.03, frames_per_batch=32):
+        """upstream's cull_mesh.py on the device: the part of the mesh (verts [nv, 3] float32, tris [nt, 3] int32, cuda) that the trajectory
+        w2c [K, 4, 4] (host, world-to-camera, camera looking along -z) saw, by the per-vertex rule of points_seen.
+          occlusion "none": the view frusta alone;
+          "depth": against the caller's sensor depth images depths [K, H, W] float32 (a tensor anywhere, or numpy), streamed to the device
+                   frames_per_batch at a time (a pixel without a measurement sees nothing);
+          "self": every batch of frames is first rendered from the mesh itself (mesh_depth at HW / intr) and tested against that (a pixel
+                  that hits nothing hides nothing).
+        The trajectory is never resident as a whole.  eps (m): how far behind the depth a vertex still counts as seen; 0.03 is this
+        project's first choice, not upstream's number.  -> dict(verts, tris, seen [nv] uint8, vertex_src, n_seen, skipped); the result
+        does not depend on frames_per_batch."""
+        import numpy as np
+        import torch
+        assert occlusion in ("none", "depth", "self"), occlusion
+        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(-1, 4, 4))
+        K, H, W = int(w.shape[0]), int(HW[0]), int(HW[1])
+        fx, fy, cx, cy = [float(x) for x in intr]
+        if occlusion == "depth":
+            assert depths is not None and tuple(depths.shape) == (K, H, W), "cull_mesh: occlusion 'depth' needs depths [K, H, W]"
+        step = max(1, int(frames_per_batch))
+        seen, n_seen = self.points_seen(verts, w[:0], intr, HW)              # (cleared)
+        for k0 in range(0, K, step):
+            wb = w[k0:k0 + step]
+            if occlusion == "none":
+                d = None
+            elif occlusion == "depth":
+                d = torch.as_tensor(np.ascontiguousarray(depths[k0:k0 + step]) if isinstance(depths, np.ndarray) else depths[k0:k0 + step])
+                d = d.to(device=verts.device, dtype=torch.float32).contiguous()
+            else:
+                d = self.mesh_depth(verts, tris, wb, H, W, fx, fy, cx, cy)
+            seen, n_seen = self.points_seen(verts, wb, intr, HW, d, edge, eps, occlusion == "self", seen)
+        ov, ot, src, skipped = self.mesh_select(verts, tris, seen, 0)
+        return dict(verts=ov, tris=ot, seen=seen, vertex_src=src, n_seen=n_seen, skipped=skipped)
+
+    def unseen_points(self, verts, tris, seen, n, seed=0):
+        """n area-weighted samples [n, 3] of the part of the mesh the trajectory did not see (mesh_select part 1, then sample_mesh): the
+        points depth_views_clear rejects views with.  n = 0, or an empty complement, gives an empty tensor."""
+        import torch
+        empty = torch.empty((0, 3), dtype=torch.float32, device=verts.device)
+        if int(n) == 0:
+            return empty
+        cv, ct, _, _ = self.mesh_select(verts, tris, seen, 1)
+        if ct.shape[0] == 0:
+            return empty
+        return self.sample_mesh(cv, ct, int(n), seed)
+
+    def depth_views_clear(self, gt_verts, unseen, n_views, HW, focal, seed=0, shrink=0.7, edge=0, max_factor=16):
+        """upstream's redraw of Depth L1 views: the first n_views candidates, in index order, of the stream depth_views draws (seed, shrink,
+        the box of gt_verts) that have none of the unseen points [P, 3] in their H x W image (fx = fy = focal, cx = W / 2 - 0.5,
+        cy = H / 2 - 0.5; points_view_counts: no depth test).  Candidates are drawn and counted in rounds; at most max_factor * n_views are
+        tried, so fewer than n_views may come back.  -> (w2c [m, 4, 4] float32, index [m] int64, tried): tried is the index of the last
+        accepted candidate + 1 when n_views were found, max_factor * n_views otherwise."""
+        import numpy as np
+        n_views, H, W = int(n_views), int(HW[0]), int(HW[1])
+        cap = int(max_factor) * n_views
+        self.depth_views(gt_verts, 0, seed, shrink)                         # (the box)
+        box = self.last_box
+        intr = (focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5)
+        ws, idx, first = [], [], 0
+        while len(idx) < n_views and first < cap:
+            need = n_views - len(idx)
+            m = min(cap - first, max(32, (need + 31) // 32 * 32))
+            w = depth_views_range(box, first, m, seed, shrink)
+            cnt = self.points_view_counts(unseen, w, (H, W), intr, edge)
+            for k in np.nonzero(cnt == 0)[0][:need]:
+                ws.append(w[k]); idx.append(first + int(k))
+            first += m
+        tried = idx[-1] + 1 if len(idx) == n_views and idx else (0 if n_views == 0 else cap)
+        w2c = np.stack(ws).astype(np.float32) if ws else np.zeros((0, 4, 4), np.float32)
+        return w2c, np.array(idx, np.int64), tried
+
     def recon_depth_l1(self, rec_verts, rec_tris, gt_verts, gt_tris, n_views=1000, HW=(500, 500), focal=300.0, seed=0, shrink=0.7,
-                       min_cover=0.0, align=False, align_threshold=0.1, align_max_iter=30):
+                       min_cover=0.0, align=False, align_threshold=0.1, align_max_iter=30, unseen=None, max_factor=16):
         """upstream's Depth L1 of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors: both meshes rendered as
         depth images from the same n_views random views inside the ground truth's box (depth_views), cx = W / 2 - 0.5, cy = H / 2 - 0.5;
         depth_l1_cm = 100 x the mean over the used views of sum |gt - rec| / n_pix.  A view is used when the ground truth covers at least
         min_cover of its pixels (0: every view, upstream's plain mean).  Also: n_used, restricted_l1_cm (the mean over the pixels of the
         used views where both meshes are hit) and the per-view arrays view_l1 (m), view_cover, stats [n_views, 4], w2c.  With align the
         reconstruction's vertices are first registered to the ground truth's (align_mesh) and the transformed mesh is rendered; the result
-        then also holds transform, icp_fitness, icp_rmse and icp_iterations."""
+        then also holds transform, icp_fitness, icp_rmse and icp_iterations.  With unseen (points [P, 3] float32 cuda: the never-observed
+        ground truth, unseen_points) the views are depth_views_clear's: the first n_views candidates of the same stream that have none of
+        those points in their image, at most max_factor * n_views candidates tried (upstream redraws such views); the per-view arrays then
+        have one entry per accepted view (possibly fewer than n_views), and the result also holds candidates_tried and view_index (the
+        accepted candidates' indices in the stream).  With None nothing changes."""
         import numpy as np
         extra = {}
         if align:
             rec_verts, extra = self._aligned(rec_verts, gt_verts, align_threshold, align_max_iter)
         H, W = int(HW[0]), int(HW[1])
         n_pix = H * W
-        w2c = self.depth_views(gt_verts, n_views, seed, shrink)
-        stats = np.zeros((int(n_views), 4), np.float64)
+        n_drawn = int(n_views)
+        if unseen is None:
+            w2c = self.depth_views(gt_verts, n_views, seed, shrink)
+        else:
+            w2c, view_index, tried = self.depth_views_clear(gt_verts, unseen, n_views, (H, W), focal, seed, shrink, 0, max_factor)
+            extra = dict(extra, candidates_tried=tried, view_index=view_index)
+            n_drawn = int(w2c.shape[0])
+        stats = np.zeros((n_drawn, 4), np.float64)
         batch = max(1, (1 << 27) // n_pix)                 # both stacks together stay below about 1 GB
         if batch > 32:
             batch -= batch % 32
-        for k0 in range(0, int(n_views), batch):
+        for k0 in range(0, n_drawn, batch):
             w = w2c[k0:k0 + batch]
             gt = self.mesh_depth(gt_verts, gt_tris, w, H, W, focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5)
             rec = self.mesh_depth(rec_verts, rec_tris, w, H, W, focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5)
@@ -653,7 +819,7 @@ class Context:
         cover = stats[:, 3] / n_pix
         used = cover >= min_cover
         n_used, l1, both, both_sum = 0, 0.0, 0.0, 0.0
-        for k in range(int(n_views)):                       # (in view order, as Mesher::eval_recon_depth adds them)
+        for k in range(n_drawn):                            # (in view order, as Mesher::eval_recon_depth adds them)
             if used[k]:
                 n_used += 1; l1 += view_l1[k]; both += stats[k, 1]; both_sum += stats[k, 2]
         nan = float("nan")
