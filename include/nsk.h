@@ -714,6 +714,44 @@ int nsk_mesh_select(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const
 int nsk_points_view_counts(nsk_ctx* ctx, const float* d_points, int n, int V, const float* h_w2c, int H, int W, float fx, float fy, float cx,
                            float cy, int edge, long long* h_count);
 
+/* ---- depth frames fused into a truncated signed distance volume on a lattice (the first half of upstream's get_bound_from_frames, whose
+ * Open3D ScalableTSDFVolume is sparse and on the host; here the volume is dense, on the device, and meshed by nsk_mesh_extract) -------- */
+/* nsk_tsdf_integrate: K depth frames at known poses integrated into d_tsdf / d_weight (device, nx * ny * nz floats each).  Node points,
+ * layout ([(k * ny + j) * nx + i]), camera convention (h_w2c [K][16] row-major world-to-camera on the host, the camera looks along -z),
+ * `edge` and the at most 2^28 nodes are as in nsk_lattice_seen.  Every operation below is an fp32 operation of its own (no FMA).
+ * Frame k SEES the node p exactly when nsk_lattice_seen says so with the same edge and trunc:
+ *   c_a = ((w[4a] p0 + w[4a+1] p1) + w[4a+2] p2) + w[4a+3], a = 0..2;   d = -c_2 > 0;
+ *   u = cx + (fx c_0) / d,  v = cy - (fy c_1) / d;   i = floor(u + 0.5), j = floor(v + 0.5)   (the nearest pixel);
+ *   edge <= i < W - edge and edge <= j < H - edge, decided on the floats (a NaN fails; an edge that leaves no pixel is valid: nothing is seen);
+ *   D = d_depth[k][j][i] is finite and > 0 (a pixel without a measurement sees nothing);   d <= D + trunc.
+ * So weight > 0 after a call from a cleared state is, byte for byte, the mask nsk_lattice_seen gives.  A frame that sees the node updates
+ * it; the frames are applied in ascending k; each of these is one rounding:
+ *   sdf = D - d;
+ *   t = min(1, sdf / trunc)   (the occlusion test already gives t >= -1 up to rounding: there is no clamp below);
+ *   T <- ((W * T) + t) / (W + 1);
+ *   W <- min(W + 1, max_weight).
+ * A frame that does not see the node leaves both values untouched.  accumulate == 0 starts every node from T = 0, W = 0 whatever the
+ * buffers held (NaN included: the old values are not read, no 0 * T_old is formed); K = 0 then clears the buffers.  accumulate != 0
+ * continues from the buffers: a trajectory streamed in batches of any size gives the bytes of one call over all frames.
+ * Errors (< 0, a message in nsk_last_error, the context stays usable): trunc not finite or <= 0; max_weight < 1 or > 2^24 (beyond it
+ * W + 1 no longer counts); more than 2^28 nodes; H or W outside 1 .. 2^24; intrinsics that are not finite; edge < 0; while a graph is
+ * being captured.  n_observed (may be NULL) receives the number of nodes with W > 0 after the call: asking for it is the call's only
+ * synchronisation.
+ * One thread per node, x fastest, loops over the frames (matrices and intrinsics ride in the kernel arguments, 32 frames per launch,
+ * longer lists in several launches); T and W stay in registers over a launch's frames and are stored once.  Every frame counts, so
+ * no wave leaves the loop early; no atomics but the one integer add per wave of the count. */
+int nsk_tsdf_integrate(nsk_ctx* ctx, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, int K, const float* d_depth,
+                       int H, int W, float fx, float fy, float cx, float cy, const float* h_w2c, int edge, float trunc, float max_weight,
+                       int accumulate, float* d_tsdf, float* d_weight, long long* n_observed);
+/* nsk_tsdf_volume: the fused values as a volume for nsk_mesh_extract (n nodes; all pointers device).  Where d_weight >= min_weight:
+ * d_volume = -T (the sign bit flipped, so +0.0 gives -0.0: nsk_mesh_extract's "inside when value > level" then puts the solid behind the
+ * surface) and d_valid = 1.  Elsewhere (a NaN weight included) d_volume is the quiet NaN 0x7fc00000 and d_valid = 0.  d_valid may be
+ * NULL: nsk_mesh_extract skips cells with a corner that is not finite anyway.  nsk_mesh_extract at level 0 then gives a welded mesh,
+ * wound towards free space, with the same bytes in two runs.  n_valid (may be NULL) receives the number of valid nodes; the call is
+ * asynchronous on the context's stream unless it is asked for.  n = 0 is valid.  Not while a graph is being captured. */
+int nsk_tsdf_volume(nsk_ctx* ctx, long long n, const float* d_tsdf, const float* d_weight, float min_weight, float* d_volume,
+                    uint8_t* d_valid, long long* n_valid);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

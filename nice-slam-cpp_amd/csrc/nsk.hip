@@ -878,6 +878,10 @@ struct nsk_ctx {
         Buf<unsigned> view_counts;                           // [V]
         Buf<unsigned> scan;                                  // vertex flags' scan | triangle flags' scan | the skipped count
     } cull;
+    // depth fusion (nsk_tsdf.h): the optional count of nsk_tsdf_integrate / nsk_tsdf_volume
+    struct Tsdf {
+        Buf<unsigned long long> count;
+    } tsdf;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -3584,6 +3588,9 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
 
 // ---- culling to what a trajectory saw (kernels and entry points: nsk_cull.h) ---------------------------------------------------------
 #include "nsk_cull.h"
+
+// ---- depth frames fused into a TSDF on a lattice (kernels and entry points: nsk_tsdf.h) -------------------------------------------------
+#include "nsk_tsdf.h"
 
 extern "C" int nsk_inside_filter(nsk_ctx* c, int N, const float* ro, const float* rd, const float* gt, uint8_t* keep)
 {

@@ -8,7 +8,8 @@
 //   meshing.remove_small_geometry_threshold (0.2), meshing.get_largest_components (false)   get_clean_mesh only: components of the mesh
 //                              with less surface than the threshold (m^2) are dropped, or all but the largest;
 // and leaves clean_mesh_bound_scale (upstream's convex hull of a TSDF fusion: get_clean_mesh culls per node with the union of the
-// keyframes' depth-truncated frusta instead), mesh_coarse_level and the render_ray_query colouring to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
+// keyframes' depth-truncated frusta instead; the fusion itself is here, get_fused_mesh / get_rendered_mesh, its convex hull is not),
+// mesh_coarse_level and the render_ray_query colouring to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
 // bound's own faces therefore show up as a shell around the scene, with padding 0 the outermost nodes (which lie ON the open bound) do.
 #pragma once
 #include <cstdint>
@@ -80,6 +81,21 @@ class Mesher {
     // stay on the device.
     void get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
                         const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color = true);
+    // The mesh of what the sensor measured: the depth frames (depths: host tensors [H, W] of metric z-depth, 0 / NaN / inf = no
+    // measurement; c2ws: [4, 4] camera-to-world, camera looking along -z, inverted in double) fused into a truncated signed distance
+    // volume on the lattice of get_mesh (resolution, padding, bound) by nsk_tsdf_integrate, 32 frames' images on the device at a time,
+    // truncation trunc_steps times the largest step (3: this project's first choice) -> nsk_tsdf_volume (min_weight) ->
+    // nsk_mesh_extract at level 0 -> nsk_mesh_filter when remove_small_geometry_threshold > 0 or get_largest_components -> PLY without
+    // colours.  Needs no map: the comparison mesh for eval_recon / eval_recon_depth / cull_mesh where the dataset ships none.
+    void get_fused_mesh(const std::string& path, const std::vector<torch::Tensor>& depths, const std::vector<torch::Tensor>& c2ws, int H, int W,
+                        float fx, float fy, float cx, float cy, float trunc_steps = 3.f, float min_weight = 1.f);
+    // The mesh of what the map renders: the same over the depth that nsk_render_image renders at every pose (stage; the sensor depth
+    // depths[k] guides the sampling as in Renderer::render_img, an empty depths vector renders without guidance; chunks of chunk_rays
+    // pixels; the render options are the context's, i.e. those of the last Renderer call).  The rendered frames stay on the device.
+    // Colours come from the colour query on the vertex buffer, as in get_mesh.
+    void get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                           const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, float trunc_steps = 3.f,
+                           float min_weight = 1.f, bool color = true, const std::string& stage = "color", int chunk_rays = 25600);
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
     static void write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int n_vertices, const int32_t* triangles, int n_triangles);
     static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& triangles);
@@ -146,4 +162,6 @@ class Mesher {
     int last_components = 0, last_kept = 0;     // get_clean_mesh: components before the filter, components kept
     long long last_seen = 0;                    // get_clean_mesh: lattice nodes at least one keyframe saw
     long long last_evaluated = 0;               // lattice nodes the decoders ran on (get_mesh without valid: all of them)
+    long long last_observed = 0, last_valid = 0; // get_fused_mesh / get_rendered_mesh: nodes with a weight > 0, nodes with weight >= min_weight
+    float fuse_max_weight = 64.f;               // the weight cap of the fusion (a running mean over at most this many frames)
 };

@@ -150,6 +150,116 @@ void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<s
     last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen; last_evaluated = n_eval;
 }
 
+// ---- depth frames fused into a TSDF, meshed by the extractor ------------------------------------------------------------------------
+namespace {
+// the fusion of one mesh: the lattice of get_mesh, the volume's buffers, the finish
+struct Fusion {
+    int n; float origin[3], step[3], trunc;
+    DevMem tsdf, weight;
+    Fusion(const Mesher& m, float trunc_steps) : n(m.resolution), tsdf((size_t)n * n * n * sizeof(float)), weight((size_t)n * n * n * sizeof(float))
+    {
+        TORCH_CHECK(m.bound.numel() == 6, "Mesher: bound must be [3,2]");
+        float smax = 0.f;
+        for (int a = 0; a < 3; ++a) {
+            const float lo = m.bound[a][0].item<float>() - m.padding, hi = m.bound[a][1].item<float>() + m.padding;
+            origin[a] = lo;
+            step[a] = (hi - lo) / (float)(n - 1);
+            smax = std::max(smax, step[a]);
+        }
+        trunc = trunc_steps * smax;
+    }
+    void integrate(const Mesher& m, int K, const float* d_depth, int H, int W, float fx, float fy, float cx, float cy, const float* w2c, bool first,
+                   long long* n_observed)
+    {
+        check(nsk_tsdf_integrate(ctx(), origin, step, n, n, n, K, d_depth, H, W, fx, fy, cx, cy, w2c, m.seen_edge, trunc, m.fuse_max_weight, first ? 0 : 1,
+                                 (float*)tsdf.p, (float*)weight.p, n_observed));
+    }
+    // volume -> extract -> (asked for) filter; the counts into the Mesher
+    void mesh(Mesher& m, float min_weight, int& nv, int& nt)
+    {
+        const size_t nodes = (size_t)n * n * n;
+        DevMem vol(nodes * sizeof(float)), valid(nodes);
+        check(nsk_tsdf_volume(ctx(), (long long)nodes, (const float*)tsdf.p, (const float*)weight.p, min_weight, (float*)vol.p, (uint8_t*)valid.p, &m.last_valid));
+        check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)valid.p, n, n, n, origin, step, 0.f, &nv, &nt));
+        m.last_components = m.last_kept = 0;
+        if (m.remove_small_geometry_threshold > 0.f || m.get_largest_components)
+            check(nsk_mesh_filter(ctx(), m.remove_small_geometry_threshold, m.get_largest_components ? 1 : 0, &nv, &nt, &m.last_components, &m.last_kept));
+        m.last_vertices = nv; m.last_triangles = nt;
+    }
+};
+// camera-to-world -> world-to-camera: inverted in double, rounded once
+void w2c_of(const torch::Tensor& c2w, int k, float* out16)
+{
+    torch::Tensor m = c2w.detach().to(torch::kCPU, torch::kFloat64).contiguous();
+    TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
+    torch::Tensor inv = torch::linalg_inv(m.view({4, 4})).to(torch::kFloat32).contiguous();
+    std::memcpy(out16, inv.data_ptr<float>(), 16 * sizeof(float));
+}
+}  // namespace
+
+void Mesher::get_fused_mesh(const std::string& path, const std::vector<torch::Tensor>& depths, const std::vector<torch::Tensor>& c2ws, int H, int W,
+                            float fx, float fy, float cx, float cy, float trunc_steps, float min_weight)
+{
+    TORCH_CHECK(depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    Fusion F(*this, trunc_steps);
+    const size_t img = (size_t)H * W;
+    const int batch = 32, K = (int)depths.size();
+    DevMem dimg((size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
+    std::vector<float> w2c((size_t)batch * 16);
+    last_observed = 0;
+    if (K == 0) F.integrate(*this, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, true, &last_observed);
+    for (int k0 = 0; k0 < K; k0 += batch) {
+        const int kb = std::min(batch, K - k0);
+        check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
+        for (int k = 0; k < kb; ++k) {
+            torch::Tensor d = depths[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k0 + k, " is not H x W");
+            if (hipMemcpy((float*)dimg.p + (size_t)k * img, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+            w2c_of(c2ws[(size_t)(k0 + k)], k0 + k, &w2c[(size_t)k * 16]);
+        }
+        F.integrate(*this, kb, (const float*)dimg.p, H, W, fx, fy, cx, cy, w2c.data(), k0 == 0, k0 + kb >= K ? &last_observed : nullptr);
+    }
+    int nv = 0, nt = 0;
+    F.mesh(*this, min_weight, nv, nt);
+    write_context_mesh(path, false, nv, nt);
+}
+
+void Mesher::get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                               const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, float trunc_steps,
+                               float min_weight, bool color, const std::string& stage, int chunk_rays)
+{
+    TORCH_CHECK(depths.empty() || depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    nskh::sync_grids(c);
+    decoders.sync_to_device();
+    TORCH_CHECK(bound.numel() == 6, "Mesher: bound must be [3,2]");
+    check(nsk_set_bound(ctx(), bound.data_ptr<float>()));
+    Fusion F(*this, trunc_steps);
+    const size_t img = (size_t)H * W;
+    const int K = (int)c2ws.size();
+    DevMem guide(img * sizeof(float)), pose(12 * sizeof(float)), rgb(img * 3 * sizeof(float)), depth(img * sizeof(float)), var(img * sizeof(float));
+    last_observed = 0;
+    F.integrate(*this, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, true, K == 0 ? &last_observed : nullptr);        // (cleared)
+    float w2c[16];
+    for (int k = 0; k < K; ++k) {
+        check(nsk_sync(ctx()));                              // (the previous frame's launches read the buffers about to be overwritten)
+        torch::Tensor m = c2ws[(size_t)k].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+        TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
+        if (hipMemcpy(pose.p, m.data_ptr<float>(), 12 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+        if (!depths.empty()) {
+            torch::Tensor d = depths[(size_t)k].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k, " is not H x W");
+            if (hipMemcpy(guide.p, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+        }
+        check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, (const float*)pose.p, 0, 0,
+                               depths.empty() ? nullptr : (const float*)guide.p, -1.f, chunk_rays, (float*)rgb.p, (float*)depth.p, (float*)var.p));
+        w2c_of(c2ws[(size_t)k], k, w2c);
+        F.integrate(*this, 1, (const float*)depth.p, H, W, fx, fy, cx, cy, w2c, false, k + 1 == K ? &last_observed : nullptr);
+    }
+    int nv = 0, nt = 0;
+    F.mesh(*this, min_weight, nv, nt);
+    write_context_mesh(path, color, nv, nt);
+}
+
 void Mesher::write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int nv, const int32_t* tris, int nt)
 {
     std::ofstream f(path, std::ios::binary);
