@@ -842,7 +842,6 @@ struct nsk_ctx {
         Buf<float> verts; Buf<int> tris;                     // [nv][3], [nt][3]
         int nv = 0, nt = 0;
         bool extracted = false;                              // a mesh (possibly empty) is there for nsk_mesh_filter
-        Buf<unsigned long long> seen_count;                  // nsk_lattice_seen's optional count
         // nsk_mesh_filter: per-vertex scratch (one group), the statistics, the compacted mesh (swapped with verts / tris)
         Buf<int> cc_label; Buf<double> cc_area; Buf<uint8_t> cc_used, cc_keep;
         Buf<CcStats> cc_stats;
@@ -872,16 +871,13 @@ struct nsk_ctx {
         int queue_cap = 1 << 18;                             // nsk_set_tuning "raster_queue_cap": entries (24 B each)
         int load_first = 1;                                  // nsk_set_tuning "raster_load_first": a plain load in front of the atomic minimum
     } raster;
-    // culling (nsk_cull.h): nsk_points_seen's optional count, nsk_points_view_counts' counters, nsk_mesh_select's scan words
+    // culling (nsk_cull.h): nsk_points_view_counts' counters, nsk_mesh_select's scan words
     struct Cull {
-        Buf<unsigned long long> seen_count;
         Buf<unsigned> view_counts;                           // [V]
         Buf<unsigned> scan;                                  // vertex flags' scan | triangle flags' scan | the skipped count
     } cull;
-    // depth fusion (nsk_tsdf.h): the optional count of nsk_tsdf_integrate / nsk_tsdf_volume
-    struct Tsdf {
-        Buf<unsigned long long> count;
-    } tsdf;
+    // the optional count of an entry point (count_begin / count_end): nsk_lattice_seen, nsk_points_seen, nsk_tsdf_integrate, nsk_tsdf_volume
+    Buf<unsigned long long> count;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
     struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -2124,6 +2120,64 @@ static int lattice_checks(const char* fn, nsk_ctx* c, const float* o, const floa
     return 0;
 }
 
+// ---- what the entry points that project points into frames share (the rule itself: nsk_view.h) ---------------------------------------
+static int view_checks(const char* fn, int H, int W, float fx, float fy, float cx, float cy, int edge)
+{
+    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail("%s: image %d x %d, need 1 .. 2^24 pixels per side", fn, H, W);
+    if (edge < 0) return fail("%s: edge = %d, must be >= 0", fn, edge);
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy)) return fail("%s: intrinsics are not finite", fn);
+    return 0;
+}
+static ViewArgs view_args(int H, int W, float fx, float fy, float cx, float cy, int edge, float reach)
+{
+    ViewArgs A;
+    memset(&A, 0, sizeof(A));
+    A.H = H; A.W = W; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.reach = reach;
+    A.ilo = A.jlo = (float)edge;                            // (edge beyond 2^24 rounds, and is beyond W and H either way)
+    A.ihi = (float)((long long)W - edge); A.jhi = (float)((long long)H - edge);
+    return A;
+}
+// rows 0..2 of the n row-major 4 x 4 matrices from k0 on
+static void view_matrices(float (*w)[12], const float* w2c, int k0, int n)
+{
+    for (int k = 0; k < n; ++k) memcpy(w[k], w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
+}
+// K frames in launches of VIEW_MAX_K: launch(A, the batch's first depth image (or NULL), its first frame k0, whether it is the last).  Every
+// launch but the first of a call that does not accumulate adds to what the ones before it left.  K = 0 still launches once: it clears, or
+// keeps, and counts.
+template <class Launch>
+static int view_batches(nsk_ctx* c, const char* name, ViewArgs A, int K, const float* w2c, const float* depth, int accumulate, Launch launch)
+{
+    int k0 = 0;
+    do {
+        A.K = std::min(K - k0, VIEW_MAX_K);
+        A.accumulate = (accumulate || k0 > 0) ? 1 : 0;
+        view_matrices(A.w, w2c, k0, A.K);
+        { ProfScope ps(c, name); launch(A, depth ? depth + (size_t)k0 * A.H * A.W : nullptr, k0, k0 + A.K >= K); }
+        HIPCHK(hipGetLastError());
+        k0 += A.K;
+    } while (k0 < K);
+    return 0;
+}
+// An entry point's optional count (h_count NULL: none): the context's one counter, zeroed in front of the launches that add to it, and
+// read back behind them, which synchronises.  (Every caller has refused a graph capture before.)
+static int count_begin(nsk_ctx* c, const long long* h_count, const char* what)
+{
+    if (!h_count) return 0;
+    CHK(grow(c, c->count, 1, what, GROW_NO_CAPTURE));
+    HIPCHK(hipMemsetAsync(c->count, 0, 8, c->stream));
+    return 0;
+}
+static int count_end(nsk_ctx* c, long long* h_count)
+{
+    if (!h_count) return 0;
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, c->count, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *h_count = (long long)cnt;
+    return 0;
+}
+
 extern "C" int nsk_eval_lattice(nsk_ctx* c, int stage, const float* o, const float* s, int nx, int ny, int nz, float* vol)
 {
     CHK(lattice_checks("nsk_eval_lattice", c, o, s, nx, ny, nz, 1));
@@ -2305,45 +2359,20 @@ extern "C" int nsk_lattice_seen(nsk_ctx* c, const float* o, const float* s, int 
     if (!valid) return fail("nsk_lattice_seen: d_valid is NULL");
     if (K < 0) return fail("nsk_lattice_seen: K = %d", K);
     if (K > 0 && (!depth || !w2c)) return fail("nsk_lattice_seen: d_depth / h_w2c is NULL with K = %d", K);
-    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail("nsk_lattice_seen: image %d x %d, need 1 .. 2^24 pixels per side", H, W);
-    if (edge < 0) return fail("nsk_lattice_seen: edge = %d, must be >= 0", edge);
+    CHK(view_checks("nsk_lattice_seen", H, W, fx, fy, cx, cy, edge));
     if (std::isnan(trunc)) return fail("nsk_lattice_seen: trunc is NaN");
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy)) return fail("nsk_lattice_seen: intrinsics are not finite");
     const long long total = (long long)nx * ny * nz;
     if (total > MC_MAX_NODES) return fail("nsk_lattice_seen: %lld nodes, at most %lld per call", total, (long long)MC_MAX_NODES);
     HIPCHK(hipSetDevice(c->device));
-    nsk_ctx::Mesh& M = c->mesh;
-    if (n_seen) {
-        CHK(grow(c, M.seen_count, 1, "the seen count", 0));
-        HIPCHK(hipMemsetAsync(M.seen_count, 0, 8, c->stream));
-    }
+    CHK(count_begin(c, n_seen, "the seen count"));
     McGeom G;
     G.nx = nx; G.ny = ny; G.nz = nz; G.nn = (int)total; G.level = 0.f;
     for (int a = 0; a < 3; ++a) { G.o[a] = o[a]; G.s[a] = s[a]; }
-    SeenArgs A;
-    memset(&A, 0, sizeof(A));
-    A.H = H; A.W = W; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.trunc = trunc;
-    A.ilo = A.jlo = (float)edge;                            // (edge beyond 2^24 rounds, and is beyond W and H either way)
-    A.ihi = (float)((long long)W - edge); A.jhi = (float)((long long)H - edge);
     const int nb = (G.nn + MC_BLOCK - 1) / MC_BLOCK;
-    int k0 = 0;
-    do {                                                    // (K = 0 still launches once: it clears, or keeps, and counts)
-        A.K = std::min(K - k0, SEEN_MAX_K);
-        A.accumulate = (accumulate || k0 > 0) ? 1 : 0;
-        for (int k = 0; k < A.K; ++k) memcpy(A.w[k], w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
-        const bool last = k0 + A.K >= K;
-        { ProfScope ps(c, "lattice_seen");
-          k_lattice_seen<<<nb, MC_BLOCK, 0, c->stream>>>(G, A, depth ? depth + (size_t)k0 * H * W : nullptr, valid, last && n_seen ? M.seen_count.get() : nullptr); }
-        HIPCHK(hipGetLastError());
-        k0 += A.K;
-    } while (k0 < K);
-    if (n_seen) {
-        unsigned long long cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, M.seen_count, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        *n_seen = (long long)cnt;
-    }
-    return 0;
+    CHK(view_batches(c, "lattice_seen", view_args(H, W, fx, fy, cx, cy, edge, trunc), K, w2c, depth, accumulate,
+                     [&](const ViewArgs& A, const float* dk, int, bool last) {
+        k_lattice_seen<<<nb, MC_BLOCK, 0, c->stream>>>(G, A, dk, valid, last && n_seen ? c->count.get() : nullptr); }));
+    return count_end(c, n_seen);
 }
 
 // connected components of the last extracted mesh, the keep rule, compaction by the multi-launch scans (nsk_mesh.h)
@@ -2389,7 +2418,7 @@ extern "C" int nsk_mesh_filter(nsk_ctx* c, float min_area, int largest_only, int
       k_cc_flags<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, M.tris, M.cc_label, M.cc_used, M.cc_keep, voff, toff); }
     HIPCHK(hipGetLastError());
     { ProfScope ps(c, "cc_scan"); CHK(mc_scan(c, voff, nv + 1)); CHK(mc_scan(c, toff, nt + 1)); }
-    { ProfScope ps(c, "cc_compact"); k_cc_compact<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, M.verts, M.tris, voff, toff, M.verts2, M.tris2); }
+    { ProfScope ps(c, "cc_compact"); k_mesh_compact<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, M.verts, M.tris, voff, toff, M.verts2, M.tris2, nullptr); }
     HIPCHK(hipGetLastError());
     CcStats st;
     unsigned tot[2] = {0, 0};
@@ -3473,7 +3502,7 @@ extern "C" int nsk_mesh_depth(nsk_ctx* c, const float* d_vertices, int n_vertice
         int k0 = 0;
         do {                                                // (V = 0 still launches once: it counts the skipped triangles)
             A.K = std::min(V - k0, RASTER_MAX_V);
-            for (int k = 0; k < A.K; ++k) memcpy(A.w[k], h_w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
+            view_matrices(A.w, h_w2c, k0, A.K);
             HIPCHK(hipMemsetAsync(R.counters, 0, 4, c->stream));
             { ProfScope ps(c, "raster_tris");
               k_raster_tris<<<nb, RASTER_BLOCK, 0, c->stream>>>(A, d_vertices, d_triangles, bits + (size_t)k0 * img, R.queue, R.counters,

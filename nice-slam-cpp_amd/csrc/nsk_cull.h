@@ -2,54 +2,22 @@
 // points of eval_recon.py's calc_2d_metric).  include/nsk.h states the contract; this file is included by nsk.hip behind the context, the
 // buffer helpers and the multi-launch scan (mc_scan), which its entry points use.
 //
-// The rule, word for word (include/nsk.h, nsk_points_seen; tests/cull_checks.py calls tests/mesh_cull_checks.py seen_f32 for it).  Frame k
-// sees the point p when, every operation an fp32 operation of its own (no FMA):
-//   c_a = ((w[4a] p0 + w[4a+1] p1) + w[4a+2] p2) + w[4a+3], a = 0..2;   d = -c_2 > 0;
-//   u = cx + (fx c_0) / d,  v = cy - (fy c_1) / d;   i = floor(u + 0.5), j = floor(v + 0.5)   (the nearest pixel);
-//   edge <= i < W - edge and edge <= j < H - edge, decided on the floats (a NaN fails);
-//   D = d_depth[k][j][i] is finite and > 0;   d <= D + eps.
+// The rule: nsk_view.h, with reach = eps (include/nsk.h, nsk_points_seen; tests/cull_checks.py calls tests/mesh_cull_checks.py seen_f32 for it).
 // zero_sees: D == 0 is read as FLT_MAX.  No depth: every pixel is read as FLT_MAX.  A point with a non-finite component is never seen.
-// The test is restated here rather than shared with k_lattice_seen, whose code stays as it is.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstring>
 #include "nsk_mesh.h"
 
-#define CULL_MAX_K 32               // frames (views) per launch: 12 floats each in the kernel arguments
-#define CULL_FLT_MAX 3.402823466e38f
-struct CullArgs {
-    float w[CULL_MAX_K][12];        // rows 0..2 of the row-major world-to-camera matrices
-    int K, n, H, W;
-    float fx, fy, cx, cy;
-    float ilo, ihi, jlo, jhi;       // edge <= i < W - edge, edge <= j < H - edge, as floats (exact: H, W <= 2^24)
-    float eps;
-    int accumulate, zero_sees;
-};
-
-__device__ __forceinline__ bool cull_finite(float x) { return fabsf(x) <= CULL_FLT_MAX; }      // (a NaN fails)
-
-// camera space and the nearest pixel of p under the frame's matrix; false: behind the camera or outside the edge bounds
-__device__ __forceinline__ bool cull_project(const CullArgs& A, const float* __restrict__ w, const float p[3], float& d, float& fi, float& fj)
-{
-    float c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        c[a] = __fadd_rn(__fadd_rn(__fadd_rn(mc_mul(w[4 * a], p[0]), mc_mul(w[4 * a + 1], p[1])), mc_mul(w[4 * a + 2], p[2])), w[4 * a + 3]);
-    d = -c[2];
-    if (!(d > 0.f)) return false;
-    const float u = __fadd_rn(A.cx, __fdiv_rn(mc_mul(A.fx, c[0]), d));
-    const float v = __fsub_rn(A.cy, __fdiv_rn(mc_mul(A.fy, c[1]), d));
-    fi = floorf(__fadd_rn(u, 0.5f)); fj = floorf(__fadd_rn(v, 0.5f));
-    return fi >= A.ilo && fi < A.ihi && fj >= A.jlo && fj < A.jhi;                      // (NaN fails; decided before any conversion to int)
-}
+__device__ __forceinline__ bool cull_finite(float x) { return fabsf(x) <= VIEW_FLT_MAX; }      // (a NaN fails)
 
 // One thread per point.  depth NULL: the frustum alone.
-__global__ __launch_bounds__(256) void k_points_seen(CullArgs A, const float* __restrict__ pts, const float* __restrict__ depth,
+__global__ __launch_bounds__(256) void k_points_seen(ViewArgs A, int n, int zero_sees, const float* __restrict__ pts, const float* __restrict__ depth,
                                                      uint8_t* __restrict__ out, unsigned long long* __restrict__ count)
 {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = q < A.n;
+    const bool live = q < n;
     bool seen = false, idle = true;                         // idle: no point, or a point no frame can see
     float p[3] = {0.f, 0.f, 0.f};
     if (live) {
@@ -57,42 +25,36 @@ __global__ __launch_bounds__(256) void k_points_seen(CullArgs A, const float* __
         seen = A.accumulate && out[q] != 0;
         idle = !(cull_finite(p[0]) && cull_finite(p[1]) && cull_finite(p[2]));
     }
-    const size_t img = (size_t)A.H * A.W;
     for (int kf = 0; kf < A.K; ++kf) {
         if (__all(seen || idle)) break;                     // the whole wave is done
         if (seen || idle) continue;
         float d, fi, fj;
-        if (!cull_project(A, A.w[kf], p, d, fi, fj)) continue;
-        float D = CULL_FLT_MAX;
+        if (!view_project(A, A.w[kf], p, d, fi, fj)) continue;
+        float D = VIEW_FLT_MAX;
         if (depth) {
-            D = depth[(size_t)kf * img + (size_t)(int)fj * A.W + (int)fi];
-            if (A.zero_sees && D == 0.f) D = CULL_FLT_MAX;  // rendered depth: nothing hit, nothing in the way
+            D = view_pixel(A, depth, kf, fi, fj);
+            if (zero_sees && D == 0.f) D = VIEW_FLT_MAX;    // rendered depth: nothing hit, nothing in the way
         }
-        if (!(D > 0.f && D <= CULL_FLT_MAX)) continue;      // no measurement: 0, negative, NaN, inf
-        seen = d <= __fadd_rn(D, A.eps);
+        if (!view_measured(D)) continue;
+        seen = d <= __fadd_rn(D, A.reach);
     }
     if (live) out[q] = seen ? 1 : 0;
-    if (count) {
-        const unsigned long long b = __ballot(live && seen);
-        if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
-    }
+    if (count) wave_count(live && seen, count);
 }
 
 // One thread per point; every lane of a wave walks every view (the ballot needs them all), one integer add per wave and view.
-__global__ __launch_bounds__(256) void k_points_view_counts(CullArgs A, const float* __restrict__ pts, unsigned* __restrict__ counts)
+__global__ __launch_bounds__(256) void k_points_view_counts(ViewArgs A, int n, const float* __restrict__ pts, unsigned* __restrict__ counts)
 {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     bool ok = false;
     float p[3] = {0.f, 0.f, 0.f};
-    if (q < A.n) {
+    if (q < n) {
         p[0] = pts[3 * (size_t)q]; p[1] = pts[3 * (size_t)q + 1]; p[2] = pts[3 * (size_t)q + 2];
         ok = cull_finite(p[0]) && cull_finite(p[1]) && cull_finite(p[2]);
     }
     for (int kf = 0; kf < A.K; ++kf) {
         float d, fi, fj;
-        const bool in = ok && cull_project(A, A.w[kf], p, d, fi, fj);
-        const unsigned long long b = __ballot(in);
-        if ((threadIdx.x & 63) == 0 && b) atomicAdd(counts + kf, (unsigned)__popcll(b));
+        wave_count(ok && view_project(A, A.w[kf], p, d, fi, fj), counts + kf);
     }
 }
 
@@ -113,45 +75,11 @@ __global__ __launch_bounds__(256) void k_select_flags(int nv, int nt, const int*
             if (all == (part == 0)) { tflag[t] = 1u; vflag[a] = 1u; vflag[b] = 1u; vflag[c] = 1u; }
         }
     }
-    const unsigned long long m = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(skipped, (unsigned)__popcll(m));
+    wave_count(bad, skipped);
 }
-// voff / toff: the exclusive scans of the flags, one slot more than elements (the last is the total); as k_cc_compact, plus the source index
-__global__ __launch_bounds__(256) void k_select_compact(int nv, int nt, const float* __restrict__ verts, const int* __restrict__ tris,
-                                                        const unsigned* __restrict__ voff, const unsigned* __restrict__ toff,
-                                                        float* __restrict__ verts2, int* __restrict__ tris2, int* __restrict__ vsrc)
-{
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q < nv) {
-        const unsigned d = voff[q];
-        if (voff[q + 1] != d) {
-            for (int a = 0; a < 3; ++a) verts2[3 * (size_t)d + a] = verts[3 * (size_t)q + a];
-            if (vsrc) vsrc[d] = (int)q;
-        }
-    }
-    if (q < nt) {
-        const unsigned d = toff[q];
-        if (toff[q + 1] != d)                               // (a kept triangle: its indices are in range)
-            for (int a = 0; a < 3; ++a) tris2[3 * (size_t)d + a] = (int)voff[tris[3 * (size_t)q + a]];
-    }
-}
+// (the compaction behind the scans of these flags: k_mesh_compact, nsk_mesh.h)
 
 // ---- entry points ------------------------------------------------------------------------------------------------------------------
-static int cull_image_checks(const char* fn, int H, int W, float fx, float fy, float cx, float cy, int edge)
-{
-    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail("%s: image %d x %d, need 1 .. 2^24 pixels per side", fn, H, W);
-    if (edge < 0) return fail("%s: edge = %d, must be >= 0", fn, edge);
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy)) return fail("%s: intrinsics are not finite", fn);
-    return 0;
-}
-static void cull_args(CullArgs& A, int n, int H, int W, float fx, float fy, float cx, float cy, int edge)
-{
-    memset(&A, 0, sizeof(A));
-    A.n = n; A.H = H; A.W = W; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy;
-    A.ilo = A.jlo = (float)edge;                            // (edge beyond 2^24 rounds, and is beyond W and H either way)
-    A.ihi = (float)((long long)W - edge); A.jhi = (float)((long long)H - edge);
-}
-
 extern "C" int nsk_points_seen(nsk_ctx* c, const float* pts, int n, int K, const float* depth, int H, int W, float fx, float fy, float cx, float cy,
                                const float* w2c, int edge, float eps, int zero_sees, int accumulate, uint8_t* seen, long long* n_seen)
 {
@@ -159,39 +87,18 @@ extern "C" int nsk_points_seen(nsk_ctx* c, const float* pts, int n, int K, const
     if (n < 0 || K < 0) return fail("nsk_points_seen: n = %d, K = %d", n, K);
     if (n > 0 && (!pts || !seen)) return fail("nsk_points_seen: d_points / d_seen is NULL with n = %d", n);
     if (K > 0 && !w2c) return fail("nsk_points_seen: h_w2c is NULL with K = %d", K);
-    CHK(cull_image_checks("nsk_points_seen", H, W, fx, fy, cx, cy, edge));
+    CHK(view_checks("nsk_points_seen", H, W, fx, fy, cx, cy, edge));
     if (std::isnan(eps)) return fail("nsk_points_seen: eps is NaN");
     if (c->capturing) return fail("nsk_points_seen: not while a graph is being captured");
     if (n_seen) *n_seen = 0;
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    nsk_ctx::Cull& U = c->cull;
-    if (n_seen) {
-        CHK(grow(c, U.seen_count, 1, "the seen count", GROW_NO_CAPTURE));
-        HIPCHK(hipMemsetAsync(U.seen_count, 0, 8, c->stream));
-    }
-    CullArgs A;
-    cull_args(A, n, H, W, fx, fy, cx, cy, edge);
-    A.eps = eps; A.zero_sees = zero_sees ? 1 : 0;
+    CHK(count_begin(c, n_seen, "the seen count"));
     const unsigned nb = (unsigned)(((long long)n + 255) / 256);
-    int k0 = 0;
-    do {                                                    // (K = 0 still launches once: it clears, or keeps, and counts)
-        A.K = std::min(K - k0, CULL_MAX_K);
-        A.accumulate = (accumulate || k0 > 0) ? 1 : 0;
-        for (int k = 0; k < A.K; ++k) memcpy(A.w[k], w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
-        const bool last = k0 + A.K >= K;
-        { ProfScope ps(c, "points_seen");
-          k_points_seen<<<nb, 256, 0, c->stream>>>(A, pts, depth ? depth + (size_t)k0 * H * W : nullptr, seen, last && n_seen ? U.seen_count.get() : nullptr); }
-        HIPCHK(hipGetLastError());
-        k0 += A.K;
-    } while (k0 < K);
-    if (n_seen) {
-        unsigned long long cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, U.seen_count, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        *n_seen = (long long)cnt;
-    }
-    return 0;
+    CHK(view_batches(c, "points_seen", view_args(H, W, fx, fy, cx, cy, edge, eps), K, w2c, depth, accumulate,
+                     [&](const ViewArgs& A, const float* dk, int, bool last) {
+        k_points_seen<<<nb, 256, 0, c->stream>>>(A, n, zero_sees ? 1 : 0, pts, dk, seen, last && n_seen ? c->count.get() : nullptr); }));
+    return count_end(c, n_seen);
 }
 
 extern "C" int nsk_points_view_counts(nsk_ctx* c, const float* pts, int n, int V, const float* w2c, int H, int W, float fx, float fy, float cx,
@@ -201,7 +108,7 @@ extern "C" int nsk_points_view_counts(nsk_ctx* c, const float* pts, int n, int V
     if (n < 0 || V < 0) return fail("nsk_points_view_counts: n = %d, V = %d", n, V);
     if (V > 0 && (!w2c || !h_count)) return fail("nsk_points_view_counts: h_w2c / h_count is NULL with V = %d", V);
     if (n > 0 && !pts) return fail("nsk_points_view_counts: d_points is NULL with n = %d", n);
-    CHK(cull_image_checks("nsk_points_view_counts", H, W, fx, fy, cx, cy, edge));
+    CHK(view_checks("nsk_points_view_counts", H, W, fx, fy, cx, cy, edge));
     if (c->capturing) return fail("nsk_points_view_counts: not while a graph is being captured");
     for (int k = 0; k < V; ++k) h_count[k] = 0;
     if (V == 0 || n == 0) return 0;
@@ -209,15 +116,10 @@ extern "C" int nsk_points_view_counts(nsk_ctx* c, const float* pts, int n, int V
     nsk_ctx::Cull& U = c->cull;
     CHK(grow(c, U.view_counts, (size_t)V, "the view counts", GROW_NO_CAPTURE));
     HIPCHK(hipMemsetAsync(U.view_counts, 0, (size_t)V * 4, c->stream));
-    CullArgs A;
-    cull_args(A, n, H, W, fx, fy, cx, cy, edge);
     const unsigned nb = (unsigned)(((long long)n + 255) / 256);
-    for (int k0 = 0; k0 < V; k0 += CULL_MAX_K) {
-        A.K = std::min(V - k0, CULL_MAX_K);
-        for (int k = 0; k < A.K; ++k) memcpy(A.w[k], w2c + 16 * (size_t)(k0 + k), 12 * sizeof(float));
-        { ProfScope ps(c, "points_view_counts"); k_points_view_counts<<<nb, 256, 0, c->stream>>>(A, pts, U.view_counts.get() + k0); }
-        HIPCHK(hipGetLastError());
-    }
+    CHK(view_batches(c, "points_view_counts", view_args(H, W, fx, fy, cx, cy, edge, 0.f), V, w2c, nullptr, 0,
+                     [&](const ViewArgs& A, const float*, int k0, bool) {
+        k_points_view_counts<<<nb, 256, 0, c->stream>>>(A, n, pts, U.view_counts.get() + k0); }));
     std::vector<unsigned> h((size_t)V);
     HIPCHK(hipMemcpyAsync(h.data(), U.view_counts, (size_t)V * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -250,7 +152,7 @@ extern "C" int nsk_mesh_select(nsk_ctx* c, const float* verts, int nv, const int
     { ProfScope ps(c, "select_flags"); k_select_flags<<<nbt, MC_BLOCK, 0, c->stream>>>(nv, nt, tris, seen, part, voff, toff, skipped); }
     HIPCHK(hipGetLastError());
     { ProfScope ps(c, "select_scan"); CHK(mc_scan(c, voff, nv + 1)); CHK(mc_scan(c, toff, nt + 1)); }
-    { ProfScope ps(c, "select_compact"); k_select_compact<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, verts, tris, voff, toff, out_v, out_t, vsrc); }
+    { ProfScope ps(c, "select_compact"); k_mesh_compact<<<nbm, MC_BLOCK, 0, c->stream>>>(nv, nt, verts, tris, voff, toff, out_v, out_t, vsrc); }
     HIPCHK(hipGetLastError());
     unsigned tot[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(&tot[0], voff + nv, 4, hipMemcpyDeviceToHost, c->stream));

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstring>
 #include "nsk_reduce.h"
+#include "nsk_view.h"
 
 #define MC_ROW 16                   // table row stride in edge numbers: the largest case has 5 triangles (tests/test_mesh_cpu.py asserts it)
 #define MC_BLOCK 256                // nodes per workgroup of the extraction passes, elements per workgroup of the scan passes
@@ -105,8 +106,13 @@ struct McGeom {
     float level;
 };
 
-__device__ __forceinline__ float mc_mul(float a, float b) { float r = a * b; asm("" : "+v"(r)); return r; }      // (keeps the product out of an FMA)
-__device__ __forceinline__ float mc_coord(float o, int i, float s) { return __fadd_rn(o, mc_mul((float)i, s)); }
+__device__ __forceinline__ float mc_coord(float o, int i, float s) { return __fadd_rn(o, mul_rn((float)i, s)); }       // (mul_rn: never fused)
+// node n (x fastest) as a point
+__device__ __forceinline__ void lattice_node(const McGeom& G, int n, float p[3])
+{
+    const int i = n % G.nx, r = n / G.nx, j = r % G.ny, k = r / G.ny;
+    p[0] = mc_coord(G.o[0], i, G.s[0]); p[1] = mc_coord(G.o[1], j, G.s[1]); p[2] = mc_coord(G.o[2], k, G.s[2]);
+}
 
 // the lattice nodes [n0, n0 + cnt) as points for the decoders' forward
 __global__ __launch_bounds__(256) void k_lattice_points(McGeom G, long long n0, int cnt, float* __restrict__ pts)
@@ -233,7 +239,7 @@ __global__ __launch_bounds__(256) void k_mc_edges(McGeom G, const float* __restr
         const float p1 = mc_coord(G.o[a], idx[a] + 1, G.s[a]);
         const float t = __fdiv_rn(__fsub_rn(G.level, v0), __fsub_rn(v1[a], v0));
         float q[3] = {p[0], p[1], p[2]};
-        q[a] = __fadd_rn(p[a], mc_mul(t, __fsub_rn(p1, p[a])));
+        q[a] = __fadd_rn(p[a], mul_rn(t, __fsub_rn(p1, p[a])));
         verts[3 * (size_t)id] = q[0]; verts[3 * (size_t)id + 1] = q[1]; verts[3 * (size_t)id + 2] = q[2];
         emap[3 * (size_t)n + a] = (int)id;
         ++id;
@@ -324,18 +330,8 @@ __global__ __launch_bounds__(256) void k_lattice_finish_idx(int cnt, const float
 // ---- seen mask of a lattice (nsk_lattice_seen) -------------------------------------------------------------------------
 // One thread per node, x fastest.  A node is seen by keyframe k when it lies in front of the camera (which looks along -z), projects onto
 // a pixel at least `edge` pixels inside the image, that pixel carries a finite positive depth D, and the node is no farther than
-// D + trunc.  Every operation is an fp32 operation of its own (tests/mesh_cull_checks.py seen_f32 restates them one by one).
-#define SEEN_MAX_K 32               // keyframes per launch: 12 floats each in the kernel arguments
-struct SeenArgs {
-    float w[SEEN_MAX_K][12];        // rows 0..2 of the row-major world-to-camera matrices
-    int K, H, W;
-    float fx, fy, cx, cy;
-    float ilo, ihi, jlo, jhi;       // edge <= i < W - edge, edge <= j < H - edge, as floats (exact: H, W <= 2^24)
-    float trunc;
-    int accumulate;
-};
-
-__global__ __launch_bounds__(256) void k_lattice_seen(McGeom G, SeenArgs A, const float* __restrict__ depth, uint8_t* __restrict__ valid,
+// D + trunc: the rule of nsk_view.h, with reach = trunc.
+__global__ __launch_bounds__(256) void k_lattice_seen(McGeom G, ViewArgs A, const float* __restrict__ depth, uint8_t* __restrict__ valid,
                                                       unsigned long long* __restrict__ count)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
@@ -343,34 +339,20 @@ __global__ __launch_bounds__(256) void k_lattice_seen(McGeom G, SeenArgs A, cons
     bool seen = false;
     float p[3] = {0.f, 0.f, 0.f};
     if (live) {
-        const int i = n % G.nx, r = n / G.nx, j = r % G.ny, k = r / G.ny;
-        p[0] = mc_coord(G.o[0], i, G.s[0]); p[1] = mc_coord(G.o[1], j, G.s[1]); p[2] = mc_coord(G.o[2], k, G.s[2]);
+        lattice_node(G, n, p);
         seen = A.accumulate && valid[n] != 0;
     }
-    const size_t img = (size_t)A.H * A.W;
     for (int kf = 0; kf < A.K; ++kf) {
         if (__all(seen || !live)) break;                    // the whole wave is done
         if (seen || !live) continue;
-        const float* w = A.w[kf];
-        float c[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            c[a] = __fadd_rn(__fadd_rn(__fadd_rn(mc_mul(w[4 * a], p[0]), mc_mul(w[4 * a + 1], p[1])), mc_mul(w[4 * a + 2], p[2])), w[4 * a + 3]);
-        const float d = -c[2];
-        if (!(d > 0.f)) continue;
-        const float u = __fadd_rn(A.cx, __fdiv_rn(mc_mul(A.fx, c[0]), d));
-        const float v = __fsub_rn(A.cy, __fdiv_rn(mc_mul(A.fy, c[1]), d));
-        const float fi = floorf(__fadd_rn(u, 0.5f)), fj = floorf(__fadd_rn(v, 0.5f));
-        if (!(fi >= A.ilo && fi < A.ihi && fj >= A.jlo && fj < A.jhi)) continue;        // (NaN fails; decided before any conversion to int)
-        const float D = depth[(size_t)kf * img + (size_t)(int)fj * A.W + (int)fi];
-        if (!(D > 0.f && D <= 3.402823466e38f)) continue;  // no measurement: 0, negative, NaN, inf
-        seen = d <= __fadd_rn(D, A.trunc);
+        float d, fi, fj;
+        if (!view_project(A, A.w[kf], p, d, fi, fj)) continue;
+        const float D = view_pixel(A, depth, kf, fi, fj);
+        if (!view_measured(D)) continue;
+        seen = d <= __fadd_rn(D, A.reach);
     }
     if (live) valid[n] = seen ? 1 : 0;
-    if (count) {
-        const unsigned long long b = __ballot(live && seen);
-        if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
-    }
+    if (count) wave_count(live && seen, count);
 }
 
 // ---- connected components of the extracted mesh (nsk_mesh_filter) ----------------------------------------------------------
@@ -453,9 +435,9 @@ __global__ __launch_bounds__(256) void k_cc_area(int nt, const int* __restrict__
                 const float v0 = verts[3 * (size_t)i0 + q];
                 e[q] = __fsub_rn(verts[3 * (size_t)i1 + q], v0); f[q] = __fsub_rn(verts[3 * (size_t)i2 + q], v0);
             }
-            const float x = __fsub_rn(mc_mul(e[1], f[2]), mc_mul(e[2], f[1])), y = __fsub_rn(mc_mul(e[2], f[0]), mc_mul(e[0], f[2])),
-                        z = __fsub_rn(mc_mul(e[0], f[1]), mc_mul(e[1], f[0]));
-            a = (double)mc_mul(0.5f, __fsqrt_rn(__fadd_rn(__fadd_rn(mc_mul(x, x), mc_mul(y, y)), mc_mul(z, z))));
+            const float x = __fsub_rn(mul_rn(e[1], f[2]), mul_rn(e[2], f[1])), y = __fsub_rn(mul_rn(e[2], f[0]), mul_rn(e[0], f[2])),
+                        z = __fsub_rn(mul_rn(e[0], f[1]), mul_rn(e[1], f[0]));
+            a = (double)mul_rn(0.5f, __fsqrt_rn(__fadd_rn(__fadd_rn(mul_rn(x, x), mul_rn(y, y)), mul_rn(z, z))));
         }
         const int first = __ffsll((unsigned long long)__ballot(live)) - 1;
         if (first < 0) break;                               // (wave-uniform: nothing left for this wave)
@@ -510,20 +492,23 @@ __global__ __launch_bounds__(256) void k_cc_flags(int nv, int nt, const int* __r
     if (q < nv) vflag[q] = used[q] && keepc[label[q]] ? 1u : 0u;
     if (q < nt) tflag[q] = keepc[label[tris[3 * (size_t)q]]] ? 1u : 0u;
 }
-// voff / toff: the exclusive scans of the flags, one slot more than elements (the last is the total)
-__global__ __launch_bounds__(256) void k_cc_compact(int nv, int nt, const float* __restrict__ verts, const int* __restrict__ tris,
-                                                    const unsigned* __restrict__ voff, const unsigned* __restrict__ toff,
-                                                    float* __restrict__ verts2, int* __restrict__ tris2)
+// voff / toff: the exclusive scans of the flags, one slot more than elements (the last is the total).  vsrc (or NULL): the source index of
+// every vertex kept.  nsk_mesh_filter's flags come from k_cc_flags, nsk_mesh_select's (nsk_cull.h) from k_select_flags
+__global__ __launch_bounds__(256) void k_mesh_compact(int nv, int nt, const float* __restrict__ verts, const int* __restrict__ tris,
+                                                      const unsigned* __restrict__ voff, const unsigned* __restrict__ toff,
+                                                      float* __restrict__ verts2, int* __restrict__ tris2, int* __restrict__ vsrc)
 {
-    const int q = blockIdx.x * 256 + threadIdx.x;
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     if (q < nv) {
         const unsigned d = voff[q];
-        if (voff[q + 1] != d)
+        if (voff[q + 1] != d) {
             for (int a = 0; a < 3; ++a) verts2[3 * (size_t)d + a] = verts[3 * (size_t)q + a];
+            if (vsrc) vsrc[d] = (int)q;
+        }
     }
     if (q < nt) {
         const unsigned d = toff[q];
-        if (toff[q + 1] != d)
+        if (toff[q + 1] != d)                               // (a kept triangle: its indices are in range)
             for (int a = 0; a < 3; ++a) tris2[3 * (size_t)d + a] = (int)voff[tris[3 * (size_t)q + a]];
     }
 }

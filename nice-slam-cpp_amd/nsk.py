@@ -175,6 +175,26 @@ def _mat16(M):
     return (C.c_double * 16)(*[float(x) for x in np.asarray(M, np.float64).reshape(16)])
 
 
+def _w2c16(w2c, K=-1):
+    """world-to-camera matrices (anything numpy reads) as contiguous float32 [K, 16] and its pointer for the C ABI (None without a frame)"""
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(w2c, dtype=np.float32).reshape(K, 16))
+    return w, (w.ctypes.data_as(C.c_void_p) if w.shape[0] else None)
+
+
+def _intr4(intr):
+    """(fx, fy, cx, cy) as the four floats of the C ABI (c_float: right with and without declared argument types)"""
+    fx, fy, cx, cy = [C.c_float(float(x)) for x in intr]
+    return fx, fy, cx, cy
+
+
+def _vec3(v):
+    """origin / step as contiguous float32 [3] and its pointer for the C ABI"""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(v, np.float32).reshape(3))
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
 def _stage(s):
     return STAGES[s] if isinstance(s, str) else int(s)
 
@@ -616,13 +636,12 @@ class Context:
         import numpy as np
         import torch
         assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
-        w = np.ascontiguousarray(np.asarray(w2c, dtype=np.float32).reshape(-1, 16))
+        w, wp = _w2c16(w2c)
         V, nv, nt = int(w.shape[0]), int(verts.shape[0]), int(tris.shape[0])
         depth = torch.empty((V, int(H), int(W)), dtype=torch.float32, device=verts.device)
         sk = C.c_int(0)
-        _chk(lib().nsk_mesh_depth(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, V,
-                                  w.ctypes.data_as(C.c_void_p) if V else None, int(H), int(W), C.c_float(fx), C.c_float(fy), C.c_float(cx),
-                                  C.c_float(cy), _ptr(depth) if V else None, C.byref(sk) if want_skipped else None))
+        _chk(lib().nsk_mesh_depth(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, V, wp, int(H), int(W), C.c_float(fx),
+                                  C.c_float(fy), C.c_float(cx), C.c_float(cy), _ptr(depth) if V else None, C.byref(sk) if want_skipped else None))
         if want_skipped:
             self.last_skipped = int(sk.value)
         return depth
@@ -664,7 +683,7 @@ class Context:
         import numpy as np
         import torch
         assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[-1] == 3
-        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(-1, 16))
+        w, wp = _w2c16(w2c)
         K, n, H, W = int(w.shape[0]), int(points.shape[0]), int(HW[0]), int(HW[1])
         if depths is not None:
             assert depths.dtype == torch.float32 and tuple(depths.shape) == (K, H, W)
@@ -673,11 +692,10 @@ class Context:
             assert seen.dtype == torch.uint8 and seen.numel() == n
         else:
             seen = torch.empty((n,), dtype=torch.uint8, device=points.device)
-        fx, fy, cx, cy = [float(x) for x in intr]
         cnt = C.c_longlong(0)
-        _chk(lib().nsk_points_seen(self.h, _ptr(points) if n else None, n, K, _ptr(depths) if depths is not None and K else None, H, W, fx, fy,
-                                   cx, cy, w.ctypes.data_as(C.c_void_p) if K else None, int(edge), float(eps), int(bool(zero_sees)), int(acc),
-                                   _ptr(seen) if n else None, C.byref(cnt)))
+        _chk(lib().nsk_points_seen(self.h, _ptr(points) if n else None, n, K, _ptr(depths) if depths is not None and K else None, H, W,
+                                   *_intr4(intr), wp, int(edge), float(eps), int(bool(zero_sees)), int(acc), _ptr(seen) if n else None,
+                                   C.byref(cnt)))
         return seen, int(cnt.value)
 
     @_ordered
@@ -706,12 +724,11 @@ class Context:
         import numpy as np
         import torch
         assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[-1] == 3
-        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(-1, 16))
+        w, wp = _w2c16(w2c)
         V, n = int(w.shape[0]), int(points.shape[0])
         out = np.zeros(V, np.int64)
-        fx, fy, cx, cy = [float(x) for x in intr]
-        _chk(lib().nsk_points_view_counts(self.h, _ptr(points) if n else None, n, V, w.ctypes.data_as(C.c_void_p) if V else None, int(HW[0]),
-                                          int(HW[1]), fx, fy, cx, cy, int(edge), out.ctypes.data_as(C.c_void_p) if V else None))
+        _chk(lib().nsk_points_view_counts(self.h, _ptr(points) if n else None, n, V, wp, int(HW[0]), int(HW[1]), *_intr4(intr), int(edge),
+                                          out.ctypes.data_as(C.c_void_p) if V else None))
         return out
 
     depth_views_range = staticmethod(depth_views_range)
@@ -919,17 +936,14 @@ class Context:
         import torch
         assert depths.dim() == 3 and depths.dtype == torch.float32
         K, H, W = depths.shape
-        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(K, 16))
-        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
+        (w, wp), (o, op), (s, sp) = _w2c16(w2c, K), _vec3(origin), _vec3(step)
         acc = valid is not None
         if acc:
             assert valid.dtype == torch.uint8 and valid.numel() == int(nx) * int(ny) * int(nz)
         else:
             valid = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.uint8, device="cuda:%d" % self.device)
-        fx, fy, cx, cy = [C.c_float(float(x)) for x in intr]
         n = C.c_longlong(0)
-        _chk(lib().nsk_lattice_seen(self.h, o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), int(K),
-                                    _ptr(depths) if K else None, int(H), int(W), fx, fy, cx, cy, w.ctypes.data_as(C.c_void_p) if K else None,
+        _chk(lib().nsk_lattice_seen(self.h, op, sp, int(nx), int(ny), int(nz), int(K), _ptr(depths) if K else None, int(H), int(W), *_intr4(intr), wp,
                                     int(edge), C.c_float(trunc), int(acc), _ptr(valid), C.byref(n)))
         return valid, int(n.value)
 
@@ -953,8 +967,7 @@ class Context:
         import torch
         assert depths.dim() == 3 and depths.dtype == torch.float32
         K, H, W = depths.shape
-        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(K, 16))
-        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3)); s = np.ascontiguousarray(np.asarray(step, np.float32).reshape(3))
+        (w, wp), (o, op), (s, sp) = _w2c16(w2c, K), _vec3(origin), _vec3(step)
         nodes = int(nx) * int(ny) * int(nz)
         acc = state is not None
         if acc:
@@ -964,11 +977,9 @@ class Context:
         else:
             tsdf = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.float32, device="cuda:%d" % self.device)
             weight = torch.empty_like(tsdf)
-        fx, fy, cx, cy = [float(x) for x in intr]
         n = C.c_longlong(0)
-        _chk(lib().nsk_tsdf_integrate(self.h, o.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), int(nx), int(ny), int(nz), int(K),
-                                      _ptr(depths) if K else None, int(H), int(W), fx, fy, cx, cy, w.ctypes.data_as(C.c_void_p) if K else None,
-                                      int(edge), float(trunc), float(max_weight), int(acc), _ptr(tsdf), _ptr(weight), C.byref(n)))
+        _chk(lib().nsk_tsdf_integrate(self.h, op, sp, int(nx), int(ny), int(nz), int(K), _ptr(depths) if K else None, int(H), int(W), *_intr4(intr),
+                                      wp, int(edge), float(trunc), float(max_weight), int(acc), _ptr(tsdf), _ptr(weight), C.byref(n)))
         return tsdf, weight, int(n.value)
 
     @_ordered

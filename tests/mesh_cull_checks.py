@@ -16,31 +16,71 @@ CLASS_NAMES = ("seen", "behind the camera", "left of the image", "right of the i
                "zero depth", "NaN depth", "inf depth", "behind depth + trunc")
 
 
-def seen_f32(pts, depths, intr, w2c, edge, trunc):
-    """the rule of include/nsk.h in float32, one numpy operation per fp32 operation.  pts [n, 3] float32, depths [K, H, W] float32,
-    intr = (fx, fy, cx, cy), w2c [K, 4, 4] float32 -> uint8 [n]"""
-    pts = np.asarray(pts, F)
-    K, H, W = depths.shape
+def project_f32(pts, w_k, intr):
+    """camera depth and nearest pixel of the points under one frame, by the rule of include/nsk.h in float32, one numpy operation per fp32
+    operation.  pts [n, 3] float32, w_k: the frame's row-major world-to-camera matrix (16 float32), intr = (fx, fy, cx, cy)
+    -> (d, fi, fj) float32 [n]: fi, fj are floats, and a NaN among them fails every comparison of the pixel test"""
+    pts, w = np.asarray(pts, F), np.asarray(w_k, F).reshape(16)
     fx, fy, cx, cy = [F(x) for x in intr]
+    with np.errstate(all="ignore"):
+        c = []
+        for a in range(3):
+            s = (w[4 * a] * pts[:, 0]).astype(F) + (w[4 * a + 1] * pts[:, 1]).astype(F)
+            s = s.astype(F) + (w[4 * a + 2] * pts[:, 2]).astype(F)
+            c.append((s.astype(F) + w[4 * a + 3]).astype(F))
+        d = -c[2]
+        u = (cx + ((fx * c[0]).astype(F) / d).astype(F)).astype(F)
+        v = (cy - ((fy * c[1]).astype(F) / d).astype(F)).astype(F)
+        return d, np.floor((u + F(0.5)).astype(F)), np.floor((v + F(0.5)).astype(F))
+
+
+def project_f64(pts, w_k, intr):
+    """project_f32's geometry in float64 on the same float32 inputs -> (d, fi, fj, E_d, m_pix), float64 [n].  E_d = 6 eps S bounds what
+    float32 can have moved d by; m_pix is the margin of the pixel tests, the smaller of u's and v's (0 where d - E_d <= 0).  seen_f64's
+    docstring derives both."""
+    P, w = np.asarray(pts, F).astype(np.float64), np.asarray(w_k, F).astype(np.float64).reshape(16)
+    fx, fy, cx, cy = [float(F(x)) for x in intr]
+    with np.errstate(all="ignore"):
+        c, Ec = [], []
+        for a in range(3):
+            terms = [w[4 * a + q] * P[:, q] for q in range(3)]
+            c.append(terms[0] + terms[1] + terms[2] + w[4 * a + 3])
+            Ec.append(6 * EPS * (np.abs(terms[0]) + np.abs(terms[1]) + np.abs(terms[2]) + abs(w[4 * a + 3])))
+        d, Ed = -c[2], Ec[2]
+        dlo = d - Ed
+        t, m_t = [], []
+        for f, ca, Eca, c0, sign in ((fx, c[0], Ec[0], cx, 1.0), (fy, c[1], Ec[1], cy, -1.0)):
+            q = f * ca
+            r = q / d
+            uu = c0 + sign * r
+            tt = uu + 0.5
+            Er = EPS * np.abs(r) + (EPS * np.abs(q) + f * Eca + np.abs(r) * Ed) / np.where(dlo > 0, dlo, np.nan)
+            Et = Er + EPS * (np.abs(uu) + np.abs(tt))
+            t.append(tt)
+            m_t.append(np.where(dlo > 0, np.abs(tt - np.round(tt)) / Et, 0.0))
+        return d, np.floor(t[0]), np.floor(t[1]), Ed, np.minimum(m_t[0], m_t[1])
+
+
+def pixel_of(d, fi, fj, depth_k, edge):
+    """the pixel test on a projection, in its own precision: in front of the camera and at least `edge` pixels inside the image, decided on
+    the floats (a NaN fails) -> (ok, D): the frame's depth at the nearest pixel (pixel (0, 0)'s where ok is False)"""
+    H, W = depth_k.shape
+    lo, ihi, jhi = d.dtype.type(edge), d.dtype.type(W - edge), d.dtype.type(H - edge)
+    ok = (d > 0) & (fi >= lo) & (fi < ihi) & (fj >= lo) & (fj < jhi)
+    return ok, depth_k[np.where(ok, fj, 0).astype(np.int64), np.where(ok, fi, 0).astype(np.int64)].astype(d.dtype)
+
+
+def seen_f32(pts, depths, intr, w2c, edge, trunc):
+    """the rule of include/nsk.h in float32, one numpy operation per fp32 operation (project_f32).  pts [n, 3] float32, depths [K, H, W]
+    float32, intr = (fx, fy, cx, cy), w2c [K, 4, 4] float32 -> uint8 [n]"""
+    K = depths.shape[0]
     w = np.asarray(w2c, F).reshape(K, 16)
     trunc = F(trunc)
     seen = np.zeros(len(pts), bool)
     with np.errstate(all="ignore"):
         for k in range(K):
-            c = []
-            for a in range(3):
-                s = (w[k, 4 * a] * pts[:, 0]).astype(F) + (w[k, 4 * a + 1] * pts[:, 1]).astype(F)
-                s = s.astype(F) + (w[k, 4 * a + 2] * pts[:, 2]).astype(F)
-                c.append((s.astype(F) + w[k, 4 * a + 3]).astype(F))
-            d = -c[2]
-            u = (cx + ((fx * c[0]).astype(F) / d).astype(F)).astype(F)
-            v = (cy - ((fy * c[1]).astype(F) / d).astype(F)).astype(F)
-            fi = np.floor((u + F(0.5)).astype(F))
-            fj = np.floor((v + F(0.5)).astype(F))
-            ok = (d > 0) & (fi >= F(edge)) & (fi < F(W - edge)) & (fj >= F(edge)) & (fj < F(H - edge))          # decided on the floats; NaN fails
-            ii = np.where(ok, fi, 0).astype(np.int64)
-            jj = np.where(ok, fj, 0).astype(np.int64)
-            D = depths[k][jj, ii]
+            d, fi, fj = project_f32(pts, w[k], intr)
+            ok, D = pixel_of(d, fi, fj, depths[k], edge)
             ok &= np.isfinite(D) & (D > 0)
             ok &= d <= (D + trunc).astype(F)
             seen |= ok
@@ -64,47 +104,25 @@ def seen_f64(pts, depths, intr, w2c, edge, trunc):
       d <= D + trunc: D and trunc are float32 inputs, their sum is one rounding                 ->  E = E_d + eps |D + trunc|
     A pair decided by d <= 0 has the margin of that test alone; a pair that reaches a pixel with a measurement takes the minimum over all
     four tests, one that does not (outside the image, no measurement) over the first three.  A node's margin is the minimum over the keyframes."""
-    P = np.asarray(pts, F).astype(np.float64)
     K, H, W = depths.shape
-    fx, fy, cx, cy = [float(F(x)) for x in intr]
-    w = np.asarray(w2c, F).astype(np.float64).reshape(K, 16)
+    w = np.asarray(w2c, F).reshape(K, 16)
     trunc = float(F(trunc))
-    n = len(P)
+    n = len(pts)
     seen = np.zeros(n, bool)
     margin = np.full(n, np.inf)
     classes = np.zeros((K, n), np.int64)
     with np.errstate(all="ignore"):
         for k in range(K):
-            c, Ec = [], []
-            for a in range(3):
-                terms = [w[k, 4 * a + q] * P[:, q] for q in range(3)]
-                c.append(terms[0] + terms[1] + terms[2] + w[k, 4 * a + 3])
-                Ec.append(6 * EPS * (np.abs(terms[0]) + np.abs(terms[1]) + np.abs(terms[2]) + abs(w[k, 4 * a + 3])))
-            d, Ed = -c[2], Ec[2]
+            d, fi, fj, Ed, m_pix = project_f64(pts, w[k], intr)
             m_d = np.abs(d) / Ed
-            dlo = d - Ed
             front = d > 0
-            t, m_t = [], []
-            for f, ca, Eca, c0, sign in ((fx, c[0], Ec[0], cx, 1.0), (fy, c[1], Ec[1], cy, -1.0)):
-                q = f * ca
-                r = q / d
-                uu = c0 + sign * r
-                tt = uu + 0.5
-                Er = EPS * np.abs(r) + (EPS * np.abs(q) + f * Eca + np.abs(r) * Ed) / np.where(dlo > 0, dlo, np.nan)
-                Et = Er + EPS * (np.abs(uu) + np.abs(tt))
-                t.append(tt)
-                m_t.append(np.where(dlo > 0, np.abs(tt - np.round(tt)) / Et, 0.0))
-            fi, fj = np.floor(t[0]), np.floor(t[1])
-            inimg = front & (fi >= edge) & (fi < W - edge) & (fj >= edge) & (fj < H - edge)
-            ii = np.where(inimg, fi, 0).astype(np.int64)
-            jj = np.where(inimg, fj, 0).astype(np.int64)
-            D = depths[k][jj, ii].astype(np.float64)
+            inimg, D = pixel_of(d, fi, fj, depths[k], edge)
             meas = inimg & np.isfinite(D) & (D > 0)
             lim = D + trunc
             m_z = np.abs(d - lim) / (Ed + EPS * np.abs(lim))
             ok = meas & (d <= lim)
             seen |= ok
-            m = np.where(~front, m_d, np.minimum(m_d, np.minimum(m_t[0], m_t[1])))
+            m = np.where(~front, m_d, np.minimum(m_d, m_pix))
             m = np.where(meas, np.minimum(m, m_z), m)
             margin = np.minimum(margin, np.nan_to_num(m, nan=0.0))
             cl = np.full(n, FAR)
@@ -177,6 +195,24 @@ def cull_scene(bound, shape=(37, 23, 29), pad=0.3, keyframes=(0, 1, 2), params=(
     return dict(origin=origin, step=step, nx=nx, ny=ny, nz=nz, depths=depths, intr=INTR, c2w=c2w, params=tuple(params),
                 away=list(keyframes).index(2) if 2 in keyframes else None,
                 w2c=np.stack([w2c_of(m) for m in c2w]), pts=mc.lattice_points(origin, step, nx, ny, nz))
+
+
+def view_scene(K, shape=(11, 7, 5)):
+    """a small lattice (385 nodes by default: two workgroups, a partial last wave) round the origin and K frames: seven look_at poses
+    (five round the lattice looking in, one inside it, the last looking away) cycled, five depth_image ramps cycled, so frame k's pose and image
+    both differ from those of frames k - 32 and k - 1"""
+    nx, ny, nz = shape
+    step = np.full(3, 0.2, F)
+    origin = (-0.5 * step * (np.array(shape, F) - F(1))).astype(F)
+    eyes = [((3.0, 0.3, 0.2), (0.1, 0.0, 0.0), 0.04), ((-2.6, -0.4, 0.5), (0.0, 0.1, 0.0), -0.06), ((0.4, 2.8, 0.9), (0.0, 0.0, 0.1), 0.03),
+            ((0.2, 0.1, 0.15), (0.9, 0.3, -0.2), 0.05), ((1.9, -1.8, -1.7), (0.0, 0.0, 0.0), 0.07), ((-0.5, -0.3, 3.1), (0.1, -0.1, 0.0), -0.02),
+            ((3.0, 0.3, 0.2), (6.0, 0.8, 0.5), 0.02)]
+    c2w = np.stack([look_at(e, t, r) for e, t, r in eyes]).astype(F).astype(np.float64)
+    w2c = np.stack([w2c_of(m) for m in c2w])
+    images = np.stack([depth_image(IMG_H, IMG_W, near, far) for near, far in ((2.2, 3.6), (0.3, 1.4), (2.6, 3.1), (1.8, 4.0), (2.9, 3.3))])
+    ks = np.arange(K)
+    return dict(origin=origin, step=step, nx=nx, ny=ny, nz=nz, intr=INTR, w2c=w2c[ks % len(w2c)].reshape(K, 4, 4),
+                depths=images[ks % len(images)].reshape(K, IMG_H, IMG_W), pts=mc.lattice_points(origin, step, nx, ny, nz))
 
 
 MESHER_N, MESHER_PAD = 40, 0.1

@@ -14,9 +14,7 @@ EPS = cc.EPS
 def fuse_f32(pts, depths, intr, w2c, edge, trunc, max_weight=64, state=None):
     """the rule in float32, one numpy operation per fp32 operation.  pts [n, 3] float32, depths [K, H, W] float32, intr = (fx, fy, cx, cy),
     w2c [K, 4, 4] float32; state: (T, W) float32 [n] to continue from (not changed) -> (T, W) float32 [n]"""
-    pts = np.asarray(pts, F)
-    K, H, W = depths.shape
-    fx, fy, cx, cy = [F(x) for x in intr]
+    K = depths.shape[0]
     w = np.asarray(w2c, F).reshape(K, 16)
     trunc, max_weight = F(trunc), F(max_weight)
     if state is None:
@@ -25,20 +23,8 @@ def fuse_f32(pts, depths, intr, w2c, edge, trunc, max_weight=64, state=None):
         T, Wt = np.array(state[0], F).reshape(-1), np.array(state[1], F).reshape(-1)
     with np.errstate(all="ignore"):
         for k in range(K):
-            c = []
-            for a in range(3):
-                s = (w[k, 4 * a] * pts[:, 0]).astype(F) + (w[k, 4 * a + 1] * pts[:, 1]).astype(F)
-                s = s.astype(F) + (w[k, 4 * a + 2] * pts[:, 2]).astype(F)
-                c.append((s.astype(F) + w[k, 4 * a + 3]).astype(F))
-            d = -c[2]
-            u = (cx + ((fx * c[0]).astype(F) / d).astype(F)).astype(F)
-            v = (cy - ((fy * c[1]).astype(F) / d).astype(F)).astype(F)
-            fi = np.floor((u + F(0.5)).astype(F))
-            fj = np.floor((v + F(0.5)).astype(F))
-            ok = (d > 0) & (fi >= F(edge)) & (fi < F(W - edge)) & (fj >= F(edge)) & (fj < F(H - edge))          # decided on the floats; NaN fails
-            ii = np.where(ok, fi, 0).astype(np.int64)
-            jj = np.where(ok, fj, 0).astype(np.int64)
-            D = depths[k][jj, ii]
+            d, fi, fj = cc.project_f32(pts, w[k], intr)
+            ok, D = cc.pixel_of(d, fi, fj, depths[k], edge)
             ok &= np.isfinite(D) & (D > 0)
             ok &= d <= (D + trunc).astype(F)
             sdf = (D - d).astype(F)
@@ -64,12 +50,10 @@ def fuse_f64(pts, depths, intr, w2c, edge, trunc, max_weight=64, state=None):
       b = a + t: one rounding                                                                                 ->  E_b = E_a + E_t + eps (|b| + E_a + E_t)
       T' = b / (W + 1): W + 1 is exact; one rounding                                                          ->  E_T' = E_b / (W + 1) + eps (|T'| + E_b / (W + 1))
     A frame that does not see the node leaves E_T as it is.  state: (T, W) float32 values, taken as exact (E_T = 0)."""
-    P = np.asarray(pts, F).astype(np.float64)
-    K, H, W = depths.shape
-    fx, fy, cx, cy = [float(F(x)) for x in intr]
-    w = np.asarray(w2c, F).astype(np.float64).reshape(K, 16)
+    K = depths.shape[0]
+    w = np.asarray(w2c, F).reshape(K, 16)
     trunc, max_weight = float(F(trunc)), float(F(max_weight))
-    n = len(P)
+    n = len(pts)
     if state is None:
         T, Wt = np.zeros(n), np.zeros(n)
     else:
@@ -77,19 +61,8 @@ def fuse_f64(pts, depths, intr, w2c, edge, trunc, max_weight=64, state=None):
     ET = np.zeros(n)
     with np.errstate(all="ignore"):
         for k in range(K):
-            c = []
-            for a in range(3):
-                terms = [w[k, 4 * a + q] * P[:, q] for q in range(3)]
-                c.append(terms[0] + terms[1] + terms[2] + w[k, 4 * a + 3])
-                if a == 2:
-                    Ed = 6 * EPS * (np.abs(terms[0]) + np.abs(terms[1]) + np.abs(terms[2]) + abs(w[k, 4 * a + 3]))
-            d = -c[2]
-            fi = np.floor(cx + fx * c[0] / d + 0.5)
-            fj = np.floor(cy - fy * c[1] / d + 0.5)
-            ok = (d > 0) & (fi >= edge) & (fi < W - edge) & (fj >= edge) & (fj < H - edge)
-            ii = np.where(ok, fi, 0).astype(np.int64)
-            jj = np.where(ok, fj, 0).astype(np.int64)
-            D = depths[k][jj, ii].astype(np.float64)
+            d, fi, fj, Ed, _ = cc.project_f64(pts, w[k], intr)
+            ok, D = cc.pixel_of(d, fi, fj, depths[k], edge)
             ok &= np.isfinite(D) & (D > 0)
             ok &= d <= D + trunc
             sdf = D - d
