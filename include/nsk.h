@@ -520,6 +520,35 @@ int nsk_render_image(nsk_ctx* ctx, int stage, int H0, int H1, int W0, int W1, in
  * one synchronisation. */
 int nsk_image_metrics(nsk_ctx* ctx, int Hv, int Wv, const float* d_rgb, const float* d_depth, const float* d_gt_depth,
                       const float* d_gt_color, float* d_res_depth, float* d_res_color, double h_out[8]);
+/* nsk_image_ssim: structural similarity of two images d_a, d_b ([Hv][Wv][C] float32, channel-interleaved as d_rgb is; C = 1..4, a depth
+ * image is C = 1), on the device: SSIM (Wang et al. 2004) and, with levels > 1, MS-SSIM, with the conventions of the pytorch_msssim package.
+ *   Window: win odd, 3..15; g_k = exp(-(k - win/2)^2 / (2 sigma^2)) divided by the sum of the g_k taken in index order, formed on the host
+ *     in double.  Padding is "valid": the map has Hm = Hv - win + 1 rows and Wm = Wv - win + 1 columns.
+ *   Every pixel is widened to double once; everything after that is fp64, every multiply and add an operation of its own (no FMA).
+ *   Five images are filtered, x, y, x x, y y, x y (each product formed per pixel), along W first, then along H, the taps in increasing index
+ *     order: acc = g_0 v_0, then acc = acc + g_k v_k.
+ *   Per window, with C1 = (k1 L)^2, C2 = (k2 L)^2, L = data_range:  sx = F(xx) - mx mx, sy = F(yy) - my my, sxy = F(xy) - mx my,
+ *     cs = (2 sxy + C2) / ((sx + sy) + C2),  ssim = ((2 (mx my) + C1) / ((mx mx + my my) + C1)) cs.  ssim(x, x) is 1.0 exactly.
+ *   Sums, per level and channel: the sum of ssim, the sum of cs and the count of the windows where both are finite; a window with a
+ *     non-finite value is left out of both sums and counted as left out (as nsk_image_metrics does).  The association is that of the row
+ *     reductions (256 threads, at most 1024 rows), the element the window index i Wm + j, the columns 3 c + {0 ssim, 1 cs, 2 count}.  No
+ *     floating-point atomics: two runs give the same bytes.
+ *   MS-SSIM: level l + 1 is the 2 x 2 average of level l with p = size mod 2 of zero padding per axis: pixel (i, j) =
+ *     ((v(2i-p_h, 2j-p_w) + v(2i-p_h, 2j-p_w+1)) + (v(2i-p_h+1, 2j-p_w) + v(2i-p_h+1, 2j-p_w+1))) 0.25, a source pixel outside the image
+ *     counting as 0; its size is (size + 2 p) / 2.  Level images stay in fp64.  The per-channel value of a level is its mean cs, of the last
+ *     level its mean ssim; the result is the mean over channels of prod_l max(value_l, 0)^w_l, combined on the host in double.  h_weights
+ *     ([levels] doubles, host) may be NULL only for levels = 1, or for levels = 5: the standard 0.0448, 0.2856, 0.3001, 0.2363, 0.1333.
+ *     Every level must be at least win on both sides, else the call fails and names the smallest side that would do
+ *     ((win - 1) 2^(levels - 1) + 1: 161 for the defaults).
+ *   d_map [Hm][Wm][C] (or NULL): the level-0 ssim of every window, rounded to float32.
+ *   h_out[0] the result: SSIM when levels = 1, else MS-SSIM;  [1] the level-0 SSIM, the mean over channels of the per-channel means;
+ *     [2] windows counted over all levels and channels;  [3] windows left out;  [4] levels;  [5] Hm;  [6] Wm;  [7] 0.
+ *   h_levels [levels][C][4] (host, or NULL): the sum of ssim, the sum of cs, the count, the value used for that level.
+ * A channel-level without a finite window makes [0] NaN; that is not an error.  Not capturable (the workspace of the windows' values and of
+ * the pooled levels grows to the largest call).  No other context state is read or written: a batch registered with nsk_map_prepare stays
+ * registered.  Reading h_out is the call's one synchronisation. */
+int nsk_image_ssim(nsk_ctx* ctx, int Hv, int Wv, int C, const float* d_a, const float* d_b, int win, double sigma, double data_range,
+                   double k1, double k2, int levels, const double* h_weights, float* d_map, double h_out[8], double* h_levels);
 
 /* ---- reconstruction metrics: accuracy, completion, completion ratio (upstream src/tools/eval_recon.py) ----------------------- */
 /* nsk_mesh_sample: n area-weighted surface samples of a triangle mesh (d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3]).

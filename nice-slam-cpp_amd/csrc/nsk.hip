@@ -6,6 +6,7 @@
 #include "nsk_bf16.h"
 #include "nsk_mesh.h"
 #include "nsk_image.h"
+#include "nsk_ssim.h"
 #include "nsk_cloud.h"
 #include "nsk_icp.h"
 #include "nsk_rigid.h"
@@ -853,6 +854,11 @@ struct nsk_ctx {
     struct Image {
         Buf<float> ro, rd, gd;                               // [chunk][3], [chunk][3], [chunk]: one group
     } img;
+    // structural similarity (nsk_image_ssim): the pooled levels of both images, and the windows' (ssim, cs) of the level being summed
+    struct Ssim {
+        Buf<double> pyr;                                     // levels 1 .. of a, then of b: [H_l][W_l][C] each
+        Buf<double> terms;                                   // [Hm Wm][C][2] of level 0 (the largest)
+    } ssim;
     // reconstruction metrics (nsk_mesh_sample / nsk_cloud_nearest / nsk_cloud_stats): scratch that grows to the largest call and stays
     struct Cloud {
         Buf<double> cum, bsum;                               // [triangles] cumulative areas, [workgroups] their totals
@@ -984,21 +990,32 @@ static int grow(nsk_ctx* c, Buf<T>& b, size_t n, const char* what, unsigned flag
     return dev_alloc(b, n, what);
 }
 
+// the rows of a row reduction (nsk_reduce.h) of n elements: a function of n alone
+static int rows_count(long long n, int block, int cap) { return (int)std::min<long long>((n + block - 1) / block, cap); }
+// the launches of a row reduction alone: launch(nrows, rows) the caller's partial-rows kernel, then the finisher's groups * Cols::N results
+// into `out` (rows, out: device memory of the caller's choice; nsk_image_ssim queues one reduction per level and reads them back together)
+template <class Cols, class Launch>
+static int rows_launch(nsk_ctx* c, const char* name, int groups, int nrows, double* rows, double* out, Launch launch)
+{
+    const size_t nout = (size_t)groups * Cols::N;
+    { ProfScope ps(c, name);
+      launch(nrows, rows);
+      k_rows_finish<Cols><<<(unsigned)((nout + 255) / 256), 256, 0, c->stream>>>(groups, nrows, rows, out); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // A row reduction (nsk_reduce.h) of `groups` sets of n elements each: min(ceil(n / block), cap) rows per group -- a function of n alone --
 // in the context's one scratch, launch(nrows, rows) the caller's partial-rows kernel, the finisher, groups * Cols::N doubles back to the
 // host.  Synchronises, so the scratch is free again when it returns.
 template <class Cols, class Launch>
 static int rows_reduce(nsk_ctx* c, const char* name, const char* what, int groups, long long n, int block, int cap, Launch launch, double* h_out)
 {
-    const int nrows = (int)std::min<long long>((n + block - 1) / block, cap);
+    const int nrows = rows_count(n, block, cap);
     const size_t nout = (size_t)groups * Cols::N;
     CHK(grow(c, c->rows, (size_t)groups * (cap + 1) * Cols::N, what, GROW_NO_CAPTURE));
     double* rows = c->rows;
     double* out = rows + (size_t)nrows * nout;
-    { ProfScope ps(c, name);
-      launch(nrows, rows);
-      k_rows_finish<Cols><<<(unsigned)((nout + 255) / 256), 256, 0, c->stream>>>(groups, nrows, rows, out); }
-    HIPCHK(hipGetLastError());
+    CHK(rows_launch<Cols>(c, name, groups, nrows, rows, out, launch));
     HIPCHK(hipMemcpyAsync(h_out, out, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -3174,6 +3191,104 @@ extern "C" int nsk_image_metrics(nsk_ctx* c, int Hv, int Wv, const float* d_rgb,
     h_out[0] = (double)n;
     for (int k = 0; k < 4; ++k) h_out[1 + k] = cols[k];
     h_out[5] = cols[4]; h_out[6] = h_out[7] = 0.0;
+    return 0;
+}
+
+// ---- structural similarity (nsk_ssim.h) ------------------------------------------------------------------------------------------
+template <int C, class T>
+static int ssim_level(nsk_ctx* c, const SsimArgs& A, const T* a, const T* b, float* d_map, double* rows, double* out)
+{
+    const int n = A.Hm * A.Wm;
+    double* terms = c->ssim.terms;
+    { ProfScope ps(c, "ssim_tile");
+      k_ssim_tile<T><<<dim3((unsigned)(A.tiles_x * ((A.Hm + SSIM_TILE_H - 1) / SSIM_TILE_H)), (unsigned)C), 256, 0, c->stream>>>(A, a, b, terms, d_map); }
+    HIPCHK(hipGetLastError());
+    return rows_launch<RowSums<3 * C>>(c, "ssim_sums", 1, rows_count(n, 256, IMG_MAX_ROWS), rows, out, [&](int nrows, double* r) {
+        k_ssim_sums<C><<<nrows, 256, 0, c->stream>>>(n, terms, r); });
+}
+
+template <int C>
+static int ssim_run(nsk_ctx* c, int levels, const int* Hl, const int* Wl, const float* d_a, const float* d_b, int win, const double* g, double C1,
+                    double C2, float* d_map, double* h_sums)
+{
+    // per level its partial rows, then every level's 3 C results side by side: one copy, one synchronisation
+    const size_t per = (size_t)IMG_MAX_ROWS * 3 * C;
+    double* rows = c->rows;
+    double* out = rows + (size_t)levels * per;
+    size_t off = 0, half = 0;
+    for (int l = 1; l < levels; ++l) half += (size_t)Hl[l] * Wl[l] * C;
+    const double* pa = nullptr; const double* pb = nullptr;
+    for (int l = 0; l < levels; ++l) {
+        if (l > 0) {                                        // level l from level l - 1
+            double* na = c->ssim.pyr.get() + off; double* nb = na + half;
+            const size_t n = (size_t)Hl[l] * Wl[l] * C;
+            const dim3 grid((unsigned)((n + 255) / 256), 2);
+            { ProfScope ps(c, "ssim_pool");
+              if (l == 1) k_ssim_pool<float><<<grid, 256, 0, c->stream>>>(Hl[0], Wl[0], C, Hl[1], Wl[1], d_a, d_b, na, nb);
+              else k_ssim_pool<double><<<grid, 256, 0, c->stream>>>(Hl[l - 1], Wl[l - 1], C, Hl[l], Wl[l], pa, pb, na, nb); }
+            HIPCHK(hipGetLastError());
+            pa = na; pb = nb; off += n;
+        }
+        SsimArgs A;
+        A.H = Hl[l]; A.W = Wl[l]; A.C = C; A.win = win; A.Hm = Hl[l] - win + 1; A.Wm = Wl[l] - win + 1;
+        A.tiles_x = (A.Wm + SSIM_TILE_W - 1) / SSIM_TILE_W; A.C1 = C1; A.C2 = C2;
+        for (int k = 0; k < SSIM_MAX_WIN; ++k) A.g[k] = k < win ? g[k] : 0.0;
+        if (l == 0) CHK((ssim_level<C, float>(c, A, d_a, d_b, d_map, rows, out)));
+        else CHK((ssim_level<C, double>(c, A, pa, pb, nullptr, rows + l * per, out + (size_t)l * 3 * C)));
+    }
+    HIPCHK(hipMemcpyAsync(h_sums, out, (size_t)levels * 3 * C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static bool pos_finite(double v) { return v > 0.0 && v < std::numeric_limits<double>::infinity(); }
+
+extern "C" int nsk_image_ssim(nsk_ctx* c, int Hv, int Wv, int C, const float* d_a, const float* d_b, int win, double sigma, double data_range,
+                              double k1, double k2, int levels, const double* h_weights, float* d_map, double h_out[8], double* h_levels)
+{
+    if (!c) return fail("nsk_image_ssim: null ctx");
+    if (!d_a || !d_b) return fail("nsk_image_ssim: d_a / d_b is NULL");
+    if (!h_out) return fail("nsk_image_ssim: h_out is NULL");
+    if (C < 1 || C > SSIM_MAX_C) return fail("nsk_image_ssim: C = %d, must be 1..%d", C, SSIM_MAX_C);
+    if (win < 3 || win > SSIM_MAX_WIN || win % 2 == 0) return fail("nsk_image_ssim: win = %d, must be odd and 3..%d", win, SSIM_MAX_WIN);
+    if (!pos_finite(sigma)) return fail("nsk_image_ssim: sigma = %g, must be positive and finite", sigma);
+    if (!pos_finite(data_range)) return fail("nsk_image_ssim: data_range = %g, must be positive and finite", data_range);
+    if (!pos_finite(k1)) return fail("nsk_image_ssim: k1 = %g, must be positive and finite", k1);
+    if (!pos_finite(k2)) return fail("nsk_image_ssim: k2 = %g, must be positive and finite", k2);
+    if (Hv < win || Wv < win || (long long)Hv * Wv > (1LL << 30) / SSIM_MAX_C)
+        return fail("nsk_image_ssim: Hv, Wv = %d x %d, need at least win = %d on both sides and at most 2^28 pixels", Hv, Wv, win);
+    if (levels < 1 || levels > SSIM_MAX_LEVELS) return fail("nsk_image_ssim: levels = %d, must be 1..%d", levels, SSIM_MAX_LEVELS);
+    if (!h_weights && levels != 1 && levels != 5) return fail("nsk_image_ssim: h_weights is NULL (only levels = 1, or 5 with the standard weights, need none)");
+    int Hl[SSIM_MAX_LEVELS], Wl[SSIM_MAX_LEVELS];
+    const int bad = ssim_plan_levels(Hv, Wv, win, levels, Hl, Wl);
+    if (bad >= 0)
+        return fail("nsk_image_ssim: level %d of %d x %d is %d x %d, smaller than win = %d; with levels = %d the smallest side that would do is %lld",
+                    bad, Hv, Wv, Hl[bad], Wl[bad], win, levels, ssim_min_side(win, levels));
+    if (c->capturing) return fail("nsk_image_ssim: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    size_t pyr = 0;
+    for (int l = 1; l < levels; ++l) pyr += (size_t)Hl[l] * Wl[l] * C * 2;
+    CHK(grow(c, c->ssim.pyr, pyr, "the pooled levels", GROW_NO_CAPTURE));
+    CHK(grow(c, c->ssim.terms, (size_t)(Hv - win + 1) * (Wv - win + 1) * C * 2, "the windows' values", GROW_NO_CAPTURE));
+    CHK(grow(c, c->rows, (size_t)levels * (IMG_MAX_ROWS + 1) * 3 * C, "the similarity's partial sums", GROW_NO_CAPTURE));
+    double g[SSIM_MAX_WIN];
+    ssim_window(win, sigma, g);
+    const double C1 = (k1 * data_range) * (k1 * data_range), C2 = (k2 * data_range) * (k2 * data_range);
+    double sums[SSIM_MAX_LEVELS * SSIM_MAX_C * 3];
+    switch (C) {
+        case 1: CHK(ssim_run<1>(c, levels, Hl, Wl, d_a, d_b, win, g, C1, C2, d_map, sums)); break;
+        case 2: CHK(ssim_run<2>(c, levels, Hl, Wl, d_a, d_b, win, g, C1, C2, d_map, sums)); break;
+        case 3: CHK(ssim_run<3>(c, levels, Hl, Wl, d_a, d_b, win, g, C1, C2, d_map, sums)); break;
+        default: CHK(ssim_run<4>(c, levels, Hl, Wl, d_a, d_b, win, g, C1, C2, d_map, sums)); break;
+    }
+    ssim_combine(levels, C, sums, h_weights ? h_weights : ssim_standard_weights(), h_levels, h_out);
+    double counted = 0.0, windows = 0.0;
+    for (int l = 0; l < levels; ++l) {
+        windows += (double)(Hl[l] - win + 1) * (Wl[l] - win + 1) * C;
+        for (int ch = 0; ch < C; ++ch) counted += sums[(l * C + ch) * 3 + 2];
+    }
+    h_out[2] = counted; h_out[3] = windows - counted; h_out[4] = (double)levels;
+    h_out[5] = (double)(Hv - win + 1); h_out[6] = (double)(Wv - win + 1); h_out[7] = 0.0;
     return 0;
 }
 

@@ -2,6 +2,7 @@
 // signatures (note rays_d before rays_o).  Every call marshals into include/nsk.h.
 #pragma once
 #include <tuple>
+#include <utility>
 #include <torch/torch.h>
 #include "models/NICE.h"
 
@@ -19,6 +20,10 @@ class Renderer {
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> render_img(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor c2w,
                                                                          std::string stage, torch::Tensor gt_depth, int H, int W, float fx,
                                                                          float fy, float cx, float cy);
+    // not in the reference (the evaluation of rendered keyframes): structural similarity of two images, [H][W] or [H][W][C] with C <= 4, on
+    // the device (nsk_image_ssim with the defaults win 11, sigma 1.5, k1 0.01, k2 0.03; levels = 5: MS-SSIM with the standard weights).
+    // Returns (the result: SSIM for levels = 1, else MS-SSIM; the level-0 SSIM).  h_out (or NULL): the call's eight doubles.
+    std::pair<double, double> image_ssim(torch::Tensor a, torch::Tensor b, int levels = 1, double data_range = 1.0, double* h_out = nullptr);
     // not in the reference: the scene bound is hard-coded there in five places (src/Renderer.cpp:15 ...)
     void set_bound(torch::Tensor bound_3x2);
     torch::Tensor bound;

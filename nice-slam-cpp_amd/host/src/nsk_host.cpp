@@ -423,6 +423,18 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> Renderer::render_img(c10
     return std::make_tuple(o_d.download({H, W}).to(dev), o_v.download({H, W}).to(dev), o_rgb.download({H, W, 3}).to(dev));
 }
 
+std::pair<double, double> Renderer::image_ssim(torch::Tensor a, torch::Tensor b, int levels, double data_range, double* h_out)
+{
+    TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && a.sizes() == b.sizes(), "image_ssim: a and b must have one shape, [H,W] or [H,W,C]");
+    const int H = (int)a.size(0), W = (int)a.size(1), C = a.dim() == 3 ? (int)a.size(2) : 1;
+    DevBuf da, db;
+    da.upload(a.reshape({-1})); db.upload(b.reshape({-1}));
+    double h[8];
+    check(nsk_image_ssim(ctx(), H, W, C, da.p, db.p, 11, 1.5, data_range, 0.01, 0.03, levels, nullptr, nullptr, h, nullptr));
+    if (h_out) for (int k = 0; k < 8; ++k) h_out[k] = h[k];
+    return std::make_pair(h[0], h[1]);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // torchlib/utils.h
 // ---------------------------------------------------------------------------------------------------------

@@ -27,13 +27,16 @@ SYMBOLS = (
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
-    "nsk_image_rays", "nsk_render_image", "nsk_image_metrics",
+    "nsk_image_rays", "nsk_render_image", "nsk_image_metrics", "nsk_image_ssim",
     "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
     "nsk_cloud_pair_sums", "nsk_rigid_from_sums", "nsk_cloud_icp", "nsk_cloud_transform",
     "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views", "nsk_depth_views_range",
     "nsk_points_seen", "nsk_mesh_select", "nsk_points_view_counts",
     "nsk_tsdf_integrate", "nsk_tsdf_volume",
 )
+
+
+SSIM_TILE = (8, 32)          # windows per workgroup of nsk_image_ssim's tile kernel, rows x columns (csrc/nsk_ssim.h: SSIM_TILE_H, SSIM_TILE_W)
 
 
 class NskError(RuntimeError):
@@ -109,6 +112,9 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
         L.nsk_tsdf_volume.restype = C.c_int
         L.nsk_tsdf_volume.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.nsk_image_ssim.restype = C.c_int
+        L.nsk_image_ssim.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_int, PD, C.c_void_p, PD, PD]
         _lib = L
     return _lib
 
@@ -498,6 +504,38 @@ class Context:
         if want_residuals:
             out["res_depth"], out["res_color"] = res_d, res_c
         return out
+
+    def image_ssim(self, a, b, data_range=1.0, win=11, sigma=1.5, k1=0.01, k2=0.03, levels=1, weights=None, want_map=False):
+        """nsk_image_ssim: structural similarity of two images ([H, W] or [H, W, C], C <= 4; tensors anywhere or numpy arrays) -> dict with
+        ssim (the level-0 SSIM), ms_ssim (None when levels = 1), per_level (numpy [levels, C, 4]: the sum of ssim, the sum of cs, the windows
+        counted, the value the level contributes), left_out (windows with a non-finite value), map (with want_map the level-0 ssim of every
+        window, a float32 cuda tensor [Hm, Wm] or [Hm, Wm, C]; else None) and h_out (the eight doubles of include/nsk.h).  weights: one per
+        level; None only for levels = 1, or 5 with the standard weights.  Synchronises."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        # (moved and converted on torch's current stream, before the context's stream is ordered behind it)
+        a, b = ((t if torch.is_tensor(t) else torch.tensor(np.asarray(t, dtype=np.float32))).to(device=dev, dtype=torch.float32).contiguous() for t in (a, b))
+        if a.shape != b.shape or a.dim() not in (2, 3):
+            raise NskError("image_ssim: a and b must have one shape, [H, W] or [H, W, C] (got %s and %s)" % (tuple(a.shape), tuple(b.shape)))
+        if weights is not None and len(weights) != int(levels):
+            raise NskError("image_ssim: weights has %d entries for levels = %d" % (len(weights), int(levels)))
+        return self._image_ssim(a, b, float(data_range), int(win), float(sigma), float(k1), float(k2), int(levels), weights, want_map)
+
+    @_ordered
+    def _image_ssim(self, a, b, data_range, win, sigma, k1, k2, levels, weights, want_map):
+        import numpy as np
+        import torch
+        Hv, Wv = int(a.shape[0]), int(a.shape[1])
+        Cn = int(a.shape[2]) if a.dim() == 3 else 1
+        w = None if weights is None else (C.c_double * len(weights))(*[float(v) for v in weights])
+        m = torch.empty((max(Hv - win + 1, 0), max(Wv - win + 1, 0)) + ((Cn,) if a.dim() == 3 else ()), dtype=torch.float32, device=a.device) if want_map else None
+        h = (C.c_double * 8)()
+        hl = (C.c_double * (max(levels, 1) * max(Cn, 1) * 4))()
+        _chk(lib().nsk_image_ssim(self.h, Hv, Wv, Cn, _ptr(a), _ptr(b), win, sigma, data_range, k1, k2, levels, w, _ptr(m), h, hl))
+        h = [float(x) for x in h]
+        return dict(ssim=h[1], ms_ssim=h[0] if levels > 1 else None, per_level=np.array(hl[:levels * Cn * 4], np.float64).reshape(levels, Cn, 4),
+                    left_out=int(h[3]), map=m, h_out=h)
 
     @_ordered
     def sample_mesh(self, verts, tris, n, seed, want_tri=False):
