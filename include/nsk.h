@@ -118,7 +118,16 @@ int nsk_set_sort_mode(nsk_ctx* ctx, int mode);
  *   "no_occ_role" 1 | 2: the forward's middle and fine decoders never | always as one workgroup role (default: where the split predicts
  *                      the shorter launch; same results either way);
  *   "no_dead_skip" 1:  the backward's frozen roles run every tile even where an optimiser mask discards all it scatters (see nsk_set_mask);
- *   "dead_tile_pct" p: what a skipped tile counts for in the backward's workgroup split, in percent of a tile that runs (default 12). */
+ *   "dead_tile_pct" p: what a skipped tile counts for in the backward's workgroup split, in percent of a tile that runs (default 12);
+ *   "static_deal" 1:   every role of the backward takes its tiles round-robin, as before the queues.  By default, in a mapping launch with a
+ *                      trainable decoder, a frozen role that skips dead tiles and whose waves have "deal_min_rounds" rounds of tiles or more
+ *                      deals only the first part of its tiles that way and claims the rest, a few consecutive tiles at a time, from a cursor
+ *                      in device memory, so that waves whose tiles were mostly dead take more (k_decode_bwd_multi_deal; same gradients up to
+ *                      the order of the atomic adds).  The deterministic mode, launches with ray gradients, the launches without a trainable
+ *                      decoder (their 16-wave kernel) and the trainable role always deal statically;
+ *   "deal_head_pct" p: share of such a role's rounds that stay dealt statically (0 .. 100, default 75);
+ *   "deal_chunk" n:    consecutive tiles per claim of the rest (1 .. 16, default 2);
+ *   "deal_min_rounds" n: a role with fewer rounds of tiles per wave deals statically (default 24; 0: every skipping role claims: tests). */
 int nsk_set_tuning(nsk_ctx* ctx, const char* key, int value);
 
 /* Scene bound [[x0,x1],[y0,y1],[z0,z1]]; the reference hard-codes it in five places

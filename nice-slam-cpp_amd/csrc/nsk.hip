@@ -809,6 +809,13 @@ struct nsk_ctx {
     bool live_ok = false;                   // the primary sampling set holds liveness bytes for the current step (forward_core)
     Buf<int> live_cnt;                      // device: tiles run by [middle, fine, colour] + the publishing ticket
     int* live_host = nullptr; int* live_host_dev = nullptr;      // host memory the last counting workgroup writes [3 counts, tag]; never waited for
+    // ---- queue dealing of the backward's skipping roles (decode_bwd_body: Dealing)
+    Buf<int> deal_cur;                      // device: one cursor per level [middle, fine, colour], NSK_DEAL_STRIDE ints apart (a memory line each)
+    bool deal_armed = false;                // the launch in front of the coming backward zeroes the cursors (k_composite); else backward_core does, with a memset
+    int tune_static_deal = 0;               // 1: every role deals its tiles statically (tile_of), as before the cursors (A/B runs, tests)
+    int tune_deal_head_pct = 75;            // share of a skipping frozen role's rounds that stay dealt statically
+    int tune_deal_min_rounds = 24;          // a role whose waves have fewer rounds of tiles than this deals statically
+    int tune_deal_chunk = 2;                // consecutive tiles per claim of the rest (1 .. 16)
     int live_tag = 1;                       // names the current (stage, batch size, flags, masks) of the counts: a step reads only counts of its own kind
     int live_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     int dbg_wgs[3] = {0, 0, 0}, dbg_ntasks = 0;      // the last backward's split: workgroups of the role of each level (frozen or trainable), its tile count
@@ -1070,6 +1077,8 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
     HIPCHK(hipMemset(c->scal, 0, 16 * sizeof(float)));
     CHK(dev_alloc(c->live_cnt, 4, "the live-tile counters"));
     HIPCHK(hipMemset(c->live_cnt, 0, 4 * sizeof(int)));
+    CHK(dev_alloc(c->deal_cur, 3 * NSK_DEAL_STRIDE, "the dealing cursors"));
+    HIPCHK(hipMemset(c->deal_cur, 0, 3 * NSK_DEAL_STRIDE * sizeof(int)));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->live_host), 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
     memset(c->live_host, 0, 16 * sizeof(int));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->live_host_dev), c->live_host, 0));
@@ -1083,7 +1092,7 @@ extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
 #undef SETB
     CHK(set_lds(k_median_thr, 16384 * 4));
     CHK(set_lds(k_decode_fwd_multi, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_bf16<8>, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_bf16<8, 2>, 160 * 1024)); CHK(set_lds(k_decode_fwd_multi_occ<8>, 160 * 1024));
-    CHK(set_lds(k_decode_bwd_multi<false>, 160 * 1024 - 256)); CHK(set_lds(k_decode_bwd_multi<true>, 160 * 1024));      // (<false>, frozen: the scan role keeps a few words of static LDS)
+    CHK(set_lds(k_decode_bwd_multi<false>, 160 * 1024 - 256)); CHK(set_lds(k_decode_bwd_multi_deal, 160 * 1024 - 256)); CHK(set_lds(k_decode_bwd_multi<true>, 160 * 1024));      // (<false>, frozen: the scan role keeps a few words of static LDS)
     CHK(set_lds(k_decode_bwd_frozen, 160 * 1024 - 256));
     CHK(set_lds(k_decode_bwd_track, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<false>, 160 * 1024)); CHK(set_lds(k_decode_bwd_multi_full<true>, 160 * 1024));
     CHK(set_lds(k_decode_fwd_dump<0>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<1>, 160 * 1024)); CHK(set_lds(k_decode_fwd_dump<2>, 160 * 1024));
@@ -1155,6 +1164,10 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "deterministic")) { c->deterministic = value != 0; return 0; }
     if (!strcmp(key, "no_dead_skip")) { c->tune_no_dead_skip = value; return 0; }
     if (!strcmp(key, "dead_tile_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: dead_tile_pct out of range"); c->tune.dead_tile_pct = value; return 0; }
+    if (!strcmp(key, "static_deal")) { c->tune_static_deal = value; return 0; }
+    if (!strcmp(key, "deal_head_pct")) { if (value < 0 || value > 100) return fail("nsk_set_tuning: deal_head_pct out of range"); c->tune_deal_head_pct = value; return 0; }
+    if (!strcmp(key, "deal_min_rounds")) { if (value < 0) return fail("nsk_set_tuning: deal_min_rounds must be >= 0"); c->tune_deal_min_rounds = value; return 0; }
+    if (!strcmp(key, "deal_chunk")) { if (value < 1 || value > 16) return fail("nsk_set_tuning: deal_chunk must be 1 .. 16"); c->tune_deal_chunk = value; return 0; }
     if (!strcmp(key, "roctx")) { c->roctx = value != 0; return 0; }
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     if (!strcmp(key, "cloud_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: cloud_cells_x4 must be 1 .. 256"); c->cloud.cells_x4 = value; return 0; }
@@ -2547,7 +2560,7 @@ static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, int stage
 }
 
 // scan_wgs: of prep_ride_scan; extra: the workgroup that sums the per-ray losses
-static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool rays, bool full, bool frozen_only, bool track, int scan_wgs, int extra)
+static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool rays, bool full, bool frozen_only, bool track, int scan_wgs, int extra, const DealRoles* deal)
 {
     const int n = R.n; const size_t lds = R.lds;
     ProfScope ps(c, "decode_bwd_multi");
@@ -2563,6 +2576,7 @@ static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool 
         const size_t lds16 = lds - 8 * 3840 + (size_t)NSK_FROZEN_NW * 3840;      // image + one scatter scratch per wave
         k_decode_bwd_frozen<<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
     } else if (rays) k_decode_bwd_multi<true><<<MA.wg_end[n - 1] + extra, 512, lds, c->stream>>>(MA);
+    else if (deal) k_decode_bwd_multi_deal<<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA, *deal);
     else k_decode_bwd_multi<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA);
 }
 
@@ -2575,6 +2589,7 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     for (int k = 0; k < 3; ++k) { c->dbg_live[k] = -1; c->dbg_counted[k] = false; c->dbg_wgs[k] = 0; }      // (nsk_debug_live_tiles: this backward's, whichever way it leaves)
     c->dbg_ntasks = ntasks;
     CHK(flush_pending(c));                      // gradients accumulate across calls: the slabs are about to be overwritten
+    struct Disarm { nsk_ctx* c; ~Disarm() { c->deal_armed = false; } } disarm{c};      // an arming holds for this backward only
     MultiArgs MA;
     memset(&MA, 0, sizeof(MA));
     BwdRoles R;
@@ -2601,6 +2616,22 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     int tasks[3]; bool counted[3];
     bwd_liveness(c, MA, R, stage, M, flags, grids && !rays && !full && !dyn_resid, frozen_only, tasks, counted);
     plan_bwd(c->num_cu, ntasks, n, R.cost, train_role, frozen_only ? NSK_FROZEN_NW : 8, tasks, MA.wg_end);
+    // Queue dealing of the skipping roles (decode_bwd_body: Dealing).  Only where a wave has rounds enough for a claimed tail to even out: K2 and the
+    // K4 shard (11 and 10 rounds per wave, the trainable role's iterations being the launch) gain nothing, and the K4 shard pays 1.2 - 1.6 us for the claims.
+    // Not in the 16-wave kernel of the all-frozen launches: a role there is ~2000 waves of ~8 tiles, every wave claims at least twice, and adds on
+    // one address serialise at ~25 ns (K3 fine stage 83 -> 114 us with per-wave claims).  Never in the deterministic mode,
+    // which has no skipping roles.
+    bool dealt = false; DealRoles DR;
+    memset(&DR, 0, sizeof(DR));
+    for (int r = 0; r < n && !c->tune_static_deal && !frozen_only && !rays && !full && !dyn_resid; ++r) {
+        if (!counted[r]) continue;
+        const int rounds = (ntasks + role_wgs(MA.wg_end, r) * 8 - 1) / (role_wgs(MA.wg_end, r) * 8);
+        if (rounds < c->tune_deal_min_rounds) continue;
+        DR.r[r] = DealArgs{c->deal_cur + (MA.which[r] - 1) * NSK_DEAL_STRIDE, c->tune_deal_head_pct, c->tune_deal_chunk};
+        dealt = true;
+    }
+    // the cursors start at zero: the compositing launch in front of this one armed them (nsk_map_step, nsk_render_backward); a backward on its own arms here
+    if (dealt && !c->deal_armed) HIPCHK(hipMemsetAsync(c->deal_cur, 0, 3 * NSK_DEAL_STRIDE * sizeof(int), c->stream));
     for (int r = 0; r < n; ++r) {
         if (counted[r]) MA.live_wgs += role_wgs(MA.wg_end, r);
         if (MA.which[r] >= 1) c->dbg_wgs[MA.which[r] - 1] = role_wgs(MA.wg_end, r);
@@ -2616,7 +2647,7 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
         record_split(c, 1, form, n, MA.which, MA.train, MA.wg_end, track ? 0 : scan_wgs, track ? (d_loss ? 1 : 0) : extra, ntasks, MA.wg_end[n - 1] + riders);
         c->dbg_split[1][15] = track ? 1 : 0;
     }
-    launch_bwd_roles(c, MA, R, rays, full, frozen_only, dyn_resid != nullptr, scan_wgs, extra);
+    launch_bwd_roles(c, MA, R, rays, full, frozen_only, dyn_resid != nullptr, scan_wgs, extra, dealt ? &DR : nullptr);
     HIPCHK(hipGetLastError());
     if (train_role >= 0) { c->pend_w = MA.which[train_role]; c->pend_nb = role_wgs(MA.wg_end, train_role); }      // summed by k_adam_multi, or by flush_pending when someone reads the slab first
     return 0;
@@ -2634,8 +2665,10 @@ extern "C" int nsk_render_backward(nsk_ctx* c, int stage, int N, const float* ro
     comp_args(c, A, stage, N, S, ro, rd);
     A.mode = 1; A.g_rgb = g_rgb; A.g_depth = g_depth; A.g_var = g_var;
     if (flags & NSK_GRAD_RAYS) { A.g_rays_o = g_ro; A.g_rays_d = g_rd; }
+    A.deal = c->deal_cur;
     { ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A); }
     HIPCHK(hipGetLastError());
+    c->deal_armed = true;      // only now: the launch that zeroes the cursors is on the stream
     CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd));
     account(c, stage, N * S, N, true, flags);
     return 0;
@@ -2675,6 +2708,7 @@ extern "C" int nsk_map_step(nsk_ctx* c, int stage, int N, const float* ro, const
     A.mode = 2; A.gt_depth = gt; A.gt_color = gtc; A.w_color = w_color; A.use_color = use_color;
     A.rgb = rgb; A.depth = depth; A.var = var; A.loss = c->ws.ray_loss;
     if (flags & NSK_GRAD_RAYS) { A.g_rays_o = g_ro; A.g_rays_d = g_rd; }
+    A.deal = c->deal_cur;      // the cursors of the backward's queues are zeroed by this launch, whichever form it takes
     SampArgs SA; int sb = 0;
     CHK(prep_ride_sample(c, SA, &sb));
     if (sb) {            // the next batch's sampling behind this batch's compositing, one launch (k_composite_sample)
@@ -2684,6 +2718,7 @@ extern "C" int nsk_map_step(nsk_ctx* c, int stage, int N, const float* ro, const
         ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A);
     }
     HIPCHK(hipGetLastError());
+    c->deal_armed = true;      // only now: the launch is on the stream (an error return above leaves the next backward to arm with its memset)
     CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd, d_loss));
     account(c, stage, N * S, N, true, flags);
     return 0;

@@ -871,6 +871,11 @@ struct DecArgs {
     // role counts the tiles it ran; live == nullptr: every tile runs, through the body without any of this
     const uint8_t* live; unsigned live_bit; int* live_cnt;
 };
+// queue dealing of a skipping frozen role (decode_bwd_body<.., DEAL>): the role's cursor, only ever added to, armed to 0 by the launch in front of the
+// backward (nullptr: every tile dealt statically, tile_of); the role deals the first head percent of its rounds statically and claims the rest in
+// chunks of chunk consecutive tiles.  An argument of its own of the one kernel that claims (k_decode_bwd_multi_deal).
+struct DealArgs { int* cur; int head, chunk; };
+struct DealRoles { DealArgs r[3]; };      // by role of the launch (MultiArgs::a)
 
 // ray of sample mm = mm / S without the generic division (~25 vector instructions): umulhi by ceil(2^32 / S), exact for mm < 2^32 / S
 // a load at base + a 32-bit BYTE offset: scalar base, one unsigned vector offset -- no sign extension and no 64-bit shift-add per access (an
@@ -1074,7 +1079,9 @@ struct CompArgs {
     float* g_seed;                                                            // mode 5: [N][3] the d/d rays_d term of the compositing itself (g_rays_d gets 0)
     const uint8_t* keep;                                                      // [N] or nullptr: rays with keep == 0 are rendered but take no part in
                                                                               // the loss or its gradient (nsk_set_ray_mask: the reference drops them)
+    int* deal;                                                                // the backward's dealing cursors (DecArgs::deal), zeroed here for the launch behind this one, or nullptr
 };
+#define NSK_DEAL_STRIDE 32      // ints between two roles' cursors: each on a memory line of its own (adds on one line serialise)
 
 __device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
@@ -1176,6 +1183,7 @@ template <int RPW>           // rays (waves) per workgroup; bid / nb: this role'
 __device__ __forceinline__ void composite_body(const CompArgs& A, int bid, int nb)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (A.deal && bid == 0 && threadIdx.x < 3) A.deal[threadIdx.x * NSK_DEAL_STRIDE] = 0;      // as k_sample arms the bump cursor of the cell sort
     int n = bid * RPW + wave;
     if (n >= A.N) {
         if (A.mode != 4) return;
@@ -1499,11 +1507,12 @@ __device__ __forceinline__ void image_commit(f4* __restrict__ dst, const ImgRegs
 // SKIP: with an optimiser mask on this role's level, a tile none of whose samples touches a marked voxel is not run at all: everything it would
 // scatter lands on voxels whose gradient nobody reads (include/nsk.h: "gradients of unmarked voxels are discarded").  Only for launches that
 // want nothing but grid gradients from a frozen role: ray gradients (d/dp) flow through every sample whatever the voxel mask says.
-template <int WHICH, bool RAYS, int NW = 8, bool FULL = false, bool DYN = false, bool SKIP = false>      // FULL: the chain on the fp32 MFMA whatever RAYS says (nsk_set_backward_mode 0)
-__device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int nb)          // DYN: the Tracker's median mask is found and applied here (composite mode 5)
+template <int WHICH, bool RAYS, int NW = 8, bool FULL = false, bool DYN = false, bool SKIP = false, bool DEAL = false>      // DEAL: see Dealing below; FULL: the chain on the fp32 MFMA whatever RAYS says (nsk_set_backward_mode 0)
+__device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int nb, const DealArgs& D = DealArgs{})          // DYN: the Tracker's median mask is found and applied here (composite mode 5)
 {
     static_assert(!DYN || RAYS, "the deferred median mask belongs to the Tracker's ray-gradient launch");
     static_assert(!SKIP || (!RAYS && !FULL && !DYN), "dead tiles are skipped only where grid gradients are all a frozen role is asked for");
+    static_assert(!DEAL || SKIP, "only a skipping role claims tiles from a cursor");
     constexpr bool XYZ = WHICH != 0;
     constexpr int OD = WHICH == 3 ? 4 : 1;
     constexpr bool NEED_E = XYZ && RAYS;
@@ -1549,7 +1558,21 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
     // wave reads the liveness of 64 of its tiles at once -- lane l the sixteen bytes of its l-th tile, one 16-byte load, one ballot -- and walks
     // the set bits of that scalar mask: the pipeline below (this tile, the next one's loads, the index two ahead) runs over LIVE tiles only.
     // (Never in the deterministic mode: its waves meet at barriers in every round.)
+    //
+    // The pipeline's three positions k, k1, k2 are ROUNDS of the static deal (tile = tile_of(k, wg, nw), end = kmax) -- or, DEAL, the TILES themselves
+    // (end = NONE): `tile` below maps a position to its tile either way, so that without DEAL this is the loop it always was.
+    //
+    // Dealing.  Live tiles cost six to eight times what dead ones do, so equal tile counts are unequal loads.  With DEAL only the first kh rounds are
+    // dealt as ever (tile_of); the tiles from t0 = kh * nw on are claimed from the cursor D.cur in chunks of D.chunk consecutive tiles, one
+    // returning add per chunk by lane 0.  A wave keeps one chunk claimed ahead of the one it walks: the add goes out at the top of a tile, in front
+    // of that tile's staged loads, and has landed with them (the opaque use in front of the scatter); the chunk's liveness bytes are fetched at
+    // the top of the NEXT tile and land the same way -- so neither round trip is waited for where its result is used, and the tile indices are
+    // known the two live tiles ahead that the perm prefetch needs.  The cursor is only ever added to; a claim past the last chunk ends the wave's
+    // claiming.  Every tile is walked once: in its head block by its wave, or in the chunk of the one wave that claimed it.
     typedef unsigned int lu4 __attribute__((ext_vector_type(4)));
+    constexpr int NONE = 0x7fffffff;
+    auto tile = [&](int c) { if constexpr (DEAL) return c; else return tile_of(c, wg, nw); };
+    const int kend = DEAL ? NONE : kmax;
     unsigned long long lmask = 0; int lblk = 0, ran = 0;
     auto live_load = [&](int kb) {                     // the bytes of tile kb + lane of this wave (clamped into the array)
         const int t = min(tile_of(kb + lane, wg, nw), ntasks - 1);
@@ -1578,19 +1601,70 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         }
         return kmax;
     };
+    // DEAL: lmask holds the live tiles of the current block not yet handed out, tile = bbase + (bit >> bshift) * bstride: a block of the head (64 rounds,
+    // a bit each), or a claimed chunk (at most 16 consecutive tiles, every fourth bit).  A chunk's bytes are ONE register: lane l holds bytes 4 (l & 3) ..
+    // + 3 of tile pre_base + (l >> 2) -- the sixteen bytes per lane of the head's form, held over a tile, were four registers this kernel does not have.
+    const bool dyn = DEAL && D.cur != nullptr;                             // (a role of the dealt launch too short to claim: all of it is head)
+    const int kh = dyn ? kmax * D.head / 100 : kmax;                   // rounds dealt statically
+    const int t0 = dyn ? min(kh * nw, ntasks) : ntasks;                     // first tile of the claimed tail
+    const int chunk = dyn ? D.chunk : 1, nch = (ntasks - t0 + chunk - 1) / chunk;
+    const int nhead = (kh + 63) >> 6;
+    int bbase = 0, bstride = 0, bshift = 0;
+    int pend = 0, pre_base = NONE, claim_v = 0;     // pend: 1 = a claim is in flight (claim_v, lane 0), 2 = its chunk starts at pre_base and its bytes are in pre_lw
+    unsigned pre_lw = 0u;
+    auto head_block = [&](const lu4& w, int kb) {       // rounds kb .. kb + 63 of the static head; past round kh nothing is this wave's
+        lmask = live_ballot(w, kb);
+        if (kh - kb < 64) lmask &= kh > kb ? (1ull << (kh - kb)) - 1ull : 0ull;
+        bbase = tile_of(kb, wg, nw); bstride = nw; bshift = 0;
+    };
+    auto chunk_block = [&]() {                          // the claimed chunk at pre_base, its bytes in pre_lw
+        const int t = pre_base + (lane >> 2), q = lane & 3;
+        const int left = A.M - t * 16 - 4 * q;          // valid slots of the lane's four (the last tile may be ragged)
+        const unsigned keep = left >= 4 ? 0xffffffffu : (left <= 0 ? 0u : ((1u << (8 * left)) - 1u));
+        const bool lv = (pre_lw & (A.live_bit * 0x01010101u) & keep) != 0u;
+        unsigned long long b = (unsigned long long)__builtin_amdgcn_ballot_w64(lv && (lane >> 2) < chunk && t < ntasks);
+        b |= b >> 1; b |= b >> 2;
+        lmask = b & 0x1111111111111111ull;
+        bbase = pre_base; bstride = 1; bshift = 2;
+    };
+    auto claim = [&]() { if (lane == 0) claim_v = atomicAdd(D.cur, 1); pend = 1; };
+    auto resolve = [&]() {
+        const int c = __builtin_amdgcn_readfirstlane(claim_v);
+        pre_base = c < nch ? t0 + c * chunk : NONE;
+        if (pre_base != NONE) pre_lw = ld32<unsigned>(A.live, (unsigned)min(pre_base + (lane >> 2), ntasks - 1) * 16u + (unsigned)(lane & 3) * 4u);
+        pend = 2;
+    };
+    auto tick = [&]() { if (pend == 1) resolve(); };    // at the top of a tile, in front of its staged loads
+    auto next_tile = [&]() {                            // this wave's next live tile, or NONE (and NONE ever after)
+        for (;;) {
+            if (lmask) { const int i = (int)__builtin_ctzll(lmask); lmask &= lmask - 1ull; return bbase + (i >> bshift) * bstride; }
+            if (lblk + 1 < nhead) { ++lblk; head_block(live_load(lblk << 6), lblk << 6); continue; }
+            if (pend == 0) return NONE;
+            if (pend == 1) resolve();                   // (a chunk with at most one live tile: the claim behind it has not had a tile's time)
+            pend = 0;
+            if (pre_base == NONE) return NONE;
+            chunk_block();
+            claim();
+        }
+    };
     int kfirst = 0, k1 = 1;
     {
         lu4 lw0;
         if constexpr (SKIP) lw0 = live_load(0);
+        if constexpr (DEAL) { if (nch > 0) claim(); }
         int mm0 = 0;
         if constexpr (!SKIP) mm0 = slot_sample(A, slot_of(tile_of(0, wg, nw)));
         image_issue<64 * NW>(img_regs, img_src, IMG_F / 4);
-        if constexpr (SKIP) {
+        if constexpr (DEAL) {
+            head_block(lw0, 0);
+            kfirst = next_tile();
+            mm0 = slot_sample(A, slot_of(kfirst));
+        } else if constexpr (SKIP) {
             lmask = live_ballot(lw0, 0);
             kfirst = next_live(-1);
             mm0 = slot_sample(A, slot_of(tile_of(kfirst, wg, nw)));
         }
-        stage(tile_of(kfirst, wg, nw), mm0, nx);
+        stage(tile(kfirst), mm0, nx);
         if constexpr (DYN) {
             constexpr int PER = (NSK_MEDIAN_FUSED_MAX + 64 * NW - 1) / (64 * NW);
             float rv[PER];
@@ -1606,17 +1680,19 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
             __syncthreads();
         }
     }
-    if constexpr (SKIP) k1 = next_live(kfirst);
-    int mm_next = slot_sample(A, slot_of(tile_of(k1, wg, nw)));
+    if constexpr (DEAL) { tick(); k1 = next_tile(); }
+    else if constexpr (SKIP) k1 = next_live(kfirst);
+    int mm_next = slot_sample(A, slot_of(tile(k1)));
     const bool det = (A.flags & 0x8000u) != 0;      // deterministic debug mode: every wave walks all kmax rounds (they meet at barriers)
     int k2 = 2;
-    for (int k = kfirst; k < kmax; k = k1, k1 = k2) {      // !SKIP: k, k1 = k + 1, k2 = k + 2 as ever; SKIP: this wave's next live tiles
-        const int task = tile_of(k, wg, nw);
+    for (int k = kfirst; k < kend; k = k1, k1 = k2) {      // !SKIP: k, k1 = k + 1, k2 = k + 2 as ever; SKIP: this wave's next live tiles
+        const int task = tile(k);
         if constexpr (!SKIP) { if (task >= ntasks && !det) break; }
         asm volatile("" ::: "memory");      // keep the LDS fragment reads inside the loop (LICM would hoist + spill them)
         const bool valid = task * 16 + j < A.M;
         k2 = k1 + 1;
-        if constexpr (SKIP) { k2 = next_live(k1); ++ran; }      // a live tile runs whole, its dead lanes included, as ever
+        if constexpr (DEAL) { tick(); k2 = next_tile(); ++ran; }
+        else if constexpr (SKIP) { k2 = next_live(k1); ++ran; }      // a live tile runs whole, its dead lanes included, as ever
         const int mm = nx.mm;
         float px, py, pz;
         sample_finish(A, nx.r, px, py, pz);
@@ -1635,8 +1711,8 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         float unscale = 1.f;
         if constexpr (B16) unscale = chain_scale<OD>(gout);
         const unsigned long long mask = nx.mask;
-        stage(tile_of(k1, wg, nw), mm_next, nx);
-        mm_next = slot_sample(A, slot_of(tile_of(k2, wg, nw)));
+        stage(tile(k1), mm_next, nx);
+        mm_next = slot_sample(A, slot_of(tile(k2)));
         f4 xcos[6];
         if constexpr (NEED_E) { f4 e[6]; embed<true>(Bm, g, px, py, pz, e, xcos); }
         f4 gh[2];                                                // g_h4 = Wo^T g_out
@@ -1705,6 +1781,7 @@ __device__ __forceinline__ void decode_bwd_body(const DecArgs& A, int bid, int n
         // opaque use: the staged registers must hold their data here, i.e. the loads retire before the first atomic below
         asm volatile("" : "+v"(nx.r.z), "+v"(nx.r.o[0]), "+v"(nx.r.o[1]), "+v"(nx.r.o[2]), "+v"(nx.r.d[0]), "+v"(nx.r.d[1]), "+v"(nx.r.d[2]),
                           "+v"(nx.gr), "+v"(nx.mask), "+v"(mm_next));
+        if constexpr (DEAL) asm volatile("" : "+v"(claim_v), "+v"(pre_lw));      // a claim and a claimed chunk's bytes land with them (see Dealing)
         if constexpr (RAYS) {       // g_p through the embedding (g_e * cos(pB)) B^T and through the trilinear lookup
             float gp[3] = {0.f, 0.f, 0.f};
             if constexpr (NEED_E) {
@@ -1780,10 +1857,14 @@ __device__ __forceinline__ void live_publish(const MultiArgs& MA)
     __threadfence_system();
 }
 // a frozen role of a launch without ray gradients: the skipping body where the role has liveness bytes, else the body as it always was
-template <int WHICH, int NW>
-__device__ __forceinline__ void decode_bwd_frozen_role(const MultiArgs& MA, int r, int bid, int nb)
+template <int WHICH, int NW, bool DEAL = false>
+__device__ __forceinline__ void decode_bwd_frozen_role(const MultiArgs& MA, int r, int bid, int nb, const DealArgs& D = DealArgs{})
 {
-    if (MA.a[r].live) { decode_bwd_body<WHICH, false, NW, false, false, true>(MA.a[r], bid, nb); live_publish(MA); }
+    if (MA.a[r].live) {
+        if constexpr (DEAL) decode_bwd_body<WHICH, false, NW, false, false, true, true>(MA.a[r], bid, nb, D);
+        else decode_bwd_body<WHICH, false, NW, false, false, true>(MA.a[r], bid, nb);
+        live_publish(MA);
+    }
     else decode_bwd_body<WHICH, false, NW>(MA.a[r], bid, nb);
 }
 

@@ -1193,6 +1193,30 @@ __global__ __launch_bounds__(512) void k_decode_bwd_multi(MultiArgs MA)
     }
 }
 
+// The mapping launch (no ray gradients) whose skipping frozen roles claim the tail of their tiles from a cursor (decode_bwd_body: Dealing; D.r[r]: the
+// cursor of role r, or none).  A kernel of its own, so that the launches that deal statically are k_decode_bwd_multi<false> as it always was and carry
+// none of the claiming code: in their loop it cost K3 5 us, K2 and the K4 shard 1 us.
+__global__ __launch_bounds__(512) void k_decode_bwd_multi_deal(MultiArgs MA, DealRoles D)
+{
+    if (MA.sum_n > 0 && blockIdx.x == gridDim.x - 1) { block_sum(MA.sum_src, MA.sum_n, MA.sum_dst); return; }
+    if ((int)blockIdx.x >= MA.wg_end[MA.n - 1]) { sort_scan_body<2>(MA.scan, (int)blockIdx.x - MA.wg_end[MA.n - 1]); return; }
+    int r = 0;
+    while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;
+    const int b0 = r == 0 ? 0 : MA.wg_end[r - 1];
+    const int bid = blockIdx.x - b0, nb = MA.wg_end[r] - b0;
+    const int sel = MA.which[r] * 2 + (MA.train[r] ? 1 : 0);
+    switch (sel) {
+    case 0: decode_bwd_body<0, false>(MA.a[r], bid, nb); break;
+    case 1: decode_bwd_train_any<0, false>(MA.a[r], bid, nb); break;
+    case 2: decode_bwd_frozen_role<1, 8, true>(MA, r, bid, nb, D.r[r]); break;
+    case 3: decode_bwd_train_any<1, false>(MA.a[r], bid, nb); break;
+    case 4: decode_bwd_frozen_role<2, 8, true>(MA, r, bid, nb, D.r[r]); break;
+    case 5: break;     // (as in k_decode_bwd_multi)
+    case 6: decode_bwd_frozen_role<3, 8, true>(MA, r, bid, nb, D.r[r]); break;
+    default: decode_bwd_train_any<3, false>(MA.a[r], bid, nb); break;
+    }
+}
+
 // The same launch with every chain on the fp32 MFMA (nsk_set_backward_mode 0: full-width operands, what the reference's fp32 autograd multiplies,
 // src/Mapper.cpp:443-444): frozen roles = the body the ray-gradient launches use, trainable role = the one-phase-per-weight body with fp32
 // fragments.  A measuring stick (tests, bench extras), not the product path: 240 fp32 MFMAs of 32 cycles per trainable tile instead of 90 of 16.
