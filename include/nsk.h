@@ -839,6 +839,14 @@ int nsk_debug_live_tiles(nsk_ctx* ctx, int M, int* h_counts, int32_t* h_perm, ui
 #define NSK_SPLIT_BWD_FROZEN 4       /* k_decode_bwd_frozen */
 #define NSK_SPLIT_BWD_TRACK 5        /* k_decode_bwd_track */
 int nsk_debug_last_split(nsk_ctx* ctx, int dir, int* h_out);
+/* nsk_debug_decoder_images: one of the derived copies of decoder `which`'s parameters that the MFMA kernels read, copied to the host after a
+ * synchronise (tests/test_gpu_adam.py: an optimiser step rewrites them through inverse index tables, an upload builds them through the forward
+ * tables, and the two must agree byte for byte).  what = 0 the fp32 forward fragment image, 1 the fp32 backward image, 2 the forward image in
+ * 16-bit pieces (2 fp16 under matmul mode 2, 3 bf16 otherwise) followed by its fp32 tail, 3 the fp16 backward image followed by its fp32 tail
+ * (built lazily: a stale one is rebuilt first, as the next backward that reads it would).  Returns the image's size in bytes (0: the coarse
+ * decoder has no image in pieces), -1 on failure; h_out = NULL only asks for the size, otherwise capacity (bytes) must hold the image.
+ * Changes nothing a step reads. */
+int nsk_debug_decoder_images(nsk_ctx* ctx, int which, int what, void* h_out, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -2897,6 +2897,28 @@ extern "C" int nsk_debug_last_split(nsk_ctx* c, int dir, int* h_out)
     memcpy(h_out, c->dbg_split[dir], sizeof(c->dbg_split[dir]));
     return 0;
 }
+// one of a decoder's device images, to the host (layout: include/nsk.h).  Reads only: the one thing it may launch is the rebuild of a stale fp16
+// backward image (ensure_bimg16), which the next backward that reads that image would launch itself.
+extern "C" int nsk_debug_decoder_images(nsk_ctx* c, int which, int what, void* h_out, size_t capacity)
+{
+    if (!c || !which_ok(which)) return fail("nsk_debug_decoder_images: bad argument");
+    if (what < 0 || what > 3) return fail("nsk_debug_decoder_images: what = 0 (fp32 forward), 1 (fp32 backward), 2 (forward in pieces), 3 (fp16 backward)");
+    if (c->capturing) return fail("nsk_debug_decoder_images: not while a graph is being captured");
+    DecState& D = c->dec[which];
+    if (!D.loaded) return fail("decoder %d not uploaded", which);
+    HIPCHK(hipSetDevice(c->device));
+    if (what == 3) CHK(ensure_bimg16(c, which));
+    const float* src = what == 0 ? D.fimg.get() : (what == 1 ? D.bimg.get() : (what == 2 ? D.fimg16.get() : D.bimg16.get()));
+    const size_t floats = what == 0 ? (size_t)D.fimg_n : (what == 1 ? (size_t)D.bimg_n : (what == 2 ? (size_t)D.fimg16_f : (size_t)MlpBwdImgH::TOTAL_F));
+    const size_t bytes = src ? floats * 4 : 0;               // the coarse decoder has no image in pieces
+    if (bytes > (size_t)0x7fffffff) return fail("nsk_debug_decoder_images: image too large");
+    if (h_out && bytes) {
+        if (capacity < bytes) return fail("nsk_debug_decoder_images: the image has %zu bytes, the buffer %zu", bytes, capacity);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(h_out, src, bytes, hipMemcpyDeviceToHost));
+    }
+    return (int)bytes;
+}
 // the ReLU inputs of decoder `which` over the samples of the last step (same rays), by the forward body of the current matmul mode
 extern "C" int nsk_debug_preact(nsk_ctx* c, int which, int N, const float* ro, const float* rd, float* d_out /*[M][5][32] device*/)
 {

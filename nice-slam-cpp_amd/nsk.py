@@ -24,6 +24,7 @@ SYMBOLS = (
     "nsk_camera_from_tensor", "nsk_camera_backward", "nsk_inside_filter", "nsk_adam_vector", "nsk_adam_step",
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
     "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch", "nsk_debug_live_tiles", "nsk_debug_last_split",
+    "nsk_debug_decoder_images",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
@@ -1387,6 +1388,26 @@ class Context:
         n = int(h[1])
         return dict(form=(self.BWD_FORMS if backward else self.FWD_FORMS)[h[0]], n=n, which=tuple(h[2:2 + n]), train=tuple(h[5:5 + n]),
                     wgs=tuple(h[8:8 + n]), scan_wgs=int(h[11]), loss_wg=int(h[12]), tiles=int(h[13]), grid=int(h[14]), median_wg=int(h[15]))
+
+    DECODER_IMAGES = ("fwd32", "bwd32", "fwd16", "bwd16")
+
+    def debug_decoder_images(self, which, what):
+        """uint8 array: the bytes of one device image of decoder `which` (include/nsk.h) -- what = a name of DECODER_IMAGES or its index:
+        the fp32 forward / backward image, the forward image in 16-bit pieces + fp32 tail, the fp16 backward image + fp32 tail
+        (empty for an image the decoder does not have)"""
+        import numpy as np
+        w = STAGES[which] if isinstance(which, str) else int(which)
+        code = self.DECODER_IMAGES.index(what) if isinstance(what, str) else int(what)
+        n = lib().nsk_debug_decoder_images(self.h, w, code, None, C.c_size_t(0))
+        if n < 0:
+            _chk(n)
+        out = np.zeros(n, np.uint8)
+        if n:
+            got = lib().nsk_debug_decoder_images(self.h, w, code, out.ctypes.data_as(C.c_void_p), C.c_size_t(n))
+            if got != n:
+                _chk(-1 if got < 0 else 0)
+                raise NskError("nsk_debug_decoder_images: the image changed size between two calls (%d, %d bytes)" % (n, got))
+        return out
 
     @_ordered
     def debug_preact(self, which, rays_o, rays_d, M):
