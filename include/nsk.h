@@ -594,6 +594,50 @@ int nsk_cloud_nearest(nsk_ctx* ctx, const float* d_query, int n_query, const flo
  * bytes.  Reading h_out is the call's one synchronisation.  n = 0 gives zeros. */
 int nsk_cloud_stats(nsk_ctx* ctx, const float* d_dist, int n, float threshold, double h_out[4]);
 
+/* ---- reconstruction metrics against the surface itself: point-to-triangle distances, normal agreement -------------------------- */
+/* nsk_mesh_nearest: for every query point [n_query][3] the distance to the nearest point of the mesh (d_dist), the triangle that holds it
+ * (d_tri, or NULL) and that point (d_point [n_query][3], or NULL).  The results are the bits of a brute-force evaluation over all
+ * triangles; the search structure only decides which triangles are looked at.  Every operation below is an fp32 operation of its own
+ * (no FMA contraction).
+ *   Which triangles take part.  The triangles to which nsk_mesh_sample gives a positive area: a triangle is left out and counted in
+ *     *h_skipped (or NULL) when an index is outside [0, n_vertices), a vertex is non-finite, or the fp64 area is not finite or not positive.
+ *   Box.  lo and hi are the componentwise min and max of the triangle's three fp32 vertices a, b, c.
+ *   Plane candidate.  e0 = b - a, e1 = c - a, n = e0 x e1 with each component fl(fl(xy) - fl(zw));  nn = (n.x n.x + n.y n.y) + n.z n.z;
+ *     s = ((q - a) . n) / nn (a dot product is (x x' + y y') + z z');  p = q - s n.  The candidate counts when all four of these hold:
+ *     nn > 0;  ((e0 x (p - a)) . n) >= 0;  (((c - b) x (p - b)) . n) >= 0;  (((a - c) x (p - c)) . n) >= 0.
+ *   Edge candidates, in the order ab, bc, ca.  For an edge (u, v): e = v - u, w = q - u, t = clamp((w . e) / (e . e), 0, 1) with t = 0 unless
+ *     e . e > 0, p = u + t e.
+ *   Clamp.  Every candidate point is clamped componentwise to [lo, hi] (p < lo ? lo : p > hi ? hi : p).  The clamp is exact, and it is
+ *     what makes the stopping bound below hold for the value as evaluated.
+ *   Distance.  d2 = (dx dx + dy dy) + dz dz with dx = q_x - p_x, exactly as nsk_cloud_nearest forms it.
+ *   Choice.  The triangle's d2 is the smallest candidate's; ties go plane, ab, bc, ca.  Across triangles the lowest triangle index wins
+ *     among equal d2.  d_dist = the correctly rounded square root of that d2; d_point = the clamped candidate point that gave it.
+ *   Conventions, as in nsk_cloud_nearest.  A query with a non-finite component gets NaN / -1 / NaN.  Without a participating triangle
+ *     every query gets +inf / -1 / NaN (so does a query for which no candidate of any triangle has a comparable d2, which needs
+ *     coordinates whose squares overflow).  n_triangles = 0 is an error that leaves the context usable; n_query = 0 is valid.
+ * Search: a uniform grid with the planes and the cell rule of nsk_cloud_nearest over the box of the participating triangles' vertices.
+ * A triangle is registered in every cell its [lo, hi] overlaps (count -> exclusive scan -> place); the cell edge stays above 8 ulp of the
+ * largest coordinate, there are at most 2^22 cells, and the edge grows by 1.25 until the references fit their cap.  A triangle whose box
+ * covers more than 64 cells goes to a wide list that every query tests before its walk.  A query walks the shells of nsk_cloud_nearest and
+ * stops on the same rule, best d2 < fl(m m) strictly: a triangle that is registered in no cell of the searched block has its whole
+ * [lo_a, hi_a] beyond one of the block's planes on some axis a, the clamped candidate point lies inside [lo_a, hi_a], so |fl(q_a - p_a)|
+ * >= m and d2 as evaluated >= fl(m m).  nsk_set_tuning "surface_cells_x4" (cells aimed at per participating triangle, in quarters;
+ * default 16) and "surface_query_mode" (bit 0 reserved; + 2 queries always in input order, + 4 always in cell order; 0: in cell order
+ * from 2^19 queries on) change no byte of the result.  Memory O(n_triangles + references + cells + n_query), owned by the context and
+ * reused.  Not capturable.  Synchronises (the box, the skipped count and the reference count come back to the host). */
+int nsk_mesh_nearest(nsk_ctx* ctx, const float* d_query, int n_query, const float* d_vertices, int n_vertices, const int32_t* d_triangles,
+                     int n_triangles, float* d_dist, int32_t* d_tri, float* d_point, int* h_skipped);
+/* nsk_normal_stats: the agreement of the normals of n triangle pairs; pair i is triangle d_ia[i] of mesh A (d_va [nva][3], d_ta [nta][3])
+ * and triangle d_ib[i] of mesh B.
+ *   Normal: n = (b - a) x (c - a), formed in double from the float32 vertices, each operation on its own (a component is xy - zw of two
+ *     rounded products).  cos_i = |n_A . n_B| / (|n_A| |n_B|), the dot products as (x x' + y y') + z z', |n| = sqrt(n . n).
+ *   A pair is skipped when a triangle index is negative or out of range, a vertex index is out of range, or a length is not finite or not
+ *     positive.
+ *   h_out[0] the sum of cos_i;  [1] the pairs counted;  [2] the pairs skipped.  The sum is the row reduction of nsk_cloud_stats: two runs
+ *     give the same bytes.  n = 0 gives zeros.  Reading h_out is the call's one synchronisation.  Not capturable. */
+int nsk_normal_stats(nsk_ctx* ctx, int n, const float* d_va, int nva, const int32_t* d_ta, int nta, const int32_t* d_ia,
+                     const float* d_vb, int nvb, const int32_t* d_tb, int ntb, const int32_t* d_ib, double h_out[3]);
+
 /* ---- alignment: point-to-point ICP of the reconstruction onto the ground truth (upstream src/tools/eval_recon.py, align=True: Open3D's
  * registration_icp with threshold 0.1 m, identity start, 30 iterations, relative fitness / RMSE 1e-6) ------------------------------ */
 /* The rule.

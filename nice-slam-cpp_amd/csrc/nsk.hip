@@ -8,6 +8,7 @@
 #include "nsk_image.h"
 #include "nsk_ssim.h"
 #include "nsk_cloud.h"
+#include "nsk_surface.h"
 #include "nsk_icp.h"
 #include "nsk_rigid.h"
 #include "nsk_raster.h"
@@ -876,6 +877,15 @@ struct nsk_ctx {
         int cells_x4 = 4;                                    // nsk_set_tuning "cloud_cells_x4": grid cells aimed at per finite target, in quarters
         int query_mode = 0;                                  // nsk_set_tuning "cloud_query_mode": bit 0 a wave per query; + 2 queries always in input order, + 4 always in cell order (neither: by size)
     } cloud;
+    // distances to a mesh (nsk_mesh_nearest): the packed triangles and their grid; the queries' ordering reuses cloud.q*
+    struct Surface {
+        Buf<SurfTri> rec;                                    // [triangles] 48-byte records, a.w = 1: takes part
+        Buf<unsigned> start, cursor;                         // [cells + 1 + scan levels] first reference of every cell, [cells] placement cursors
+        Buf<int> refs, wide;                                 // [references] triangle indices in cell order, [triangles] the wide list
+        Buf<unsigned long long> counters;                    // [0] references, [1] wide triangles
+        int cells_x4 = SURF_CELLS_X4;                        // nsk_set_tuning "surface_cells_x4": grid cells aimed at per participating triangle, in quarters
+        int query_mode = 0;                                  // nsk_set_tuning "surface_query_mode": bit 0 reserved; + 2 queries always in input order, + 4 always in cell order (neither: by size)
+    } surface;
     // mesh depth views (nsk_mesh_depth): the queue of large pixel boxes, its cursor and the skipped count
     struct Raster {
         Buf<RasterJob> queue;                                // [queue_cap] (view, triangle, box) entries of the launch in flight
@@ -1172,6 +1182,8 @@ extern "C" int nsk_set_tuning(nsk_ctx* c, const char* key, int value)
     if (!strcmp(key, "lattice_slab")) { if (value < 0 || value >= (1 << 26)) return fail("nsk_set_tuning: lattice_slab must be 0 (automatic) or a node count below 2^26"); c->mesh.slab = value; return 0; }
     if (!strcmp(key, "cloud_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: cloud_cells_x4 must be 1 .. 256"); c->cloud.cells_x4 = value; return 0; }
     if (!strcmp(key, "cloud_query_mode")) { if (value < 0 || value > 5) return fail("nsk_set_tuning: cloud_query_mode must be 0 .. 5"); c->cloud.query_mode = value; return 0; }
+    if (!strcmp(key, "surface_cells_x4")) { if (value < 1 || value > 256) return fail("nsk_set_tuning: surface_cells_x4 must be 1 .. 256"); c->surface.cells_x4 = value; return 0; }
+    if (!strcmp(key, "surface_query_mode")) { if (value != 0 && value != 2 && value != 4) return fail("nsk_set_tuning: surface_query_mode must be 0, 2 or 4 (bit 0 is reserved)"); c->surface.query_mode = value; return 0; }
     if (!strcmp(key, "raster_inline_max")) { if (value < 0) return fail("nsk_set_tuning: raster_inline_max must be >= 0"); c->raster.inline_max = value; return 0; }
     if (!strcmp(key, "raster_queue_cap")) { if (value < 1 || value > (1 << 24)) return fail("nsk_set_tuning: raster_queue_cap must be 1 .. 2^24"); c->raster.queue_cap = value; return 0; }
     if (!strcmp(key, "raster_load_first")) { if (value < 0 || value > 1) return fail("nsk_set_tuning: raster_load_first must be 0 or 1"); c->raster.load_first = value; return 0; }
@@ -3642,6 +3654,107 @@ extern "C" int nsk_cloud_transform(nsk_ctx* c, const double* h_M, const float* d
       k_cloud_transform<<<(unsigned)(((long long)n + CLOUD_BLOCK - 1) / CLOUD_BLOCK), CLOUD_BLOCK, 0, c->stream>>>(X, n, d_in, d_out);
       HIPCHK(hipGetLastError()); }
     return 0;
+}
+
+// ---- distances to the surface (nsk_surface.h) -------------------------------------------------------------------------------------
+extern "C" int nsk_mesh_nearest(nsk_ctx* c, const float* d_query, int n_query, const float* d_vertices, int n_vertices,
+                                const int32_t* d_triangles, int n_triangles, float* d_dist, int32_t* d_tri, float* d_point, int* h_skipped)
+{
+    if (!c) return fail("nsk_mesh_nearest: null ctx");
+    if (n_query < 0 || n_vertices < 0 || n_triangles < 0) return fail("nsk_mesh_nearest: negative count");
+    if (n_triangles == 0) return fail("nsk_mesh_nearest: the mesh has no triangle");
+    if (!d_triangles || (n_vertices > 0 && !d_vertices)) return fail("nsk_mesh_nearest: d_vertices / d_triangles is NULL");
+    if (n_query > 0 && (!d_query || !d_dist)) return fail("nsk_mesh_nearest: d_query / d_dist is NULL");
+    if (c->capturing) return fail("nsk_mesh_nearest: not while a graph is being captured");
+    HIPCHK(hipSetDevice(c->device));
+    nsk_ctx::Surface& S = c->surface;
+    nsk_ctx::Cloud& K = c->cloud;
+    const int nt = n_triangles;
+    const int tb = (int)(((long long)nt + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+    const int qb = (int)(((long long)n_query + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+    CHK(grow(c, S.rec, (size_t)nt, "the packed triangles", GROW_NO_CAPTURE));
+    double cols[7];
+    CHK(rows_reduce<CloudBoxCols>(c, "surface_records", "the partial boxes", 1, nt, CLOUD_BLOCK, CLOUD_MAX_ROWS, [&](int nrows, double* rows) {
+        k_surf_records<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n_vertices, nt, d_vertices, d_triangles, S.rec, rows); }, cols));       // pass 1
+    const long long n_valid = (long long)cols[6];
+    if (h_skipped) *h_skipped = (int)(nt - n_valid);
+    if (n_query == 0) return 0;
+    CloudGrid G;
+    G.nfinite = (int)n_valid; G.h = G.inv_h = 1.f;
+    for (int a = 0; a < 3; ++a) { G.lo[a] = 0.f; G.dim[a] = 1; }
+    if (n_valid == 0) {                                         // every query: +inf / -1 / NaN (NaN for a non-finite one); no grid is read
+        ProfScope ps(c, "surface_query");
+        k_surf_query<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, nullptr, nullptr, nullptr, S.rec, nullptr, 0, d_dist, d_tri, d_point);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    float box[6];
+    for (int k = 0; k < 6; ++k) box[k] = (float)cols[k];       // (floats widened by the kernel: the same floats)
+    SurfPlan P = surf_plan(box, n_valid, S.cells_x4);
+    const long long cap = surf_ref_cap(n_valid);
+    CHK(grow(c, S.wide, (size_t)nt, "the wide triangles", GROW_NO_CAPTURE));
+    CHK(grow(c, S.counters, 2, "the reference counts", GROW_NO_CAPTURE));
+    size_t cells = 0, words = 0;
+    unsigned long long counts[2] = {0, 0};
+    for (int round = 0;; ++round) {
+        for (int a = 0; a < 3; ++a) { G.lo[a] = P.lo[a]; G.dim[a] = P.dim[a]; }
+        G.h = P.h; G.inv_h = P.inv_h;
+        cells = (size_t)P.cells(); words = mc_scan_words(cells + 1);
+        CHK(grow(c, S.start, words, "the cells' first references", GROW_NO_CAPTURE));
+        { ProfScope ps(c, "surface_grid");
+          HIPCHK(hipMemsetAsync(S.start, 0, words * 4, c->stream));
+          HIPCHK(hipMemsetAsync(S.counters, 0, 16, c->stream));
+          k_surf_count<<<tb, CLOUD_BLOCK, 0, c->stream>>>(G, nt, S.rec, S.start, S.wide, S.counters);                              // pass 2
+          HIPCHK(hipGetLastError()); }
+        HIPCHK(hipMemcpyAsync(counts, S.counters, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((long long)counts[0] <= cap) break;
+        if (round >= SURF_MAX_GROW || !surf_plan_grow(P)) return fail("nsk_mesh_nearest: %llu cell references do not fit %lld", counts[0], cap);
+    }
+    CHK(grow(c, S.cursor, cells, "the cells' placement cursors", GROW_NO_CAPTURE));
+    CHK(grow(c, S.refs, (size_t)std::max<unsigned long long>(counts[0], 1), "the cells' triangles", GROW_NO_CAPTURE));
+    { ProfScope ps(c, "surface_grid");
+      HIPCHK(hipMemsetAsync(S.cursor, 0, cells * 4, c->stream));
+      CHK(mc_scan(c, S.start, (int)cells + 1));                                                                                      // pass 3
+      k_surf_place<<<tb, CLOUD_BLOCK, 0, c->stream>>>(G, nt, S.rec, S.start, S.cursor, S.refs);                                     // pass 4
+      HIPCHK(hipGetLastError()); }
+    // queries in cell order, as nsk_cloud_nearest orders them (the same kernels, the same scratch)
+    const bool ordered = (S.query_mode & 4) || (!(S.query_mode & 2) && n_query >= CLOUD_ORDER_MIN);
+    if (ordered) {
+        CHK(grow(c, K.qcell, (size_t)n_query, "the queries' cells", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qperm, (size_t)n_query, "the queries in cell order", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qstart, words, "the cells' first queries", GROW_NO_CAPTURE));
+        CHK(grow(c, K.qcursor, cells, "the cells' query cursors", GROW_NO_CAPTURE));
+        ProfScope ps(c, "surface_order");
+        HIPCHK(hipMemsetAsync(K.qstart, 0, words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(K.qcursor, 0, cells * 4, c->stream));
+        k_cloud_cells<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, 1, K.qcell, K.qstart);
+        HIPCHK(hipGetLastError());
+        CHK(mc_scan(c, K.qstart, (int)cells + 1));
+        k_cloud_place<<<qb, CLOUD_BLOCK, 0, c->stream>>>(n_query, d_query, K.qcell, K.qstart, K.qcursor, nullptr, K.qperm);
+        HIPCHK(hipGetLastError());
+    }
+    { ProfScope ps(c, "surface_query");
+      k_surf_query<<<qb, CLOUD_BLOCK, 0, c->stream>>>(G, n_query, d_query, ordered ? K.qperm.get() : nullptr, S.start, S.refs, S.rec, S.wide,
+                                                      (int)counts[1], d_dist, d_tri, d_point);
+      HIPCHK(hipGetLastError()); }
+    return 0;
+}
+
+extern "C" int nsk_normal_stats(nsk_ctx* c, int n, const float* d_va, int nva, const int32_t* d_ta, int nta, const int32_t* d_ia,
+                                const float* d_vb, int nvb, const int32_t* d_tb, int ntb, const int32_t* d_ib, double h_out[3])
+{
+    if (!c) return fail("nsk_normal_stats: null ctx");
+    if (n < 0 || nva < 0 || nta < 0 || nvb < 0 || ntb < 0) return fail("nsk_normal_stats: negative count");
+    if (!h_out) return fail("nsk_normal_stats: h_out is NULL");
+    if (n > 0 && (!d_ia || !d_ib)) return fail("nsk_normal_stats: d_ia / d_ib is NULL");
+    if ((nta > 0 && (!d_ta || (nva > 0 && !d_va))) || (ntb > 0 && (!d_tb || (nvb > 0 && !d_vb)))) return fail("nsk_normal_stats: a mesh pointer is NULL");
+    if (c->capturing) return fail("nsk_normal_stats: not while a graph is being captured");
+    for (int k = 0; k < 3; ++k) h_out[k] = 0.0;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return rows_reduce<RowSums<3>>(c, "normal_stats", "the normal sums of the workgroups", 1, n, CLOUD_BLOCK, CLOUD_MAX_ROWS, [&](int nrows, double* rows) {
+        k_normal_stats<<<nrows, CLOUD_BLOCK, 0, c->stream>>>(n, d_va, nva, d_ta, nta, d_ia, d_vb, nvb, d_tb, ntb, d_ib, rows); }, h_out);
 }
 
 // ---- depth views of a mesh (nsk_raster.h) -----------------------------------------------------------------------------------------

@@ -29,6 +29,12 @@ struct ReconMetrics {
     double transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // align: the reconstruction was measured under this (row-major 4x4)
     double icp_fitness = 0, icp_rmse = 0;                                     // align: share of rec vertices with a gt vertex within reach, their rmse (m)
     int icp_iterations = 0;                                                   // align: updates applied
+    // surface: the samples were measured against the other MESH (nsk_mesh_nearest), not against its samples; rec_skipped / gt_skipped then
+    // count the triangles left out
+    bool surface = false;
+    double precision_pct = 0, recall_pct = 0, fscore_pct = 0;                 // rec samples below the threshold, = completion_ratio_pct, 2PR / (P + R) (0 when P + R is 0)
+    double normal_accuracy = 0, normal_completion = 0, normal_consistency = 0;        // mean |cos| of a sample's own triangle and the nearest one, each way, and their mean
+    int normal_skipped = 0;                                                   // pairs without two normals (nsk_normal_stats)
 };
 
 // upstream's 2D number of a reconstruction, Depth L1 (src/tools/eval_recon.py calc_2d_metric), and what went into it
@@ -107,12 +113,15 @@ class Mesher {
     // Accuracy / completion / completion ratio on the device: n_points area-weighted samples of each mesh (nsk_mesh_sample with seed and
     // seed + 1), exact nearest distances both ways (nsk_cloud_nearest), the sums (nsk_cloud_stats).  Coordinates in metres; the meshes
     // are taken as they are: callers that follow upstream's protocol pass meshes culled by cull_mesh.  With align the reconstruction's vertices are first registered to the ground truth's
-    // (align_recon) and the transformed mesh is measured.  A static function: it needs no map, only the process's context.
+    // (align_recon) and the transformed mesh is measured.  With surface the rec samples are measured against the gt mesh and the gt samples
+    // against the rec mesh (nsk_mesh_nearest: exact point-to-triangle distances), and precision / recall / F-score and the normal
+    // consistency (nsk_normal_stats on each sample's own triangle and the nearest one) are filled in as well.  A static function: it needs
+    // no map, only the process's context.
     static ReconMetrics eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n_points = 200000, float threshold = 0.05f,
-                                   unsigned long long seed = 0, bool align = false);
+                                   unsigned long long seed = 0, bool align = false, bool surface = false);
     static ReconMetrics eval_recon(const float* rec_xyz, int rec_vertices, const int32_t* rec_triangles, int rec_n_triangles, const float* gt_xyz,
                                    int gt_vertices, const int32_t* gt_triangles, int gt_n_triangles, int n_points = 200000,
-                                   float threshold = 0.05f, unsigned long long seed = 0, bool align = false);
+                                   float threshold = 0.05f, unsigned long long seed = 0, bool align = false, bool surface = false);
     // upstream's get_align_transformation: point-to-point ICP of the reconstruction's vertices onto the ground truth's from the identity
     // (nsk_cloud_icp: Open3D's registration_icp, relative fitness / rmse 1e-6).  Host arrays [n][3]; nothing is changed.
     static ReconAlign align_recon(const float* rec_xyz, int rec_vertices, const float* gt_xyz, int gt_vertices, float threshold = 0.1f,

@@ -484,7 +484,7 @@ template <class R> static void keep_alignment(R& M, const ReconAlign& A)
 
 // ---- reconstruction metrics ----------------------------------------------------------------------------------------------------------
 ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t* rec_tris, int rec_nt, const float* gt_xyz, int gt_nv,
-                                const int32_t* gt_tris, int gt_nt, int n, float threshold, unsigned long long seed, bool align)
+                                const int32_t* gt_tris, int gt_nt, int n, float threshold, unsigned long long seed, bool align, bool surface)
 {
     if (n < 1) throw std::runtime_error("Mesher::eval_recon: n_points must be at least 1");
     if (rec_nt < 1 || gt_nt < 1) throw std::runtime_error("Mesher::eval_recon: a mesh without a triangle");
@@ -494,25 +494,55 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
     ReconMetrics M;
     if (align) keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
     DevMem rec_pts((size_t)n * 3 * sizeof(float)), gt_pts((size_t)n * 3 * sizeof(float)), dist((size_t)n * sizeof(float));
-    {   // the meshes leave the device again as soon as their samples are drawn
-        DevMem v((size_t)rec_nv * 3 * sizeof(float)), t((size_t)rec_nt * 3 * sizeof(int32_t));
-        up(v, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(t, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
-        if (align) check(nsk_cloud_transform(ctx(), M.transform, (const float*)v.p, rec_nv, (float*)v.p));
-        check(nsk_mesh_sample(ctx(), (const float*)v.p, rec_nv, (const int32_t*)t.p, rec_nt, seed, n, (float*)rec_pts.p, nullptr, &M.rec_area, &M.rec_degenerate));
-        check(nsk_sync(ctx()));
-    }
-    {
-        DevMem v((size_t)gt_nv * 3 * sizeof(float)), t((size_t)gt_nt * 3 * sizeof(int32_t));
-        up(v, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(t, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
-        check(nsk_mesh_sample(ctx(), (const float*)v.p, gt_nv, (const int32_t*)t.p, gt_nt, seed + 1, n, (float*)gt_pts.p, nullptr, &M.gt_area, &M.gt_degenerate));
-        check(nsk_sync(ctx()));
-    }
-    double a[4], c[4];
-    check(nsk_cloud_nearest(ctx(), (const float*)rec_pts.p, n, (const float*)gt_pts.p, n, (float*)dist.p, nullptr, &M.gt_skipped));
-    check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
-    check(nsk_cloud_nearest(ctx(), (const float*)gt_pts.p, n, (const float*)rec_pts.p, n, (float*)dist.p, nullptr, &M.rec_skipped));
-    check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
     const double nan = std::nan("");
+    double a[4], c[4];
+    if (surface) {      // both meshes stay on the device: every sample is measured against the other mesh's triangles
+        DevMem rv((size_t)rec_nv * 3 * sizeof(float)), rt((size_t)rec_nt * 3 * sizeof(int32_t));
+        DevMem gv((size_t)gt_nv * 3 * sizeof(float)), gt((size_t)gt_nt * 3 * sizeof(int32_t));
+        DevMem own((size_t)n * sizeof(int32_t)), gt_own((size_t)n * sizeof(int32_t)), hit((size_t)n * sizeof(int32_t));
+        up(rv, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(rt, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
+        up(gv, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(gt, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
+        const float *RV = (const float*)rv.p, *GV = (const float*)gv.p;
+        const int32_t *RT = (const int32_t*)rt.p, *GT = (const int32_t*)gt.p;
+        if (align) check(nsk_cloud_transform(ctx(), M.transform, RV, rec_nv, (float*)rv.p));
+        check(nsk_mesh_sample(ctx(), RV, rec_nv, RT, rec_nt, seed, n, (float*)rec_pts.p, (int32_t*)own.p, &M.rec_area, &M.rec_degenerate));
+        check(nsk_mesh_sample(ctx(), GV, gt_nv, GT, gt_nt, seed + 1, n, (float*)gt_pts.p, (int32_t*)gt_own.p, &M.gt_area, &M.gt_degenerate));
+        double na[3], nc[3];
+        check(nsk_mesh_nearest(ctx(), (const float*)rec_pts.p, n, GV, gt_nv, GT, gt_nt, (float*)dist.p, (int32_t*)hit.p, nullptr, &M.gt_skipped));
+        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
+        check(nsk_normal_stats(ctx(), n, RV, rec_nv, RT, rec_nt, (const int32_t*)own.p, GV, gt_nv, GT, gt_nt, (const int32_t*)hit.p, na));
+        check(nsk_mesh_nearest(ctx(), (const float*)gt_pts.p, n, RV, rec_nv, RT, rec_nt, (float*)dist.p, (int32_t*)hit.p, nullptr, &M.rec_skipped));
+        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
+        check(nsk_normal_stats(ctx(), n, GV, gt_nv, GT, gt_nt, (const int32_t*)gt_own.p, RV, rec_nv, RT, rec_nt, (const int32_t*)hit.p, nc));
+        check(nsk_sync(ctx()));
+        M.surface = true;
+        M.precision_pct = a[1] > 0 ? 100.0 * a[2] / a[1] : nan;
+        M.recall_pct = c[1] > 0 ? 100.0 * c[2] / c[1] : nan;
+        const double pr = M.precision_pct + M.recall_pct;
+        M.fscore_pct = pr > 0 ? 2.0 * M.precision_pct * M.recall_pct / pr : (pr == 0 ? 0.0 : nan);
+        M.normal_accuracy = na[1] > 0 ? na[0] / na[1] : nan;
+        M.normal_completion = nc[1] > 0 ? nc[0] / nc[1] : nan;
+        M.normal_consistency = 0.5 * (M.normal_accuracy + M.normal_completion);
+        M.normal_skipped = (int)(na[2] + nc[2]);
+    } else {
+        {   // the meshes leave the device again as soon as their samples are drawn
+            DevMem v((size_t)rec_nv * 3 * sizeof(float)), t((size_t)rec_nt * 3 * sizeof(int32_t));
+            up(v, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(t, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
+            if (align) check(nsk_cloud_transform(ctx(), M.transform, (const float*)v.p, rec_nv, (float*)v.p));
+            check(nsk_mesh_sample(ctx(), (const float*)v.p, rec_nv, (const int32_t*)t.p, rec_nt, seed, n, (float*)rec_pts.p, nullptr, &M.rec_area, &M.rec_degenerate));
+            check(nsk_sync(ctx()));
+        }
+        {
+            DevMem v((size_t)gt_nv * 3 * sizeof(float)), t((size_t)gt_nt * 3 * sizeof(int32_t));
+            up(v, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(t, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
+            check(nsk_mesh_sample(ctx(), (const float*)v.p, gt_nv, (const int32_t*)t.p, gt_nt, seed + 1, n, (float*)gt_pts.p, nullptr, &M.gt_area, &M.gt_degenerate));
+            check(nsk_sync(ctx()));
+        }
+        check(nsk_cloud_nearest(ctx(), (const float*)rec_pts.p, n, (const float*)gt_pts.p, n, (float*)dist.p, nullptr, &M.gt_skipped));
+        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
+        check(nsk_cloud_nearest(ctx(), (const float*)gt_pts.p, n, (const float*)rec_pts.p, n, (float*)dist.p, nullptr, &M.rec_skipped));
+        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
+    }
     M.accuracy_cm = a[1] > 0 ? 100.0 * a[0] / a[1] : nan;
     M.completion_cm = c[1] > 0 ? 100.0 * c[0] / c[1] : nan;
     M.completion_ratio_pct = c[1] > 0 ? 100.0 * c[2] / c[1] : nan;
@@ -520,7 +550,8 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
     return M;
 }
 
-ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n, float threshold, unsigned long long seed, bool align)
+ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& gt_ply, int n, float threshold, unsigned long long seed, bool align,
+                                bool surface)
 {
     std::vector<float> rv, gv;
     std::vector<int32_t> rt, gt;
@@ -529,7 +560,7 @@ ReconMetrics Mesher::eval_recon(const std::string& rec_ply, const std::string& g
     if (rt.empty()) throw std::runtime_error("Mesher::eval_recon: " + rec_ply + " has no triangle");
     if (gt.empty()) throw std::runtime_error("Mesher::eval_recon: " + gt_ply + " has no triangle");
     return eval_recon(rv.data(), (int)(rv.size() / 3), rt.data(), (int)(rt.size() / 3), gv.data(), (int)(gv.size() / 3), gt.data(), (int)(gt.size() / 3),
-                      n, threshold, seed, align);
+                      n, threshold, seed, align, surface);
 }
 
 // ---- reconstruction depth L1 -----------------------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
-// eval_recon_test REC.ply GT.ply [n] [threshold] [seed] [align] -- Mesher::eval_recon on two PLY files, one JSON line (tests/test_gpu_recon.py,
-// tests/test_gpu_icp.py); align 1: the reconstruction is registered to the ground truth first and the alignment is printed too
+// eval_recon_test REC.ply GT.ply [n] [threshold] [seed] [align] [surface] -- Mesher::eval_recon on two PLY files, one JSON line
+// (tests/test_gpu_recon.py, tests/test_gpu_icp.py, tests/test_gpu_surface.py); align 1: the reconstruction is registered to the ground truth
+// first and the alignment is printed too; surface (given at all: 1 measures against the other mesh, 0 against its samples): the surface
+// fields are printed too
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
@@ -8,13 +10,14 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s REC.ply GT.ply [n] [threshold] [seed] [align]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s REC.ply GT.ply [n] [threshold] [seed] [align] [surface]\n", argv[0]); return 2; }
     const int n = argc > 3 ? std::atoi(argv[3]) : 200000;
     const float threshold = argc > 4 ? (float)std::atof(argv[4]) : 0.05f;
     const unsigned long long seed = argc > 5 ? std::strtoull(argv[5], nullptr, 10) : 0ull;
     const bool align = argc > 6 && std::atoi(argv[6]) != 0;
+    const bool has_surface = argc > 7, surface = has_surface && std::atoi(argv[7]) != 0;
     try {
-        const ReconMetrics m = Mesher::eval_recon(argv[1], argv[2], n, threshold, seed, align);
+        const ReconMetrics m = Mesher::eval_recon(argv[1], argv[2], n, threshold, seed, align, surface);
         std::printf("{\"accuracy_cm\": %.17g, \"completion_cm\": %.17g, \"completion_ratio_pct\": %.17g, \"accuracy_max_cm\": %.17g, "
                     "\"completion_max_cm\": %.17g, \"rec_area\": %.17g, \"gt_area\": %.17g, \"rec_degenerate\": %d, \"gt_degenerate\": %d, "
                     "\"rec_skipped\": %d, \"gt_skipped\": %d, \"n\": %d, \"threshold\": %.9g",
@@ -25,6 +28,10 @@ int main(int argc, char** argv)
             for (int k = 0; k < 16; ++k) std::printf("%s%.17g", k ? ", " : "", m.transform[k]);
             std::printf("]");
         }
+        if (has_surface)
+            std::printf(", \"surface\": %s, \"precision_pct\": %.17g, \"recall_pct\": %.17g, \"fscore_pct\": %.17g, \"normal_accuracy\": %.17g, "
+                        "\"normal_completion\": %.17g, \"normal_consistency\": %.17g, \"normal_skipped\": %d", m.surface ? "true" : "false",
+                        m.precision_pct, m.recall_pct, m.fscore_pct, m.normal_accuracy, m.normal_completion, m.normal_consistency, m.normal_skipped);
         std::printf("}\n");
     } catch (const std::exception& e) {
         std::fprintf(stderr, "eval_recon_test: %s\n", e.what());

@@ -29,7 +29,7 @@ SYMBOLS = (
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
     "nsk_image_rays", "nsk_render_image", "nsk_image_metrics", "nsk_image_ssim",
-    "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats",
+    "nsk_mesh_sample", "nsk_cloud_nearest", "nsk_cloud_stats", "nsk_mesh_nearest", "nsk_normal_stats",
     "nsk_cloud_pair_sums", "nsk_rigid_from_sums", "nsk_cloud_icp", "nsk_cloud_transform",
     "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views", "nsk_depth_views_range",
     "nsk_points_seen", "nsk_mesh_select", "nsk_points_view_counts",
@@ -79,6 +79,12 @@ def lib():
         L.nsk_cloud_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_cloud_stats.restype = C.c_int
         L.nsk_cloud_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_double)]
+        L.nsk_mesh_nearest.restype = C.c_int
+        L.nsk_mesh_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_int)]
+        L.nsk_normal_stats.restype = C.c_int
+        L.nsk_normal_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         PD = C.POINTER(C.c_double)
         L.nsk_cloud_pair_sums.restype = C.c_int
         L.nsk_cloud_pair_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, PD, C.c_float, PD, C.c_void_p, C.c_void_p,
@@ -580,6 +586,40 @@ class Context:
         return dict(sum=float(h[0]), count=int(h[1]), below=int(h[2]), max=float(h[3]))
 
     @_ordered
+    def mesh_nearest(self, query, verts, tris, want_tri=False, want_point=False):
+        """nsk_mesh_nearest: the exact fp32 distance from every query point [nq, 3] to the mesh (verts [nv, 3] float32, tris [nt, 3] int32)
+        -> dist [nq] (with want_tri the triangle that holds the nearest point [nq] int32, with want_point that point [nq, 3]; a tuple in
+        that order when either is asked for).  The number of triangles left out is in self.last_skipped.  Synchronises."""
+        import torch
+        assert query.dtype == torch.float32 and verts.dtype == torch.float32 and tris.dtype == torch.int32
+        assert query.shape[-1] == 3 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        nq = int(query.shape[0])
+        dist = torch.empty((nq,), dtype=torch.float32, device=query.device)
+        tri = torch.empty((nq,), dtype=torch.int32, device=query.device) if want_tri else None
+        point = torch.empty((nq, 3), dtype=torch.float32, device=query.device) if want_point else None
+        sk = C.c_int(0)
+        nv = int(verts.shape[0])
+        _chk(lib().nsk_mesh_nearest(self.h, _ptr(query) if nq else None, nq, _ptr(verts) if nv else None, nv, _ptr(tris), int(tris.shape[0]),
+                                    _ptr(dist) if nq else None, _ptr(tri) if nq else None, _ptr(point) if nq else None, C.byref(sk)))
+        self.last_skipped = int(sk.value)
+        out = (dist,) + ((tri,) if want_tri else ()) + ((point,) if want_point else ())
+        return out if len(out) > 1 else dist
+
+    @_ordered
+    def normal_stats(self, va, ta, ia, vb, tb, ib):
+        """nsk_normal_stats: the agreement |n_A . n_B| / (|n_A| |n_B|) of the normals of triangle ia[i] of mesh A (va, ta) and triangle
+        ib[i] of mesh B (vb, tb), cuda tensors (float32 [nv, 3], int32 [nt, 3], int32 [n]) -> dict(sum, count, skipped).  Synchronises."""
+        import torch
+        assert va.dtype == torch.float32 and vb.dtype == torch.float32 and all(t.dtype == torch.int32 for t in (ta, ia, tb, ib))
+        n = int(ia.numel())
+        assert int(ib.numel()) == n
+        h = (C.c_double * 3)()
+        opt = lambda t: _ptr(t) if t.numel() else None
+        _chk(lib().nsk_normal_stats(self.h, n, opt(va), int(va.shape[0]), opt(ta), int(ta.shape[0]), opt(ia), opt(vb), int(vb.shape[0]),
+                                    opt(tb), int(tb.shape[0]), opt(ib), h))
+        return dict(sum=float(h[0]), count=int(h[1]), skipped=int(h[2]))
+
+    @_ordered
     def cloud_pair_sums(self, source, target, M=None, threshold=0.1, want_pairs=False):
         """nsk_cloud_pair_sums: the 17 pair sums (numpy float64) of source [ns, 3] under the 4x4 M (None: the identity) against target
         [nt, 3]; with want_pairs also the correspondences (dist [ns] float32, index [ns] int32) by source index.  The number of non-finite
@@ -642,15 +682,22 @@ class Context:
                                                         icp_iterations=info["iterations"])
 
     def recon_metrics(self, rec_verts, rec_tris, gt_verts, gt_tris, n=200000, threshold=0.05, seed=0, align=False, align_threshold=0.1,
-                      align_max_iter=30):
+                      align_max_iter=30, surface=False):
         """upstream's three 3D numbers of a reconstruction (rec) against a ground-truth mesh (gt), both as cuda tensors (what extract_mesh /
         filter_mesh return goes in directly): n samples of each surface (seed, seed + 1), nearest distances both ways, the means in cm and
         the share of gt samples with a rec sample closer than threshold in %.  Coordinates are taken to be metres.  With align the
         reconstruction's vertices are first registered to the ground truth's (align_mesh) and the transformed mesh is measured; the
-        result then also holds transform, icp_fitness, icp_rmse and icp_iterations."""
+        result then also holds transform, icp_fitness, icp_rmse and icp_iterations.
+        With surface the rec samples are measured against the gt MESH and the gt samples against the rec mesh (mesh_nearest), which takes
+        the sampling of the other surface out of every distance; rec_skipped / gt_skipped then count the triangles left out.  The
+        result also holds surface=True, precision_pct (rec samples with d < threshold), recall_pct (= completion_ratio_pct), fscore_pct
+        = 2 P R / (P + R) (0 when P + R is 0), normal_accuracy / normal_completion (the mean |cos| between each sample's own triangle
+        and the nearest triangle of the other mesh, in [0, 1]), their mean normal_consistency, and normal_skipped."""
         extra = {}
         if align:
             rec_verts, extra = self._aligned(rec_verts, gt_verts, align_threshold, align_max_iter)
+        if surface:
+            return self._recon_metrics_surface(rec_verts, rec_tris, gt_verts, gt_tris, n, threshold, seed, extra)
         rec = self.sample_mesh(rec_verts, rec_tris, n, seed)
         rec_area, rec_deg = self.last_area, self.last_degenerate
         gt = self.sample_mesh(gt_verts, gt_tris, n, seed + 1)
@@ -666,6 +713,34 @@ class Context:
                     accuracy_max_cm=100.0 * acc["max"], completion_max_cm=100.0 * comp["max"],
                     rec_area=rec_area, gt_area=gt_area, rec_degenerate=rec_deg, gt_degenerate=gt_deg,
                     rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold), **extra)
+
+    def _recon_metrics_surface(self, rec_verts, rec_tris, gt_verts, gt_tris, n, threshold, seed, extra):
+        rec, rec_own = self.sample_mesh(rec_verts, rec_tris, n, seed, want_tri=True)
+        rec_area, rec_deg = self.last_area, self.last_degenerate
+        gt, gt_own = self.sample_mesh(gt_verts, gt_tris, n, seed + 1, want_tri=True)
+        gt_area, gt_deg = self.last_area, self.last_degenerate
+        d, hit = self.mesh_nearest(rec, gt_verts, gt_tris, want_tri=True)
+        gt_skipped = self.last_skipped
+        acc = self.cloud_stats(d, threshold)
+        n_acc = self.normal_stats(rec_verts, rec_tris, rec_own, gt_verts, gt_tris, hit)
+        d, hit = self.mesh_nearest(gt, rec_verts, rec_tris, want_tri=True)
+        rec_skipped = self.last_skipped
+        comp = self.cloud_stats(d, threshold)
+        n_comp = self.normal_stats(gt_verts, gt_tris, gt_own, rec_verts, rec_tris, hit)
+        nan = float("nan")
+        prec = 100.0 * acc["below"] / acc["count"] if acc["count"] else nan
+        rcl = 100.0 * comp["below"] / comp["count"] if comp["count"] else nan
+        na = n_acc["sum"] / n_acc["count"] if n_acc["count"] else nan
+        nc = n_comp["sum"] / n_comp["count"] if n_comp["count"] else nan
+        return dict(accuracy_cm=100.0 * acc["sum"] / acc["count"] if acc["count"] else nan,
+                    completion_cm=100.0 * comp["sum"] / comp["count"] if comp["count"] else nan,
+                    completion_ratio_pct=rcl,
+                    accuracy_max_cm=100.0 * acc["max"], completion_max_cm=100.0 * comp["max"],
+                    rec_area=rec_area, gt_area=gt_area, rec_degenerate=rec_deg, gt_degenerate=gt_deg,
+                    rec_skipped=rec_skipped, gt_skipped=gt_skipped, n=int(n), threshold=float(threshold), surface=True,
+                    precision_pct=prec, recall_pct=rcl, fscore_pct=2.0 * prec * rcl / (prec + rcl) if prec + rcl > 0 else (0.0 if prec + rcl == 0 else nan),
+                    normal_accuracy=na, normal_completion=nc, normal_consistency=0.5 * (na + nc),
+                    normal_skipped=n_acc["skipped"] + n_comp["skipped"], **extra)
 
     @_ordered
     def mesh_depth(self, verts, tris, w2c, H, W, fx, fy, cx, cy, want_skipped=False):
