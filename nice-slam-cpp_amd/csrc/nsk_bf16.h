@@ -319,14 +319,14 @@ __device__ __forceinline__ void decode_fwd_occ_body(const DecArgs& Am, const Dec
 
 // roles: [0, wg_end[0]) the merged occupancy role on (a[0] = middle, a[1] = fine); [wg_end[0], wg_end[1]) the colour decoder on a[2] (MA.n == 2) or nothing
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_decode_fwd_multi_occ(MultiArgs MA)
+NSK_SINGLE_ISSUE __global__ __launch_bounds__(64 * NW) void k_decode_fwd_multi_occ(MultiArgs MA)
 {
     if ((int)blockIdx.x < MA.wg_end[0]) decode_fwd_occ_body<NW>(MA.a[0], MA.a[1], blockIdx.x, MA.wg_end[0]);
     else decode_fwd_bf16_body<3, NW, 2>(MA.a[2], (int)blockIdx.x - MA.wg_end[0], MA.wg_end[1] - MA.wg_end[0]);
 }
 
 template <int NW, int NP = 3>
-__global__ __launch_bounds__(64 * NW) void k_decode_fwd_multi_bf16(MultiArgs MA)
+NSK_SINGLE_ISSUE __global__ __launch_bounds__(64 * NW) void k_decode_fwd_multi_bf16(MultiArgs MA)
 {
     int r = 0;
     while (r < MA.n - 1 && (int)blockIdx.x >= MA.wg_end[r]) ++r;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nsk_layout.h"
+#include "nsk_issue.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 

@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(512) void k_decode_bwd_multi(MultiArgs MA)
 // The mapping launch (no ray gradients) whose skipping frozen roles claim the tail of their tiles from a cursor (decode_bwd_body: Dealing; D.r[r]: the
 // cursor of role r, or none).  A kernel of its own, so that the launches that deal statically are k_decode_bwd_multi<false> as it always was and carry
 // none of the claiming code: in their loop it cost K3 5 us, K2 and the K4 shard 1 us.
-__global__ __launch_bounds__(512) void k_decode_bwd_multi_deal(MultiArgs MA, DealRoles D)
+NSK_SINGLE_ISSUE __global__ __launch_bounds__(512) void k_decode_bwd_multi_deal(MultiArgs MA, DealRoles D)
 {
     if (MA.sum_n > 0 && blockIdx.x == gridDim.x - 1) { block_sum(MA.sum_src, MA.sum_n, MA.sum_dst); return; }
     if ((int)blockIdx.x >= MA.wg_end[MA.n - 1]) { sort_scan_body<2>(MA.scan, (int)blockIdx.x - MA.wg_end[MA.n - 1]); return; }

@@ -26,13 +26,32 @@ TEXT = re.compile(r"^\s*\.(text\b|section\s+\.text)")
 INSTR = re.compile(r"^\s+[a-z][a-z0-9_]*(\s|$)")
 
 
+def functions(path):
+    """[(name, raw lines)] in file order: a function's lines run from its "-- Begin function" marker to the next marker or the file's tail"""
+    out, name, lines = [], None, []
+    with open(path) as f:
+        for ln in f:
+            m = BEGIN.search(ln)
+            if m or TAIL.match(ln):
+                if name is not None:
+                    out.append((name, lines))
+                name, lines = (m.group(1) if m else None), []
+            if name is not None:
+                lines.append(ln)
+    if name is not None:
+        out.append((name, lines))
+    return out
+
+
+def body(lines):
+    """the lines in front of the function's end label: its instructions, without the descriptor and the resource summary"""
+    return lines[: next((i for i, ln in enumerate(lines) if ".Lfunc_end" in ln and ln.rstrip().endswith(":")), len(lines))]
+
+
 def split(path):
     """{name: (is_kernel, instruction count, normalised text)} in file order"""
-    funcs, name, lines = {}, None, []
-
-    def close():
-        if name is None:
-            return
+    funcs = {}
+    for name, lines in functions(path):
         table = {}
 
         def renumber(m):
@@ -43,18 +62,7 @@ def split(path):
         while lines and TEXT.match(lines[-1]):          # the section switch in front of the NEXT function's marker
             lines.pop()
         text = [".text" if TEXT.match(ln) else " ".join(LOCAL.sub(renumber, ln).replace(name, "<self>").split()) for ln in lines if "__hip_cuid_" not in ln]
-        body = lines[: next((i for i, ln in enumerate(lines) if ".Lfunc_end" in ln and ln.rstrip().endswith(":")), len(lines))]
-        funcs[name] = (any(".amdhsa_kernel" in ln for ln in lines), sum(1 for ln in body if INSTR.match(ln)), "\n".join(text))
-
-    with open(path) as f:
-        for ln in f:
-            m = BEGIN.search(ln)
-            if m or TAIL.match(ln):
-                close()
-                name, lines = (m.group(1) if m else None), []
-            if name is not None:
-                lines.append(ln)
-    close()
+        funcs[name] = (any(".amdhsa_kernel" in ln for ln in lines), sum(1 for ln in body(lines) if INSTR.match(ln)), "\n".join(text))
     return funcs
 
 
