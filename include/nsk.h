@@ -834,6 +834,54 @@ int nsk_tsdf_integrate(nsk_ctx* ctx, const float h_origin[3], const float h_step
 int nsk_tsdf_volume(nsk_ctx* ctx, long long n, const float* d_tsdf, const float* d_weight, float min_weight, float* d_volume,
                     uint8_t* d_valid, long long* n_valid);
 
+/* ---- vertex normals of an indexed mesh; vertex colours from short rays along them (upstream's meshing.color_mesh_extraction_method
+ * render_ray_along_normal: mesh.compute_vertex_normals(), then a ray of 0.1 m per vertex through render_batch_ray, stage color) ------ */
+/* nsk_mesh_vertex_normals: the area-weighted unit normal of every vertex of a mesh (d_vertices [n_vertices][3] float32, d_triangles
+ * [n_triangles][3] int32) into d_normals [n_vertices][3].  With the winding of nsk_mesh_extract the normals point to free space.  Every
+ * operation below is an fp32 operation of its own (no FMA contraction).
+ *   Triangle normal.  e0 = b - a, e1 = c - a, n_t = e0 x e1 with each component fl(fl(xy) - fl(zw)): the plane candidate's normal of
+ *     nsk_mesh_nearest.  It is not normalised, so the sum below weighs a triangle by its area, as upstream's does.
+ *   Which triangles take part.  A triangle is left out and counted in h_info[0] when an index is outside [0, n_vertices) or n_t has a
+ *     component that is not finite.  A triangle that names a vertex twice takes part; its n_t is exactly zero.
+ *   Sum.  For vertex v, acc starts at +0 and receives n_t once for every (triangle, corner) that names v, in ascending triangle index,
+ *     then ascending corner: acc = fl(acc + n_t) per component.  The order is part of the contract, because an fp32 sum depends on it.
+ *   Normalise.  nn = (x x + y y) + z z of acc;  L = the correctly rounded square root of nn;  n = acc / L per component.
+ *   Vertices without a normal.  When nn is not finite or not > 0 the vertex receives (+0, +0, +0) and is counted in h_info[1]: an isolated
+ *     vertex, a vertex all of whose triangles have no area, a sum that cancels, overflows or underflows.
+ *   h_info (4 ints on the host, or NULL): [0] triangles left out;  [1] vertices without a normal;  [2] the largest number of namings of one
+ *     vertex by triangles that take part;  [3] 0.
+ * n_triangles = 0 is valid (every normal is zero); n_vertices = 0 is valid (every triangle is left out).  At most 2^30 corners
+ * (3 n_triangles) and (2^31 - 1) / 3 vertices.  How: face normals are formed once and the vertices' namings counted; the counts are
+ * scanned by the multi-launch scan of nsk_mesh_extract; every corner is placed into its vertex's segment of one list through an integer
+ * cursor; every segment is sorted by corner number (up to 32 corners by the vertex's own thread, longer ones by a workgroup each); one
+ * thread per vertex then sums over its segment in that order.  No floating-point atomic: two runs, and a run in a fresh process, give the
+ * same bytes.  Device memory, owned by the context and reused: 24 B per triangle (face normals, the corner list) and 4 B per vertex (+ the
+ * scan's upper levels); an allocation that fails names its byte count and leaves the context usable.  Reading h_info is the call's only
+ * synchronisation: without it the call is asynchronous on the context's stream.  Not while a graph is being captured. */
+int nsk_mesh_vertex_normals(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles,
+                            float* d_normals, int h_info[4]);
+/* nsk_normal_rays: for each of n vertices the ray that looks at the surface from `length` out along the normal (d_rays_o [n][3],
+ * d_rays_d [n][3], d_gt_depth [n], d_has_ray [n] bytes or NULL).  `length` must be finite and > 0.
+ *   A vertex whose normal is not zero, with every component of vertex and normal finite:  o = fl(v + fl(length n)) per component,  d = -n,
+ *     gt_depth = length,  has_ray = 1.
+ *   Every other vertex:  o = v (its bits),  d = (0, 0, -1),  gt_depth = length,  has_ray = 0: a ray that renders, whose result is not used.
+ * n = 0 is valid.  Asynchronous on the context's stream. */
+int nsk_normal_rays(nsk_ctx* ctx, int n, const float* d_vertices, const float* d_normals, float length, float* d_rays_o, float* d_rays_d,
+                    float* d_gt_depth, uint8_t* d_has_ray);
+/* nsk_mesh_vertex_colors: the colour of every vertex into d_rgb [n_vertices][3], not clamped.
+ *   With d_normals: a vertex with has_ray (nsk_normal_rays with `length`) receives, bit for bit, the rgb that nsk_render_forward gives its
+ *     ray at stage NSK_COLOR with d_gt_depth = length and gt_depth_max = length, under the context's current render options (so every
+ *     ray carries n_samples + n_surface samples, the surface samples around `length`, i.e. around the vertex).  gt_depth_max is given
+ *     and not taken from the batch, so neither the chunking nor the rays of the other vertices change a byte.  Every other vertex
+ *     receives channels 0..2 of nsk_eval_points at stage NSK_COLOR at the vertex itself, and *h_fallback (or NULL) counts them.
+ *   With d_normals NULL every vertex takes the point query (*h_fallback = n_vertices): upstream's direct_point_query.
+ * The vertices are walked in chunks of chunk_rays rays (0: 25 600, the default of nsk_render_image; at most (2^26 - 1) / samples per ray),
+ * point queries in chunks of as many samples; the chunk size changes no byte.  `length` must be finite and > 0 (it is not read without
+ * normals, and still checked).  n_vertices = 0 is valid.  Reading h_fallback is the call's only synchronisation.  Not while a graph is
+ * being captured. */
+int nsk_mesh_vertex_colors(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const float* d_normals, float length, int chunk_rays,
+                           float* d_rgb, int* h_fallback);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

@@ -899,6 +899,15 @@ struct nsk_ctx {
         Buf<unsigned> view_counts;                           // [V]
         Buf<unsigned> scan;                                  // vertex flags' scan | triangle flags' scan | the skipped count
     } cull;
+    // vertex normals and colours along them (nsk_normals.h): scratch that grows to the largest call and stays
+    struct Normals {
+        Buf<float> fn;                                       // [triangles][3] face normals, NaN = the triangle is left out
+        Buf<unsigned> off;                                   // [vertices + 1 + scan levels] namings -> first slot -> slot behind the last
+        Buf<unsigned> list;                                  // [corners] corner numbers 3 t + k, by vertex, ascending inside a vertex
+        Buf<unsigned> longq;                                 // vertices named by more than VN_SHORT corners
+        Buf<unsigned> counters;                              // [0] triangles left out, [1] vertices without a normal, [2] most namings, [3] the queue's length
+        Buf<float> raw; Buf<uint8_t> has;                    // nsk_mesh_vertex_colors: [chunk][4] point colours, [chunk] ray flags
+    } normals;
     // the optional count of an entry point (count_begin / count_end): nsk_lattice_seen, nsk_points_seen, nsk_tsdf_integrate, nsk_tsdf_volume
     Buf<unsigned long long> count;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
@@ -3905,6 +3914,9 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
 
 // ---- depth frames fused into a TSDF on a lattice (kernels and entry points: nsk_tsdf.h) -------------------------------------------------
 #include "nsk_tsdf.h"
+
+// ---- vertex normals, rays along them, the colours they composite (kernels and entry points: nsk_normals.h) ---------------------------------
+#include "nsk_normals.h"
 
 extern "C" int nsk_inside_filter(nsk_ctx* c, int N, const float* ro, const float* rd, const float* gt, uint8_t* keep)
 {

@@ -7,9 +7,13 @@
 //   meshing.level_set (0)      the occupancy level of the surface (inside = occupancy above it);
 //   meshing.remove_small_geometry_threshold (0.2), meshing.get_largest_components (false)   get_clean_mesh only: components of the mesh
 //                              with less surface than the threshold (m^2) are dropped, or all but the largest;
+//   meshing.color_mesh_extraction_method (direct_point_query)   how a vertex gets its colour: direct_point_query decodes the colour at the
+//                              vertex; render_ray_along_normal renders the colour stage along a ray of color_ray_length (0.1 m, upstream's
+//                              constant) that looks at the vertex from free space along its normal (nsk_mesh_vertex_normals,
+//                              nsk_mesh_vertex_colors), and decodes at the vertex where it has no normal.  Any other value throws;
 // and leaves clean_mesh_bound_scale (upstream's convex hull of a TSDF fusion: get_clean_mesh culls per node with the union of the
-// keyframes' depth-truncated frusta instead; the fusion itself is here, get_fused_mesh / get_rendered_mesh, its convex hull is not),
-// mesh_coarse_level and the render_ray_query colouring to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
+// keyframes' depth-truncated frusta instead; the fusion itself is here, get_fused_mesh / get_rendered_mesh, its convex hull is not) and
+// mesh_coarse_level to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
 // bound's own faces therefore show up as a shell around the scene, with padding 0 the outermost nodes (which lie ON the open bound) do.
 #pragma once
 #include <cstdint>
@@ -75,7 +79,9 @@ class Mesher {
   public:
     Mesher(YAML::Node ns_config, torch::Tensor bound_3x2 = torch::Tensor(), float padding = 0.f);
     void set_bound(torch::Tensor bound_3x2);
-    // nsk_eval_lattice (fine) -> nsk_mesh_extract -> (color) nsk_eval_points (color) on the device vertex buffer, rgb clamped to [0, 1] -> PLY.
+    // nsk_eval_lattice (fine) -> nsk_mesh_extract -> (color) nsk_mesh_vertex_colors on the device vertex buffer by color_method, rgb clamped to
+    // [0, 1] -> PLY.  get_mesh, get_clean_mesh, get_fused_mesh and get_rendered_mesh all write the context's mesh the same way: color_method,
+    // color_ray_length and write_normals hold for each of them, and the normals are those of the mesh that is written (after the filter).
     // valid: optional uint8 / bool [resolution^3] (z, y, x order), 0 = cells touching the node are skipped; the lattice is then evaluated at
     // the set nodes only (nsk_eval_lattice_masked, fill 100), which leaves the mesh unchanged.
     void get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, bool color = true,
@@ -105,6 +111,12 @@ class Mesher {
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
     static void write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int n_vertices, const int32_t* triangles, int n_triangles);
     static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& triangles);
+    // the same with vertex normals (or nullptr: the file of the function above, byte for byte): float x y z, float nx ny nz, (rgb given) uchar
+    // red green blue, in this order; and its reader (normals / rgb come back empty when the file has none)
+    static void write_ply(const std::string& path, const float* xyz, const float* normals, const uint8_t* rgb, int n_vertices, const int32_t* triangles,
+                          int n_triangles);
+    static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<float>& normals, std::vector<uint8_t>& rgb,
+                         std::vector<int32_t>& triangles);
     // Any PLY mesh, read by its header: format ascii or binary_little_endian; the vertex element's x, y, z found by name among scalar
     // properties of any type, number and order and converted to float; the face element's first list property with any count and index
     // type, polygons of more than three corners fan-triangulated (0, k, k + 1), faces of fewer than three dropped; every other element and
@@ -164,6 +176,11 @@ class Mesher {
     torch::Tensor bound;
     float remove_small_geometry_threshold;
     bool get_largest_components;
+    std::string color_method;           // meshing.color_mesh_extraction_method: "direct_point_query" or "render_ray_along_normal"
+    float color_ray_length = 0.1f;      // render_ray_along_normal: the ray starts this far (m) out along the normal (upstream's constant)
+    bool write_normals = false;         // the PLY carries nx ny nz (nsk_mesh_vertex_normals on the mesh that is written)
+    int last_color_fallback = 0;        // vertices coloured by the point query (all of them with direct_point_query)
+    int last_normals_zero = 0;          // vertices without a normal (0 when no normals were computed)
     float seen_trunc = 0.5f;    // a node counts as seen up to this far (m) behind the measured depth: the margin inside which the Mapper's own
                                 // frustum selection lets voxels train (nsk_frustum_mask)
     int seen_edge = 0;          // pixels ignored along the image border

@@ -23,6 +23,9 @@ Mesher::Mesher(YAML::Node ns, torch::Tensor bound_3x2, float padding_) : padding
     level_set = ns["meshing"]["level_set"].IsDefined() ? ns["meshing"]["level_set"].as<float>() : 0.f;
     remove_small_geometry_threshold = ns["meshing"]["remove_small_geometry_threshold"].IsDefined() ? ns["meshing"]["remove_small_geometry_threshold"].as<float>() : 0.2f;
     get_largest_components = ns["meshing"]["get_largest_components"].IsDefined() ? ns["meshing"]["get_largest_components"].as<bool>() : false;
+    color_method = ns["meshing"]["color_mesh_extraction_method"].IsDefined() ? ns["meshing"]["color_mesh_extraction_method"].as<std::string>() : "direct_point_query";
+    if (color_method != "direct_point_query" && color_method != "render_ray_along_normal")
+        throw std::runtime_error("Mesher: meshing.color_mesh_extraction_method must be direct_point_query or render_ray_along_normal, not " + color_method);
     if (resolution < 2) throw std::runtime_error("Mesher: meshing.resolution must be at least 2");
     if (!(padding >= 0.f)) throw std::runtime_error("Mesher: padding must be >= 0");
     bound = bound_3x2.defined() ? bound_3x2.detach().to(torch::kCPU, torch::kFloat32).contiguous().clone()
@@ -41,34 +44,47 @@ struct DevMem {
 };
 }  // namespace
 
-// the context's mesh (nv vertices, nt triangles) -> host, the colour query on the device vertex buffer, the PLY
-static void write_context_mesh(const std::string& path, bool color, int nv, int nt)
+// the context's mesh (nv vertices, nt triangles) -> host; asked for, the normals and the colours from the device buffers; the PLY
+static void write_context_mesh(Mesher& M, const std::string& path, bool color, int nv, int nt)
 {
+    if (M.color_method != "direct_point_query" && M.color_method != "render_ray_along_normal")
+        throw std::runtime_error("Mesher: color_method must be direct_point_query or render_ray_along_normal, not " + M.color_method);
+    const bool along = color && M.color_method == "render_ray_along_normal", want_normals = M.write_normals || along;
     std::vector<float> xyz((size_t)nv * 3);
     std::vector<int32_t> tris((size_t)nt * 3);
     check(nsk_mesh_download(ctx(), xyz.data(), tris.data()));
     std::vector<uint8_t> rgb;
-    if (color && nv > 0) {
+    std::vector<float> normals;
+    M.last_color_fallback = M.last_normals_zero = 0;
+    if ((color || want_normals) && nv > 0) {
         float* d_verts = nullptr; int32_t* d_tris = nullptr;
         check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
-        DevMem raw((size_t)nv * 4 * sizeof(float));
-        const int chunk = (1 << 26) - 1;
-        for (long long v0 = 0; v0 < nv; v0 += chunk) {
-            const int m = (int)std::min<long long>(chunk, nv - v0);
-            check(nsk_eval_points(ctx(), NSK_COLOR, m, d_verts + 3 * v0, (float*)raw.p + 4 * v0));
-        }
-        check(nsk_sync(ctx()));
-        std::vector<float> h((size_t)nv * 4);
-        if (hipMemcpy(h.data(), raw.p, h.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
-        rgb.resize((size_t)nv * 3);
-        for (size_t v = 0; v < (size_t)nv; ++v)
-            for (int k = 0; k < 3; ++k) {
-                float x = h[4 * v + k];
-                x = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;                       // clamp to [0, 1]; NaN -> 0
-                rgb[3 * v + k] = (uint8_t)std::lround(x * 255.f);
+        const size_t vb = (size_t)nv * 3 * sizeof(float);
+        DevMem dn(want_normals ? vb : 0), raw(color ? vb : 0);
+        if (want_normals) {
+            int info[4];
+            check(nsk_mesh_vertex_normals(ctx(), d_verts, nv, d_tris, nt, (float*)dn.p, info));
+            M.last_normals_zero = info[1];
+            if (M.write_normals) {
+                normals.resize((size_t)nv * 3);
+                if (hipMemcpy(normals.data(), dn.p, vb, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
             }
+        }
+        if (color) {
+            check(nsk_mesh_vertex_colors(ctx(), d_verts, nv, along ? (const float*)dn.p : nullptr, M.color_ray_length, 0, (float*)raw.p, &M.last_color_fallback));
+            std::vector<float> h((size_t)nv * 3);
+            if (hipMemcpy(h.data(), raw.p, vb, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+            rgb.resize((size_t)nv * 3);
+            for (size_t k = 0; k < h.size(); ++k) {
+                float x = h[k];
+                x = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;                       // clamp to [0, 1]; NaN -> 0
+                rgb[k] = (uint8_t)std::lround(x * 255.f);
+            }
+        }
     }
-    Mesher::write_ply(path, xyz.data(), color ? rgb.data() : nullptr, nv, tris.data(), nt);
+    static const float none[3] = {0.f, 0.f, 0.f};           // (an empty mesh still declares its normals)
+    if (M.write_normals) Mesher::write_ply(path, xyz.data(), nv > 0 ? normals.data() : none, color ? rgb.data() : nullptr, nv, tris.data(), nt);
+    else Mesher::write_ply(path, xyz.data(), color ? rgb.data() : nullptr, nv, tris.data(), nt);
 }
 
 void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, bool color, torch::Tensor valid)
@@ -98,7 +114,7 @@ void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::st
     else check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
     int nv = 0, nt = 0;
     check(nsk_mesh_extract(ctx(), (const float*)vol.p, dvalid ? (const uint8_t*)dvalid->p : nullptr, n, n, n, origin, step, level_set, &nv, &nt));
-    write_context_mesh(path, color, nv, nt);
+    write_context_mesh(*this, path, color, nv, nt);
     last_vertices = nv; last_triangles = nt; last_evaluated = n_eval;
 }
 
@@ -146,7 +162,7 @@ void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<s
     int nv = 0, nt = 0, nc = 0, nk = 0;
     check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)seen.p, n, n, n, origin, step, level_set, &nv, &nt));
     check(nsk_mesh_filter(ctx(), remove_small_geometry_threshold, get_largest_components ? 1 : 0, &nv, &nt, &nc, &nk));
-    write_context_mesh(path, color, nv, nt);
+    write_context_mesh(*this, path, color, nv, nt);
     last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen; last_evaluated = n_eval;
 }
 
@@ -221,7 +237,7 @@ void Mesher::get_fused_mesh(const std::string& path, const std::vector<torch::Te
     }
     int nv = 0, nt = 0;
     F.mesh(*this, min_weight, nv, nt);
-    write_context_mesh(path, false, nv, nt);
+    write_context_mesh(*this, path, false, nv, nt);
 }
 
 void Mesher::get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
@@ -257,25 +273,32 @@ void Mesher::get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dic
     }
     int nv = 0, nt = 0;
     F.mesh(*this, min_weight, nv, nt);
-    write_context_mesh(path, color, nv, nt);
+    write_context_mesh(*this, path, color, nv, nt);
 }
 
 void Mesher::write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int nv, const int32_t* tris, int nt)
+{
+    write_ply(path, xyz, nullptr, rgb, nv, tris, nt);
+}
+
+void Mesher::write_ply(const std::string& path, const float* xyz, const float* normals, const uint8_t* rgb, int nv, const int32_t* tris, int nt)
 {
     std::ofstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("Mesher: cannot write " + path);
     std::ostringstream h;
     h << "ply\nformat binary_little_endian 1.0\ncomment nice-slam-cpp_amd Mesher\nelement vertex " << nv
       << "\nproperty float x\nproperty float y\nproperty float z\n";
+    if (normals) h << "property float nx\nproperty float ny\nproperty float nz\n";
     if (rgb) h << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
     h << "element face " << nt << "\nproperty list uchar int vertex_indices\nend_header\n";
     const std::string hs = h.str();
     f.write(hs.data(), (std::streamsize)hs.size());
-    const size_t vrec = 12 + (rgb ? 3 : 0);
+    const size_t noff = 12, coff = noff + (normals ? 12 : 0), vrec = coff + (rgb ? 3 : 0);
     std::vector<char> buf((size_t)nv * vrec);
     for (size_t v = 0; v < (size_t)nv; ++v) {
         std::memcpy(&buf[v * vrec], xyz + 3 * v, 12);
-        if (rgb) std::memcpy(&buf[v * vrec + 12], rgb + 3 * v, 3);
+        if (normals) std::memcpy(&buf[v * vrec + noff], normals + 3 * v, 12);
+        if (rgb) std::memcpy(&buf[v * vrec + coff], rgb + 3 * v, 3);
     }
     f.write(buf.data(), (std::streamsize)buf.size());
     buf.resize((size_t)nt * 13);
@@ -287,13 +310,15 @@ void Mesher::write_ply(const std::string& path, const float* xyz, const uint8_t*
     if (!f) throw std::runtime_error("Mesher: write to " + path + " failed");
 }
 
-void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& tris)
+// the files write_ply writes: x y z, then nx ny nz and red green blue when `with_normals` / 3 further properties say so
+static void read_own_ply(const std::string& path, bool with_normals, std::vector<float>& xyz, std::vector<float>* normals, std::vector<uint8_t>& rgb,
+                         std::vector<int32_t>& tris)
 {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("Mesher: cannot open " + path);
     std::string line, element;
     long long nv = -1, nt = -1;
-    int vprops = 0;
+    std::vector<std::string> vprops;
     bool binary = false;
     while (std::getline(f, line)) {
         if (line == "end_header") break;
@@ -301,17 +326,28 @@ void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vec
         std::string w; ls >> w;
         if (w == "format") { std::string fmt; ls >> fmt; binary = fmt == "binary_little_endian"; }
         else if (w == "element") { ls >> element; if (element == "vertex") ls >> nv; else if (element == "face") ls >> nt; }
-        else if (w == "property" && element == "vertex") ++vprops;
+        else if (w == "property" && element == "vertex") { std::string t, name; ls >> t >> name; vprops.push_back(t + " " + name); }
     }
-    if (!binary || nv < 0 || nt < 0 || (vprops != 3 && vprops != 6)) throw std::runtime_error("Mesher: " + path + " is not a PLY this reader knows");
-    const bool color = vprops == 6;
-    const size_t vrec = 12 + (color ? 3 : 0);
+    const std::vector<std::string> P = {"float x", "float y", "float z"}, N = {"float nx", "float ny", "float nz"},
+                                   C = {"uchar red", "uchar green", "uchar blue"};
+    auto at = [&](size_t k, const std::vector<std::string>& want) {
+        return vprops.size() >= k + 3 && std::equal(want.begin(), want.end(), vprops.begin() + (std::ptrdiff_t)k);
+    };
+    bool known = binary && nv >= 0 && nt >= 0 && (with_normals ? at(0, P) : vprops.size() >= 3);
+    const bool has_n = with_normals && at(3, N);
+    const size_t coff = 12 + (has_n ? 12 : 0), nprop = 3 + (has_n ? 3 : 0);
+    const bool color = with_normals ? at(nprop, C) : vprops.size() == 6;
+    known = known && vprops.size() == nprop + (color ? 3 : 0);
+    if (!known) throw std::runtime_error("Mesher: " + path + " is not a PLY this reader knows");
+    const size_t vrec = coff + (color ? 3 : 0);
     std::vector<char> buf((size_t)nv * vrec);
     f.read(buf.data(), (std::streamsize)buf.size());
     xyz.resize((size_t)nv * 3); rgb.resize(color ? (size_t)nv * 3 : 0); tris.resize((size_t)nt * 3);
+    if (normals) normals->resize(has_n ? (size_t)nv * 3 : 0);
     for (size_t v = 0; v < (size_t)nv; ++v) {
         std::memcpy(&xyz[3 * v], &buf[v * vrec], 12);
-        if (color) std::memcpy(&rgb[3 * v], &buf[v * vrec + 12], 3);
+        if (has_n) std::memcpy(&(*normals)[3 * v], &buf[v * vrec + 12], 12);
+        if (color) std::memcpy(&rgb[3 * v], &buf[v * vrec + coff], 3);
     }
     buf.resize((size_t)nt * 13);
     f.read(buf.data(), (std::streamsize)buf.size());
@@ -320,6 +356,16 @@ void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vec
         if (buf[t * 13] != 3) throw std::runtime_error("Mesher: " + path + " has a face that is not a triangle");
         std::memcpy(&tris[3 * t], &buf[t * 13 + 1], 12);
     }
+}
+
+void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& tris)
+{
+    read_own_ply(path, false, xyz, nullptr, rgb, tris);
+}
+
+void Mesher::read_ply(const std::string& path, std::vector<float>& xyz, std::vector<float>& normals, std::vector<uint8_t>& rgb, std::vector<int32_t>& tris)
+{
+    read_own_ply(path, true, xyz, &normals, rgb, tris);
 }
 
 // ---- any PLY mesh ------------------------------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ SYMBOLS = (
     "nsk_mesh_depth", "nsk_depth_pair_stats", "nsk_depth_views", "nsk_depth_views_range",
     "nsk_points_seen", "nsk_mesh_select", "nsk_points_view_counts",
     "nsk_tsdf_integrate", "nsk_tsdf_volume",
+    "nsk_mesh_vertex_normals", "nsk_normal_rays", "nsk_mesh_vertex_colors",
 )
 
 
@@ -119,6 +120,12 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
         L.nsk_tsdf_volume.restype = C.c_int
         L.nsk_tsdf_volume.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.nsk_mesh_vertex_normals.restype = C.c_int
+        L.nsk_mesh_vertex_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        L.nsk_normal_rays.restype = C.c_int
+        L.nsk_normal_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nsk_mesh_vertex_colors.restype = C.c_int
+        L.nsk_mesh_vertex_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_image_ssim.restype = C.c_int
         L.nsk_image_ssim.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_int, PD, C.c_void_p, PD, PD]
@@ -604,6 +611,50 @@ class Context:
         self.last_skipped = int(sk.value)
         out = (dist,) + ((tri,) if want_tri else ()) + ((point,) if want_point else ())
         return out if len(out) > 1 else dist
+
+    @_ordered
+    def mesh_vertex_normals(self, verts, tris, want_info=False):
+        """nsk_mesh_vertex_normals: the area-weighted unit normals [nv, 3] float32 of a mesh (verts [nv, 3] float32, tris [nt, 3] int32, cuda
+        tensors); a vertex without a normal gets zeros.  With want_info also dict(left_out, zero, max_valence), which synchronises."""
+        import torch
+        assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        nv, nt = int(verts.shape[0]), int(tris.shape[0])
+        normals = torch.empty((nv, 3), dtype=torch.float32, device=verts.device)
+        info = (C.c_int * 4)()
+        _chk(lib().nsk_mesh_vertex_normals(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, _ptr(normals) if nv else None,
+                                           info if want_info else None))
+        if want_info:
+            return normals, dict(left_out=int(info[0]), zero=int(info[1]), max_valence=int(info[2]))
+        return normals
+
+    @_ordered
+    def normal_rays(self, verts, normals, length=0.1):
+        """nsk_normal_rays: the rays that look at the vertices from `length` out along their normals -> (rays_o [n, 3], rays_d [n, 3],
+        gt_depth [n], has_ray [n] uint8); a vertex without a normal, or with a non-finite component, gets a ray whose result is not used"""
+        import torch
+        assert verts.dtype == torch.float32 and normals.dtype == torch.float32 and verts.shape[-1] == 3 and normals.shape == verts.shape
+        n = int(verts.shape[0])
+        dev = verts.device
+        ro = torch.empty((n, 3), dtype=torch.float32, device=dev); rd = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        gd = torch.empty((n,), dtype=torch.float32, device=dev); has = torch.empty((n,), dtype=torch.uint8, device=dev)
+        opt = lambda t: _ptr(t) if n else None
+        _chk(lib().nsk_normal_rays(self.h, n, opt(verts), opt(normals), C.c_float(length), opt(ro), opt(rd), opt(gd), opt(has)))
+        return ro, rd, gd, has
+
+    @_ordered
+    def mesh_vertex_colors(self, verts, normals=None, length=0.1, chunk_rays=None, want_fallback=False):
+        """nsk_mesh_vertex_colors: the colours [nv, 3] float32 (not clamped) of the vertices: with normals the colour stage rendered along
+        the ray of normal_rays(verts, normals, length), the point query where a vertex has no ray; without normals the point query
+        everywhere.  chunk_rays None: the library's default.  With want_fallback also the number of point queries, which synchronises."""
+        import torch
+        assert verts.dtype == torch.float32 and verts.shape[-1] == 3
+        assert normals is None or (normals.dtype == torch.float32 and normals.shape == verts.shape)
+        nv = int(verts.shape[0])
+        rgb = torch.empty((nv, 3), dtype=torch.float32, device=verts.device)
+        fb = C.c_int(0)
+        _chk(lib().nsk_mesh_vertex_colors(self.h, _ptr(verts) if nv else None, nv, _ptr(normals) if (normals is not None and nv) else None,
+                                          C.c_float(length), int(chunk_rays or 0), _ptr(rgb) if nv else None, C.byref(fb) if want_fallback else None))
+        return (rgb, int(fb.value)) if want_fallback else rgb
 
     @_ordered
     def normal_stats(self, va, ta, ia, vb, tb, ib):
