@@ -882,6 +882,58 @@ int nsk_normal_rays(nsk_ctx* ctx, int n, const float* d_vertices, const float* d
 int nsk_mesh_vertex_colors(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const float* d_normals, float length, int chunk_rays,
                            float* d_rgb, int* h_fallback);
 
+/* ---- raw frames prepared on the device (upstream NICE-SLAM's dataset layer, src/utils/datasets.py __getitem__: cv2.undistort, cv2.resize
+ * to the depth size, F.interpolate to cam.crop_size, cam.crop_edge cut off, the intrinsics moved along) --------------------------------- */
+#define NSK_FRAME_U8 0      /* colour [n][H][W][3] bytes */
+#define NSK_FRAME_U16 1     /* depth [n][H][W] 16-bit */
+#define NSK_FRAME_F32 2     /* either, float32 */
+typedef struct nsk_frame_opts {
+    float fx, fy, cx, cy;            /* for the depth size Hd x Wd (the cam block's meaning) */
+    int n_dist;                      /* 0 (no undistortion), 4, 5 or 8 coefficients */
+    float dist[8];                   /* OpenCV's order k1 k2 p1 p2 [k3 [k4 k5 k6]]; those beyond n_dist are not read (they are zeros in the rule) */
+    int crop_H, crop_W;              /* cam.crop_size; both 0 = off */
+    int crop_edge;                   /* cam.crop_edge */
+    float png_depth_scale, scale;    /* depth = (float(v) / png_depth_scale) * scale */
+    int swap_rb;                     /* exchange channels 0 and 2 of the colour output */
+} nsk_frame_opts;
+/* The rule.  Every operation is an fp32 operation of its own (no FMA contraction), every stage's result a rounded fp32 value; a stage that
+ * is off is skipped, not run with neutral parameters.  tests/frame_checks.py restates it one numpy operation per operation.
+ *   S0 conversion.  uint8 colour: float(v) / 255.0f, a correctly rounded division; float32 colour passes.  Depth, both types:
+ *     (float(v) / png_depth_scale) * scale.
+ *   S1 undistort (colour only; on when n_dist > 0; needs Hc == Hd and Wc == Wd).  OpenCV's undistort with newCameraMatrix = K.  For the
+ *     destination pixel (u, v):  x = (u - cx) / fx,  y = (v - cy) / fy,  xx = x x, yy = y y, xy = x y, r2 = xx + yy, r4 = r2 r2, r6 = r4 r2,
+ *     rad = (((1 + k1 r2) + k2 r4) + k3 r6) / (((1 + k4 r2) + k5 r4) + k6 r6),
+ *     xd = (x rad + (2 p1) xy) + p2 (r2 + 2 xx),   yd = (y rad + p1 (r2 + 2 yy)) + (2 p2) xy,   us = fx xd + cx,   vs = fy yd + cy.
+ *     Taps at i0 = floor(us), i0 + 1 (likewise j0 from vs) with l1 = us - float(i0), l0 = 1 - l1; a tap outside the image has the value 0
+ *     (OpenCV's constant border); when !(us > -1 && us < Wc && vs > -1 && vs < Hc) the pixel is 0, which also catches NaN.  Zero
+ *     coefficients with n_dist > 0 still run the arithmetic.
+ *   S2 colour to the depth size (on when the sizes differ): cv2.resize INTER_LINEAR = F.interpolate(bilinear, align_corners=False).  Per
+ *     axis  s = float(in) / float(out),  r = max((float(o) + 0.5f) s - 0.5f, 0),  i0 = min(int(r), in - 1),  i1 = min(i0 + 1, in - 1),
+ *     l1 = r - float(i0),  l0 = 1 - l1.
+ *   S3 crop_size (on when crop_H, crop_W > 0).  Colour: F.interpolate(bilinear, align_corners=True): s = float(in - 1) / float(out - 1)
+ *     (0 when out == 1), r = float(o) s, taps as in S2.  Depth: F.interpolate(nearest): src = min(int(floorf(float(o) (float(in) /
+ *     float(out)))), in - 1); depth is never interpolated.
+ *   Every bilinear value:  top = lx0 v00 + lx1 v01,  bot = lx0 v10 + lx1 v11,  out = ly0 top + ly1 bot, each product and sum rounded.
+ *   S4 crop_edge: e pixels off every side.
+ *   Intrinsics (fp32, on the host): with crop_size sx = float(crop_W) / float(Wd), sy = float(crop_H) / float(Hd), fx *= sx, cx *= sx,
+ *     fy *= sy, cy *= sy; with crop_edge cx -= e, cy -= e.
+ * nsk_frame_plan: validates the options for a colour size Hc x Wc and a depth size Hd x Wd and returns the output size and the intrinsics
+ * [fx fy cx cy].  It takes no context and works without a GPU.  Errors (< 0, nsk_last_error names the option): a size < 1; n_dist not 0,
+ * 4, 5 or 8; crop_edge < 0; exactly one of crop_H, crop_W positive, or one negative; undistortion with Hc != Hd or Wc != Wd; 2 crop_edge
+ * >= a side of the image it is cut from. */
+int nsk_frame_plan(const nsk_frame_opts* opts, int Hc, int Wc, int Hd, int Wd, int* H_out, int* W_out, float intr_out[4]);
+/* nsk_frame_prepare: n raw frames (d_color_raw [n][Hc][Wc][3] of color_type NSK_FRAME_U8 / _F32, d_depth_raw [n][Hd][Wd] of depth_type
+ * NSK_FRAME_U16 / _F32) -> d_color_out [n][H'][W'][3] and d_depth_out [n][H'][W'] float32, the layouts nsk_prepare_rays,
+ * nsk_tsdf_integrate and nsk_points_seen take.  Either pair (raw and out) may be NULL to prepare only the other; the sizes of the absent
+ * image still decide the stages.  One launch; a thread per output pixel evaluates the stages that are on by recursion over taps (at most
+ * 16 raw taps per channel), so no intermediate image exists and the bytes are the rule's.
+ * *h_n_border (or NULL): the number of output colour pixels, over all frames, that read at least one S1 tap outside the image through
+ * whatever stages follow (a tap of weight 0 counts, a pixel S1 sets to 0 counts); 0 without S1 or without colour.  Reading it is the
+ * call's only synchronisation.  n = 0 is valid.  Errors: those of nsk_frame_plan; a type the image does not have; n < 0, n > 65535 or
+ * n H' W' >= 2^31; they leave the outputs untouched.  Not while a graph is being captured. */
+int nsk_frame_prepare(nsk_ctx* ctx, const nsk_frame_opts* opts, int n, const void* d_color_raw, int color_type, int Hc, int Wc,
+                      const void* d_depth_raw, int depth_type, int Hd, int Wd, float* d_color_out, float* d_depth_out, int* h_n_border);
+
 /* ---- introspection for benchmarks ------------------------------------------------------------------------ */
 /* algorithmic bytes / flops of the last render or step call (SURVEY.md section 8d accounting) */
 int nsk_last_call_stats(nsk_ctx* ctx, double* alg_bytes, double* alg_flops, int* samples);

@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#define NSK_VERSION 100
+#define NSK_VERSION 101
 
 static thread_local std::string g_err;
 static int fail(const char* fmt, ...)
@@ -3917,6 +3917,9 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
 
 // ---- vertex normals, rays along them, the colours they composite (kernels and entry points: nsk_normals.h) ---------------------------------
 #include "nsk_normals.h"
+
+// ---- raw frames prepared on the device: undistort, resize, crop (kernel and entry points: nsk_frame.h) -----------------------------------
+#include "nsk_frame.h"
 
 extern "C" int nsk_inside_filter(nsk_ctx* c, int N, const float* ro, const float* rd, const float* gt, uint8_t* keep)
 {

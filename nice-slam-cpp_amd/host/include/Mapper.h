@@ -32,6 +32,8 @@ class Mapper {
     // not in the reference
     void set_frustum_mask(const std::string& grid_key, torch::Tensor mask_zyx);     // bool/uint8 [Z,Y,X]; undefined tensor = all
     void set_bound(torch::Tensor bound_3x2);
+    // the camera of the frames run() will be given, instead of the cam block's (frames prepared by nskh::FramePrep: its H, W, fx, fy, cx, cy)
+    void set_camera(int H_, int W_, float fx_, float fy_, float cx_, float cy_) { H = H_; W = W_; fx = fx_; fy = fy_; cx = cx_; cy = cy_; }
     void seed(uint64_t s) { rng_seed = s; draw_calls = 0; }
     // N > 1 (BASELINE configs[3], [4]): every rank draws the window's whole batch (the pixel draw is a counter hash of the seed: identical on
     // every rank, one small launch), renders the contiguous shard [lo, hi) of it with the batch's max(gt_depth) taken over the whole batch

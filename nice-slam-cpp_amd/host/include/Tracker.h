@@ -26,6 +26,8 @@ class Tracker {
     double last_run_us = 0.0;                      // wall time of the last run()'s iteration loop, stream-synchronised
     void seed(uint64_t s) { rng_seed = s; }
     void set_bound(torch::Tensor bound_3x2);
+    // the camera of the frames run() will be given, instead of the cam block's (frames prepared by nskh::FramePrep: its H, W, fx, fy, cx, cy)
+    void set_camera(int H_, int W_, float fx_, float fy_, float cx_, float cy_) { H = H_; W = W_; fx = fx_; fy = fy_; cx = cx_; cy = cy_; }
 
   private:
     int H, W;

@@ -33,6 +33,7 @@ class SequenceReader {
     Kind kind;
     std::string input_folder;
     cv::Mat depth, rgb;
+    cv::Mat raw_rgb, raw_depth;          // the same frame as the files hold it: CV_8UC3 (B,G,R) and CV_16UC1, what nskh::FramePrep::prepare takes
     Eigen::Matrix4f c2w;                 // pose of the frame getNext() loaded
 
     int width, height;

@@ -1,6 +1,7 @@
 // Minimal stand-in for the subset of yaml-cpp the reference's drivers use (YAML::LoadFile, Node::operator[],
 // Node::as<T>, IsDefined): yaml-cpp is not installed in this image.  Parses the
-// indentation-based maps of config/nice_slam.yaml and config/cofusion.yaml (scalars, nested maps, comments).
+// indentation-based maps of config/nice_slam.yaml and config/cofusion.yaml (scalars, nested maps, comments) and one-line flow sequences
+// of scalars (`crop_size: [384, 512]`, upstream NICE-SLAM's cam blocks): IsSequence, size, operator[](int).
 // If the real yaml-cpp is available, drop this directory from the include path -- the host classes only use
 // the calls listed above.
 #pragma once
@@ -19,6 +20,13 @@ class Node {
     Node() : d_(std::make_shared<Data>()) {}
     bool IsDefined() const { return d_->defined; }
     bool IsMap() const { return !d_->kids.empty(); }
+    bool IsSequence() const { return d_->is_seq; }
+    size_t size() const { return d_->is_seq ? d_->seq.size() : d_->kids.size(); }
+    Node operator[](int i) const
+    {
+        if (!d_->is_seq || i < 0 || (size_t)i >= d_->seq.size()) return Node::undefined(std::to_string(i));
+        return d_->seq[(size_t)i];
+    }
     Node operator[](const std::string& key) const
     {
         auto it = d_->kids.find(key);
@@ -33,9 +41,27 @@ class Node {
     // builder access (used by the parser and by tests that assemble configs in memory)
     Node& set(const std::string& key, const Node& n) { d_->kids[key] = n; d_->defined = true; return *this; }
     static Node scalar(const std::string& v) { Node n; n.d_->defined = true; n.d_->scalar = v; return n; }
+    // `[a, b, ...]` -> a sequence of scalars (quotes around an element are dropped; `[]` is the empty sequence)
+    static Node flow_sequence(const std::string& text)
+    {
+        Node n; n.d_->defined = true; n.d_->is_seq = true; n.d_->scalar = text;
+        const std::string body = text.substr(1, text.size() - 2);
+        size_t a = 0;
+        while (a <= body.size()) {
+            size_t b = body.find(',', a);
+            if (b == std::string::npos) b = body.size();
+            std::string e = body.substr(a, b - a);
+            const size_t e0 = e.find_first_not_of(" \t"), e1 = e.find_last_not_of(" \t");
+            e = e0 == std::string::npos ? "" : e.substr(e0, e1 - e0 + 1);
+            if (e.size() >= 2 && ((e.front() == '\'' && e.back() == '\'') || (e.front() == '"' && e.back() == '"'))) e = e.substr(1, e.size() - 2);
+            if (!e.empty()) n.d_->seq.push_back(Node::scalar(e));
+            a = b + 1;
+        }
+        return n;
+    }
 
   private:
-    struct Data { bool defined = false; std::string scalar; std::map<std::string, Node> kids; };
+    struct Data { bool defined = false, is_seq = false; std::string scalar; std::map<std::string, Node> kids; std::vector<Node> seq; };
     std::shared_ptr<Data> d_;
     static Node undefined(const std::string& key) { Node n; n.d_->scalar = key; return n; }
     template <typename T> static T convert(const std::string& s);
@@ -80,6 +106,8 @@ inline Node Load(std::istream& in)
             Node child;
             stack.back().node.set(key, child);
             stack.push_back({indent, child});
+        } else if (val.size() >= 2 && val.front() == '[' && val.back() == ']') {
+            stack.back().node.set(key, Node::flow_sequence(val));
         } else {
             stack.back().node.set(key, Node::scalar(val));
         }

@@ -1064,3 +1064,60 @@ void Mapper::run(NICE& decoders, c10::Dict<std::string, torch::Tensor>& c, std::
     }
     first_frame = false;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// nskh::FramePrep (FramePrep.h): raw frames prepared on the device through nsk_frame_prepare
+// ---------------------------------------------------------------------------------------------------------
+#include "FramePrep.h"
+
+struct nskh::FramePrep::Dev {                                   // one frame at a time; the buffers grow to the largest frame and stay
+    DevArr<uint8_t> rgb;
+    DevArr<uint16_t> depth;
+    DevArr<float> color_out, depth_out;
+};
+
+nskh::FramePrep::FramePrep(const YAML::Node& cam) : dev(std::make_shared<Dev>())
+{
+    std::memset(&opts, 0, sizeof(opts));
+    Hd = cam["H"].as<int>(); Wd = cam["W"].as<int>();
+    opts.fx = cam["fx"].as<float>(); opts.fy = cam["fy"].as<float>(); opts.cx = cam["cx"].as<float>(); opts.cy = cam["cy"].as<float>();
+    if (cam["crop_edge"].IsDefined()) opts.crop_edge = cam["crop_edge"].as<int>();
+    if (cam["crop_size"].IsDefined()) {
+        TORCH_CHECK(cam["crop_size"].IsSequence() && cam["crop_size"].size() == 2, "cam.crop_size must be [H, W]");
+        opts.crop_H = cam["crop_size"][0].as<int>(); opts.crop_W = cam["crop_size"][1].as<int>();
+    }
+    if (cam["distortion"].IsDefined()) {
+        const YAML::Node d = cam["distortion"];
+        TORCH_CHECK(d.IsSequence() && d.size() <= 8, "cam.distortion must be a list of 4, 5 or 8 coefficients");
+        opts.n_dist = (int)d.size();                            // (a count nsk_frame_plan does not know is refused there, by name)
+        for (int i = 0; i < opts.n_dist; ++i) opts.dist[i] = d[i].as<float>();
+    }
+    has_png_depth_scale = cam["png_depth_scale"].IsDefined();
+    opts.png_depth_scale = has_png_depth_scale ? cam["png_depth_scale"].as<float>() : 1.f;
+    opts.scale = cam["scale"].IsDefined() ? cam["scale"].as<float>() : 1.f;
+    float intr[4];
+    check(nsk_frame_plan(&opts, Hd, Wd, Hd, Wd, &H, &W, intr));
+    fx = intr[0]; fy = intr[1]; cx = intr[2]; cy = intr[3];
+}
+
+std::pair<torch::Tensor, torch::Tensor> nskh::FramePrep::prepare(const cv::Mat& raw_rgb, const cv::Mat& raw_depth)
+{
+    TORCH_CHECK(!raw_rgb.empty() && raw_rgb.type() == CV_8UC3, "FramePrep::prepare: raw_rgb must be CV_8UC3");
+    TORCH_CHECK(!raw_depth.empty() && raw_depth.type() == CV_16UC1, "FramePrep::prepare: raw_depth must be CV_16UC1");
+    float intr[4];
+    check(nsk_frame_plan(&opts, raw_rgb.rows, raw_rgb.cols, raw_depth.rows, raw_depth.cols, &H, &W, intr));
+    fx = intr[0]; fy = intr[1]; cx = intr[2]; cy = intr[3];
+    DevArr<uint8_t>& d_rgb = dev->rgb;
+    DevArr<uint16_t>& d_depth = dev->depth;
+    DevArr<float>& d_color_out = dev->color_out; DevArr<float>& d_depth_out = dev->depth_out;
+    const size_t n_out = (size_t)H * W;
+    d_color_out.ensure(3 * n_out); d_depth_out.ensure(n_out);
+    d_rgb.upload(raw_rgb.ptr<uint8_t>(), raw_rgb.total() * 3);
+    d_depth.upload(raw_depth.ptr<uint16_t>(), raw_depth.total());
+    check(nsk_frame_prepare(ctx(), &opts, 1, d_rgb.p, NSK_FRAME_U8, raw_rgb.rows, raw_rgb.cols, d_depth.p, NSK_FRAME_U16, raw_depth.rows, raw_depth.cols,
+                            d_color_out.p, d_depth_out.p, &last_border));
+    torch::Tensor color = torch::empty({H, W, 3}, torch::kFloat32), depth = torch::empty({H, W}, torch::kFloat32);
+    d_color_out.download(color.data_ptr<float>(), 3 * n_out);
+    d_depth_out.download(depth.data_ptr<float>(), n_out);
+    return {color, depth};
+}

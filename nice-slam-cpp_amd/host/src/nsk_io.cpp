@@ -462,6 +462,7 @@ void SequenceReader::getNext()
     }
     cv::Mat d16 = cv::imread(depth_files[fptr], cv::IMREAD_UNCHANGED);
     if (d16.empty() || d16.channels() != 1) throw std::runtime_error("SequenceReader: cannot read " + depth_files[fptr] + " as a one-channel depth image");
+    raw_rgb = rgb.clone(); raw_depth = d16;
     rgb.convertTo(rgb, CV_32FC3, 1.0 / 255.0);
     d16.convertTo(depth, CV_32FC1, 1.0 / png_depth_scale);
     width = depth.cols; height = depth.rows;

@@ -2,6 +2,9 @@
 // sequence) through the C++ classes with the reference's surface and a SequenceReader; src/main.cpp wires up the Tracker only.
 //   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE]
 // --mesh FILE: after the last frame the scene mesh (Mesher, meshing.resolution / meshing.level_set of nice_slam.yaml) goes to FILE as a PLY.
+// When the cam block of <cofusion.yaml> has a crop_size, a distortion or a crop_edge > 0 (upstream NICE-SLAM's TUM and ScanNet blocks), every
+// frame goes through nskh::FramePrep (undistort, resize, crop on the device from the reader's raw bytes) and the Tracker and the Mapper get
+// its camera; without them the loop is what it was, byte for byte.  A block without png_depth_scale takes the reader's.
 // <sequence dir>/bound.txt holds the scene bound (6 numbers: x0 x1 y0 y1 z0 z1; the reference hard-codes its own).  Writes est_poses.npy,
 // gt_poses.npy [F,4,4], track_loss.npy [F] (last iteration's loss; 0 for frame 0), map_loss.npy [mapped frames].
 // On a node (BASELINE configs[4], one process per GPU): NSK_RANK / NSK_WORLD / NSK_DEVICE (= local rank) / NSK_RCCL_ID_FILE (a path every rank
@@ -16,6 +19,7 @@
 
 #include <sstream>
 
+#include "FramePrep.h"
 #include "Mapper.h"
 #include "Mesher.h"
 #include "Tracker.h"
@@ -72,6 +76,14 @@ int main(int argc, char** argv)
         Mapper mapper(ns, cf, false);
         tracker.set_bound(bound); mapper.set_bound(bound);
         tracker.seed(100); mapper.seed(200);
+        nskh::FramePrep prep(cf["cam"]);
+        const bool prepared = prep.active();
+        if (prepared) {
+            if (!prep.has_png_depth_scale) prep.opts.png_depth_scale = reader.png_depth_scale;
+            tracker.set_camera(prep.H, prep.W, prep.fx, prep.fy, prep.cx, prep.cy);
+            mapper.set_camera(prep.H, prep.W, prep.fx, prep.fy, prep.cx, prep.cy);
+            std::printf("frames are prepared on the device: %d x %d, fx %.3f fy %.3f cx %.3f cy %.3f\n", prep.H, prep.W, prep.fx, prep.fy, prep.cx, prep.cy);
+        }
         nskh::Dist dist;
         if (const char* w = std::getenv("NSK_WORLD")) {
             dist.world = std::atoi(w);
@@ -90,8 +102,14 @@ int main(int argc, char** argv)
         std::vector<float> tl, ml;
         for (int i = 0; i < F && reader.hasMore(); ++i) {
             reader.getNext();
-            torch::Tensor depth_t = torch::from_blob(reader.depth.data, {reader.depth.rows, reader.depth.cols}, torch::kFloat32).clone();
-            torch::Tensor color_t = torch::from_blob(reader.rgb.data, {reader.rgb.rows, reader.rgb.cols, 3}, torch::kFloat32).clone();
+            torch::Tensor depth_t, color_t;
+            if (prepared) {
+                std::tie(color_t, depth_t) = prep.prepare(reader.raw_rgb, reader.raw_depth);
+                if (i == 0 && prep.last_border > 0) std::printf("frame 0: %d colour pixels read outside the distorted image (crop_edge %d)\n", prep.last_border, prep.opts.crop_edge);
+            } else {
+                depth_t = torch::from_blob(reader.depth.data, {reader.depth.rows, reader.depth.cols}, torch::kFloat32).clone();
+                color_t = torch::from_blob(reader.rgb.data, {reader.rgb.rows, reader.rgb.cols, 3}, torch::kFloat32).clone();
+            }
             torch::Tensor gt = torch::zeros({4, 4});
             for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) gt[r][q] = reader.c2w(r, q);
             gts[i] = gt;

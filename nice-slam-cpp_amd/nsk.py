@@ -35,7 +35,31 @@ SYMBOLS = (
     "nsk_points_seen", "nsk_mesh_select", "nsk_points_view_counts",
     "nsk_tsdf_integrate", "nsk_tsdf_volume",
     "nsk_mesh_vertex_normals", "nsk_normal_rays", "nsk_mesh_vertex_colors",
+    "nsk_frame_plan", "nsk_frame_prepare",
 )
+
+FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
+
+
+class FrameOpts(C.Structure):
+    """nsk_frame_opts of include/nsk.h"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("n_dist", C.c_int), ("dist", C.c_float * 8),
+                ("crop_H", C.c_int), ("crop_W", C.c_int), ("crop_edge", C.c_int), ("png_depth_scale", C.c_float), ("scale", C.c_float),
+                ("swap_rb", C.c_int)]
+
+
+def frame_opts(intr, distortion=None, crop_size=None, crop_edge=0, png_depth_scale=1.0, scale=1.0, swap_rb=False):
+    """the options of frame_plan / Context.prepare_frames as an nsk_frame_opts; intr = (fx, fy, cx, cy) for the depth size"""
+    o = FrameOpts()
+    o.fx, o.fy, o.cx, o.cy = (float(v) for v in intr)
+    dist = [] if distortion is None else [float(v) for v in distortion]
+    o.n_dist = len(dist)
+    for i, v in enumerate(dist[:8]):
+        o.dist[i] = v
+    o.crop_H, o.crop_W = (0, 0) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    o.crop_edge = int(crop_edge)
+    o.png_depth_scale, o.scale, o.swap_rb = float(png_depth_scale), float(scale), int(bool(swap_rb))
+    return o
 
 
 SSIM_TILE = (8, 32)          # windows per workgroup of nsk_image_ssim's tile kernel, rows x columns (csrc/nsk_ssim.h: SSIM_TILE_H, SSIM_TILE_W)
@@ -120,6 +144,11 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
         L.nsk_tsdf_volume.restype = C.c_int
         L.nsk_tsdf_volume.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.nsk_frame_plan.restype = C.c_int
+        L.nsk_frame_plan.argtypes = [C.POINTER(FrameOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.nsk_frame_prepare.restype = C.c_int
+        L.nsk_frame_prepare.argtypes = [C.c_void_p, C.POINTER(FrameOpts), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_mesh_vertex_normals.restype = C.c_int
         L.nsk_mesh_vertex_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.nsk_normal_rays.restype = C.c_int
@@ -153,6 +182,16 @@ def mesh_table(case):
     if n < 0:
         raise NskError(lib().nsk_last_error().decode())
     return [(int(buf[3 * t]), int(buf[3 * t + 1]), int(buf[3 * t + 2])) for t in range(n)]
+
+
+def frame_plan(color_size, depth_size, intr, distortion=None, crop_size=None, crop_edge=0, png_depth_scale=1.0, scale=1.0, swap_rb=False):
+    """nsk_frame_plan: what Context.prepare_frames will give for raw colour images of color_size (H, W) and depth images of depth_size,
+    intr = (fx, fy, cx, cy) for the depth size -> (H', W', intr_out [4] float32); an invalid option set raises NskError; needs no GPU"""
+    import numpy as np
+    o = frame_opts(intr, distortion, crop_size, crop_edge, png_depth_scale, scale, swap_rb)
+    H, W, out = C.c_int(0), C.c_int(0), (C.c_float * 4)()
+    _chk(lib().nsk_frame_plan(C.byref(o), int(color_size[0]), int(color_size[1]), int(depth_size[0]), int(depth_size[1]), C.byref(H), C.byref(W), out))
+    return int(H.value), int(W.value), np.array(list(out), np.float32)
 
 
 def depth_views_from_box(box, n_views, seed=0, shrink=0.7):
@@ -655,6 +694,37 @@ class Context:
         _chk(lib().nsk_mesh_vertex_colors(self.h, _ptr(verts) if nv else None, nv, _ptr(normals) if (normals is not None and nv) else None,
                                           C.c_float(length), int(chunk_rays or 0), _ptr(rgb) if nv else None, C.byref(fb) if want_fallback else None))
         return (rgb, int(fb.value)) if want_fallback else rgb
+
+    @_ordered
+    def prepare_frames(self, color, depth, intr, distortion=None, crop_size=None, crop_edge=0, png_depth_scale=1.0, scale=1.0, swap_rb=False,
+                       depth_size=None):
+        """nsk_frame_prepare: raw frames made ready on the device.  color [n, Hc, Wc, 3] uint8 or float32, depth [n, Hd, Wd] uint16 (or
+        int16 holding the same bits) or float32, cuda tensors; either may be None (depth_size then names the absent depth image's size,
+        default: the colour's).  intr = (fx, fy, cx, cy) for the depth size; distortion: 4, 5 or 8 coefficients in OpenCV's order.
+        -> (color [n, H', W', 3] float32 or None, depth [n, H', W'] float32 or None, intr_out [4] float32 numpy, n_border).
+        Synchronises when it undistorts (the border count)."""
+        import torch
+        assert color is not None or depth is not None
+        ref = color if color is not None else depth
+        n = int(ref.shape[0])
+        if color is not None:
+            assert color.dim() == 4 and color.shape[-1] == 3 and color.dtype in (torch.uint8, torch.float32), "color: [n, H, W, 3] uint8 / float32"
+        if depth is not None:
+            assert depth.dim() == 3 and int(depth.shape[0]) == n and depth.dtype in (torch.uint16, torch.int16, torch.float32), "depth: [n, H, W] uint16 / float32"
+            Hd, Wd = int(depth.shape[1]), int(depth.shape[2])
+        else:
+            Hd, Wd = (int(depth_size[0]), int(depth_size[1])) if depth_size is not None else (int(color.shape[1]), int(color.shape[2]))
+        Hc, Wc = (int(color.shape[1]), int(color.shape[2])) if color is not None else (Hd, Wd)
+        o = frame_opts(intr, distortion, crop_size, crop_edge, png_depth_scale, scale, swap_rb)
+        H, W, intr_out = frame_plan((Hc, Wc), (Hd, Wd), intr, distortion, crop_size, crop_edge, png_depth_scale, scale, swap_rb)
+        c_out = torch.empty((n, H, W, 3), dtype=torch.float32, device=ref.device) if color is not None else None
+        d_out = torch.empty((n, H, W), dtype=torch.float32, device=ref.device) if depth is not None else None
+        nb = C.c_int(0)
+        ct = FRAME_U8 if color is not None and color.dtype == torch.uint8 else FRAME_F32
+        dt = FRAME_F32 if depth is not None and depth.dtype == torch.float32 else FRAME_U16
+        _chk(lib().nsk_frame_prepare(self.h, C.byref(o), n, _ptr(color) if n else None, ct, Hc, Wc, _ptr(depth) if n else None, dt, Hd, Wd,
+                                     _ptr(c_out) if n else None, _ptr(d_out) if n else None, C.byref(nb)))
+        return c_out, d_out, intr_out, int(nb.value)
 
     @_ordered
     def normal_stats(self, va, ta, ia, vb, tb, ib):
