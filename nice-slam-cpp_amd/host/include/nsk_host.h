@@ -36,13 +36,4 @@ struct Dist {
 // ncclGetUniqueId on rank 0, its 128 bytes through a file every rank can read, ncclCommInitRank on the current device (librccl is dlopen'ed)
 void* rccl_comm_from_file(int rank, int world, const std::string& id_file);
 
-// small device-buffer helper: float data of a (CPU or CUDA) tensor made available at a device pointer
-struct DevBuf {
-    float* p = nullptr; size_t n = 0;
-    ~DevBuf();
-    void ensure(size_t count);
-    void upload(const torch::Tensor& t);        // any float tensor -> contiguous fp32 on the device
-    torch::Tensor download(at::IntArrayRef shape) const;   // -> CPU tensor
-};
-
 }  // namespace nskh

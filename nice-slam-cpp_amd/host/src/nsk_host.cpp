@@ -2,8 +2,6 @@
 // helpers) marshalling into the C-ABI of include/nsk.h.  libtorch is used as a host-side tensor container and for
 // host-side bookkeeping (pixel sampling, the 7-parameter pose optimiser); no libtorch GPU compute op is called.
 // Each function cites the reference code whose behaviour it reproduces (intended semantics).
-#include <hip/hip_runtime_api.h>
-
 #include <dlfcn.h>
 
 #include <chrono>
@@ -15,7 +13,7 @@
 
 #include "Mapper.h"
 #include "Tracker.h"
-#include "nsk_host.h"
+#include "nsk_devarr.h"
 #include "torchlib/utils.h"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -119,27 +117,17 @@ void* rccl_comm_from_file(int rank, int world, const std::string& id_file)
     return comm;
 }
 
-DevBuf::~DevBuf() { if (p) hipFree(p); }
-void DevBuf::ensure(size_t count)
-{
-    if (count <= n) return;
-    if (p) hipFree(p);
-    if (hipMalloc((void**)&p, count * sizeof(float)) != hipSuccess) throw std::runtime_error("hipMalloc failed");
-    n = count;
-}
-void DevBuf::upload(const torch::Tensor& t)
+DevArr<float> to_device(const torch::Tensor& t)
 {
     torch::Tensor h = t.detach().to(torch::kCPU, torch::kFloat32).contiguous();
-    ensure((size_t)h.numel());
-    if (hipMemcpy(p, h.data_ptr<float>(), h.numel() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        throw std::runtime_error("hipMemcpy H2D failed");
+    DevArr<float> d;
+    d.upload(h.data_ptr<float>(), (size_t)h.numel());
+    return d;
 }
-torch::Tensor DevBuf::download(at::IntArrayRef shape) const
+torch::Tensor to_host(const DevArr<float>& d, at::IntArrayRef shape)
 {
     torch::Tensor h = torch::empty(shape, torch::kFloat32);
-    check(nsk_sync(ctx()));
-    if (hipMemcpy(h.data_ptr<float>(), p, h.numel() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        throw std::runtime_error("hipMemcpy D2H failed");
+    d.download(h.data_ptr<float>(), (size_t)h.numel());
     return h;
 }
 
@@ -183,7 +171,9 @@ static void set_bound_ctx(const torch::Tensor& b)
 
 using nskh::check;
 using nskh::ctx;
-using nskh::DevBuf;
+using nskh::DevArr;
+using nskh::to_device;
+using nskh::to_host;
 
 // ---------------------------------------------------------------------------------------------------------
 // models
@@ -288,10 +278,9 @@ static torch::Tensor decoder_alone(int which, torch::Tensor p, std::map<std::str
     TORCH_CHECK(which == NSK_COARSE || which == NSK_MIDDLE, "stand-alone forward is defined for the coarse and middle decoders "
                 "(fine and color are only meaningful inside a stage: NICE::forward)");
     torch::Tensor pts = p.reshape({-1, 3});
-    DevBuf dp, dr;
-    dp.upload(pts); dr.ensure((size_t)pts.size(0) * 4);
-    check(nsk_eval_points(ctx(), which, (int)pts.size(0), dp.p, dr.p));
-    return dr.download({pts.size(0), 4}).index({Slice(), 3});
+    DevArr<float> dp = to_device(pts), dr((size_t)pts.size(0) * 4);
+    check(nsk_eval_points(ctx(), which, (int)pts.size(0), dp.p(), dr.p()));
+    return to_host(dr, {pts.size(0), 4}).index({Slice(), 3});
 }
 torch::Tensor MLP::forward(torch::Tensor p, std::map<std::string, torch::Tensor> c_grid)
 {
@@ -349,10 +338,9 @@ torch::Tensor NICE::forward(torch::Tensor p, c10::Dict<std::string, torch::Tenso
     nskh::sync_grids(c_grid);
     sync_to_device();
     torch::Tensor pts = p.reshape({-1, 3});
-    DevBuf dp, dr;
-    dp.upload(pts); dr.ensure((size_t)pts.size(0) * 4);
-    check(nsk_eval_points(ctx(), nskh::stage_id(stage), (int)pts.size(0), dp.p, dr.p));
-    return dr.download({pts.size(0), 4}).to(p.device());
+    DevArr<float> dp = to_device(pts), dr((size_t)pts.size(0) * 4);
+    check(nsk_eval_points(ctx(), nskh::stage_id(stage), (int)pts.size(0), dp.p(), dr.p()));
+    return to_host(dr, {pts.size(0), 4}).to(p.device());
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -392,14 +380,13 @@ void Renderer::render_batch_ray(c10::Dict<std::string, torch::Tensor> c, NICE de
     const int N = (int)rays_o.size(0);
     const bool has_gt = gt_depth.defined();
     const int S = N_samples + (has_gt ? N_surface : 0);                                       // D8: N_surface is not mutated
-    DevBuf ro, rd, gd, o_rgb, o_d, o_v, o_w;
-    ro.upload(rays_o.reshape({-1, 3})); rd.upload(rays_d.reshape({-1, 3}));
-    if (has_gt) gd.upload(gt_depth.reshape({-1}));
-    o_rgb.ensure((size_t)N * 3); o_d.ensure(N); o_v.ensure(N); o_w.ensure((size_t)N * S);
-    check(nsk_render_forward(ctx(), nskh::stage_id(stage), N, ro.p, rd.p, has_gt ? gd.p : nullptr, -1.f, o_rgb.p, o_d.p, o_v.p, o_w.p));
+    DevArr<float> ro = to_device(rays_o.reshape({-1, 3})), rd = to_device(rays_d.reshape({-1, 3})), gd;
+    if (has_gt) gd = to_device(gt_depth.reshape({-1}));
+    DevArr<float> o_rgb((size_t)N * 3), o_d((size_t)N), o_v((size_t)N), o_w((size_t)N * S);
+    check(nsk_render_forward(ctx(), nskh::stage_id(stage), N, ro.p(), rd.p(), has_gt ? gd.p() : nullptr, -1.f, o_rgb.p(), o_d.p(), o_v.p(), o_w.p()));
     auto dev = rays_o.device();
-    rgb_map = o_rgb.download({N, 3}).to(dev); depth_map = o_d.download({N}).to(dev);
-    depth_var = o_v.download({N}).to(dev); weights = o_w.download({N, S}).to(dev);
+    rgb_map = to_host(o_rgb, {N, 3}).to(dev); depth_map = to_host(o_d, {N}).to(dev);
+    depth_var = to_host(o_v, {N}).to(dev); weights = to_host(o_w, {N, S}).to(dev);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> Renderer::render_img(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor c2w,
@@ -412,25 +399,23 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> Renderer::render_img(c10
     TORCH_CHECK(c2w.dim() == 2 && c2w.size(0) >= 3 && c2w.size(1) == 4, "c2w must be [3,4] or [4,4]");
     const bool has_gt = gt_depth.defined();
     if (has_gt) TORCH_CHECK(gt_depth.numel() == (int64_t)H * W, "gt_depth must be [H,W]");
-    DevBuf pose, gd, o_rgb, o_d, o_v;
-    pose.upload(c2w.detach().to(torch::kCPU, torch::kFloat32).index({Slice(None, 3), Slice(None, 4)}).reshape({12}));
-    if (has_gt) gd.upload(gt_depth.reshape({-1}));
+    DevArr<float> pose = to_device(c2w.detach().to(torch::kCPU, torch::kFloat32).index({Slice(None, 3), Slice(None, 4)}).reshape({12})), gd;
+    if (has_gt) gd = to_device(gt_depth.reshape({-1}));
     const size_t n = (size_t)H * W;
-    o_rgb.ensure(n * 3); o_d.ensure(n); o_v.ensure(n);
-    check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, pose.p, 0, 0, has_gt ? gd.p : nullptr, -1.f,
-                           ray_batch_size, o_rgb.p, o_d.p, o_v.p));
+    DevArr<float> o_rgb(n * 3), o_d(n), o_v(n);
+    check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, pose.p(), 0, 0, has_gt ? gd.p() : nullptr, -1.f,
+                           ray_batch_size, o_rgb.p(), o_d.p(), o_v.p()));
     auto dev = c2w.device();
-    return std::make_tuple(o_d.download({H, W}).to(dev), o_v.download({H, W}).to(dev), o_rgb.download({H, W, 3}).to(dev));
+    return std::make_tuple(to_host(o_d, {H, W}).to(dev), to_host(o_v, {H, W}).to(dev), to_host(o_rgb, {H, W, 3}).to(dev));
 }
 
 std::pair<double, double> Renderer::image_ssim(torch::Tensor a, torch::Tensor b, int levels, double data_range, double* h_out)
 {
     TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && a.sizes() == b.sizes(), "image_ssim: a and b must have one shape, [H,W] or [H,W,C]");
     const int H = (int)a.size(0), W = (int)a.size(1), C = a.dim() == 3 ? (int)a.size(2) : 1;
-    DevBuf da, db;
-    da.upload(a.reshape({-1})); db.upload(b.reshape({-1}));
+    DevArr<float> da = to_device(a.reshape({-1})), db = to_device(b.reshape({-1}));
     double h[8];
-    check(nsk_image_ssim(ctx(), H, W, C, da.p, db.p, 11, 1.5, data_range, 0.01, 0.03, levels, nullptr, nullptr, h, nullptr));
+    check(nsk_image_ssim(ctx(), H, W, C, da.p(), db.p(), 11, 1.5, data_range, 0.01, 0.03, levels, nullptr, nullptr, h, nullptr));
     if (h_out) for (int k = 0; k < 8; ++k) h_out[k] = h[k];
     return std::make_pair(h[0], h[1]);
 }
@@ -469,13 +454,12 @@ void raw2outputs_nerf_color(torch::Tensor raw, torch::Tensor z_vals, bool occupa
                             torch::Tensor& depth_map, torch::Tensor& depth_var, torch::Tensor& weights)      // utils.h:148-172
 {
     const int N = (int)z_vals.size(0), S = (int)z_vals.size(1);
-    DevBuf r, z, d, o_rgb, o_d, o_v, o_w;
-    r.upload(raw.reshape({-1, 4})); z.upload(z_vals); d.upload(rays_d.reshape({-1, 3}));
-    o_rgb.ensure((size_t)N * 3); o_d.ensure(N); o_v.ensure(N); o_w.ensure((size_t)N * S);
-    check(nsk_raw2outputs(ctx(), N, S, r.p, z.p, d.p, occupancy ? 1 : 0, o_rgb.p, o_d.p, o_v.p, o_w.p));
+    DevArr<float> r = to_device(raw.reshape({-1, 4})), z = to_device(z_vals), d = to_device(rays_d.reshape({-1, 3}));
+    DevArr<float> o_rgb((size_t)N * 3), o_d((size_t)N), o_v((size_t)N), o_w((size_t)N * S);
+    check(nsk_raw2outputs(ctx(), N, S, r.p(), z.p(), d.p(), occupancy ? 1 : 0, o_rgb.p(), o_d.p(), o_v.p(), o_w.p()));
     auto dev = raw.device();
-    rgb_map = o_rgb.download({N, 3}).to(dev); depth_map = o_d.download({N}).to(dev);
-    depth_var = o_v.download({N}).to(dev); weights = o_w.download({N, S}).to(dev);
+    rgb_map = to_host(o_rgb, {N, 3}).to(dev); depth_map = to_host(o_d, {N}).to(dev);
+    depth_var = to_host(o_v, {N}).to(dev); weights = to_host(o_w, {N, S}).to(dev);
 }
 
 torch::Tensor quad2rotation(torch::Tensor quad)                                               // utils.h:174-195
@@ -527,39 +511,7 @@ static torch::Tensor inside_mask(const torch::Tensor& bound, const torch::Tensor
 // ---------------------------------------------------------------------------------------------------------
 // device-resident state shared by Tracker::run and Mapper::optimize_map
 // ---------------------------------------------------------------------------------------------------------
-#define HIPOK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 namespace {
-
-// grow-only device array; uploads and downloads go through the kernels' stream, so they are ordered with the launches
-template <typename T>
-struct DevArr {
-    T* p = nullptr; size_t cap = 0;
-    ~DevArr() { if (p) hipFree(p); }
-    DevArr() {}
-    DevArr(const DevArr&) = delete;
-    DevArr& operator=(const DevArr&) = delete;
-    void ensure(size_t n)
-    {
-        if (n <= cap) return;
-        check(nsk_sync(ctx()));                          // nobody may still be reading the old buffer
-        if (p) HIPOK(hipFree(p));
-        HIPOK(hipMalloc((void**)&p, n * sizeof(T)));
-        cap = n;
-    }
-    void upload(const T* h, size_t n)
-    {
-        ensure(n);
-        HIPOK(hipMemcpyAsync(p, h, n * sizeof(T), hipMemcpyHostToDevice, (hipStream_t)nsk_stream(ctx())));
-        check(nsk_sync(ctx()));                          // h may be a temporary
-    }
-    void zero(size_t n) { ensure(n); HIPOK(hipMemsetAsync(p, 0, n * sizeof(T), (hipStream_t)nsk_stream(ctx()))); }
-    void download(T* h, size_t n) const
-    {
-        HIPOK(hipMemcpyAsync(h, p, n * sizeof(T), hipMemcpyDeviceToHost, (hipStream_t)nsk_stream(ctx())));
-        check(nsk_sync(ctx()));
-    }
-};
 
 // one frame's images on the device, keyed by the host tensors they came from (a keyframe is uploaded once, not once per iteration)
 struct DevFrame {
@@ -652,16 +604,16 @@ torch::Tensor Tracker::optimize_cam_in_batch(torch::Tensor cam_tensor, torch::Te
     decoders.sync_to_device();
     RayBufs& R = D.rays;
     // utils.h:19-52 + :198 + Tracker.cpp:48-58 in one launch: pixel draw, ground-truth gather, pose -> rays, inside filter
-    const nsk_frame_rays fr = {D.frame.depth.p, D.frame.color.p, D.cam.p, 1, rng_seed++};
+    const nsk_frame_rays fr = {D.frame.depth.p(), D.frame.color.p(), D.cam.p(), 1, rng_seed++};
     check(nsk_prepare_rays(ctx(), 1, &fr, N, ignore_edge_h, H - ignore_edge_h, ignore_edge_w, W - ignore_edge_w, D.frame.H, D.frame.W, fx, fy, cx, cy, 0,
-                           R.pi.p, R.pj.p, R.gd.p, R.gc.p, R.ro.p, R.rd.p, R.keep.p));
-    check(nsk_set_ray_mask(ctx(), R.keep.p));
-    check(nsk_track_step(ctx(), NSK_COLOR, N, R.ro.p, R.rd.p, R.gd.p, R.gc.p, -1.f, w_color_loss, use_color_in_tracking ? 1 : 0,
-                         handle_dynamic ? 1 : 0, 1, NSK_GRAD_RAYS, D.losses.p, R.g_ro.p, R.g_rd.p));      // stage "color": :61 (D19)
+                           R.pi.p(), R.pj.p(), R.gd.p(), R.gc.p(), R.ro.p(), R.rd.p(), R.keep.p()));
+    check(nsk_set_ray_mask(ctx(), R.keep.p()));
+    check(nsk_track_step(ctx(), NSK_COLOR, N, R.ro.p(), R.rd.p(), R.gd.p(), R.gc.p(), -1.f, w_color_loss, use_color_in_tracking ? 1 : 0,
+                         handle_dynamic ? 1 : 0, 1, NSK_GRAD_RAYS, D.losses.p(), R.g_ro.p(), R.g_rd.p()));      // stage "color": :61 (D19)
     check(nsk_set_ray_mask(ctx(), nullptr));
-    float* g_c2w = D.m.p;              // 12 floats of scratch
-    check(nsk_rays_backward(ctx(), N, R.pi.p, R.pj.p, fx, fy, cx, cy, 0, R.g_ro.p, R.g_rd.p, g_c2w));
-    check(nsk_camera_backward(ctx(), D.cam.p, g_c2w, D.losses.p + 1));          // losses[1..7] = d loss / d pose
+    float* g_c2w = D.m.p();              // 12 floats of scratch
+    check(nsk_rays_backward(ctx(), N, R.pi.p(), R.pj.p(), fx, fy, cx, cy, 0, R.g_ro.p(), R.g_rd.p(), g_c2w));
+    check(nsk_camera_backward(ctx(), D.cam.p(), g_c2w, D.losses.p() + 1));          // losses[1..7] = d loss / d pose
     float h[8];
     D.losses.download(h, 8);
     cam_tensor.mutable_grad() = torch::from_blob(h + 1, {7}, torch::kFloat32).clone().to(cam_tensor.device());       // loss.backward() :84
@@ -688,14 +640,14 @@ void Tracker::run(NICE decoders, torch::Tensor gt_color_t, torch::Tensor gt_dept
     check(nsk_sync(ctx()));
     const double t0 = now_us();
     for (int i = 0; i < iters; ++i) {                                                 // :108-112, every operand resident on the device
-        const nsk_frame_rays fr = {D.frame.depth.p, D.frame.color.p, D.cam.p, 1, rng_seed++};
+        const nsk_frame_rays fr = {D.frame.depth.p(), D.frame.color.p(), D.cam.p(), 1, rng_seed++};
         check(nsk_prepare_rays(ctx(), 1, &fr, N, ignore_edge_h, H - ignore_edge_h, ignore_edge_w, W - ignore_edge_w, D.frame.H, D.frame.W, fx, fy, cx, cy, 0,
-                               R.pi.p, R.pj.p, R.gd.p, R.gc.p, R.ro.p, R.rd.p, R.keep.p));
-        check(nsk_set_ray_mask(ctx(), R.keep.p));
-        check(nsk_track_step(ctx(), NSK_COLOR, N, R.ro.p, R.rd.p, R.gd.p, R.gc.p, -1.f, w_color_loss, use_color_in_tracking ? 1 : 0,
-                             handle_dynamic ? 1 : 0, 1, NSK_GRAD_RAYS, D.losses.p + i, R.g_ro.p, R.g_rd.p));
+                               R.pi.p(), R.pj.p(), R.gd.p(), R.gc.p(), R.ro.p(), R.rd.p(), R.keep.p()));
+        check(nsk_set_ray_mask(ctx(), R.keep.p()));
+        check(nsk_track_step(ctx(), NSK_COLOR, N, R.ro.p(), R.rd.p(), R.gd.p(), R.gc.p(), -1.f, w_color_loss, use_color_in_tracking ? 1 : 0,
+                             handle_dynamic ? 1 : 0, 1, NSK_GRAD_RAYS, D.losses.p() + i, R.g_ro.p(), R.g_rd.p()));
         check(nsk_set_ray_mask(ctx(), nullptr));
-        check(nsk_pose_step(ctx(), N, R.pi.p, R.pj.p, fx, fy, cx, cy, 0, R.g_ro.p, R.g_rd.p, D.cam.p, D.m.p, D.v.p, lr, 0.9f, 0.999f, 1e-8f, i + 1, nullptr));   // config tracking.lr (D25)
+        check(nsk_pose_step(ctx(), N, R.pi.p(), R.pj.p(), fx, fy, cx, cy, 0, R.g_ro.p(), R.g_rd.p(), D.cam.p(), D.m.p(), D.v.p(), lr, 0.9f, 0.999f, 1e-8f, i + 1, nullptr));   // config tracking.lr (D25)
     }
     check(nsk_sync(ctx()));
     last_run_us = now_us() - t0;
@@ -810,7 +762,7 @@ void Mapper::get_mask_from_c2w(cv::Mat depth_mat, torch::Tensor c2w, torch::Tens
     DevArr<float> img;
     img.upload(depth_mat.ptr<float>(), depth_mat.total());
     torch::Tensor out = torch::zeros({Z, Y, X}, torch::kUInt8);
-    check(nsk_frustum_mask(ctx(), level, img.p, depth_mat.rows, depth_mat.cols, fx, fy, cx, cy, pose.data_ptr<float>(), out.data_ptr<uint8_t>()));
+    check(nsk_frustum_mask(ctx(), level, img.p(), depth_mat.rows, depth_mat.cols, fx, fy, cx, cy, pose.data_ptr<float>(), out.data_ptr<uint8_t>()));
     mask = out.to(torch::kBool).permute({2, 1, 0}).contiguous();          // [X,Y,Z], the layout the reference's caller permutes back (:260)
 }
 
@@ -828,15 +780,15 @@ void Mapper::keyframe_selection_overlap(torch::Tensor gt_color_, torch::Tensor g
     torch::Tensor pose = c2w.detach().to(torch::kCPU, torch::kFloat32).contiguous();
     D.poses.upload(pose.data_ptr<float>(), 12);
     const uint64_t call_seed = draw_seed(rng_seed, ++draw_calls);                             // a new draw every call (the reference: torch::randint)
-    check(nsk_sample_pixels(ctx(), call_seed + 0x9e3779b9ull * (uint64_t)(K + 1), n, 0, H, 0, W, D.kf_pi.p, D.kf_pj.p));        // get_samples(0,H,0,W,100,...) :137
-    check(nsk_gather_pixels(ctx(), n, D.kf_pi.p, D.kf_pj.p, D.cur.H, D.cur.W, D.cur.depth.p, nullptr, D.kf_gd.p, nullptr));
-    check(nsk_rays_from_pixels(ctx(), n, D.kf_pi.p, D.kf_pj.p, fx, fy, cx, cy, D.poses.p, 0, D.kf_ro.p, D.kf_rd.p));
+    check(nsk_sample_pixels(ctx(), call_seed + 0x9e3779b9ull * (uint64_t)(K + 1), n, 0, H, 0, W, D.kf_pi.p(), D.kf_pj.p()));        // get_samples(0,H,0,W,100,...) :137
+    check(nsk_gather_pixels(ctx(), n, D.kf_pi.p(), D.kf_pj.p(), D.cur.H, D.cur.W, D.cur.depth.p(), nullptr, D.kf_gd.p(), nullptr));
+    check(nsk_rays_from_pixels(ctx(), n, D.kf_pi.p(), D.kf_pj.p(), fx, fy, cx, cy, D.poses.p(), 0, D.kf_ro.p(), D.kf_rd.p()));
     std::vector<float> poses((size_t)K * 16), pct((size_t)K);
     for (int k = 0; k < K; ++k) {
         torch::Tensor m = keyframe_vector_[k].est_c2w.detach().to(torch::kCPU, torch::kFloat32).contiguous();
         std::memcpy(poses.data() + 16 * k, m.data_ptr<float>(), 16 * sizeof(float));
     }
-    check(nsk_keyframe_overlap(ctx(), n, D.kf_ro.p, D.kf_rd.p, D.kf_gd.p, ns, H, W, fx, fy, cx, cy, K, poses.data(), pct.data()));
+    check(nsk_keyframe_overlap(ctx(), n, D.kf_ro.p(), D.kf_rd.p(), D.kf_gd.p(), ns, H, W, fx, fy, cx, cy, K, poses.data(), pct.data()));
     std::vector<int> order;
     for (int k = 0; k < K; ++k) if (pct[k] > 0.f) order.push_back(k);                         // :178-179
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pct[a] > pct[b]; });   // :186-190
@@ -880,7 +832,7 @@ void Mapper::optimize_map(int num_joint_iters_, c10::Dict<std::string, torch::Te
     if (frustum_feature_selection) {                                            // :231-281 (depth_mat = cur_gt_depth intended, D21)
         torch::Tensor pose = cur_c2w.detach().to(torch::kCPU, torch::kFloat32).contiguous();
         for (int level = 0; level < 4; ++level)
-            if (!user_mask[level]) check(nsk_frustum_mask(ctx(), level, D.cur.depth.p, D.cur.H, D.cur.W, fx, fy, cx, cy, pose.data_ptr<float>(), nullptr));
+            if (!user_mask[level]) check(nsk_frustum_mask(ctx(), level, D.cur.depth.p(), D.cur.H, D.cur.W, fx, fy, cx, cy, pose.data_ptr<float>(), nullptr));
     } else {
         for (int level = 0; level < 4; ++level) if (!user_mask[level]) check(nsk_set_mask(ctx(), level, nullptr));
     }
@@ -941,11 +893,11 @@ void Mapper::optimize_map(int num_joint_iters_, c10::Dict<std::string, torch::Te
         for (int i = 0; i < nf; ++i) {
             const int f = optimize_frame[i];
             const DevFrame& F = f >= 0 ? *D.kf[f] : D.cur;
-            frame_tab[i] = nsk_frame_rays{F.depth.p, F.color.p, is_ba[i] ? D.cams.p + 8 * i : D.poses.p + 12 * i, is_ba[i] ? 1 : 0,
+            frame_tab[i] = nsk_frame_rays{F.depth.p(), F.color.p(), is_ba[i] ? D.cams.p() + 8 * i : D.poses.p() + 12 * i, is_ba[i] ? 1 : 0,
                                           call_seed + 0x100000001b3ull * (uint64_t)(it * nf + i + 1)};
         }
-        check(nsk_prepare_rays(ctx(), nf, frame_tab.data(), pixs_per_image, 0, H, 0, W, D.cur.H, D.cur.W, fx, fy, cx, cy, 0, R.pi.p, R.pj.p, R.gd.p, R.gc.p,
-                               R.ro.p, R.rd.p, R.keep.p));                                    // :416-427 included: rays that leave the bound before their depth
+        check(nsk_prepare_rays(ctx(), nf, frame_tab.data(), pixs_per_image, 0, H, 0, W, D.cur.H, D.cur.W, fx, fy, cx, cy, 0, R.pi.p(), R.pj.p(), R.gd.p(), R.gc.p(),
+                               R.ro.p(), R.rd.p(), R.keep.p()));                                    // :416-427 included: rays that leave the bound before their depth
     };                                                                                        // ... are neutralised in place (no count on the host)
     int drawn_upto = -1;                                                                      // last iteration whose rays have been drawn
     for (int joint_iter = 0; joint_iter < num_joint_iters_; ++joint_iter) {
@@ -966,45 +918,45 @@ void Mapper::optimize_map(int num_joint_iters_, c10::Dict<std::string, torch::Te
         if (joint_iter + 1 < num_joint_iters_ && !(any_ba && stage_of(joint_iter + 1) == "color") && Nl > 0) {
             RayBufs& Rn = *bufs[(joint_iter + 1) & 1];
             draw_rays(joint_iter + 1, Rn); drawn_upto = joint_iter + 1;
-            if (sharded) check(nsk_set_depth_max_batch(ctx(), Rn.gd.p, Rn.keep.p, N));          // (remembered with the registration, like the mask)
-            check(nsk_set_ray_mask(ctx(), Rn.keep.p + lo));
-            check(nsk_map_prepare(ctx(), nskh::stage_id(render_stage_of(joint_iter + 1)), Nl, Rn.ro.p + 3 * (size_t)lo, Rn.rd.p + 3 * (size_t)lo, Rn.gd.p + lo, -1.f,
+            if (sharded) check(nsk_set_depth_max_batch(ctx(), Rn.gd.p(), Rn.keep.p(), N));          // (remembered with the registration, like the mask)
+            check(nsk_set_ray_mask(ctx(), Rn.keep.p() + lo));
+            check(nsk_map_prepare(ctx(), nskh::stage_id(render_stage_of(joint_iter + 1)), Nl, Rn.ro.p() + 3 * (size_t)lo, Rn.rd.p() + 3 * (size_t)lo, Rn.gd.p() + lo, -1.f,
                                   NSK_GRAD_GRIDS | NSK_GRAD_DECODERS));
         }
         unsigned flags = NSK_GRAD_GRIDS | NSK_GRAD_DECODERS | (ba_now ? NSK_GRAD_RAYS : 0u);
         const std::string render_stage = render_stage_of(joint_iter);
         if (!sharded) {
-            check(nsk_set_ray_mask(ctx(), R.keep.p));
-            check(nsk_map_step(ctx(), nskh::stage_id(render_stage), N, R.ro.p, R.rd.p, R.gd.p, R.gc.p, -1.f, w_color_loss, stage == "color" ? 1 : 0, flags,
-                               D.loss.p + joint_iter, nullptr, nullptr, nullptr, ba_now ? R.g_ro.p : nullptr, ba_now ? R.g_rd.p : nullptr));      // :430-444
+            check(nsk_set_ray_mask(ctx(), R.keep.p()));
+            check(nsk_map_step(ctx(), nskh::stage_id(render_stage), N, R.ro.p(), R.rd.p(), R.gd.p(), R.gc.p(), -1.f, w_color_loss, stage == "color" ? 1 : 0, flags,
+                               D.loss.p() + joint_iter, nullptr, nullptr, nullptr, ba_now ? R.g_ro.p() : nullptr, ba_now ? R.g_rd.p() : nullptr));      // :430-444
             check(nsk_set_ray_mask(ctx(), nullptr));
             check(nsk_adam_step(ctx(), lr, 0.9f, 0.999f, 1e-8f));                             // :445-446
             if (ba_now)                                                                       // pose gradients through the ray generator and quad2rotation + Adam: every frame of the window in one launch
-                check(nsk_pose_step_multi(ctx(), nf, fr_first.data(), fr_count.data(), fr_active.data(), R.pi.p, R.pj.p, fx, fy, cx, cy, 0, R.g_ro.p, R.g_rd.p,
-                                          D.cams.p, D.cam_m.p, D.cam_v.p, BA_cam_lr, 0.9f, 0.999f, 1e-8f, ++ba_step, D.cam_g.p, nullptr, 0));
+                check(nsk_pose_step_multi(ctx(), nf, fr_first.data(), fr_count.data(), fr_active.data(), R.pi.p(), R.pj.p(), fx, fy, cx, cy, 0, R.g_ro.p(), R.g_rd.p(),
+                                          D.cams.p(), D.cam_m.p(), D.cam_v.p(), BA_cam_lr, 0.9f, 0.999f, 1e-8f, ++ba_step, D.cam_g.p(), nullptr, 0));
             continue;
         }
         // ---- N > 1: the shard's step, one exchange, the replicated optimiser steps ------------------------------------------------
-        float* xt = ba_now ? D.x_ba.p : D.x_plain.p;                                          // what travels beside the grids this iteration
+        float* xt = ba_now ? D.x_ba.p() : D.x_plain.p();                                          // what travels beside the grids this iteration
         float* loss_slot = ba_now ? xt + (size_t)nf * 8 : xt;
-        check(nsk_set_depth_max_batch(ctx(), R.gd.p, R.keep.p, N));                           // max(gt_depth) over the WHOLE batch (Renderer.cpp:76,93)
-        check(nsk_set_ray_mask(ctx(), R.keep.p + lo));
+        check(nsk_set_depth_max_batch(ctx(), R.gd.p(), R.keep.p(), N));                           // max(gt_depth) over the WHOLE batch (Renderer.cpp:76,93)
+        check(nsk_set_ray_mask(ctx(), R.keep.p() + lo));
         if (Nl > 0)
-            check(nsk_map_step(ctx(), nskh::stage_id(render_stage), Nl, R.ro.p + 3 * (size_t)lo, R.rd.p + 3 * (size_t)lo, R.gd.p + lo, R.gc.p + 3 * (size_t)lo, -1.f,
+            check(nsk_map_step(ctx(), nskh::stage_id(render_stage), Nl, R.ro.p() + 3 * (size_t)lo, R.rd.p() + 3 * (size_t)lo, R.gd.p() + lo, R.gc.p() + 3 * (size_t)lo, -1.f,
                                w_color_loss, stage == "color" ? 1 : 0, flags, loss_slot, nullptr, nullptr, nullptr,
-                               ba_now ? R.g_ro.p + 3 * (size_t)lo : nullptr, ba_now ? R.g_rd.p + 3 * (size_t)lo : nullptr));
+                               ba_now ? R.g_ro.p() + 3 * (size_t)lo : nullptr, ba_now ? R.g_rd.p() + 3 * (size_t)lo : nullptr));
         check(nsk_set_ray_mask(ctx(), nullptr));
         check(nsk_set_depth_max_batch(ctx(), nullptr, nullptr, 0));
         if (ba_now)                                                                           // this shard's part of every frame's pose gradient (no step yet) + its kept-ray count
-            check(nsk_pose_step_multi(ctx(), nf, fr_first.data(), fr_count.data(), fr_active.data(), R.pi.p, R.pj.p, fx, fy, cx, cy, 0, R.g_ro.p, R.g_rd.p,
-                                      D.cams.p, nullptr, nullptr, 0.f, 0.9f, 0.999f, 1e-8f, 0, xt, R.keep.p + lo, Nl));
+            check(nsk_pose_step_multi(ctx(), nf, fr_first.data(), fr_count.data(), fr_active.data(), R.pi.p(), R.pj.p(), fx, fy, cx, cy, 0, R.g_ro.p(), R.g_rd.p(),
+                                      D.cams.p(), nullptr, nullptr, 0.f, 0.9f, 0.999f, 1e-8f, 0, xt, R.keep.p() + lo, Nl));
         check(nsk_grad_extra(ctx(), xt, ba_now ? (size_t)nf * 8 + 8 : 4));
         dist.allreduce_grads();                                                               // the ONE exchange of the iteration
         check(nsk_grad_extra(ctx(), nullptr, 0));
-        HIPOK(hipMemcpyAsync(D.loss.p + joint_iter, loss_slot, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)nsk_stream(ctx())));
+        nskh::hip_ok(hipMemcpyAsync(D.loss.p() + joint_iter, loss_slot, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)nsk_stream(ctx())), "hipMemcpyAsync D2D");
         check(nsk_adam_step(ctx(), lr, 0.9f, 0.999f, 1e-8f));
         if (ba_now)                                                                           // every pose at once on the summed gradients (zero for the frames left fixed: no move)
-            check(nsk_adam_vector(ctx(), nf * 8, D.cams.p, xt, D.cam_m.p, D.cam_v.p, BA_cam_lr, 0.9f, 0.999f, 1e-8f, ++ba_step));
+            check(nsk_adam_vector(ctx(), nf * 8, D.cams.p(), xt, D.cam_m.p(), D.cam_v.p(), BA_cam_lr, 0.9f, 0.999f, 1e-8f, ++ba_step));
     }
     check(nsk_sync(ctx()));
     last_iter_us = (now_us() - t0) / num_joint_iters_;
@@ -1114,8 +1066,8 @@ std::pair<torch::Tensor, torch::Tensor> nskh::FramePrep::prepare(const cv::Mat& 
     d_color_out.ensure(3 * n_out); d_depth_out.ensure(n_out);
     d_rgb.upload(raw_rgb.ptr<uint8_t>(), raw_rgb.total() * 3);
     d_depth.upload(raw_depth.ptr<uint16_t>(), raw_depth.total());
-    check(nsk_frame_prepare(ctx(), &opts, 1, d_rgb.p, NSK_FRAME_U8, raw_rgb.rows, raw_rgb.cols, d_depth.p, NSK_FRAME_U16, raw_depth.rows, raw_depth.cols,
-                            d_color_out.p, d_depth_out.p, &last_border));
+    check(nsk_frame_prepare(ctx(), &opts, 1, d_rgb.p(), NSK_FRAME_U8, raw_rgb.rows, raw_rgb.cols, d_depth.p(), NSK_FRAME_U16, raw_depth.rows, raw_depth.cols,
+                            d_color_out.p(), d_depth_out.p(), &last_border));
     torch::Tensor color = torch::empty({H, W, 3}, torch::kFloat32), depth = torch::empty({H, W}, torch::kFloat32);
     d_color_out.download(color.data_ptr<float>(), 3 * n_out);
     d_depth_out.download(depth.data_ptr<float>(), n_out);

@@ -10,12 +10,11 @@
 #include <iterator>
 #include <sstream>
 
-#include <hip/hip_runtime_api.h>
-
-#include "nsk_host.h"
+#include "nsk_devarr.h"
 
 using nskh::check;
 using nskh::ctx;
+using nskh::DevArr;
 
 Mesher::Mesher(YAML::Node ns, torch::Tensor bound_3x2, float padding_) : padding(padding_)
 {
@@ -35,13 +34,85 @@ Mesher::Mesher(YAML::Node ns, torch::Tensor bound_3x2, float padding_) : padding
 void Mesher::set_bound(torch::Tensor b) { bound = b.detach().to(torch::kCPU, torch::kFloat32).contiguous().clone(); }
 
 namespace {
-struct DevMem {
-    void* p = nullptr;
-    explicit DevMem(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) throw std::runtime_error("Mesher: hipMalloc of " + std::to_string(bytes) + " bytes failed"); }
-    ~DevMem() { if (p) hipFree(p); }
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
+// the lattice of a Mesher: `resolution` nodes per axis over the bound enlarged by the padding
+struct Lattice {
+    int n; float origin[3], step[3];
+    explicit Lattice(const Mesher& m) : n(m.resolution)
+    {
+        TORCH_CHECK(m.bound.numel() == 6, "Mesher: bound must be [3,2]");
+        for (int a = 0; a < 3; ++a) {
+            const float lo = m.bound[a][0].item<float>() - m.padding, hi = m.bound[a][1].item<float>() + m.padding;
+            origin[a] = lo;
+            step[a] = (hi - lo) / (float)(n - 1);
+        }
+    }
+    size_t nodes() const { return (size_t)n * n * n; }
 };
+
+// a mesh on the device: uploaded once per public call
+struct DevMesh {
+    int nv, nt;
+    DevArr<float> v; DevArr<int32_t> t;
+    DevMesh(const float* xyz, int nv_, const int32_t* tris, int nt_) : nv(nv_), nt(nt_), v((size_t)nv_ * 3), t((size_t)nt_ * 3)
+    {
+        v.upload(xyz, (size_t)nv * 3); t.upload(tris, (size_t)nt * 3);
+    }
+};
+
+// camera-to-world -> world-to-camera: inverted in double, rounded once
+void w2c_of(const torch::Tensor& c2w, int k, float* out16)
+{
+    torch::Tensor m = c2w.detach().to(torch::kCPU, torch::kFloat64).contiguous();
+    TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
+    torch::Tensor inv = torch::linalg_inv(m.view({4, 4})).to(torch::kFloat32).contiguous();
+    std::memcpy(out16, inv.data_ptr<float>(), 16 * sizeof(float));
+}
+
+// K frames as the public calls take them: host tensors (depth [H, W], camera-to-world [4, 4]), or host arrays (depths [K][img] or none,
+// world-to-camera [K][16])
+struct Frames {
+    int K; size_t img;                                   // img = H * W
+    const std::vector<torch::Tensor>* depth_t; const std::vector<torch::Tensor>* c2w_t;
+    const float* depth_h; const float* w2c_h;
+    Frames(const std::vector<torch::Tensor>& depths, const std::vector<torch::Tensor>& c2ws, size_t img_)
+        : K((int)depths.size()), img(img_), depth_t(&depths), c2w_t(&c2ws), depth_h(nullptr), w2c_h(nullptr)
+    {
+        TORCH_CHECK(depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    }
+    Frames(const float* depths, const float* w2c, int K_, size_t img_) : K(K_), img(img_), depth_t(nullptr), c2w_t(nullptr), depth_h(depths), w2c_h(w2c) {}
+    // frames [k0, k0 + kb): their images to the front of d (nothing where there are none) -> their [kb][16] world-to-camera rows, made in tmp
+    // where the poses came as camera-to-world
+    const float* upload(int k0, int kb, DevArr<float>& d, std::vector<float>& tmp) const
+    {
+        if (!depth_t) {
+            if (depth_h) d.upload(depth_h + (size_t)k0 * img, (size_t)kb * img);
+            return w2c_h + 16 * (size_t)k0;
+        }
+        tmp.resize((size_t)kb * 16);
+        for (int k = 0; k < kb; ++k) {
+            torch::Tensor h = (*depth_t)[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK((size_t)h.numel() == img, "Mesher: depth image ", k0 + k, " is not H x W");
+            d.upload(h.data_ptr<float>(), img, (size_t)k * img);
+            w2c_of((*c2w_t)[(size_t)(k0 + k)], k0 + k, &tmp[(size_t)k * 16]);
+        }
+        return tmp.data();
+    }
+};
+
+// The frames streamed, at most `batch` depth images on the device at a time: fn(k0, kb, d_depth, w2c) per batch, in order.  d_depth holds
+// the batch's images; with images = false it has no element, with frames that carry no images it is fn's own to fill.
+template <class Fn>
+void stream_frames(const Frames& F, int batch, bool images, Fn fn)
+{
+    DevArr<float> dimg(images ? (size_t)std::min(std::max(F.K, 1), batch) * F.img : 0);
+    std::vector<float> tmp;
+    for (int k0 = 0; k0 < F.K; k0 += batch) {
+        const int kb = std::min(batch, F.K - k0);
+        // (no nsk_sync here: the upload goes through the context's stream, behind the previous batch's launch that reads these images)
+        const float* w2c = F.upload(k0, kb, dimg, tmp);
+        fn(k0, kb, dimg.p(), w2c);
+    }
+}
 }  // namespace
 
 // the context's mesh (nv vertices, nt triangles) -> host; asked for, the normals and the colours from the device buffers; the PLY
@@ -59,22 +130,22 @@ static void write_context_mesh(Mesher& M, const std::string& path, bool color, i
     if ((color || want_normals) && nv > 0) {
         float* d_verts = nullptr; int32_t* d_tris = nullptr;
         check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
-        const size_t vb = (size_t)nv * 3 * sizeof(float);
-        DevMem dn(want_normals ? vb : 0), raw(color ? vb : 0);
+        const size_t nf = (size_t)nv * 3;
+        DevArr<float> dn(want_normals ? nf : 0), raw(color ? nf : 0);
         if (want_normals) {
             int info[4];
-            check(nsk_mesh_vertex_normals(ctx(), d_verts, nv, d_tris, nt, (float*)dn.p, info));
+            check(nsk_mesh_vertex_normals(ctx(), d_verts, nv, d_tris, nt, dn.p(), info));
             M.last_normals_zero = info[1];
             if (M.write_normals) {
-                normals.resize((size_t)nv * 3);
-                if (hipMemcpy(normals.data(), dn.p, vb, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+                normals.resize(nf);
+                dn.download(normals.data(), nf);
             }
         }
         if (color) {
-            check(nsk_mesh_vertex_colors(ctx(), d_verts, nv, along ? (const float*)dn.p : nullptr, M.color_ray_length, 0, (float*)raw.p, &M.last_color_fallback));
-            std::vector<float> h((size_t)nv * 3);
-            if (hipMemcpy(h.data(), raw.p, vb, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
-            rgb.resize((size_t)nv * 3);
+            check(nsk_mesh_vertex_colors(ctx(), d_verts, nv, along ? dn.p() : nullptr, M.color_ray_length, 0, raw.p(), &M.last_color_fallback));
+            std::vector<float> h(nf);
+            raw.download(h.data(), nf);
+            rgb.resize(nf);
             for (size_t k = 0; k < h.size(); ++k) {
                 float x = h[k];
                 x = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;                       // clamp to [0, 1]; NaN -> 0
@@ -91,29 +162,22 @@ void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::st
 {
     nskh::sync_grids(c);
     decoders.sync_to_device();
-    TORCH_CHECK(bound.numel() == 6, "Mesher: bound must be [3,2]");
+    const Lattice L(*this);
     check(nsk_set_bound(ctx(), bound.data_ptr<float>()));
-    const int n = resolution;
-    float origin[3], step[3];
-    for (int a = 0; a < 3; ++a) {
-        const float lo = bound[a][0].item<float>() - padding, hi = bound[a][1].item<float>() + padding;
-        origin[a] = lo;
-        step[a] = (hi - lo) / (float)(n - 1);
-    }
-    const size_t nodes = (size_t)n * n * n;
-    DevMem vol(nodes * sizeof(float));
-    std::unique_ptr<DevMem> dvalid;
+    const int n = L.n;
+    const size_t nodes = L.nodes();
+    DevArr<float> vol(nodes);
+    DevArr<uint8_t> dvalid;                              // (allocated only with a mask)
     if (valid.defined()) {
         torch::Tensor h = valid.detach().to(torch::kCPU, torch::kUInt8).contiguous();
         TORCH_CHECK((size_t)h.numel() == nodes, "Mesher: valid must have resolution^3 entries");
-        dvalid.reset(new DevMem(nodes));
-        if (hipMemcpy(dvalid->p, h.data_ptr<uint8_t>(), nodes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+        dvalid.upload(h.data_ptr<uint8_t>(), nodes);
     }
     long long n_eval = (long long)nodes;
-    if (dvalid) check(nsk_eval_lattice_masked(ctx(), NSK_FINE, origin, step, n, n, n, (const uint8_t*)dvalid->p, 100.f, (float*)vol.p, &n_eval));
-    else check(nsk_eval_lattice(ctx(), NSK_FINE, origin, step, n, n, n, (float*)vol.p));
+    if (dvalid.p()) check(nsk_eval_lattice_masked(ctx(), NSK_FINE, L.origin, L.step, n, n, n, dvalid.p(), 100.f, vol.p(), &n_eval));
+    else check(nsk_eval_lattice(ctx(), NSK_FINE, L.origin, L.step, n, n, n, vol.p()));
     int nv = 0, nt = 0;
-    check(nsk_mesh_extract(ctx(), (const float*)vol.p, dvalid ? (const uint8_t*)dvalid->p : nullptr, n, n, n, origin, step, level_set, &nv, &nt));
+    check(nsk_mesh_extract(ctx(), vol.p(), dvalid.p(), n, n, n, L.origin, L.step, level_set, &nv, &nt));
     write_context_mesh(*this, path, color, nv, nt);
     last_vertices = nv; last_triangles = nt; last_evaluated = n_eval;
 }
@@ -121,46 +185,26 @@ void Mesher::get_mesh(const std::string& path, NICE& decoders, c10::Dict<std::st
 void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
                             const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color)
 {
-    TORCH_CHECK(depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    const Frames F(depths, c2ws, (size_t)H * W);
     nskh::sync_grids(c);
     decoders.sync_to_device();
-    TORCH_CHECK(bound.numel() == 6, "Mesher: bound must be [3,2]");
+    const Lattice L(*this);
     check(nsk_set_bound(ctx(), bound.data_ptr<float>()));
-    const int n = resolution;
-    float origin[3], step[3];
-    for (int a = 0; a < 3; ++a) {
-        const float lo = bound[a][0].item<float>() - padding, hi = bound[a][1].item<float>() + padding;
-        origin[a] = lo;
-        step[a] = (hi - lo) / (float)(n - 1);
-    }
-    const size_t nodes = (size_t)n * n * n, img = (size_t)H * W;
-    DevMem vol(nodes * sizeof(float)), seen(nodes);
+    const int n = L.n, K = F.K;
+    DevArr<float> vol(L.nodes());
+    DevArr<uint8_t> seen(L.nodes());
     // the seen mask, streamed: at most 16 depth images on the device at a time
-    const int batch = 16, K = (int)depths.size();
-    DevMem dimg((size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
-    std::vector<float> w2c((size_t)batch * 16);
     long long n_seen = 0;
-    if (K == 0) check(nsk_lattice_seen(ctx(), origin, step, n, n, n, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, seen_edge, seen_trunc, 0, (uint8_t*)seen.p, &n_seen));
-    for (int k0 = 0; k0 < K; k0 += batch) {
-        const int kb = std::min(batch, K - k0);
-        check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
-        for (int k = 0; k < kb; ++k) {
-            torch::Tensor d = depths[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat32).contiguous();
-            TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k0 + k, " is not H x W");
-            if (hipMemcpy((float*)dimg.p + (size_t)k * img, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-            torch::Tensor m = c2ws[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat64).contiguous();
-            TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k0 + k, " is not 4 x 4");
-            torch::Tensor inv = torch::linalg_inv(m.view({4, 4})).to(torch::kFloat32).contiguous();      // inverted in double, rounded once
-            std::memcpy(&w2c[(size_t)k * 16], inv.data_ptr<float>(), 16 * sizeof(float));
-        }
-        check(nsk_lattice_seen(ctx(), origin, step, n, n, n, kb, (const float*)dimg.p, H, W, fx, fy, cx, cy, w2c.data(), seen_edge, seen_trunc, k0 > 0,
-                               (uint8_t*)seen.p, k0 + kb >= K ? &n_seen : nullptr));
-    }
+    if (K == 0) check(nsk_lattice_seen(ctx(), L.origin, L.step, n, n, n, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, seen_edge, seen_trunc, 0, seen.p(), &n_seen));
+    stream_frames(F, 16, true, [&](int k0, int kb, const float* d_depth, const float* w2c) {
+        check(nsk_lattice_seen(ctx(), L.origin, L.step, n, n, n, kb, d_depth, H, W, fx, fy, cx, cy, w2c, seen_edge, seen_trunc, k0 > 0, seen.p(),
+                               k0 + kb >= K ? &n_seen : nullptr));
+    });
     // the decoders run at the seen nodes only: a cell with an unseen corner is not processed, so the extraction never uses the rest
     long long n_eval = 0;
-    check(nsk_eval_lattice_masked(ctx(), NSK_FINE, origin, step, n, n, n, (const uint8_t*)seen.p, 100.f, (float*)vol.p, &n_eval));
+    check(nsk_eval_lattice_masked(ctx(), NSK_FINE, L.origin, L.step, n, n, n, seen.p(), 100.f, vol.p(), &n_eval));
     int nv = 0, nt = 0, nc = 0, nk = 0;
-    check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)seen.p, n, n, n, origin, step, level_set, &nv, &nt));
+    check(nsk_mesh_extract(ctx(), vol.p(), seen.p(), n, n, n, L.origin, L.step, level_set, &nv, &nt));
     check(nsk_mesh_filter(ctx(), remove_small_geometry_threshold, get_largest_components ? 1 : 0, &nv, &nt, &nc, &nk));
     write_context_mesh(*this, path, color, nv, nt);
     last_vertices = nv; last_triangles = nt; last_components = nc; last_kept = nk; last_seen = n_seen; last_evaluated = n_eval;
@@ -170,71 +214,47 @@ void Mesher::get_clean_mesh(const std::string& path, NICE& decoders, c10::Dict<s
 namespace {
 // the fusion of one mesh: the lattice of get_mesh, the volume's buffers, the finish
 struct Fusion {
-    int n; float origin[3], step[3], trunc;
-    DevMem tsdf, weight;
-    Fusion(const Mesher& m, float trunc_steps) : n(m.resolution), tsdf((size_t)n * n * n * sizeof(float)), weight((size_t)n * n * n * sizeof(float))
+    const Lattice L;
+    const int n; float trunc;
+    DevArr<float> tsdf, weight;
+    Fusion(const Mesher& m, float trunc_steps) : L(m), n(L.n), tsdf(L.nodes()), weight(L.nodes())
     {
-        TORCH_CHECK(m.bound.numel() == 6, "Mesher: bound must be [3,2]");
         float smax = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            const float lo = m.bound[a][0].item<float>() - m.padding, hi = m.bound[a][1].item<float>() + m.padding;
-            origin[a] = lo;
-            step[a] = (hi - lo) / (float)(n - 1);
-            smax = std::max(smax, step[a]);
-        }
+        for (int a = 0; a < 3; ++a) smax = std::max(smax, L.step[a]);
         trunc = trunc_steps * smax;
     }
     void integrate(const Mesher& m, int K, const float* d_depth, int H, int W, float fx, float fy, float cx, float cy, const float* w2c, bool first,
                    long long* n_observed)
     {
-        check(nsk_tsdf_integrate(ctx(), origin, step, n, n, n, K, d_depth, H, W, fx, fy, cx, cy, w2c, m.seen_edge, trunc, m.fuse_max_weight, first ? 0 : 1,
-                                 (float*)tsdf.p, (float*)weight.p, n_observed));
+        check(nsk_tsdf_integrate(ctx(), L.origin, L.step, n, n, n, K, d_depth, H, W, fx, fy, cx, cy, w2c, m.seen_edge, trunc, m.fuse_max_weight, first ? 0 : 1,
+                                 tsdf.p(), weight.p(), n_observed));
     }
     // volume -> extract -> (asked for) filter; the counts into the Mesher
     void mesh(Mesher& m, float min_weight, int& nv, int& nt)
     {
-        const size_t nodes = (size_t)n * n * n;
-        DevMem vol(nodes * sizeof(float)), valid(nodes);
-        check(nsk_tsdf_volume(ctx(), (long long)nodes, (const float*)tsdf.p, (const float*)weight.p, min_weight, (float*)vol.p, (uint8_t*)valid.p, &m.last_valid));
-        check(nsk_mesh_extract(ctx(), (const float*)vol.p, (const uint8_t*)valid.p, n, n, n, origin, step, 0.f, &nv, &nt));
+        DevArr<float> vol(L.nodes());
+        DevArr<uint8_t> valid(L.nodes());
+        check(nsk_tsdf_volume(ctx(), (long long)L.nodes(), tsdf.p(), weight.p(), min_weight, vol.p(), valid.p(), &m.last_valid));
+        check(nsk_mesh_extract(ctx(), vol.p(), valid.p(), n, n, n, L.origin, L.step, 0.f, &nv, &nt));
         m.last_components = m.last_kept = 0;
         if (m.remove_small_geometry_threshold > 0.f || m.get_largest_components)
             check(nsk_mesh_filter(ctx(), m.remove_small_geometry_threshold, m.get_largest_components ? 1 : 0, &nv, &nt, &m.last_components, &m.last_kept));
         m.last_vertices = nv; m.last_triangles = nt;
     }
 };
-// camera-to-world -> world-to-camera: inverted in double, rounded once
-void w2c_of(const torch::Tensor& c2w, int k, float* out16)
-{
-    torch::Tensor m = c2w.detach().to(torch::kCPU, torch::kFloat64).contiguous();
-    TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
-    torch::Tensor inv = torch::linalg_inv(m.view({4, 4})).to(torch::kFloat32).contiguous();
-    std::memcpy(out16, inv.data_ptr<float>(), 16 * sizeof(float));
-}
 }  // namespace
 
 void Mesher::get_fused_mesh(const std::string& path, const std::vector<torch::Tensor>& depths, const std::vector<torch::Tensor>& c2ws, int H, int W,
                             float fx, float fy, float cx, float cy, float trunc_steps, float min_weight)
 {
-    TORCH_CHECK(depths.size() == c2ws.size(), "Mesher: ", depths.size(), " depth images, ", c2ws.size(), " poses");
+    const Frames frames(depths, c2ws, (size_t)H * W);
     Fusion F(*this, trunc_steps);
-    const size_t img = (size_t)H * W;
-    const int batch = 32, K = (int)depths.size();
-    DevMem dimg((size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
-    std::vector<float> w2c((size_t)batch * 16);
+    const int K = frames.K;
     last_observed = 0;
     if (K == 0) F.integrate(*this, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, true, &last_observed);
-    for (int k0 = 0; k0 < K; k0 += batch) {
-        const int kb = std::min(batch, K - k0);
-        check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
-        for (int k = 0; k < kb; ++k) {
-            torch::Tensor d = depths[(size_t)(k0 + k)].detach().to(torch::kCPU, torch::kFloat32).contiguous();
-            TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k0 + k, " is not H x W");
-            if (hipMemcpy((float*)dimg.p + (size_t)k * img, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-            w2c_of(c2ws[(size_t)(k0 + k)], k0 + k, &w2c[(size_t)k * 16]);
-        }
-        F.integrate(*this, kb, (const float*)dimg.p, H, W, fx, fy, cx, cy, w2c.data(), k0 == 0, k0 + kb >= K ? &last_observed : nullptr);
-    }
+    stream_frames(frames, 32, true, [&](int k0, int kb, const float* d_depth, const float* w2c) {
+        F.integrate(*this, kb, d_depth, H, W, fx, fy, cx, cy, w2c, k0 == 0, k0 + kb >= K ? &last_observed : nullptr);
+    });
     int nv = 0, nt = 0;
     F.mesh(*this, min_weight, nv, nt);
     write_context_mesh(*this, path, false, nv, nt);
@@ -252,24 +272,24 @@ void Mesher::get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dic
     Fusion F(*this, trunc_steps);
     const size_t img = (size_t)H * W;
     const int K = (int)c2ws.size();
-    DevMem guide(img * sizeof(float)), pose(12 * sizeof(float)), rgb(img * 3 * sizeof(float)), depth(img * sizeof(float)), var(img * sizeof(float));
+    DevArr<float> guide(img), pose(12), rgb(img * 3), depth(img), var(img);
     last_observed = 0;
     F.integrate(*this, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, true, K == 0 ? &last_observed : nullptr);        // (cleared)
     float w2c[16];
     for (int k = 0; k < K; ++k) {
-        check(nsk_sync(ctx()));                              // (the previous frame's launches read the buffers about to be overwritten)
+        // (no nsk_sync here: the uploads go through the context's stream, behind the previous frame's launches that read these buffers)
         torch::Tensor m = c2ws[(size_t)k].detach().to(torch::kCPU, torch::kFloat32).contiguous();
         TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
-        if (hipMemcpy(pose.p, m.data_ptr<float>(), 12 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+        pose.upload(m.data_ptr<float>(), 12);
         if (!depths.empty()) {
             torch::Tensor d = depths[(size_t)k].detach().to(torch::kCPU, torch::kFloat32).contiguous();
             TORCH_CHECK((size_t)d.numel() == img, "Mesher: depth image ", k, " is not H x W");
-            if (hipMemcpy(guide.p, d.data_ptr<float>(), img * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
+            guide.upload(d.data_ptr<float>(), img);
         }
-        check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, (const float*)pose.p, 0, 0,
-                               depths.empty() ? nullptr : (const float*)guide.p, -1.f, chunk_rays, (float*)rgb.p, (float*)depth.p, (float*)var.p));
+        check(nsk_render_image(ctx(), nskh::stage_id(stage), 0, H, 0, W, 1, H, W, fx, fy, cx, cy, pose.p(), 0, 0, depths.empty() ? nullptr : guide.p(), -1.f,
+                               chunk_rays, rgb.p(), depth.p(), var.p()));
         w2c_of(c2ws[(size_t)k], k, w2c);
-        F.integrate(*this, 1, (const float*)depth.p, H, W, fx, fy, cx, cy, w2c, false, k + 1 == K ? &last_observed : nullptr);
+        F.integrate(*this, 1, depth.p(), H, W, fx, fy, cx, cy, w2c, false, k + 1 == K ? &last_observed : nullptr);
     }
     int nv = 0, nt = 0;
     F.mesh(*this, min_weight, nv, nt);
@@ -507,25 +527,31 @@ void Mesher::read_ply_mesh(const std::string& path, std::vector<float>& xyz, std
 }
 
 // ---- alignment -------------------------------------------------------------------------------------------------------------------------
-ReconAlign Mesher::align_recon(const float* rec_xyz, int rec_nv, const float* gt_xyz, int gt_nv, float threshold, int max_iter)
+// align_recon on vertices that are on the device already
+static ReconAlign align_device(const float* d_rec, int rec_nv, const float* d_gt, int gt_nv, float threshold = 0.1f, int max_iter = 30)
 {
     if (rec_nv < 1 || gt_nv < 1) throw std::runtime_error("Mesher::align_recon: a mesh without a vertex");
-    DevMem rv((size_t)rec_nv * 3 * sizeof(float)), gv((size_t)gt_nv * 3 * sizeof(float));
-    if (hipMemcpy(rv.p, rec_xyz, (size_t)rec_nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(gv.p, gt_xyz, (size_t)gt_nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        throw std::runtime_error("Mesher: H2D failed");
     ReconAlign A;
     double info[8];
-    check(nsk_cloud_icp(ctx(), (const float*)rv.p, rec_nv, (const float*)gv.p, gt_nv, threshold, max_iter, 1e-6, 1e-6, nullptr, A.transform, info));
+    check(nsk_cloud_icp(ctx(), d_rec, rec_nv, d_gt, gt_nv, threshold, max_iter, 1e-6, 1e-6, nullptr, A.transform, info));
     A.iterations = (int)info[0]; A.fitness = info[1]; A.rmse = info[2]; A.correspondences = (int)info[3];
     A.converged = info[4] != 0.0; A.degenerate = info[7] != 0.0;
     return A;
 }
-// the fields both results share
-template <class R> static void keep_alignment(R& M, const ReconAlign& A)
+ReconAlign Mesher::align_recon(const float* rec_xyz, int rec_nv, const float* gt_xyz, int gt_nv, float threshold, int max_iter)
 {
+    if (rec_nv < 1 || gt_nv < 1) throw std::runtime_error("Mesher::align_recon: a mesh without a vertex");
+    DevArr<float> rv((size_t)rec_nv * 3), gv((size_t)gt_nv * 3);
+    rv.upload(rec_xyz, (size_t)rec_nv * 3); gv.upload(gt_xyz, (size_t)gt_nv * 3);
+    return align_device(rv.p(), rec_nv, gv.p(), gt_nv, threshold, max_iter);
+}
+// the reconstruction registered to the ground truth where it lies, on the device; the fields both results share
+template <class R> static void align_on_device(R& M, DevMesh& rec, const DevMesh& gt)
+{
+    const ReconAlign A = align_device(rec.v.p(), rec.nv, gt.v.p(), gt.nv);
     for (int k = 0; k < 16; ++k) M.transform[k] = A.transform[k];
     M.icp_fitness = A.fitness; M.icp_rmse = A.rmse; M.icp_iterations = A.iterations;
+    check(nsk_cloud_transform(ctx(), M.transform, rec.v.p(), rec.nv, rec.v.p()));
 }
 
 // ---- reconstruction metrics ----------------------------------------------------------------------------------------------------------
@@ -534,32 +560,25 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
 {
     if (n < 1) throw std::runtime_error("Mesher::eval_recon: n_points must be at least 1");
     if (rec_nt < 1 || gt_nt < 1) throw std::runtime_error("Mesher::eval_recon: a mesh without a triangle");
-    auto up = [](DevMem& d, const void* h, size_t bytes) {
-        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-    };
     ReconMetrics M;
-    if (align) keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
-    DevMem rec_pts((size_t)n * 3 * sizeof(float)), gt_pts((size_t)n * 3 * sizeof(float)), dist((size_t)n * sizeof(float));
+    DevArr<float> rec_pts((size_t)n * 3), gt_pts((size_t)n * 3), dist((size_t)n);
     const double nan = std::nan("");
     double a[4], c[4];
     if (surface) {      // both meshes stay on the device: every sample is measured against the other mesh's triangles
-        DevMem rv((size_t)rec_nv * 3 * sizeof(float)), rt((size_t)rec_nt * 3 * sizeof(int32_t));
-        DevMem gv((size_t)gt_nv * 3 * sizeof(float)), gt((size_t)gt_nt * 3 * sizeof(int32_t));
-        DevMem own((size_t)n * sizeof(int32_t)), gt_own((size_t)n * sizeof(int32_t)), hit((size_t)n * sizeof(int32_t));
-        up(rv, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(rt, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
-        up(gv, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(gt, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
-        const float *RV = (const float*)rv.p, *GV = (const float*)gv.p;
-        const int32_t *RT = (const int32_t*)rt.p, *GT = (const int32_t*)gt.p;
-        if (align) check(nsk_cloud_transform(ctx(), M.transform, RV, rec_nv, (float*)rv.p));
-        check(nsk_mesh_sample(ctx(), RV, rec_nv, RT, rec_nt, seed, n, (float*)rec_pts.p, (int32_t*)own.p, &M.rec_area, &M.rec_degenerate));
-        check(nsk_mesh_sample(ctx(), GV, gt_nv, GT, gt_nt, seed + 1, n, (float*)gt_pts.p, (int32_t*)gt_own.p, &M.gt_area, &M.gt_degenerate));
+        DevMesh rec(rec_xyz, rec_nv, rec_tris, rec_nt), gt(gt_xyz, gt_nv, gt_tris, gt_nt);
+        DevArr<int32_t> own((size_t)n), gt_own((size_t)n), hit((size_t)n);
+        if (align) align_on_device(M, rec, gt);
+        const float *RV = rec.v.p(), *GV = gt.v.p();
+        const int32_t *RT = rec.t.p(), *GT = gt.t.p();
+        check(nsk_mesh_sample(ctx(), RV, rec_nv, RT, rec_nt, seed, n, rec_pts.p(), own.p(), &M.rec_area, &M.rec_degenerate));
+        check(nsk_mesh_sample(ctx(), GV, gt_nv, GT, gt_nt, seed + 1, n, gt_pts.p(), gt_own.p(), &M.gt_area, &M.gt_degenerate));
         double na[3], nc[3];
-        check(nsk_mesh_nearest(ctx(), (const float*)rec_pts.p, n, GV, gt_nv, GT, gt_nt, (float*)dist.p, (int32_t*)hit.p, nullptr, &M.gt_skipped));
-        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
-        check(nsk_normal_stats(ctx(), n, RV, rec_nv, RT, rec_nt, (const int32_t*)own.p, GV, gt_nv, GT, gt_nt, (const int32_t*)hit.p, na));
-        check(nsk_mesh_nearest(ctx(), (const float*)gt_pts.p, n, RV, rec_nv, RT, rec_nt, (float*)dist.p, (int32_t*)hit.p, nullptr, &M.rec_skipped));
-        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
-        check(nsk_normal_stats(ctx(), n, GV, gt_nv, GT, gt_nt, (const int32_t*)gt_own.p, RV, rec_nv, RT, rec_nt, (const int32_t*)hit.p, nc));
+        check(nsk_mesh_nearest(ctx(), rec_pts.p(), n, GV, gt_nv, GT, gt_nt, dist.p(), hit.p(), nullptr, &M.gt_skipped));
+        check(nsk_cloud_stats(ctx(), dist.p(), n, threshold, a));
+        check(nsk_normal_stats(ctx(), n, RV, rec_nv, RT, rec_nt, own.p(), GV, gt_nv, GT, gt_nt, hit.p(), na));
+        check(nsk_mesh_nearest(ctx(), gt_pts.p(), n, RV, rec_nv, RT, rec_nt, dist.p(), hit.p(), nullptr, &M.rec_skipped));
+        check(nsk_cloud_stats(ctx(), dist.p(), n, threshold, c));
+        check(nsk_normal_stats(ctx(), n, GV, gt_nv, GT, gt_nt, gt_own.p(), RV, rec_nv, RT, rec_nt, hit.p(), nc));
         check(nsk_sync(ctx()));
         M.surface = true;
         M.precision_pct = a[1] > 0 ? 100.0 * a[2] / a[1] : nan;
@@ -572,22 +591,16 @@ ReconMetrics Mesher::eval_recon(const float* rec_xyz, int rec_nv, const int32_t*
         M.normal_skipped = (int)(na[2] + nc[2]);
     } else {
         {   // the meshes leave the device again as soon as their samples are drawn
-            DevMem v((size_t)rec_nv * 3 * sizeof(float)), t((size_t)rec_nt * 3 * sizeof(int32_t));
-            up(v, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(t, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
-            if (align) check(nsk_cloud_transform(ctx(), M.transform, (const float*)v.p, rec_nv, (float*)v.p));
-            check(nsk_mesh_sample(ctx(), (const float*)v.p, rec_nv, (const int32_t*)t.p, rec_nt, seed, n, (float*)rec_pts.p, nullptr, &M.rec_area, &M.rec_degenerate));
+            DevMesh rec(rec_xyz, rec_nv, rec_tris, rec_nt), gt(gt_xyz, gt_nv, gt_tris, gt_nt);
+            if (align) align_on_device(M, rec, gt);
+            check(nsk_mesh_sample(ctx(), rec.v.p(), rec_nv, rec.t.p(), rec_nt, seed, n, rec_pts.p(), nullptr, &M.rec_area, &M.rec_degenerate));
+            check(nsk_mesh_sample(ctx(), gt.v.p(), gt_nv, gt.t.p(), gt_nt, seed + 1, n, gt_pts.p(), nullptr, &M.gt_area, &M.gt_degenerate));
             check(nsk_sync(ctx()));
         }
-        {
-            DevMem v((size_t)gt_nv * 3 * sizeof(float)), t((size_t)gt_nt * 3 * sizeof(int32_t));
-            up(v, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(t, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
-            check(nsk_mesh_sample(ctx(), (const float*)v.p, gt_nv, (const int32_t*)t.p, gt_nt, seed + 1, n, (float*)gt_pts.p, nullptr, &M.gt_area, &M.gt_degenerate));
-            check(nsk_sync(ctx()));
-        }
-        check(nsk_cloud_nearest(ctx(), (const float*)rec_pts.p, n, (const float*)gt_pts.p, n, (float*)dist.p, nullptr, &M.gt_skipped));
-        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, a));
-        check(nsk_cloud_nearest(ctx(), (const float*)gt_pts.p, n, (const float*)rec_pts.p, n, (float*)dist.p, nullptr, &M.rec_skipped));
-        check(nsk_cloud_stats(ctx(), (const float*)dist.p, n, threshold, c));
+        check(nsk_cloud_nearest(ctx(), rec_pts.p(), n, gt_pts.p(), n, dist.p(), nullptr, &M.gt_skipped));
+        check(nsk_cloud_stats(ctx(), dist.p(), n, threshold, a));
+        check(nsk_cloud_nearest(ctx(), gt_pts.p(), n, rec_pts.p(), n, dist.p(), nullptr, &M.rec_skipped));
+        check(nsk_cloud_stats(ctx(), dist.p(), n, threshold, c));
     }
     M.accuracy_cm = a[1] > 0 ? 100.0 * a[0] / a[1] : nan;
     M.completion_cm = c[1] > 0 ? 100.0 * c[0] / c[1] : nan;
@@ -617,35 +630,26 @@ ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int3
     if (n_views < 1) throw std::runtime_error("Mesher::eval_recon_depth: n_views must be at least 1");
     if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::eval_recon_depth: the image must have 1 .. 2^24 pixels");
     if (gt_nv < 1) throw std::runtime_error("Mesher::eval_recon_depth: the ground truth has no vertex");
-    auto up = [](DevMem& d, const void* h, size_t bytes) {
-        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-    };
     const size_t n_pix = (size_t)H * W;
-    DevMem rv((size_t)rec_nv * 3 * sizeof(float)), rt((size_t)rec_nt * 3 * sizeof(int32_t));
-    DevMem gv((size_t)gt_nv * 3 * sizeof(float)), gtt((size_t)gt_nt * 3 * sizeof(int32_t));
-    up(rv, rec_xyz, (size_t)rec_nv * 3 * sizeof(float)); up(rt, rec_tris, (size_t)rec_nt * 3 * sizeof(int32_t));
-    up(gv, gt_xyz, (size_t)gt_nv * 3 * sizeof(float)); up(gtt, gt_tris, (size_t)gt_nt * 3 * sizeof(int32_t));
+    DevMesh rec(rec_xyz, rec_nv, rec_tris, rec_nt), gt(gt_xyz, gt_nv, gt_tris, gt_nt);
     ReconDepth M;
-    if (align) {
-        keep_alignment(M, align_recon(rec_xyz, rec_nv, gt_xyz, gt_nv));
-        check(nsk_cloud_transform(ctx(), M.transform, (const float*)rv.p, rec_nv, (float*)rv.p));
-    }
+    if (align) align_on_device(M, rec, gt);
     const float cx = (float)(W / 2.0 - 0.5), cy = (float)(H / 2.0 - 0.5);
     float box[6];
     if (unseen_xyz && n_unseen > 0) {
         // upstream's redraw: the first n_views candidates of the stream without an unseen point in their image, counted in rounds
         const int round = 32, cap_factor = 16;
         const long long cap = (long long)cap_factor * n_views;
-        DevMem up_((size_t)n_unseen * 3 * sizeof(float));
-        up(up_, unseen_xyz, (size_t)n_unseen * 3 * sizeof(float));
-        check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, 0, nullptr));        // (the box)
+        DevArr<float> unseen((size_t)n_unseen * 3);
+        unseen.upload(unseen_xyz, (size_t)n_unseen * 3);
+        check(nsk_depth_views(ctx(), gt.v.p(), gt_nv, box, seed, shrink, 0, nullptr));        // (the box)
         std::vector<float> w((size_t)round * 16);
         std::vector<long long> cnt((size_t)round);
         long long first = 0;
         while ((int)M.view_index.size() < n_views && first < cap) {
             const int m = (int)std::min<long long>(round, cap - first);
             check(nsk_depth_views_range(box, seed, shrink, first, m, w.data()));
-            check(nsk_points_view_counts(ctx(), (const float*)up_.p, n_unseen, m, w.data(), H, W, focal, focal, cx, cy, 0, cnt.data()));
+            check(nsk_points_view_counts(ctx(), unseen.p(), n_unseen, m, w.data(), H, W, focal, focal, cx, cy, 0, cnt.data()));
             for (int k = 0; k < m && (int)M.view_index.size() < n_views; ++k) {
                 if (cnt[(size_t)k] != 0) continue;
                 M.view_index.push_back(first + k);
@@ -657,22 +661,20 @@ ReconDepth Mesher::eval_recon_depth(const float* rec_xyz, int rec_nv, const int3
         n_views = (int)M.view_index.size();
     } else {
         M.w2c.assign((size_t)n_views * 16, 0.f);
-        check(nsk_depth_views(ctx(), (const float*)gv.p, gt_nv, box, seed, shrink, n_views, M.w2c.data()));
+        check(nsk_depth_views(ctx(), gt.v.p(), gt_nv, box, seed, shrink, n_views, M.w2c.data()));
     }
     M.n_views = n_views;
     M.stats.assign((size_t)n_views * 4, 0.0);
     int batch = (int)std::max<size_t>(1, ((size_t)1 << 27) / n_pix);          // both stacks together stay below about 1 GB
     if (batch > 32) batch -= batch % 32;
     batch = std::max(1, std::min(batch, n_views));
-    DevMem dg((size_t)batch * n_pix * sizeof(float)), dr((size_t)batch * n_pix * sizeof(float));
+    DevArr<float> dg((size_t)batch * n_pix), dr((size_t)batch * n_pix);
     for (int k0 = 0; k0 < n_views; k0 += batch) {
         const int V = std::min(batch, n_views - k0);
         const float* w = M.w2c.data() + 16 * (size_t)k0;
-        check(nsk_mesh_depth(ctx(), (const float*)gv.p, gt_nv, (const int32_t*)gtt.p, gt_nt, V, w, H, W, focal, focal, cx, cy, (float*)dg.p,
-                             k0 == 0 ? &M.gt_skipped : nullptr));
-        check(nsk_mesh_depth(ctx(), (const float*)rv.p, rec_nv, (const int32_t*)rt.p, rec_nt, V, w, H, W, focal, focal, cx, cy, (float*)dr.p,
-                             k0 == 0 ? &M.rec_skipped : nullptr));
-        check(nsk_depth_pair_stats(ctx(), (const float*)dg.p, (const float*)dr.p, V, (int)n_pix, M.stats.data() + 4 * (size_t)k0));
+        check(nsk_mesh_depth(ctx(), gt.v.p(), gt_nv, gt.t.p(), gt_nt, V, w, H, W, focal, focal, cx, cy, dg.p(), k0 == 0 ? &M.gt_skipped : nullptr));
+        check(nsk_mesh_depth(ctx(), rec.v.p(), rec_nv, rec.t.p(), rec_nt, V, w, H, W, focal, focal, cx, cy, dr.p(), k0 == 0 ? &M.rec_skipped : nullptr));
+        check(nsk_depth_pair_stats(ctx(), dg.p(), dr.p(), V, (int)n_pix, M.stats.data() + 4 * (size_t)k0));
     }
     M.view_l1.resize((size_t)n_views); M.view_cover.resize((size_t)n_views);
     double l1 = 0.0, both = 0.0, both_sum = 0.0;
@@ -708,38 +710,24 @@ CulledMesh Mesher::cull_mesh(const float* xyz, int nv, const int32_t* tris, int 
     if (nv < 0 || nt < 0 || K < 0) throw std::runtime_error("Mesher::cull_mesh: negative count");
     if (H < 1 || W < 1 || (long long)H * W > (1LL << 24)) throw std::runtime_error("Mesher::cull_mesh: the image must have 1 .. 2^24 pixels");
     if (mode == 1 && K > 0 && !depths) throw std::runtime_error("Mesher::cull_mesh: occlusion depth needs the depth images");
-    auto up = [](DevMem& d, const void* h, size_t bytes) {
-        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-    };
-    auto down = [](void* h, const DevMem& d, size_t bytes) {
-        if (bytes && hipMemcpy(h, d.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
-    };
-    const size_t img = (size_t)H * W, vb = (size_t)nv * 3 * sizeof(float), tb = (size_t)nt * 3 * sizeof(int32_t);
-    const int batch = std::max(1, frames_per_batch);
-    DevMem v(vb), t(tb), seen((size_t)nv), ov(vb), ot(tb), src((size_t)nv * sizeof(int32_t));
-    DevMem dimg(mode == 0 ? 0 : (size_t)std::min(std::max(K, 1), batch) * img * sizeof(float));
-    up(v, xyz, vb); up(t, tris, tb);
+    const DevMesh in(xyz, nv, tris, nt);
+    DevArr<uint8_t> seen((size_t)nv);
+    DevArr<float> ov((size_t)nv * 3);
+    DevArr<int32_t> ot((size_t)nt * 3), src((size_t)nv);
     CulledMesh R;
-    check(nsk_points_seen(ctx(), (const float*)v.p, nv, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, edge, eps, 0, 0, (uint8_t*)seen.p, nullptr));     // (cleared)
-    for (int k0 = 0; k0 < K; k0 += batch) {
-        const int kb = std::min(batch, K - k0);
-        const float* w = w2c + 16 * (size_t)k0;
-        if (mode == 1) {
-            check(nsk_sync(ctx()));                              // (the previous batch's launch reads the images about to be overwritten)
-            up(dimg, depths + (size_t)k0 * img, (size_t)kb * img * sizeof(float));
-        } else if (mode == 2) {
-            check(nsk_mesh_depth(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, kb, w, H, W, fx, fy, cx, cy, (float*)dimg.p, nullptr));
-        }
-        check(nsk_points_seen(ctx(), (const float*)v.p, nv, kb, mode == 0 ? nullptr : (const float*)dimg.p, H, W, fx, fy, cx, cy, w, edge, eps,
-                              mode == 2 ? 1 : 0, 1, (uint8_t*)seen.p, k0 + kb >= K ? &R.n_seen : nullptr));
-    }
+    check(nsk_points_seen(ctx(), in.v.p(), nv, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, edge, eps, 0, 0, seen.p(), nullptr));     // (cleared)
+    // depth: the sensor's images are streamed;  self: every batch's images are rendered from the mesh into the streamer's buffer;  none: no images
+    const Frames frames(mode == 1 ? depths : nullptr, w2c, K, (size_t)H * W);
+    stream_frames(frames, std::max(1, frames_per_batch), mode != 0, [&](int k0, int kb, float* d_depth, const float* w) {
+        if (mode == 2) check(nsk_mesh_depth(ctx(), in.v.p(), nv, in.t.p(), nt, kb, w, H, W, fx, fy, cx, cy, d_depth, nullptr));
+        check(nsk_points_seen(ctx(), in.v.p(), nv, kb, mode == 0 ? nullptr : d_depth, H, W, fx, fy, cx, cy, w, edge, eps, mode == 2 ? 1 : 0, 1, seen.p(),
+                              k0 + kb >= K ? &R.n_seen : nullptr));
+    });
     int onv = 0, ont = 0;
-    check(nsk_mesh_select(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, (const uint8_t*)seen.p, 0, (float*)ov.p, (int32_t*)ot.p,
-                          (int32_t*)src.p, &onv, &ont, &R.skipped));
+    check(nsk_mesh_select(ctx(), in.v.p(), nv, in.t.p(), nt, seen.p(), 0, ov.p(), ot.p(), src.p(), &onv, &ont, &R.skipped));
     R.xyz.resize((size_t)onv * 3); R.triangles.resize((size_t)ont * 3); R.vertex_src.resize((size_t)onv); R.seen.resize((size_t)nv);
-    check(nsk_sync(ctx()));
-    down(R.xyz.data(), ov, R.xyz.size() * sizeof(float)); down(R.triangles.data(), ot, R.triangles.size() * sizeof(int32_t));
-    down(R.vertex_src.data(), src, R.vertex_src.size() * sizeof(int32_t)); down(R.seen.data(), seen, R.seen.size());
+    ov.download(R.xyz.data(), R.xyz.size()); ot.download(R.triangles.data(), R.triangles.size());
+    src.download(R.vertex_src.data(), R.vertex_src.size()); seen.download(R.seen.data(), R.seen.size());
     return R;
 }
 
@@ -759,21 +747,18 @@ std::vector<float> Mesher::unseen_points(const float* xyz, int nv, const int32_t
 {
     std::vector<float> out;
     if (n < 1 || nt < 1 || nv < 1) return out;
-    auto up = [](DevMem& d, const void* h, size_t bytes) {
-        if (bytes && hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("Mesher: H2D failed");
-    };
-    const size_t vb = (size_t)nv * 3 * sizeof(float), tb = (size_t)nt * 3 * sizeof(int32_t);
-    DevMem v(vb), t(tb), s((size_t)nv), ov(vb), ot(tb), pts((size_t)n * 3 * sizeof(float));
-    up(v, xyz, vb); up(t, tris, tb); up(s, seen, (size_t)nv);
+    const DevMesh in(xyz, nv, tris, nt);
+    DevArr<uint8_t> s((size_t)nv);
+    DevArr<float> ov((size_t)nv * 3), pts((size_t)n * 3);
+    DevArr<int32_t> ot((size_t)nt * 3);
+    s.upload(seen, (size_t)nv);
     int onv = 0, ont = 0;
-    check(nsk_mesh_select(ctx(), (const float*)v.p, nv, (const int32_t*)t.p, nt, (const uint8_t*)s.p, 1, (float*)ov.p, (int32_t*)ot.p, nullptr, &onv,
-                          &ont, nullptr));
+    check(nsk_mesh_select(ctx(), in.v.p(), nv, in.t.p(), nt, s.p(), 1, ov.p(), ot.p(), nullptr, &onv, &ont, nullptr));
     if (ont == 0) return out;
     double area = 0.0;
     int degenerate = 0;
-    check(nsk_mesh_sample(ctx(), (const float*)ov.p, onv, (const int32_t*)ot.p, ont, seed, n, (float*)pts.p, nullptr, &area, &degenerate));
-    check(nsk_sync(ctx()));
+    check(nsk_mesh_sample(ctx(), ov.p(), onv, ot.p(), ont, seed, n, pts.p(), nullptr, &area, &degenerate));
     out.resize((size_t)n * 3);
-    if (hipMemcpy(out.data(), pts.p, out.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("Mesher: D2H failed");
+    pts.download(out.data(), out.size());
     return out;
 }

@@ -19,7 +19,7 @@
 
 #include "Mapper.h"
 #include "Tracker.h"
-#include "nsk_host.h"
+#include "nsk_devarr.h"
 #include "torchlib/utils.h"
 
 static void save_npy(const std::string& path, torch::Tensor t)
@@ -160,13 +160,10 @@ int main(int argc, char** argv)
                 cam7.index_put_({Slice(None, 7)}, tr.last_camera_tensor);
             }
             if (dist.on()) {
-                float* d_pose = nullptr;
-                if (hipMalloc((void**)&d_pose, 8 * sizeof(float)) != hipSuccess) throw std::runtime_error("hipMalloc failed");
-                if (hipMemcpy(d_pose, cam7.data_ptr<float>(), 8 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("H2D failed");
-                dist.broadcast0(d_pose, 8);
-                nskh::check(nsk_sync(nskh::ctx()));
-                if (hipMemcpy(cam7.data_ptr<float>(), d_pose, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("D2H failed");
-                (void)hipFree(d_pose);
+                nskh::DevArr<float> d_pose;
+                d_pose.upload(cam7.data_ptr<float>(), 8);
+                dist.broadcast0(d_pose.p(), 8);
+                d_pose.download(cam7.data_ptr<float>(), 8);
             }
             save_npy(out + "tracked.npy", cam7);
         }

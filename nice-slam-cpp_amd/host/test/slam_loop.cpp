@@ -15,15 +15,13 @@
 #include <cstdlib>
 #include <fstream>
 
-#include <hip/hip_runtime_api.h>
-
 #include <sstream>
 
 #include "FramePrep.h"
 #include "Mapper.h"
 #include "Mesher.h"
 #include "Tracker.h"
-#include "nsk_host.h"
+#include "nsk_devarr.h"
 #include "torchlib/utils.h"
 
 static void save_npy(const std::string& path, torch::Tensor t)
@@ -95,8 +93,7 @@ int main(int argc, char** argv)
                 mapper.set_distributed(dist);
             }
         }
-        float* d_pose = nullptr;                                              // 8 floats on the device for the pose broadcast
-        if (dist.on() && hipMalloc((void**)&d_pose, 8 * sizeof(float)) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 1; }
+        nskh::DevArr<float> d_pose;                                           // 8 floats on the device for the pose broadcast
         const int F = max_frames > 0 ? std::min(max_frames, reader.n_imgs) : reader.n_imgs;
         std::vector<torch::Tensor> est(F), gts(F);
         std::vector<float> tl, ml;
@@ -121,10 +118,9 @@ int main(int argc, char** argv)
                     cam7.index_put_({Slice(None, 7)}, tracker.last_camera_tensor);
                 }
                 if (dist.on()) {                                              // rank 0's pose to every rank
-                    if (hipMemcpy(d_pose, cam7.data_ptr<float>(), 8 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("H2D failed");
-                    dist.broadcast0(d_pose, 8);
-                    nskh::check(nsk_sync(nskh::ctx()));
-                    if (hipMemcpy(cam7.data_ptr<float>(), d_pose, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("D2H failed");
+                    d_pose.upload(cam7.data_ptr<float>(), 8);
+                    dist.broadcast0(d_pose.p(), 8);
+                    d_pose.download(cam7.data_ptr<float>(), 8);
                 }
                 torch::Tensor RT = get_camera_from_tensor(cam7.index({Slice(None, 7)}).contiguous());
                 est[i] = torch::cat({RT, torch::tensor({{0.f, 0.f, 0.f, 1.f}})}, 0);

@@ -215,6 +215,19 @@ def view_scene(K, shape=(11, 7, 5)):
                 depths=images[ks % len(images)].reshape(K, IMG_H, IMG_W), pts=mc.lattice_points(origin, step, nx, ny, nz))
 
 
+def long_trajectory(sc, order, shift=(0.01, -0.005, 0.0075)):
+    """a trajectory longer than a scene's own: frame k is keyframe order[k] of `sc` (cull_scene) with its camera moved by k * shift (m, world)
+    and its depth image scaled by 1 + k / 256 (zeros, NaN and inf stay what they are), so that no two frames are alike.
+    -> dict(c2w [K, 4, 4] float64 holding float32 values, w2c [K, 4, 4] float32, depths [K, H, W] float32)"""
+    order = list(order)
+    k = np.arange(len(order))
+    c2w = sc["c2w"][order].copy()
+    c2w[:, :3, 3] += k[:, None] * np.asarray(shift, np.float64)
+    c2w = c2w.astype(F).astype(np.float64)
+    depths = (sc["depths"][order] * (F(1) + k.astype(F) / F(256))[:, None, None]).astype(F)
+    return dict(c2w=c2w, w2c=np.stack([w2c_of(m) for m in c2w]), depths=depths)
+
+
 MESHER_N, MESHER_PAD = 40, 0.1
 
 

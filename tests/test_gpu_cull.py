@@ -368,3 +368,34 @@ def test_host_program_culls_the_room_as_python_does(ctx, tmp_path):
     tol = 2e-6
     assert (np.abs(u[:, 0] - cc.ROOM_HI[0]) <= tol).all() and (np.abs(u[:, 1]) <= 1.0 + tol).all() and (np.abs(u[:, 2]) <= 2.0 + tol).all(), "an unseen point off the wall x = hi"
     assert u.tobytes() == ctx.unseen_points(cu(verts), cui(tris), py["seen"], 300, 0).cpu().numpy().tobytes()
+
+
+def test_host_program_streams_more_frames_than_a_batch(ctx, tmp_path):
+    """33 frames of 24 x 32 pixels cross the 32-frame batch of Mesher::cull_mesh with the sensor's depth images: the room's first two poses
+    32 times, each moved along y by its own multiple of 1 / 64 (exact, like the inversion of these poses), and, alone in the second batch,
+    the third pose.  Each batch sees vertices the other does not (a condition of the input); the PLY and the counts are those of the
+    Python path, whose result does not depend on its own batch (test_cull_mesh_equals_the_restatement)."""
+    exe = os.path.join(HOST, "cull_mesh_test")
+    assert os.path.exists(exe), "build() makes host/cull_mesh_test"
+    verts, tris, wall, twall = cc.room_with_panel()
+    c2w = cc.panel_trajectory()[[0, 1] * 16 + [2]].astype(np.float64)
+    c2w[:, 1, 3] += (np.arange(33) - 16) / 64.0
+    c2w = c2w.astype(F)
+    w2c = np.stack([mcc.w2c_of(m) for m in c2w])
+    sensor = ctx.mesh_depth(cu(verts), cui(tris[twall != 1]), w2c, H, W, *INTR)
+    cull = lambda sl: ctx.cull_mesh(cu(verts), cui(tris), w2c[sl], INTR, (H, W), sensor[sl], "depth", 0, cc.E2E_EPS)
+    py = cull(slice(None))
+    n_first, n_last = cull(slice(0, 32))["n_seen"], cull(slice(32, 33))["n_seen"]
+    print("33 frames: %d vertices seen, %d by the first batch alone, %d by the second alone" % (py["n_seen"], n_first, n_last))
+    assert len(w2c) == 33 and 0 < n_first < py["n_seen"] and 0 < n_last < py["n_seen"]
+    d = str(tmp_path)
+    np.save(os.path.join(d, "c2ws.npy"), c2w); np.save(os.path.join(d, "intr.npy"), np.array(INTR, F))
+    np.save(os.path.join(d, "depths.npy"), sensor.cpu().numpy())
+    _write_ply(os.path.join(d, "in.ply"), verts, tris)
+    out = subprocess.run([exe, d, os.path.join(d, "in.ply"), os.path.join(d, "out.ply"), "depth", "0", repr(cc.E2E_EPS)], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    js = json.loads(out.stdout.strip().splitlines()[-1])
+    pv, pt = _read_ply(os.path.join(d, "out.ply"))
+    assert len(pt) > 0 and pv.tobytes() == py["verts"].cpu().numpy().tobytes() and pt.tobytes() == py["tris"].cpu().numpy().tobytes()
+    assert js["frames"] == 33 and js["vertices"] == len(pv) and js["triangles"] == len(pt) and js["n_seen"] == py["n_seen"] and js["skipped"] == 0

@@ -264,3 +264,43 @@ def test_clean_mesh_cpp_equals_the_python_path(tmp_path):
             assert (pc == np.floor(x.astype(np.float64) + 0.5).astype(np.uint8)).all()
         else:
             assert pc is None
+
+
+def test_clean_mesh_cpp_streams_more_keyframes_than_a_batch(tmp_path):
+    """17 keyframes cross the 16-frame batch of Mesher::get_clean_mesh on a 24^3 lattice: sixteen views from outside, no two alike, and,
+    alone in the second batch, the view from inside.  Each batch sees nodes the other does not (a condition of the input), and the PLY
+    and the counts are those of the Python path, whose result does not depend on its own batch (test_accumulate_batches_and_clear)."""
+    exe = os.path.join(HOST, "clean_mesh_test")
+    if not os.path.exists(exe):
+        pytest.fail("clean_mesh_test is not built (run __graft_entry__.build())")
+    sc = scenes.make_scene(1, scenes.SMALL_GRID_SHAPES, grid_std=0.3, bias_std=0.1)
+    ctx = make_ctx(sc)
+    n, pad = 24, np.float32(0.1)
+    ks = cc.cull_scene(sc["bound"], (n,) * 3, float(pad), keyframes=(0, 1), params=((0, 0.5),))
+    tr = cc.long_trajectory(ks, [0] * 16 + [1])
+    b = sc["bound"]
+    lo, hi = (b[:, 0] - pad).astype(np.float32), (b[:, 1] + pad).astype(np.float32)
+    origin, step = lo, ((hi - lo) / np.float32(n - 1)).astype(np.float32)          # the Mesher's own expressions
+    seen_of = lambda sl: ctx.lattice_seen(origin, step, n, n, n, cu(tr["depths"][sl]), ks["intr"], tr["w2c"][sl], 0, 0.5)
+    valid, n_seen = seen_of(slice(None))
+    n_first, n_last = seen_of(slice(0, 16))[1], seen_of(slice(16, 17))[1]
+    print("17 keyframes: %d nodes seen, %d by the first batch alone, %d by the second alone" % (n_seen, n_first, n_last))
+    assert len(tr["w2c"]) == 17 and 0 < n_first < n_seen and 0 < n_last < n_seen
+    vol = ctx.eval_lattice("fine", origin, step, n, n, n)
+    ctx.extract_mesh(vol, origin, step, 0.0, valid)
+    v, t, nc, nk = ctx.filter_mesh(0.0, False)
+    d = str(tmp_path)
+    np.save(os.path.join(d, "bound.npy"), sc["bound"].astype(np.float32))
+    for k in scenes.LEVELS:
+        np.save(os.path.join(d, "grid_%s.npy" % k), sc["grids"][k][None].astype(np.float32))
+        np.save(os.path.join(d, "dec_%s.npy" % k), sc["decoders"][k].astype(np.float32))
+    np.save(os.path.join(d, "depths.npy"), tr["depths"])
+    np.save(os.path.join(d, "c2ws.npy"), tr["c2w"].astype(np.float32))
+    np.save(os.path.join(d, "intr.npy"), np.array(ks["intr"], np.float32))
+    r = subprocess.run([exe, d, str(n), "0", "0.1", "0.0", "0"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "clean_mesh_test ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    m = re.search(r"ok: (\d+) vertices, (\d+) triangles, (\d+) components, (\d+) kept, (\d+) seen", r.stdout)
+    assert [int(x) for x in m.groups()] == [len(v), len(t), nc, nk, n_seen], (r.stdout, len(v), len(t), nc, nk, n_seen)
+    pv, pc, pf = mc.read_ply(os.path.join(d, "clean_mesh.ply"))
+    assert len(v) > 0 and pc is None
+    assert pv.tobytes() == v.cpu().numpy().tobytes() and pf.tobytes() == t.cpu().numpy().tobytes()

@@ -305,3 +305,33 @@ def test_fuse_mesh_cpp_equals_the_python_path(ctx, sphere, tmp_path):
     assert out["mode"] == "depth" and out["frames"] == 8 and out["resolution"] == sc["nx"]
     assert out["n_observed"] == info["n_observed"] and out["n_valid"] == info["n_valid"]
     assert out["vertices"] == len(v) and out["triangles"] == len(t)
+
+
+def test_fuse_mesh_cpp_streams_more_frames_than_a_batch(ctx, tmp_path):
+    """33 frames cross the 32-frame batch of Mesher::get_fused_mesh on a 24^3 lattice: 32 views from outside, no two alike (the running mean
+    depends on their order), and, alone in the second batch, the view from inside.  Each batch observes nodes the other does not (a
+    condition of the input); the PLY and the counts are those of the Python path, whose result does not depend on its own batch
+    (test_fused_sphere_mesh)."""
+    exe = os.path.join(HOST, "fuse_mesh_test")
+    if not os.path.exists(exe):
+        pytest.fail("fuse_mesh_test is not built (run __graft_entry__.build())")
+    n, HW = 24, (cc.IMG_H, cc.IMG_W)
+    sc = cc.cull_scene(scenes.REF_BOUND, (n,) * 3, 0.0, keyframes=(0, 1))         # (no padding: the lattice of a Mesher with padding 0)
+    tr = cc.long_trajectory(sc, [0] * 32 + [1])
+    fuse = lambda sl: ctx.fuse_depth_mesh(sc["origin"], sc["step"], n, tr["depths"][sl], tr["w2c"][sl], sc["intr"], HW)
+    v, t, info = fuse(slice(None))
+    n_first, n_last = fuse(slice(0, 32))[2]["n_observed"], fuse(slice(32, 33))[2]["n_observed"]
+    print("33 frames: %s; %d nodes observed by the first batch alone, %d by the second alone" % (info, n_first, n_last))
+    assert len(tr["w2c"]) == 33 and 0 < n_first < info["n_observed"] and 0 < n_last < info["n_observed"]
+    d = str(tmp_path)
+    np.save(os.path.join(d, "bound.npy"), np.asarray(scenes.REF_BOUND, F))
+    save_frames(d, tr | {"intr": sc["intr"]})
+    r = subprocess.run([exe, d, os.path.join(d, "fused.ply"), str(n), "3", "1"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    pv, pc, pf = mc.read_ply(os.path.join(d, "fused.ply"))
+    assert pc is None and len(v) > 0
+    assert pv.tobytes() == v.cpu().numpy().tobytes() and pf.tobytes() == t.cpu().numpy().tobytes()
+    assert out["mode"] == "depth" and out["frames"] == 33 and out["resolution"] == n
+    assert out["n_observed"] == info["n_observed"] and out["n_valid"] == info["n_valid"]
+    assert out["vertices"] == len(v) and out["triangles"] == len(t)
