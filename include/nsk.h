@@ -140,6 +140,50 @@ int nsk_set_bound(nsk_ctx* ctx, const float h_bound[6]);
 int nsk_set_render_opts(nsk_ctx* ctx, int n_samples, int n_surface, int lindisp, float perturb, int occupancy,
                         uint64_t seed);
 
+/* ---- hierarchical importance sampling: rendering.N_importance (upstream NICE-SLAM's sample_pdf) ----------
+ * n_importance > 0 makes every renderer of the context (nsk_render_forward, nsk_render_backward, nsk_map_step, nsk_track_step,
+ * nsk_render_image, nsk_mesh_vertex_colors) run two passes: a first pass over the stratified and surface samples, then n_importance extra
+ * depths drawn from the compositing weights of that pass, then a second pass over the merged set, which is what the call returns: its
+ * samples per ray are S2 = n_samples (+ n_surface with a depth) + n_importance, d_weights is [N][S2].  Default 0: one pass, as before.
+ *
+ * The rule (upstream's sample_pdf, fixed operation by operation).  The first pass has S1 = n_samples (+ n_surface with a depth) sorted
+ * depths z[0..S1) and compositing weights w[0..S1), the weights nsk_render_forward returns.  With Ni = n_importance > 0, per ray, every
+ * operation is an fp32 operation of its own (rounded add, multiply, subtract, divide; no contraction):
+ *    1. bins[k] = 0.5 * (z[k+1] + z[k]), k = 0..S1-2 (S1-1 bins).
+ *    2. q[k] = w[k+1] + 1e-5f, k = 0..S1-3 (the interior weights w[1..S1-1)).
+ *    3. total = the sum of q taken left to right.
+ *    4. pdf[k] = q[k] / total.
+ *    5. cdf[0] = 0, cdf[k+1] = cdf[k] + pdf[k], left to right (S1-1 entries).
+ *    6. u[j], j = 0..Ni-1: with perturb == 0 (deterministic) u[j] is the t of at::linspace(0, 1, Ni) at j, the helper the first-pass
+ *       samples use (step = 1 / (Ni-1); j < Ni/2: step * j, else 1 - step * (Ni-1-j); Ni = 1: 0).  Otherwise
+ *       u[j] = (hash(seed, ray, 64 + j) >> 8) * 2^-24, the counter hash of the perturbation; the offset 64 keeps the stream apart from
+ *       the perturbation's lanes.
+ *    7. inds = the number of cdf entries <= u[j] (searchsorted, right = true; a NaN compares false).
+ *    8. below = max(inds - 1, 0), above = min(inds, S1 - 2).
+ *    9. denom = cdf[above] - cdf[below]; if denom < 1e-5f then denom = 1.
+ *   10. t = (u[j] - cdf[below]) / denom.
+ *   11. zs[j] = bins[below] + t * (bins[above] - bins[below]).
+ *   12. The second pass's depths are the S2 = S1 + Ni values of [z, zs], rank-sorted by the sampling's rule: ascending; ties by position
+ *       in the concatenation; a NaN ranks as +inf.  Then come points, decoders and compositing, exactly as for any z.
+ * zs is a constant to the backward (upstream detaches it): gradients flow through the second pass only, and the first pass saves nothing
+ * for a backward.  A ray whose first-pass weights are not finite gets NaN extra depths and renders non-finite; no other ray sees it.
+ *
+ * Needs n_samples >= 3 and n_samples + n_surface + n_importance <= 64 (one wave per ray); refused otherwise, and when negative;
+ * nsk_set_render_opts makes the same check against the installed value.  Setting another value invalidates captured graphs, as the matmul
+ * mode does; a step with n_importance > 0 is captured like any other.  With n_importance > 0 nsk_map_prepare registers nothing and returns
+ * success (no launch of the running step can carry a resampling): the batch's own step samples it.  nsk_last_call_stats counts both passes.
+ * Not done: gradients through zs, a separate coarse network for the first pass (upstream has none either), more than 64 samples per ray. */
+int nsk_set_importance(nsk_ctx* ctx, int n_importance);
+
+/* The installed n_importance (-1: null ctx).  A caller that changes the sample counts and n_importance together reads it to order its two
+ * calls so that each check passes: towards a smaller n_importance that one first, towards a larger one nsk_set_render_opts first. */
+int nsk_get_importance(nsk_ctx* ctx);
+
+/* Steps 1 - 12 above on their own, beside nsk_raw2outputs: d_z [N][S] sorted depths, d_weights [N][S] -> d_z_out [N][S + n_importance].
+ * det != 0: the deterministic u of step 6, else the hash of (seed, ray index, 64 + j).  S >= 3, n_importance >= 1, S + n_importance <= 64. */
+int nsk_importance_resample(nsk_ctx* ctx, int N, int S, const float* d_z, const float* d_weights, int n_importance, int det, uint64_t seed,
+                            float* d_z_out);
+
 /* ---- feature grids: c10::Dict<string,Tensor> "grid_<level>" [1,C,Z,Y,X] fp32 (src/main.cpp:33-78) ------ */
 /* h_czyx is the reference layout [C][Z][Y][X] (C must be 32); the device copy is voxel-major [Z][Y][X][C]
  * so that the 32 channels of a voxel are one 128-byte line (conversion happens here).

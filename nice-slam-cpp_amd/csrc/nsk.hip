@@ -2,6 +2,7 @@
 // Built only for gfx950:  hipcc --offload-arch=gfx950 -O3 -shared -fPIC nsk.hip -o libnsk.so
 #include "../../include/nsk.h"
 #include "nsk_device.h"
+#include "nsk_importance.h"
 #include "nsk_train.h"
 #include "nsk_bf16.h"
 #include "nsk_mesh.h"
@@ -755,6 +756,7 @@ struct Workspace {
     // step that finds its batch prepared swaps the two (forward_core).  Both are kept at the same capacities (ensure_next).
     SampleSet cur, next;
     Buf<float> occ[3], rgb4;
+    Buf<float> imp_z, imp_w;         // importance sampling (forward_core): the first pass's depths and compositing weights [m], allocated with the first such step
     Buf<unsigned long long> masks[4];
     Buf<f4> hsave[4];                // block outputs of trainable decoders saved by the forward (save_h)
     int hsave_M[4] = {0, 0, 0, 0};   // sample count of the forward that filled hsave (0 = stale)
@@ -772,6 +774,7 @@ struct nsk_ctx {
     bool own_stream = false;
     int num_cu = 256;
     RParams R;
+    int n_importance = 0;                   // nsk_set_importance: extra depths per ray drawn from a first pass's weights (0: one pass)
     Buf<float> d_bound;
     GridState grid[4];
     DecState dec[4];
@@ -1224,10 +1227,38 @@ extern "C" int nsk_set_bound(nsk_ctx* c, const float h_bound[6])
     return 0;
 }
 
+// the sample counts importance sampling can live with: both passes in one wave, and a first pass with an interior weight
+static int importance_fits(const char* who, int n_samples, int n_surface, int n_importance)
+{
+    if (n_importance == 0) return 0;
+    if (n_samples + n_surface + n_importance > 64) return fail("%s: need n_samples+n_surface+n_importance <= 64 (got %d+%d+%d)", who, n_samples, n_surface, n_importance);
+    if (n_samples < 3) return fail("%s: n_importance > 0 needs n_samples >= 3 (got %d)", who, n_samples);
+    return 0;
+}
+
+static int prep_drop(nsk_ctx* c);
+extern "C" int nsk_set_importance(nsk_ctx* c, int n_importance)
+{
+    if (!c) return fail("null ctx");
+    if (n_importance < 0) return fail("nsk_set_importance: n_importance must be >= 0 (got %d)", n_importance);
+    if (c->capturing) return fail("nsk_set_importance: not while a graph is being captured");
+    CHK(importance_fits("nsk_set_importance", c->R.n_samples, c->R.n_surface, n_importance));
+    if (n_importance == c->n_importance) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(prep_drop(c));                          // a registered or prepared batch was sized for the other sample count
+    c->n_importance = n_importance;
+    invalidate_graphs(c);                       // the recorded steps have the other launch sequence
+    return 0;
+}
+
+extern "C" int nsk_get_importance(nsk_ctx* c) { return c ? c->n_importance : -1; }
+
 extern "C" int nsk_set_render_opts(nsk_ctx* c, int n_samples, int n_surface, int lindisp, float perturb, int occupancy, uint64_t seed)
 {
     if (!c) return fail("null ctx");
     if (n_samples < 1 || n_surface < 0 || n_samples + n_surface > 64) return fail("nsk_set_render_opts: need 1 <= n_samples, n_samples+n_surface <= 64 (got %d+%d)", n_samples, n_surface);
+    CHK(importance_fits("nsk_set_render_opts", n_samples, n_surface, c->n_importance));
     c->R.n_samples = n_samples; c->R.n_surface = n_surface; c->R.lindisp = lindisp ? 1 : 0; c->R.perturb = perturb;
     c->R.occupancy = occupancy ? 1 : 0; c->R.seed = seed;
     return 0;
@@ -1807,8 +1838,11 @@ static int launch_decode_fwd_stage(nsk_ctx* c, int stage, int M, int S, const fl
     return 0;
 }
 
-// algorithmic bytes / flops per sample
-static void account(nsk_ctx* c, int stage, int M, int N, bool bwd, unsigned flags)
+// importance sampling: the samples of the first pass behind a batch of N rays with S samples each in the second (forward_core's M1); 0 without
+static int first_pass_samples(const nsk_ctx* c, int N, int S) { return c->n_importance > 0 ? N * (S - c->n_importance) : 0; }
+
+// algorithmic bytes / flops per sample; M1 > 0: a first pass of M1 samples, a forward, went before the M counted here
+static void account(nsk_ctx* c, int stage, int M, int M1, bool bwd, unsigned flags)
 {
     static const double fwd_b[4] = {1024, 1024, 2048, 3072}, fwd_f[4] = {12.4e3, 31.0e3, 72.2e3, 103.3e3};
     double b = fwd_b[stage] + 5.0, f = fwd_f[stage];
@@ -1818,7 +1852,8 @@ static void account(nsk_ctx* c, int stage, int M, int N, bool bwd, unsigned flag
         f *= 2.0;
         if (flags & NSK_GRAD_DECODERS) for (int q = 0; q < 3; ++q) { int w = STAGE_DEC[stage][q]; if (w >= 0 && c->dec[w].trainable) f += 2.0 * (w == 0 ? 6176 : (w == 2 ? 20599 : 15500)); }
     }
-    c->last_bytes = b * M; c->last_flops = f * M; c->last_samples = M; (void)N;
+    c->last_bytes = b * M; c->last_flops = f * M; c->last_samples = M;
+    if (M1 > 0) { c->last_bytes += (fwd_b[stage] + 5.0) * M1; c->last_flops += fwd_f[stage] * M1; c->last_samples += M1; }
 }
 
 // sampling + decoders of the stage; leaves z / occ / rgb4 (and ReLU bits) in the workspace
@@ -2055,6 +2090,7 @@ static int prep_drop(nsk_ctx* c)
     return 0;
 }
 
+static void comp_args(nsk_ctx* c, CompArgs& A, int stage, int N, int S, const float* ro, const float* rd);
 static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, const float* gt, float gtmax, bool save_masks,
                         bool sorted = false, const nsk_ctx::DMax* dmax = nullptr)      // dmax: instead of the installed depth-max batch (nsk_render_image: none)
 {
@@ -2068,7 +2104,42 @@ static int forward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, co
     };
     nsk_ctx::Prep& P = c->prep;
     if (!c->capturing) CHK(prep_finish(c));                 // (also when the set is for another batch: the sampling below needs the cell histogram; nsk_graph_begin has settled it before a capture)
-    if (is_this_batch(P)) {
+    if (c->n_importance > 0) {
+        // Importance sampling (include/nsk.h): a first pass over the S1 stratified and surface samples in ray order, whose compositing weights
+        // place n_importance further depths; the S samples of the merged set are then an ordinary batch for everything downstream.  The first
+        // pass keeps nothing for a backward.  No batch is ever prepared for such a step (nsk_map_prepare).
+        const int Ni = c->n_importance, S1 = S - Ni, M1 = N * S1;
+        Workspace& w = c->ws;
+        const size_t m = (size_t)w.capM + 64;
+        CHK(grow(c, w.imp_z, m, "the first pass's depths", GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
+        CHK(grow(c, w.imp_w, m, "the first pass's weights", GROW_NO_CAPTURE | GROW_STALE_GRAPHS));
+        const nsk_ctx::DMax& dm = dmax ? *dmax : c->dmax;
+        c->sorted = false;
+        w.cur.z.swap(w.imp_z);                              // the launches of the first pass read their depths where every launch does
+        int r = launch_sampling(c, c->R, stage, N, S1, ro, rd, gt, gtmax, mask, false, w.cur, false, dm);
+        if (r == 0) r = launch_decode_fwd_stage(c, stage, M1, S1, ro, rd, false);
+        if (r == 0) {
+            CompArgs A;
+            comp_args(c, A, stage, N, S1, ro, rd);
+            A.keep = nullptr; A.weights = w.imp_w; A.mode = 0;
+            ProfScope ps(c, "composite_first"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A);
+        }
+        w.cur.z.swap(w.imp_z);                              // back: imp_z holds the first pass's depths, cur.z takes the merged ones
+        CHK(r);
+        HIPCHK(hipGetLastError());
+        c->sorted = sorted;
+        if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
+        if (want_live) CHK(ensure_live_stage(c, stage));
+        {
+            ProfScope ps(c, "resample");
+            ResampArgs A;
+            samp_args(c, A.P, c->R, stage, N, S, ro, rd, gt, gtmax, nullptr, mask, sorted, w.cur, want_live, dm);
+            A.z1 = w.imp_z; A.w = w.imp_w; A.S1 = S1; A.Ni = Ni; A.det = c->R.perturb > 0.f ? 0 : 1;
+            k_resample<<<(N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS, 64 * NSK_SAMPLE_RAYS, 0, c->stream>>>(A);
+        }
+        CHK(launch_sampling(c, c->R, stage, N, S, ro, rd, gt, gtmax, mask, sorted, w.cur, want_live, dm, PREP_SAMPLED));      // the cell sort, if any
+        c->live_ok = want_live;
+    } else if (is_this_batch(P)) {
         // this batch was sampled during the previous step (nsk_map_prepare): take its outputs
         c->ws.cur.swap(c->ws.next);                         // (both sets are kept at the same capacities: ensure_next)
         c->ws_flip ^= 1;
@@ -2106,7 +2177,7 @@ static int common_checks(nsk_ctx* c, int stage, int N, const float* ro, const fl
     if (!ro || !rd) return fail("rays_o / rays_d is NULL");
     CHK(check_stage(c, stage));
     HIPCHK(hipSetDevice(c->device));
-    int S = c->R.n_samples + (gt ? c->R.n_surface : 0);
+    int S = c->R.n_samples + (gt ? c->R.n_surface : 0) + c->n_importance;      // with importance sampling: the merged set of the second pass
     if ((long long)N * S >= (1LL << 26)) return fail("N*S too large (%lld samples; at most 2^26 - 1 per call)", (long long)N * S);      // (also the range of ray_of)
     CHK(ensure_ws(c, N, N * S));
     *S_out = S;
@@ -2124,7 +2195,7 @@ extern "C" int nsk_render_forward(nsk_ctx* c, int stage, int N, const float* ro,
     A.rgb = rgb; A.depth = depth; A.var = var; A.weights = weights; A.mode = 0;
     { ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A); }
     HIPCHK(hipGetLastError());
-    account(c, stage, N * S, N, false, 0);
+    account(c, stage, N * S, first_pass_samples(c, N, S), false, 0);
     return 0;
 }
 
@@ -2135,6 +2206,29 @@ extern "C" int nsk_raw2outputs(nsk_ctx* c, int N, int S, const float* raw, const
     if (N < 1 || S < 1 || S > 64) return fail("nsk_raw2outputs: need N >= 1 and 1 <= S <= 64");
     HIPCHK(hipSetDevice(c->device));
     k_raw2outputs<<<(N + 3) / 4, 256, 0, c->stream>>>(N, S, occupancy, raw, z, rd, rgb, depth, var, weights);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the resampling launch on its own: no rays, no cell keys, no liveness bytes
+extern "C" int nsk_importance_resample(nsk_ctx* c, int N, int S, const float* z, const float* weights, int n_importance, int det, uint64_t seed,
+                                       float* z_out)
+{
+    if (!c || !z || !weights || !z_out) return fail("nsk_importance_resample: null argument");
+    if (N < 1 || S < 3 || n_importance < 1 || S + n_importance > 64)
+        return fail("nsk_importance_resample: need N >= 1, S >= 3, n_importance >= 1 and S + n_importance <= 64 (got N = %d, %d + %d)", N, S, n_importance);
+    if ((long long)N * (S + n_importance) >= (1LL << 31)) return fail("nsk_importance_resample: N * (S + n_importance) must stay below 2^31");
+    {   // rows are read with stride S and written with stride S + n_importance: never in place
+        const uintptr_t o0 = (uintptr_t)z_out, o1 = o0 + (size_t)N * (S + n_importance) * sizeof(float), in_bytes = (size_t)N * S * sizeof(float);
+        for (const float* in : {z, weights})
+            if ((uintptr_t)in < o1 && o0 < (uintptr_t)in + in_bytes) return fail("nsk_importance_resample: d_z_out overlaps %s", in == z ? "d_z" : "d_weights");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    ResampArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P.N = N; A.P.S = S + n_importance; A.P.R.seed = seed; A.P.z_out = z_out;
+    A.z1 = z; A.w = weights; A.S1 = S; A.Ni = n_importance; A.det = det ? 1 : 0;
+    { ProfScope ps(c, "resample"); k_resample<<<(N + NSK_SAMPLE_RAYS - 1) / NSK_SAMPLE_RAYS, 64 * NSK_SAMPLE_RAYS, 0, c->stream>>>(A); }
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2691,7 +2785,7 @@ extern "C" int nsk_render_backward(nsk_ctx* c, int stage, int N, const float* ro
     HIPCHK(hipGetLastError());
     c->deal_armed = true;      // only now: the launch that zeroes the cursors is on the stream
     CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd));
-    account(c, stage, N * S, N, true, flags);
+    account(c, stage, N * S, first_pass_samples(c, N, S), true, flags);
     return 0;
 }
 
@@ -2706,6 +2800,7 @@ extern "C" int nsk_map_prepare(nsk_ctx* c, int stage, int N, const float* ro, co
     if (!gt) return fail("nsk_map_prepare: gt_depth is NULL");
     if (c && c->capturing) return fail("nsk_map_prepare: not inside a graph capture");
     CHK(common_checks(c, stage, N, ro, rd, &S, gt));
+    if (c->n_importance > 0) return 0;           // no rider carries a resampling (its first pass reads the map this step's optimiser leaves): the batch's own step samples it
     const bool sorted = sort_pays(c, stage, N * S, flags);
     if (sorted) CHK(ensure_hist(c, stage_bins(c, stage)));
     CHK(ensure_next(c, sorted));
@@ -2741,7 +2836,7 @@ extern "C" int nsk_map_step(nsk_ctx* c, int stage, int N, const float* ro, const
     HIPCHK(hipGetLastError());
     c->deal_armed = true;      // only now: the launch is on the stream (an error return above leaves the next backward to arm with its memset)
     CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd, d_loss));
-    account(c, stage, N * S, N, true, flags);
+    account(c, stage, N * S, first_pass_samples(c, N, S), true, flags);
     return 0;
 }
 
@@ -2793,7 +2888,7 @@ extern "C" int nsk_track_step(nsk_ctx* c, int stage, int N, const float* ro, con
     { ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A); }
     HIPCHK(hipGetLastError());
     CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd, d_loss, deferred ? c->ws.tmp_depth : nullptr));
-    account(c, stage, N * S, N, true, flags);
+    account(c, stage, N * S, first_pass_samples(c, N, S), true, flags);
     return 0;
 }
 
@@ -3213,7 +3308,7 @@ extern "C" int nsk_render_image(nsk_ctx* c, int stage, int H0, int H1, int W0, i
     if (!d_pose) return fail("nsk_render_image: d_pose is NULL");
     if (!d_rgb || !d_depth || !d_var) return fail("nsk_render_image: d_rgb / d_depth / d_var is NULL");
     CHK(check_stage(c, stage));
-    const int S = c->R.n_samples + (d_depth_img ? c->R.n_surface : 0);
+    const int S = c->R.n_samples + (d_depth_img ? c->R.n_surface : 0) + c->n_importance;
     const int chunk_max = (int)(((1LL << 26) - 1) / S);
     if (chunk_rays < 1 || chunk_rays > chunk_max)
         return fail("nsk_render_image: chunk_rays = %d, must be 1..%d (%d samples per ray, fewer than 2^26 samples per chunk)", chunk_rays, chunk_max, S);
@@ -3245,8 +3340,8 @@ extern "C" int nsk_render_image(nsk_ctx* c, int stage, int H0, int H1, int W0, i
         { ProfScope ps(c, "composite"); k_composite<<<(n + 3) / 4, 256, 0, c->stream>>>(A); }
         HIPCHK(hipGetLastError());
     }
-    account(c, stage, S, 1, false, 0);
-    c->last_bytes *= total; c->last_flops *= total; c->last_samples = (int)std::min<long long>((long long)total * S, 0x7fffffffLL);
+    account(c, stage, S, first_pass_samples(c, 1, S), false, 0);
+    c->last_bytes *= total; c->last_flops *= total; c->last_samples = (int)std::min<long long>((long long)total * c->last_samples, 0x7fffffffLL);
     return 0;
 }
 

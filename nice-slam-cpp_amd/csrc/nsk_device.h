@@ -172,18 +172,100 @@ struct SampArgs {
     const float* mx_gt; const uint8_t* mx_keep; int mx_n;      // what the batch maximum of gt_depth runs over: the call's own rays, or the whole batch a shard belongs to (nsk_set_depth_max_batch)
     LiveArgs L;               // optional (L.out != nullptr): one liveness byte per sample for the backward's dead-tile skip
 };
+// What follows a ray's z store, for the wave of ray n (lane = sample slot, z the lane's sorted depth, o / d the ray): cell keys, arrival ranks,
+// the workgroup's LDS cell table, the histogram adds and the liveness bytes.  Shared by k_sample and k_resample (nsk_importance.h); every thread of
+// the workgroup must call it (it has barriers), active or not.
+__device__ __forceinline__ void sample_keys(const SampArgs& P, int bid, int n, bool active, int lane, float z,
+                                            float ox, float oy, float oz, float dx, float dy, float dz)
+{
+    const RParams& R = P.R;
+    const int S = P.S, kX = P.kX, kY = P.kY, kZ = P.kZ, pX = P.pX, pY = P.pY, pZ = P.pZ, ncell2 = P.ncell2;
+    int* __restrict__ skey = P.skey; int* __restrict__ srank = P.srank; int* __restrict__ hist = P.hist;
+    __shared__ int tkey[NSK_SAMPLE_TABLE], tcnt[NSK_SAMPLE_TABLE], tbase[NSK_SAMPLE_TABLE];
+    __shared__ int tlist[64 * NSK_SAMPLE_RAYS], nlist;      // the occupied slots of the table, in order of arrival
+    uint8_t* __restrict__ live_out = P.L.out;
+    if (!skey && !live_out) return;                                         // uniform over the launch
+    // ---- cell keys and ranks for the cell sort -----------------------------------------------------------------------------
+    if (skey) {
+        if (bid == 0 && threadIdx.x == 0) hist[-1] = 0;             // the bump cursor of k_sort_scan (one int in front of the histogram)
+        for (int i = threadIdx.x; i < NSK_SAMPLE_TABLE; i += 64 * NSK_SAMPLE_RAYS) { tkey[i] = -1; tcnt[i] = 0; }
+        if (threadIdx.x == 0) nlist = 0;
+    }
+    int cell = -1;
+    if (active && lane < S) {
+        const float px = add_rn(ox, mul_rn(dx, z)), py = add_rn(oy, mul_rn(dy, z)), pz = add_rn(oz, mul_rn(dz, z));   // = sample_finish
+        const int kc = cell_index(kX, kY, kZ, R.bound, px, py, pz);
+        cell = kc * 8;
+        int pcell = kc;
+        // The coarser level read beside the key level (grid_middle under grid_fine / grid_color) does not nest in it: grid_sample's
+        // align_corners scaling puts its cell faces INSIDE key cells, so the samples of one key cell fall into up to 2 x 2 x 2 parent
+        // cells.  Three parity bits of the parent cell order them inside the key cell; without them they alternate at random and
+        // the parent level's scatter finds a new run at every other sample.
+        if (pX > 0) {
+            const int pc = cell_index(pX, pY, pZ, R.bound, px, py, pz);
+            const int ix = pc % pX, iy = (pc / pX) % pY, iz = pc / (pX * pY);
+            cell += (ix & 1) | ((iy & 1) << 1) | ((iz & 1) << 2);
+            pcell = pc;
+        }
+        if (live_out) {                 // the cells are those tri_setup finds in the decoders: the same point, the same operation sequence
+            unsigned b = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const uint8_t* __restrict__ lv = P.L.lv[k];
+                unsigned on = 1u;
+                if (lv) {
+                    const int ci = P.L.src[k] == 0 ? kc : (P.L.src[k] == 1 ? pcell : cell_index(P.L.X[k], P.L.Y[k], P.L.Z[k], R.bound, px, py, pz));
+                    on = lv[ci] ? 1u : 0u;
+                }
+                b |= on << k;
+            }
+            live_out[(size_t)n * S + lane] = (uint8_t)b;
+        }
+    }
+    if (!skey) return;
+    // A ray crosses a cell once, so equal cells are consecutive lanes: one histogram add per run, made by its first lane.  The
+    // runs of the workgroup's rays are first merged in an LDS table (rays of one frame all start in the cells around the camera,
+    // and a thousand adds on one 64-byte line take 25 us: same-line atomics serialise at the memory side), then every
+    // distinct cell of the workgroup makes ONE returning add on the global histogram.
+    const int prev = __shfl_up(cell, 1);
+    const bool leader = active && lane < S && (lane == 0 || prev != cell);
+    const unsigned long long lead = __builtin_amdgcn_ballot_w64(leader);
+    const unsigned long long upto = (2ull << lane) - 1ull;                       // bits 0..lane
+    const int start = 63 - __builtin_clzll((lead & upto) | 1ull);
+    const unsigned long long above = lead & ~upto;
+    const int next = above ? __builtin_ctzll(above) : S;
+    __syncthreads();
+    int slot = 0, off = 0;
+    if (leader) {
+        unsigned h = ((unsigned)cell * 2654435761u) >> 21;                        // 11 bits
+        for (;;) {
+            const int old = atomicCAS(&tkey[h], -1, cell);
+            if (old == -1) { tlist[atomicAdd(&nlist, 1)] = (int)h; break; }       // first run of this cell in the workgroup
+            if (old == cell) break;
+            h = (h + 1) & (NSK_SAMPLE_TABLE - 1);
+        }
+        slot = (int)h;
+        off = atomicAdd(&tcnt[h], next - lane);
+    }
+    __syncthreads();
+    // one returning add per distinct cell, ONE per thread (at most 64 x rays distinct cells): walking the table itself, a thread met up to
+    // four occupied slots and made their adds one after the other -- two to three round trips of the 18 us this launch took at 5000 rays
+    if ((int)threadIdx.x < nlist) { const int i = tlist[threadIdx.x]; tbase[i] = atomicAdd(hist + hist_slot(tkey[i], ncell2), tcnt[i]); }
+    __syncthreads();
+    int base = leader ? tbase[slot] + off : 0;
+    base = __shfl(base, start);
+    if (active && lane < S) { skey[(size_t)n * S + lane] = cell; srank[(size_t)n * S + lane] = base + (lane - start); }
+}
 // (a body, so that the sampling of the NEXT batch can ride in the composite launch of the current step: k_composite_sample, nsk_map_prepare)
 __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
 {
     const RParams& R = P.R;
-    const int N = P.N, S = P.S, kX = P.kX, kY = P.kY, kZ = P.kZ, pX = P.pX, pY = P.pY, pZ = P.pZ, ncell2 = P.ncell2;
+    const int N = P.N, S = P.S;
     const float* __restrict__ rays_o = P.rays_o; const float* __restrict__ rays_d = P.rays_d; const float* __restrict__ gt_depth = P.gt_depth;
     const float gtmax_host = P.gtmax_host; const float* __restrict__ gtmax_dev = P.gtmax_dev; const uint8_t* __restrict__ keep = P.keep;
-    float* __restrict__ z_out = P.z_out; int* __restrict__ skey = P.skey; int* __restrict__ srank = P.srank; int* __restrict__ hist = P.hist;
+    float* __restrict__ z_out = P.z_out;
     __shared__ float sh[NSK_SAMPLE_RAYS][64];
     __shared__ float sh2[NSK_SAMPLE_RAYS][64];
-    __shared__ int tkey[NSK_SAMPLE_TABLE], tcnt[NSK_SAMPLE_TABLE], tbase[NSK_SAMPLE_TABLE];
-    __shared__ int tlist[64 * NSK_SAMPLE_RAYS], nlist;      // the occupied slots of the table, in order of arrival
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = bid * NSK_SAMPLE_RAYS + wave;
     const bool active = n < N;                          // whole waves; inactive ones only take part in the barriers below
@@ -265,78 +347,7 @@ __device__ __forceinline__ void sample_body(const SampArgs& P, int bid)
         z = sh2[wave][lane];
     }
     if (active && lane < S) z_out[(size_t)n * S + lane] = z;
-    uint8_t* __restrict__ live_out = P.L.out;
-    if (!skey && !live_out) return;                                         // uniform over the launch
-    // ---- cell keys and ranks for the cell sort -----------------------------------------------------------------------------
-    if (skey) {
-        if (bid == 0 && threadIdx.x == 0) hist[-1] = 0;             // the bump cursor of k_sort_scan (one int in front of the histogram)
-        for (int i = threadIdx.x; i < NSK_SAMPLE_TABLE; i += 64 * NSK_SAMPLE_RAYS) { tkey[i] = -1; tcnt[i] = 0; }
-        if (threadIdx.x == 0) nlist = 0;
-    }
-    int cell = -1;
-    if (active && lane < S) {
-        const float px = add_rn(ox, mul_rn(dx, z)), py = add_rn(oy, mul_rn(dy, z)), pz = add_rn(oz, mul_rn(dz, z));   // = sample_finish
-        const int kc = cell_index(kX, kY, kZ, R.bound, px, py, pz);
-        cell = kc * 8;
-        int pcell = kc;
-        // The coarser level read beside the key level (grid_middle under grid_fine / grid_color) does not nest in it: grid_sample's
-        // align_corners scaling puts its cell faces INSIDE key cells, so the samples of one key cell fall into up to 2 x 2 x 2 parent
-        // cells.  Three parity bits of the parent cell order them inside the key cell; without them they alternate at random and
-        // the parent level's scatter finds a new run at every other sample.
-        if (pX > 0) {
-            const int pc = cell_index(pX, pY, pZ, R.bound, px, py, pz);
-            const int ix = pc % pX, iy = (pc / pX) % pY, iz = pc / (pX * pY);
-            cell += (ix & 1) | ((iy & 1) << 1) | ((iz & 1) << 2);
-            pcell = pc;
-        }
-        if (live_out) {                 // the cells are those tri_setup finds in the decoders: the same point, the same operation sequence
-            unsigned b = 0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint8_t* __restrict__ lv = P.L.lv[k];
-                unsigned on = 1u;
-                if (lv) {
-                    const int ci = P.L.src[k] == 0 ? kc : (P.L.src[k] == 1 ? pcell : cell_index(P.L.X[k], P.L.Y[k], P.L.Z[k], R.bound, px, py, pz));
-                    on = lv[ci] ? 1u : 0u;
-                }
-                b |= on << k;
-            }
-            live_out[(size_t)n * S + lane] = (uint8_t)b;
-        }
-    }
-    if (!skey) return;
-    // A ray crosses a cell once, so equal cells are consecutive lanes: one histogram add per run, made by its first lane.  The
-    // runs of the workgroup's rays are first merged in an LDS table (rays of one frame all start in the cells around the camera,
-    // and a thousand adds on one 64-byte line take 25 us: same-line atomics serialise at the memory side), then every
-    // distinct cell of the workgroup makes ONE returning add on the global histogram.
-    const int prev = __shfl_up(cell, 1);
-    const bool leader = active && lane < S && (lane == 0 || prev != cell);
-    const unsigned long long lead = __builtin_amdgcn_ballot_w64(leader);
-    const unsigned long long upto = (2ull << lane) - 1ull;                       // bits 0..lane
-    const int start = 63 - __builtin_clzll((lead & upto) | 1ull);
-    const unsigned long long above = lead & ~upto;
-    const int next = above ? __builtin_ctzll(above) : S;
-    __syncthreads();
-    int slot = 0, off = 0;
-    if (leader) {
-        unsigned h = ((unsigned)cell * 2654435761u) >> 21;                        // 11 bits
-        for (;;) {
-            const int old = atomicCAS(&tkey[h], -1, cell);
-            if (old == -1) { tlist[atomicAdd(&nlist, 1)] = (int)h; break; }       // first run of this cell in the workgroup
-            if (old == cell) break;
-            h = (h + 1) & (NSK_SAMPLE_TABLE - 1);
-        }
-        slot = (int)h;
-        off = atomicAdd(&tcnt[h], next - lane);
-    }
-    __syncthreads();
-    // one returning add per distinct cell, ONE per thread (at most 64 x rays distinct cells): walking the table itself, a thread met up to
-    // four occupied slots and made their adds one after the other -- two to three round trips of the 18 us this launch took at 5000 rays
-    if ((int)threadIdx.x < nlist) { const int i = tlist[threadIdx.x]; tbase[i] = atomicAdd(hist + hist_slot(tkey[i], ncell2), tcnt[i]); }
-    __syncthreads();
-    int base = leader ? tbase[slot] + off : 0;
-    base = __shfl(base, start);
-    if (active && lane < S) { skey[(size_t)n * S + lane] = cell; srank[(size_t)n * S + lane] = base + (lane - start); }
+    sample_keys(P, bid, n, active, lane, z, ox, oy, oz, dx, dy, dz);
 }
 __global__ __launch_bounds__(64 * NSK_SAMPLE_RAYS) void k_sample(SampArgs P) { sample_body(P, blockIdx.x); }
 

@@ -273,7 +273,7 @@ extern "C" int nsk_mesh_vertex_colors(nsk_ctx* c, const float* verts, int nv, co
     CHK(normal_rays_checks("nsk_mesh_vertex_colors", c, nv, verts, length));
     if (nv > 0 && !rgb) return fail("nsk_mesh_vertex_colors: d_rgb is NULL");
     CHK(check_stage(c, NSK_COLOR));
-    const int S = c->R.n_samples + c->R.n_surface;          // (every ray carries its depth)
+    const int S = c->R.n_samples + c->R.n_surface + c->n_importance;      // (every ray carries its depth)
     const int chunk_max = (int)(((1LL << 26) - 1) / S);
     if (chunk_rays == 0) chunk_rays = 25600;                // nsk_render_image's default
     if (chunk_rays < 1 || chunk_rays > chunk_max)

@@ -35,6 +35,8 @@ class Mapper {
     // the camera of the frames run() will be given, instead of the cam block's (frames prepared by nskh::FramePrep: its H, W, fx, fy, cx, cy)
     void set_camera(int H_, int W_, float fx_, float fy_, float cx_, float cy_) { H = H_; W = W_; fx = fx_; fy = fy_; cx = cx_; cy = cy_; }
     void seed(uint64_t s) { rng_seed = s; draw_calls = 0; }
+    // rendering.N_importance of ns_config as this Mapper's Renderer took it (an absent key: 0); every iteration renders with it
+    int n_importance() const { return renderer.N_importance; }
     // N > 1 (BASELINE configs[3], [4]): every rank draws the window's whole batch (the pixel draw is a counter hash of the seed: identical on
     // every rank, one small launch), renders the contiguous shard [lo, hi) of it with the batch's max(gt_depth) taken over the whole batch
     // (nsk_set_depth_max_batch: no collective), and ONE all-reduce per iteration sums the marked voxels' gradients, the colour decoder's, the

@@ -4,11 +4,15 @@
 #include <tuple>
 #include <utility>
 #include <torch/torch.h>
+#include <yaml-cpp/yaml.h>
 #include "models/NICE.h"
 
 class Renderer {
   public:
     Renderer();
+    // not in the reference (its constants are literals): the constants above, then the keys of the configuration's `rendering:` block that
+    // are honoured here -- rendering.N_importance, an absent key or block meaning 0.  The Tracker and the Mapper build their Renderer so.
+    explicit Renderer(const YAML::Node& ns_config);
     torch::Tensor eval_points(torch::Tensor p, NICE decoders, c10::Dict<std::string, torch::Tensor> c, std::string stage);
     void render_batch_ray(c10::Dict<std::string, torch::Tensor> c, NICE decoders, torch::Tensor rays_d, torch::Tensor rays_o,
                           std::string stage, torch::Tensor gt_depth, torch::Tensor& rgb_map, torch::Tensor& depth_map,
@@ -27,6 +31,9 @@ class Renderer {
     // not in the reference: the scene bound is hard-coded there in five places (src/Renderer.cpp:15 ...)
     void set_bound(torch::Tensor bound_3x2);
     torch::Tensor bound;
+    // N_importance (rendering.N_importance through Renderer(ns_config), default 0): extra depths per ray drawn from the compositing weights of a first pass; every
+    // renderer that takes this Renderer's constants (render_batch_ray, render_img, the Mapper's, the Tracker's, and the Mesher's calls that
+    // follow) then returns the second pass over N_samples (+ N_surface) + N_importance samples (include/nsk.h: nsk_set_importance)
     int N_samples, N_surface, N_importance;
     bool lindisp, occupancy;
     float perturb;

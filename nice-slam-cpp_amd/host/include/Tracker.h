@@ -28,6 +28,8 @@ class Tracker {
     void set_bound(torch::Tensor bound_3x2);
     // the camera of the frames run() will be given, instead of the cam block's (frames prepared by nskh::FramePrep: its H, W, fx, fy, cx, cy)
     void set_camera(int H_, int W_, float fx_, float fy_, float cx_, float cy_) { H = H_; W = W_; fx = fx_; fy = fy_; cx = cx_; cy = cy_; }
+    // rendering.N_importance of ns_config as this Tracker's Renderer took it (an absent key: 0); every iteration renders with it
+    int n_importance() const { return renderer.N_importance; }
 
   private:
     int H, W;

@@ -167,6 +167,20 @@ static void set_bound_ctx(const torch::Tensor& b)
     check(nsk_set_bound(ctx(), h.data_ptr<float>()));
 }
 
+// a Renderer's constants to the context, rendering.N_importance among them.  The sample counts are checked against the installed
+// N_importance and the other way round; whichever of the two calls shrinks the sample set goes first, so each check sees a set that
+// fits whenever the Renderer's own does, and a Renderer whose constants do not fit fails with the context's message.
+// An unchanged N_importance costs nothing.  Another one synchronises the stream, drops a prepared batch and invalidates the captured
+// graphs (nsk_set_importance): Renderers that share the context and alternate, such as a Tracker's and a Mapper's, should carry the same
+// value, as they do when both are built from one configuration.
+static void set_render_opts_ctx(const Renderer& r)
+{
+    const bool shrink = r.N_importance < nsk_get_importance(ctx());
+    if (shrink) check(nsk_set_importance(ctx(), r.N_importance));
+    check(nsk_set_render_opts(ctx(), r.N_samples, r.N_surface, r.lindisp ? 1 : 0, r.perturb, r.occupancy ? 1 : 0, 0));
+    if (!shrink) check(nsk_set_importance(ctx(), r.N_importance));
+}
+
 }  // namespace nskh
 
 using nskh::check;
@@ -356,12 +370,18 @@ Renderer::Renderer()                                                            
     bound = torch::tensor({{-4.5, 3.82}, {-1.5, 2.02}, {-3.0, 2.76}});
 }
 
+Renderer::Renderer(const YAML::Node& ns_config) : Renderer()
+{
+    const YAML::Node r = ns_config["rendering"];
+    if (r.IsDefined() && r["N_importance"].IsDefined()) N_importance = r["N_importance"].as<int>();
+}
+
 void Renderer::set_bound(torch::Tensor b) { bound = b.detach().to(torch::kCPU, torch::kFloat32).clone(); }
 
 void Renderer::push_opts()
 {
     nskh::set_bound_ctx(bound);
-    check(nsk_set_render_opts(ctx(), N_samples, N_surface, lindisp ? 1 : 0, perturb, occupancy ? 1 : 0, 0));
+    nskh::set_render_opts_ctx(*this);
 }
 
 torch::Tensor Renderer::eval_points(torch::Tensor p, NICE decoders, c10::Dict<std::string, torch::Tensor> c, std::string stage)    // :19-42
@@ -379,7 +399,7 @@ void Renderer::render_batch_ray(c10::Dict<std::string, torch::Tensor> c, NICE de
     decoders.sync_to_device();
     const int N = (int)rays_o.size(0);
     const bool has_gt = gt_depth.defined();
-    const int S = N_samples + (has_gt ? N_surface : 0);                                       // D8: N_surface is not mutated
+    const int S = N_samples + (has_gt ? N_surface : 0) + N_importance;                        // D8: N_surface is not mutated; the second pass's set
     DevArr<float> ro = to_device(rays_o.reshape({-1, 3})), rd = to_device(rays_d.reshape({-1, 3})), gd;
     if (has_gt) gd = to_device(gt_depth.reshape({-1}));
     DevArr<float> o_rgb((size_t)N * 3), o_d((size_t)N), o_v((size_t)N), o_w((size_t)N * S);
@@ -563,7 +583,7 @@ struct Tracker::Dev {
     DevArr<float> cam, m, v, losses;     // pose 7-vector, its Adam moments, one loss per iteration
 };
 
-Tracker::Tracker(YAML::Node ns_config, YAML::Node cf_config, c10::Dict<std::string, torch::Tensor> c_dict) : renderer()      // Tracker.cpp:5-34
+Tracker::Tracker(YAML::Node ns_config, YAML::Node cf_config, c10::Dict<std::string, torch::Tensor> c_dict) : renderer(ns_config)      // Tracker.cpp:5-34
 {
     handle_dynamic = ns_config["tracking"]["handle_dynamic"].as<bool>();
     use_color_in_tracking = ns_config["tracking"]["use_color_in_tracking"].as<bool>();
@@ -599,7 +619,7 @@ torch::Tensor Tracker::optimize_cam_in_batch(torch::Tensor cam_tensor, torch::Te
     const int N = batch_size;
     D.rays.ensure((size_t)N); D.losses.ensure(8); D.m.ensure(16);      // losses: [loss, d loss / d pose (7)]
     nskh::set_bound_ctx(bound);
-    check(nsk_set_render_opts(ctx(), renderer.N_samples, renderer.N_surface, renderer.lindisp, renderer.perturb, renderer.occupancy, 0));
+    nskh::set_render_opts_ctx(renderer);
     nskh::sync_grids(c);
     decoders.sync_to_device();
     RayBufs& R = D.rays;
@@ -633,7 +653,7 @@ void Tracker::run(NICE decoders, torch::Tensor gt_color_t, torch::Tensor gt_dept
     const int N = tracking_pixels, iters = num_cam_iters;
     D.rays.ensure((size_t)N); D.losses.ensure((size_t)std::max(iters, 8));
     nskh::set_bound_ctx(bound);
-    check(nsk_set_render_opts(ctx(), renderer.N_samples, renderer.N_surface, renderer.lindisp, renderer.perturb, renderer.occupancy, 0));
+    nskh::set_render_opts_ctx(renderer);
     nskh::sync_grids(c);
     decoders.sync_to_device();
     RayBufs& R = D.rays;
@@ -706,7 +726,7 @@ struct Mapper::Dev {
     DevArr<int32_t> kf_pi, kf_pj;
 };
 
-Mapper::Mapper(YAML::Node ns_config, YAML::Node cf_config, bool cmapr) : renderer()           // Mapper.cpp:6-36
+Mapper::Mapper(YAML::Node ns_config, YAML::Node cf_config, bool cmapr) : renderer(ns_config)           // Mapper.cpp:6-36
 {
     ns_cfg = ns_config; cf_cfg = cf_config;
     color_refine = ns_cfg["mapping"]["color_refine"].as<bool>();
@@ -822,7 +842,7 @@ void Mapper::optimize_map(int num_joint_iters_, c10::Dict<std::string, torch::Te
     if (N == 0 || num_joint_iters_ <= 0) return;
 
     nskh::set_bound_ctx(bound);
-    check(nsk_set_render_opts(ctx(), renderer.N_samples, renderer.N_surface, renderer.lindisp, renderer.perturb, renderer.occupancy, 0));
+    nskh::set_render_opts_ctx(renderer);
     nskh::sync_grids(c);
     decoders.sync_to_device();
     // frame images: the current frame and every keyframe of the window, resident on the device (uploaded when first seen)

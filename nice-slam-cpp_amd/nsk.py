@@ -36,6 +36,7 @@ SYMBOLS = (
     "nsk_tsdf_integrate", "nsk_tsdf_volume",
     "nsk_mesh_vertex_normals", "nsk_normal_rays", "nsk_mesh_vertex_colors",
     "nsk_frame_plan", "nsk_frame_prepare",
+    "nsk_set_importance", "nsk_get_importance", "nsk_importance_resample",
 )
 
 FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
@@ -158,6 +159,12 @@ def lib():
         L.nsk_image_ssim.restype = C.c_int
         L.nsk_image_ssim.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_int, PD, C.c_void_p, PD, PD]
+        L.nsk_set_importance.restype = C.c_int
+        L.nsk_set_importance.argtypes = [C.c_void_p, C.c_int]
+        L.nsk_get_importance.restype = C.c_int
+        L.nsk_get_importance.argtypes = [C.c_void_p]
+        L.nsk_importance_resample.restype = C.c_int
+        L.nsk_importance_resample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -329,6 +336,16 @@ class Context:
     def set_matmul_mode(self, mode):
         _chk(lib().nsk_set_matmul_mode(self.h, int(mode)))
 
+    def set_importance(self, n):
+        """nsk_set_importance: n extra depths per ray drawn from the compositing weights of a first pass (rendering.N_importance; 0: one
+        pass).  Every renderer of the context then returns the second pass over n_samples (+ n_surface) + n samples per ray."""
+        _chk(lib().nsk_set_importance(self.h, int(n)))
+        self.n_importance = int(n)
+
+    def get_importance(self):
+        """nsk_get_importance: the installed n_importance"""
+        return int(lib().nsk_get_importance(self.h))
+
     def set_ray_mask(self, keep):
         """uint8 cuda tensor [N] (or None): rays with keep == 0 take no part in the loss, its gradients and the batch statistics"""
         self._ray_mask = keep                     # keep the tensor alive while the context points at it
@@ -478,7 +495,7 @@ class Context:
 
     # -- rendering (torch CUDA tensors in, torch CUDA tensors out) ------------------------------------------
     def _S(self, gt_depth):
-        return getattr(self, "n_samples", 32) + (getattr(self, "n_surface", 16) if gt_depth is not None else 0)
+        return getattr(self, "n_samples", 32) + (getattr(self, "n_surface", 16) if gt_depth is not None else 0) + getattr(self, "n_importance", 0)
 
     @_ordered
     def render_forward(self, stage, rays_o, rays_d, gt_depth=None, gt_depth_max=-1.0, want_weights=True):
@@ -1315,6 +1332,19 @@ class Context:
         _chk(lib().nsk_raw2outputs(self.h, N, S, _ptr(raw), _ptr(z), _ptr(rays_d), int(occupancy), _ptr(rgb), _ptr(depth),
                                    _ptr(var), _ptr(w)))
         return rgb, depth, var, w
+
+    @_ordered
+    def importance_resample(self, z, weights, n, det=True, seed=0):
+        """nsk_importance_resample: z, weights [N, S] cuda tensors (sorted depths and their compositing weights) -> the [N, S + n] sorted
+        depths of the second pass; det: the evenly spaced u, else the hash of (seed, ray, 64 + j) (include/nsk.h)"""
+        import torch
+        assert z.dtype == torch.float32 and weights.dtype == torch.float32 and z.dim() == 2 and weights.shape == z.shape
+        assert z.is_cuda and weights.device == z.device
+        N, S = z.shape
+        out = torch.empty(N, S + int(n), device=z.device)
+        _chk(lib().nsk_importance_resample(self.h, N, S, _ptr(z), _ptr(weights), int(n), int(bool(det)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                           _ptr(out)))
+        return out
 
     @_ordered
     def render_backward(self, stage, rays_o, rays_d, gt_depth, gt_depth_max, g_rgb, g_depth, g_var=None, flags=GRAD_GRIDS):
