@@ -497,7 +497,8 @@ int nsk_mesh_table(int case_index, int8_t* h_edges, int capacity);
 /* The nodes of a lattice (origin, step, nx, ny, nz and the node points as in nsk_eval_lattice; at most 2^28 nodes) that at least one of K
  * keyframes saw: d_valid[(k * ny + j) * nx + i] = 1, else 0 -- the d_valid of nsk_mesh_extract.  accumulate != 0 ORs the old byte in, so a
  * long keyframe list can be streamed through in batches of a few depth images; K = 0 with accumulate = 0 clears the mask.  This is a union
- * of depth-truncated view frusta, per node (not the convex hull of a TSDF fusion that upstream's clean_mesh takes: tighter, no hull library).
+ * of depth-truncated view frusta, per node: tighter than the convex hull of a TSDF fusion that upstream's get_mesh takes, which
+ * nsk_points_hull / nsk_lattice_in_hull give.
  * d_depth [K][H][W] floats on the device; h_w2c [K][16] row-major world-to-camera on the host (the caller inverts its c2w, so that rounding
  * is the caller's); the camera looks along -z, as in nsk_frustum_mask and nsk_rays_from_camera.  Keyframe k sees the node p when, every
  * operation an fp32 operation of its own (no FMA):
@@ -880,6 +881,63 @@ int nsk_tsdf_volume(nsk_ctx* ctx, long long n, const float* d_tsdf, const float*
 
 /* ---- vertex normals of an indexed mesh; vertex colours from short rays along them (upstream's meshing.color_mesh_extraction_method
  * render_ray_along_normal: mesh.compute_vertex_normals(), then a ray of 0.1 m per vertex through render_batch_ray, stage color) ------ */
+/* ---- the convex hull of a point cloud, and the lattice nodes inside the scaled hull (the second half of upstream's
+ * get_bound_from_frames: the hull of the fusion's vertices and the camera centres, scaled by meshing.clean_mesh_bound_scale; Mesher.get_mesh
+ * evaluates the map only inside it) ------------------------------------------------------------------------------------------------------ */
+/* nsk_points_hull: the hull of d_points [n][3] float32 (device) followed by h_extra [n_extra][3] (host: the camera centres); indices run
+ * over the concatenation, n + n_extra <= 2^31 - 1; either part may be empty.  Every decision is an integer comparison, so two runs, a
+ * fresh context and tests/hull_checks.py give the same bytes however many points are coplanar or collinear:
+ *   1. a point with a non-finite coordinate is left out and counted;
+ *   2. lo_a / hi_a: the finite points' minimum / maximum per axis, widened to double; E = max_a(hi_a - lo_a) (E == 0: no hull);
+ *      s = (2^20 - 1) / E;  q_a = (int64) rint((double(p_a) - lo_a) * s), every operation an fp64 operation of its own, rint to even;
+ *   3. det(a, b, c, p) = ((q_b - q_a) x (q_c - q_a)) . (q_p - q_a) in int64 (differences < 2^20, cross components < 2^41, the dot product
+ *      < 3 * 2^61: no overflow); p is OUTSIDE the face (a, b, c) when det > 0, strictly;
+ *   4. i0: the lexicographically smallest (q_x, q_y, q_z, index); i1: the largest squared distance from i0; i2: the largest
+ *      max(|c_x|, |c_y|, |c_z|) of c = (q_i1 - q_i0) x (q_p - q_i0); i3: the largest |det(i0, i1, i2, p)|; every tie to the smallest index.
+ *      A maximum of 0 means a point, a line or a plane: no hull, and info carries the rank (0, 1, 2).  If det(i0, i1, i2, i3) > 0, i1 and i2
+ *      are swapped.  Faces 0..3 are (i0, i1, i2), (i0, i3, i1), (i1, i3, i2), (i2, i3, i0);
+ *   5. every other finite point belongs to the lowest-numbered face it is outside of; a point outside no face is interior for good;
+ *   6. until no live face has an outside point: F = the lowest-numbered live face with one; the apex = F's outside point with the largest
+ *      det, ties to the smallest index; the visible faces = all live faces with det(face, apex) > 0; a horizon edge = a directed edge
+ *      (u, v) of a visible face whose twin (v, u) belongs to a live face that is not visible; the new faces (u, v, apex) are created in
+ *      ascending (visible face number, edge slot), the slots of (a, b, c) being (a, b), (b, c), (c, a), and take the next face numbers
+ *      (never reused); the visible faces die; the points of their outside sets, but the apex, go to the lowest-numbered NEW face they are
+ *      outside of, or become interior;
+ *   7. the faces: the live faces in ascending number, as index triples wound so that outside is det > 0; the vertices: the ascending list
+ *      of the indices the faces name.  (A tie can elect a point in the interior of a flat face, and it then stays a vertex: harmless for
+ *      an inside test, and part of the rule.)
+ * The quantum E / (2^20 - 1) is about 8 um for an 8 m room: 16 fp32 ulps at that magnitude, far below any lattice step.
+ * h_info: [0] finite points, [1] points left out, [2] rank (3: there is a hull; 0 also without a finite point), [3] vertices, [4] faces,
+ * [5] insertions, [6] the quantum as the bits of a double (0 without one), [7] re-compactions of the list of outside points.  The call
+ * succeeds without a hull ([3] = [4] = 0).
+ * What grows with n runs on the device: the bounds, the quantisation to int32 triples, the four selection passes, and per insertion one
+ * launch over the compacted list of the points still outside, which re-homes the points whose face died (a point decides that itself:
+ * the apex sees its face) and combines each new face's count and largest det (64-bit integer maxima, then a minimum of the index among the
+ * points that reach it: no result depends on the order of the atomics) in LDS before at most one global update per workgroup and face.
+ * The list is re-compacted (the multi-launch scan of nsk_mesh_extract) when less than half of it is still outside.  The face table
+ * (csrc/nsk_hull_plan.h: a few thousand faces) lives on the host: per insertion one upload of the new faces' planes, one download of their
+ * counts and apexes -- one synchronisation per hull vertex.  Device memory: 16 B per point, + 4 B per point outside at the first
+ * re-compaction, + 40 B per face ever made.  A failing allocation names its byte count; the context stays usable.  Not while a graph is
+ * being captured.  The hull stays in the context until the next nsk_points_hull or nsk_hull_upload. */
+int nsk_points_hull(nsk_ctx* ctx, const float* d_points, int n, const float* h_extra, int n_extra, long long h_info[8]);
+/* the last hull: h_vertices [info[3]] ascending indices, h_faces [info[4]][3]; either may be NULL; nothing is written without a hull */
+int nsk_hull_download(nsk_ctx* ctx, int32_t* h_vertices, int32_t* h_faces);
+/* a caller's own convex mesh as the bound: h_xyz [n_vertices][3] finite coordinates, h_faces [n_faces][3] vertex numbers, wound so that
+ * (B - A) x (C - A) points outwards; at least 4 and at most 2^24 of each.  Convexity and closedness are the caller's business. */
+int nsk_hull_upload(nsk_ctx* ctx, const float* h_xyz, int n_vertices, const int32_t* h_faces, int n_faces);
+/* nsk_lattice_in_hull: d_valid[(k * ny + j) * nx + i] = 1 for the lattice nodes (origin, step, nx, ny, nz, node points and the at most 2^28
+ * nodes as in nsk_lattice_seen) inside the last hull scaled about its centre, else 0 -- the d_valid of nsk_mesh_extract and
+ * nsk_eval_lattice_masked.  All of it fp64, every operation rounded on its own (no FMA):
+ *   the hull vertices' own fp32 coordinates (not the quantised ones) widened; c = their sum in ascending index order, left to right, divided
+ *   by their number;  V' = c + scale * (V - c);  per face u = B' - A', v = C' - A', n = u x v (each product and each difference rounded);
+ *   the node P formed in fp32 as nsk_eval_lattice forms it, then widened;  w = P - A';  s = (w_x n_x + w_y n_y) + w_z n_z.
+ * A node is inside when it lies in the box of the V' (lo_a <= P_a <= hi_a) and no face has s > 0.  accumulate != 0 ORs the old byte in.
+ * Without a hull every node is outside.  One thread per node loops over the faces; the planes are computed once per call, on the host; a
+ * node outside the box never enters the loop, and a wave leaves it when all its nodes are outside.  n_inside (may be NULL) receives the
+ * number of set bytes after the call.  scale > 0 and finite.  Not while a graph is being captured. */
+int nsk_lattice_in_hull(nsk_ctx* ctx, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, double scale,
+                        int accumulate, uint8_t* d_valid, long long* n_inside);
+
 /* nsk_mesh_vertex_normals: the area-weighted unit normal of every vertex of a mesh (d_vertices [n_vertices][3] float32, d_triangles
  * [n_triangles][3] int32) into d_normals [n_vertices][3].  With the winding of nsk_mesh_extract the normals point to free space.  Every
  * operation below is an fp32 operation of its own (no FMA contraction).

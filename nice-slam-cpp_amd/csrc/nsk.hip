@@ -16,6 +16,7 @@
 #include "nsk_reduce.h"
 #include "nsk_buf.h"
 #include "nsk_split.h"
+#include "nsk_hull_plan.h"
 
 #include <dlfcn.h>
 #include <cstdarg>
@@ -911,7 +912,30 @@ struct nsk_ctx {
         Buf<unsigned> counters;                              // [0] triangles left out, [1] vertices without a normal, [2] most namings, [3] the queue's length
         Buf<float> raw; Buf<uint8_t> has;                    // nsk_mesh_vertex_colors: [chunk][4] point colours, [chunk] ray flags
     } normals;
-    // the optional count of an entry point (count_begin / count_end): nsk_lattice_seen, nsk_points_seen, nsk_tsdf_integrate, nsk_tsdf_volume
+    // convex hull of a cloud and the lattice nodes inside it (nsk_hull.h): the points' side of the insertion loop, and the last hull
+    struct Hull {
+        Buf<int> q, face_of;                                 // [points][3] quantised coordinates, [points] the face a point is outside of (-1: none)
+        Buf<int> list[2];                                    // the points still outside, re-compacted from one into the other
+        Buf<unsigned> scan;
+        Buf<HullFaceRec> faces;                              // every face's plane, by face number
+        Buf<unsigned long long> best, cnt; Buf<unsigned> arg; Buf<HullReport> rep;      // per new face of the insertion in flight: one group
+        Buf<long long> part;                                 // partial results of the bounds and selection passes
+        Buf<float> extra, gxyz; Buf<int> gidx;               // the host points; the hull vertices' coordinates and indices on their way to the host
+        Buf<double> planes;                                  // nsk_lattice_in_hull: [faces][6]
+        // the hull of the last nsk_points_hull / nsk_hull_upload: ascending vertex indices, faces as index triples, the vertices' fp32
+        // coordinates, the faces as positions in `verts`
+        std::vector<int> verts, tris, local;
+        std::vector<float> xyz;
+        void clear() { verts.clear(); tris.clear(); local.clear(); xyz.clear(); }
+        void set(const std::vector<int>& v, const std::vector<int>& t, const std::vector<float>& x)
+        {
+            verts = v; tris = t; xyz = x;
+            local.resize(t.size());
+            for (size_t k = 0; k < t.size(); ++k) local[k] = (int)(std::lower_bound(verts.begin(), verts.end(), t[k]) - verts.begin());
+        }
+    } hull;
+    // the optional count of an entry point (count_begin / count_end): nsk_lattice_seen, nsk_points_seen, nsk_tsdf_integrate, nsk_tsdf_volume,
+    // nsk_lattice_in_hull
     Buf<unsigned long long> count;
     // optional per-kernel timing with HIP events on the context's stream (nsk_profile_begin / _end)
     bool prof = false;
@@ -4012,6 +4036,9 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
 
 // ---- vertex normals, rays along them, the colours they composite (kernels and entry points: nsk_normals.h) ---------------------------------
 #include "nsk_normals.h"
+
+// ---- convex hull of a point cloud, lattice nodes inside the scaled hull (kernels and entry points: nsk_hull.h) ---------------------------
+#include "nsk_hull.h"
 
 // ---- raw frames prepared on the device: undistort, resize, crop (kernel and entry points: nsk_frame.h) -----------------------------------
 #include "nsk_frame.h"

@@ -11,9 +11,12 @@
 //                              vertex; render_ray_along_normal renders the colour stage along a ray of color_ray_length (0.1 m, upstream's
 //                              constant) that looks at the vertex from free space along its normal (nsk_mesh_vertex_normals,
 //                              nsk_mesh_vertex_colors), and decodes at the vertex where it has no normal.  Any other value throws;
-// and leaves clean_mesh_bound_scale (upstream's convex hull of a TSDF fusion: get_clean_mesh culls per node with the union of the
-// keyframes' depth-truncated frusta instead; the fusion itself is here, get_fused_mesh / get_rendered_mesh, its convex hull is not) and
-// mesh_coarse_level to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
+//   meshing.clean_mesh_bound_scale (1.02)   get_hull_mesh only: upstream's get_mesh bound.  The keyframes' depth is fused (as in
+//                              get_fused_mesh), the convex hull of the fusion's vertices and the camera centres is taken on the device
+//                              (nsk_points_hull), scaled about its centre by this factor, and the map is evaluated and meshed at the lattice
+//                              nodes inside it (nsk_lattice_in_hull).  get_clean_mesh culls per node with the union of the keyframes'
+//                              depth-truncated frusta instead: tighter, and with holes wherever nothing was observed;
+// and leaves mesh_coarse_level to the caller.  Points outside the bound have occupancy 100 (src/Renderer.cpp:36): with padding > 0 the
 // bound's own faces therefore show up as a shell around the scene, with padding 0 the outermost nodes (which lie ON the open bound) do.
 #pragma once
 #include <cstdint>
@@ -108,6 +111,17 @@ class Mesher {
     void get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
                            const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, float trunc_steps = 3.f,
                            float min_weight = 1.f, bool color = true, const std::string& stage = "color", int chunk_rays = 25600);
+    // Upstream's Mesher.get_mesh: the room, including the parts no camera saw but the map fills in, without the shell the bound's faces
+    // and the untrained corners of the grids leave around it.  The frames are fused on the lattice of get_mesh as in get_fused_mesh (no
+    // component filter); nsk_points_hull takes the hull of the fused vertices, still in the context's device buffer, and the camera centres
+    // c2w[:3, 3]; nsk_lattice_in_hull marks the nodes inside the hull scaled by clean_mesh_bound_scale; nsk_eval_lattice_masked (fine)
+    // decodes at those nodes, 100 elsewhere; nsk_mesh_extract runs WITH the mask.  So, like get_clean_mesh and unlike upstream's
+    // z[~mask] = 100, no shell is drawn along the hull: a surface that crosses it ends there.  Colours, normals and the PLY as in get_mesh.
+    // Without a hull (fewer than four points in general position) the mesh is empty.  hull_from_context: the fusion and the hull are
+    // skipped and the hull the context holds is taken (nsk_hull_upload: a caller's own convex bound).
+    void get_hull_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                       const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color = true,
+                       float trunc_steps = 3.f, float min_weight = 1.f);
     // binary little-endian PLY: float x y z, (rgb given) uchar red green blue, list uchar int vertex_indices
     static void write_ply(const std::string& path, const float* xyz, const uint8_t* rgb, int n_vertices, const int32_t* triangles, int n_triangles);
     static void read_ply(const std::string& path, std::vector<float>& xyz, std::vector<uint8_t>& rgb, std::vector<int32_t>& triangles);
@@ -189,5 +203,10 @@ class Mesher {
     long long last_seen = 0;                    // get_clean_mesh: lattice nodes at least one keyframe saw
     long long last_evaluated = 0;               // lattice nodes the decoders ran on (get_mesh without valid: all of them)
     long long last_observed = 0, last_valid = 0; // get_fused_mesh / get_rendered_mesh: nodes with a weight > 0, nodes with weight >= min_weight
+    float clean_mesh_bound_scale;               // meshing.clean_mesh_bound_scale (1.02): get_hull_mesh scales the hull about its centre by it
+    bool hull_from_context = false;             // get_hull_mesh: take the hull the context holds instead of fusing the frames
+    std::vector<int32_t> last_hull_vertices;    // get_hull_mesh: the hull's vertices, ascending indices into (fused vertices, then camera centres)
+    std::vector<int32_t> last_hull_faces;       // [faces][3], wound outwards
+    long long last_inside = 0;                  // lattice nodes inside the scaled hull
     float fuse_max_weight = 64.f;               // the weight cap of the fusion (a running mean over at most this many frames)
 };

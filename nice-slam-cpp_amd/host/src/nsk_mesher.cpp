@@ -22,6 +22,8 @@ Mesher::Mesher(YAML::Node ns, torch::Tensor bound_3x2, float padding_) : padding
     level_set = ns["meshing"]["level_set"].IsDefined() ? ns["meshing"]["level_set"].as<float>() : 0.f;
     remove_small_geometry_threshold = ns["meshing"]["remove_small_geometry_threshold"].IsDefined() ? ns["meshing"]["remove_small_geometry_threshold"].as<float>() : 0.2f;
     get_largest_components = ns["meshing"]["get_largest_components"].IsDefined() ? ns["meshing"]["get_largest_components"].as<bool>() : false;
+    clean_mesh_bound_scale = ns["meshing"]["clean_mesh_bound_scale"].IsDefined() ? ns["meshing"]["clean_mesh_bound_scale"].as<float>() : 1.02f;
+    if (!(clean_mesh_bound_scale > 0.f) || !std::isfinite(clean_mesh_bound_scale)) throw std::runtime_error("Mesher: meshing.clean_mesh_bound_scale must be positive and finite");
     color_method = ns["meshing"]["color_mesh_extraction_method"].IsDefined() ? ns["meshing"]["color_mesh_extraction_method"].as<std::string>() : "direct_point_query";
     if (color_method != "direct_point_query" && color_method != "render_ray_along_normal")
         throw std::runtime_error("Mesher: meshing.color_mesh_extraction_method must be direct_point_query or render_ray_along_normal, not " + color_method);
@@ -258,6 +260,55 @@ void Mesher::get_fused_mesh(const std::string& path, const std::vector<torch::Te
     int nv = 0, nt = 0;
     F.mesh(*this, min_weight, nv, nt);
     write_context_mesh(*this, path, false, nv, nt);
+}
+
+void Mesher::get_hull_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,
+                           const std::vector<torch::Tensor>& c2ws, int H, int W, float fx, float fy, float cx, float cy, bool color, float trunc_steps,
+                           float min_weight)
+{
+    const Frames frames(depths, c2ws, (size_t)H * W);
+    nskh::sync_grids(c);
+    decoders.sync_to_device();
+    const Lattice L(*this);
+    check(nsk_set_bound(ctx(), bound.data_ptr<float>()));
+    const int n = L.n, K = frames.K;
+    if (!hull_from_context) {
+        // the fusion's mesh stays in the context's buffers: the hull reads its vertices there
+        Fusion F(*this, trunc_steps);
+        last_observed = 0;
+        if (K == 0) F.integrate(*this, 0, nullptr, H, W, fx, fy, cx, cy, nullptr, true, &last_observed);
+        stream_frames(frames, 32, true, [&](int k0, int kb, const float* d_depth, const float* w2c) {
+            F.integrate(*this, kb, d_depth, H, W, fx, fy, cx, cy, w2c, k0 == 0, k0 + kb >= K ? &last_observed : nullptr);
+        });
+        int fv = 0, ft = 0;
+        {
+            DevArr<float> fvol(L.nodes());
+            DevArr<uint8_t> fvalid(L.nodes());
+            check(nsk_tsdf_volume(ctx(), (long long)L.nodes(), F.tsdf.p(), F.weight.p(), min_weight, fvol.p(), fvalid.p(), &last_valid));
+            check(nsk_mesh_extract(ctx(), fvol.p(), fvalid.p(), n, n, n, L.origin, L.step, 0.f, &fv, &ft));
+        }
+        std::vector<float> centres((size_t)K * 3);
+        for (int k = 0; k < K; ++k) {
+            torch::Tensor m = c2ws[(size_t)k].detach().to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK(m.numel() == 16, "Mesher: c2w ", k, " is not 4 x 4");
+            for (int a = 0; a < 3; ++a) centres[(size_t)k * 3 + a] = m.data_ptr<float>()[4 * a + 3];
+        }
+        float* d_verts = nullptr; int32_t* d_tris = nullptr;
+        check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
+        long long info[8];
+        check(nsk_points_hull(ctx(), fv > 0 ? d_verts : nullptr, fv, K > 0 ? centres.data() : nullptr, K, info));
+        last_hull_vertices.assign((size_t)info[3], 0); last_hull_faces.assign((size_t)info[4] * 3, 0);
+        check(nsk_hull_download(ctx(), last_hull_vertices.data(), last_hull_faces.data()));
+    }
+    DevArr<float> vol(L.nodes());
+    DevArr<uint8_t> inside(L.nodes());
+    check(nsk_lattice_in_hull(ctx(), L.origin, L.step, n, n, n, (double)clean_mesh_bound_scale, 0, inside.p(), &last_inside));
+    long long n_eval = 0;
+    check(nsk_eval_lattice_masked(ctx(), NSK_FINE, L.origin, L.step, n, n, n, inside.p(), 100.f, vol.p(), &n_eval));
+    int nv = 0, nt = 0;
+    check(nsk_mesh_extract(ctx(), vol.p(), inside.p(), n, n, n, L.origin, L.step, level_set, &nv, &nt));
+    write_context_mesh(*this, path, color, nv, nt);
+    last_vertices = nv; last_triangles = nt; last_evaluated = n_eval;
 }
 
 void Mesher::get_rendered_mesh(const std::string& path, NICE& decoders, c10::Dict<std::string, torch::Tensor> c, const std::vector<torch::Tensor>& depths,

@@ -1,7 +1,9 @@
 // slam_loop.cpp -- the frame loop BASELINE.json's K5 describes (Tracker on every frame, Mapper on every `every`-th, over a posed RGB-D
 // sequence) through the C++ classes with the reference's surface and a SequenceReader; src/main.cpp wires up the Tracker only.
-//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE]
+//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull]
 // --mesh FILE: after the last frame the scene mesh (Mesher, meshing.resolution / meshing.level_set of nice_slam.yaml) goes to FILE as a PLY.
+// --mesh-hull: with --mesh, the loop keeps the mapped frames' depth images and estimated poses and the mesh is bounded as upstream's get_mesh
+//              bounds it (Mesher::get_hull_mesh: the convex hull of the frames' fusion and the camera centres, meshing.clean_mesh_bound_scale).
 // When the cam block of <cofusion.yaml> has a crop_size, a distortion or a crop_edge > 0 (upstream NICE-SLAM's TUM and ScanNet blocks), every
 // frame goes through nskh::FramePrep (undistort, resize, crop on the device from the reader's raw bytes) and the Tracker and the Mapper get
 // its camera; without them the loop is what it was, byte for byte.  A block without png_depth_scale takes the reader's.
@@ -50,7 +52,16 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
-    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE]\n"); return 2; }
+    bool mesh_hull = false;
+    for (int a = 1; a < argc; ++a)
+        if (std::string(argv[a]) == "--mesh-hull") {
+            mesh_hull = true;
+            for (int b = a; b + 1 < argc; ++b) argv[b] = argv[b + 1];
+            argc -= 1;
+            break;
+        }
+    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull]\n"); return 2; }
+    mesh_hull = mesh_hull && !mesh_path.empty();
     const std::string kind = argv[1], seq = argv[2], out = std::string(argv[5]) + "/";
     const int max_frames = argc > 6 ? std::atoi(argv[6]) : -1, every = argc > 7 ? std::atoi(argv[7]) : 1;
     try {
@@ -97,6 +108,7 @@ int main(int argc, char** argv)
         const int F = max_frames > 0 ? std::min(max_frames, reader.n_imgs) : reader.n_imgs;
         std::vector<torch::Tensor> est(F), gts(F);
         std::vector<float> tl, ml;
+        std::vector<torch::Tensor> hull_depths; std::vector<int> hull_frames;     // --mesh-hull: the mapped frames' depth images, their numbers
         for (int i = 0; i < F && reader.hasMore(); ++i) {
             reader.getNext();
             torch::Tensor depth_t, color_t;
@@ -130,6 +142,7 @@ int main(int argc, char** argv)
             if (i % every == 0) {
                 mapper.run(decoders, c, est, color_t, depth_t, gt, i, F);
                 ml.push_back(mapper.last_loss);
+                if (mesh_hull) { hull_depths.push_back(depth_t.detach().to(torch::kCPU, torch::kFloat32).contiguous().clone()); hull_frames.push_back(i); }
             }
             std::printf("frame %d: track loss %.4f, |t_est - t_gt| %.4f m%s\n", i, tl.back(),
                         (est[i].index({Slice(None, 3), 3}) - gt.index({Slice(None, 3), 3})).norm().item<float>(), i % every == 0 ? ", mapped" : "");
@@ -143,7 +156,17 @@ int main(int argc, char** argv)
         for (auto k : keys) save_npy(out + k + ".npy", c.at(k));
         if (!mesh_path.empty()) {
             Mesher mesher(ns, bound);
-            mesher.get_mesh(mesh_path, decoders, c, true);
+            if (mesh_hull) {
+                std::vector<torch::Tensor> poses;
+                for (int i : hull_frames) poses.push_back(est[(size_t)i]);
+                const int H = prepared ? prep.H : cf["cam"]["H"].as<int>(), W = prepared ? prep.W : cf["cam"]["W"].as<int>();
+                const float fx = prepared ? prep.fx : cf["cam"]["fx"].as<float>(), fy = prepared ? prep.fy : cf["cam"]["fy"].as<float>();
+                const float cx = prepared ? prep.cx : cf["cam"]["cx"].as<float>(), cy = prepared ? prep.cy : cf["cam"]["cy"].as<float>();
+                mesher.get_hull_mesh(mesh_path, decoders, c, hull_depths, poses, H, W, fx, fy, cx, cy, true);
+                std::printf("hull: %zu vertices, %zu faces, %lld of %lld nodes inside (scale %.4g)\n", mesher.last_hull_vertices.size(), mesher.last_hull_faces.size() / 3,
+                            mesher.last_inside, (long long)mesher.resolution * mesher.resolution * mesher.resolution, (double)mesher.clean_mesh_bound_scale);
+            } else
+                mesher.get_mesh(mesh_path, decoders, c, true);
             std::printf("mesh: %d vertices, %d triangles -> %s\n", mesher.last_vertices, mesher.last_triangles, mesh_path.c_str());
         }
         std::printf("slam_loop ok\n");

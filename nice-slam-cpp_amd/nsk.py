@@ -37,6 +37,7 @@ SYMBOLS = (
     "nsk_mesh_vertex_normals", "nsk_normal_rays", "nsk_mesh_vertex_colors",
     "nsk_frame_plan", "nsk_frame_prepare",
     "nsk_set_importance", "nsk_get_importance", "nsk_importance_resample",
+    "nsk_points_hull", "nsk_hull_download", "nsk_hull_upload", "nsk_lattice_in_hull",
 )
 
 FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
@@ -165,6 +166,15 @@ def lib():
         L.nsk_get_importance.argtypes = [C.c_void_p]
         L.nsk_importance_resample.restype = C.c_int
         L.nsk_importance_resample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
+        L.nsk_points_hull.restype = C.c_int
+        L.nsk_points_hull.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
+        L.nsk_hull_download.restype = C.c_int
+        L.nsk_hull_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nsk_hull_upload.restype = C.c_int
+        L.nsk_hull_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.nsk_lattice_in_hull.restype = C.c_int
+        L.nsk_lattice_in_hull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
 
@@ -1320,6 +1330,69 @@ class Context:
                                                       (tsdf, weight))
         verts, tris, info = self._fused_mesh(origin, step, tsdf, weight, n_obs, min_weight, min_area, largest_only)
         info.update(trunc=float(trunc), frames=K)
+        return verts, tris, info
+
+    # -- the convex hull of a cloud, the lattice nodes inside it (nsk_hull.h) -------------------------------------------------------------
+    @_ordered
+    def points_hull(self, points, extra=None):
+        """nsk_points_hull: the convex hull of points [n, 3] (float32 cuda tensor, n may be 0) followed by extra [m, 3] (host: anything numpy
+        reads, e.g. the camera centres).  -> (vertices int32 [nv] ascending indices into the concatenation, faces int32 [nf, 3] wound
+        outwards, info int64 [8]: finite points, left out, rank (3 = a hull), vertices, faces, insertions, the quantum as the bits of a
+        double, re-compactions), the arrays numpy.  Without a hull (rank < 3) both arrays are empty.  The hull stays in the context for
+        lattice_in_hull.  Synchronises once per hull vertex."""
+        import numpy as np
+        import torch
+        n = 0 if points is None else int(points.shape[0])
+        if n:
+            assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3
+        e = np.zeros((0, 3), np.float32) if extra is None else np.ascontiguousarray(np.asarray(extra, np.float32).reshape(-1, 3))
+        info = (C.c_longlong * 8)()
+        _chk(lib().nsk_points_hull(self.h, _ptr(points) if n else None, n, e.ctypes.data_as(C.c_void_p) if e.shape[0] else None, int(e.shape[0]), info))
+        info = np.array(info[:], np.int64)
+        verts, faces = np.zeros(int(info[3]), np.int32), np.zeros((int(info[4]), 3), np.int32)
+        _chk(lib().nsk_hull_download(self.h, verts.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
+        return verts, faces, info
+
+    def hull_upload(self, xyz, faces):
+        """nsk_hull_upload: a convex mesh of the caller's (xyz [nv, 3], faces [nf, 3] wound outwards, host) as the hull lattice_in_hull uses"""
+        import numpy as np
+        v = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3)); f = np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 3))
+        _chk(lib().nsk_hull_upload(self.h, v.ctypes.data_as(C.c_void_p), int(v.shape[0]), f.ctypes.data_as(C.c_void_p), int(f.shape[0])))
+
+    @_ordered
+    def lattice_in_hull(self, origin, step, nx, ny, nz, scale=1.02, valid=None):
+        """nsk_lattice_in_hull: the lattice nodes inside the last hull scaled about its centre (upstream's clean_mesh_bound_scale).  valid:
+        uint8 cuda tensor [nz, ny, nx] to OR into (default: a new one).  -> (valid, n_inside)"""
+        import torch
+        (o, op), (s, sp) = _vec3(origin), _vec3(step)
+        acc = valid is not None
+        if acc:
+            assert valid.dtype == torch.uint8 and valid.numel() == int(nx) * int(ny) * int(nz)
+        else:
+            valid = torch.empty((int(nz), int(ny), int(nx)), dtype=torch.uint8, device="cuda:%d" % self.device)
+        n = C.c_longlong(0)
+        _chk(lib().nsk_lattice_in_hull(self.h, op, sp, int(nx), int(ny), int(nz), float(scale), int(acc), _ptr(valid), C.byref(n)))
+        return valid, int(n.value)
+
+    def hull_mesh(self, stage, origin, step, n, depths, w2c, intr, HW, centres=None, scale=1.02, level=0.0, trunc=None, min_weight=1,
+                  frames_per_batch=32, edge=0, max_weight=64):
+        """Upstream's Mesher.get_mesh bound: the depth frames fused as in fuse_depth_mesh; the hull of the fused vertices and the camera
+        centres (centres [K, 3] host; None: the translations of the inverted w2c); the lattice nodes inside the hull scaled by `scale`;
+        the map's occupancy (eval_lattice of `stage`, fill 100) at those nodes only; extract_mesh at `level` WITH the mask, so no shell is
+        drawn along the hull (upstream sets the outside to 100 and meshes the wall that makes).
+        -> (vertices, triangles, dict: the fusion's counts, hull info, n_inside, valid)"""
+        import numpy as np
+        nx, ny, nz = self._lattice_shape(n)
+        fv, ft, info = self.fuse_depth_mesh(origin, step, (nx, ny, nz), depths, w2c, intr, HW, trunc, min_weight, frames_per_batch, 0, False, edge,
+                                            max_weight)
+        if centres is None:
+            w = np.asarray(w2c, np.float64).reshape(-1, 4, 4)
+            centres = np.stack([np.linalg.inv(m)[:3, 3] for m in w]).astype(np.float32) if w.shape[0] else np.zeros((0, 3), np.float32)
+        hv, hf, hinfo = self.points_hull(fv, centres)
+        valid, n_inside = self.lattice_in_hull(origin, step, nx, ny, nz, scale)
+        vol = self.eval_lattice(stage, origin, step, nx, ny, nz, valid=valid, fill=100.0)
+        verts, tris = self.extract_mesh(vol, origin, step, level, valid)
+        info = dict(fused=info, hull_vertices=hv, hull_faces=hf, hull_info=hinfo, n_inside=n_inside, valid=valid, fused_vertices=fv)
         return verts, tris, info
 
     @_ordered
