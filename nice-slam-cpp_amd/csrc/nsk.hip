@@ -225,16 +225,25 @@ __global__ __launch_bounds__(256) void k_xchg_multi(XArgs A)
     if (A.gather) *bf = *sl; else *sl = *bf;
 }
 
+// Adam on one float: ONE body for k_adam_scalar, k_pose_step and k_pose_multi, which are asserted to agree bit for bit (tests/test_gpu_pose.py).
+// Left to hipcc's default contraction the same three lines were compiled differently per kernel: rounded products and a sum for both moments in
+// k_adam_scalar and k_pose_step, FMAs in k_pose_multi.  Here the moments are spelled as the first two had them (every product and the sum rounded on
+// its own) and the one fused operation all three had, p - step_size * r, is written as the fmaf it was: their bits stay, k_pose_multi's follow.
+__device__ __forceinline__ void adam_scalar_update(float gg, float& p, float& m, float& v, float step_size, float bc2s, float b1, float b2, float eps)
+{
+#pragma clang fp contract(off)
+    const float mm = b1 * m + (1.f - b1) * gg;
+    const float vv = b2 * v + (1.f - b2) * gg * gg;
+    p = fmaf(-step_size, mm / (sqrtf(vv) / bc2s + eps), p);
+    m = mm; v = vv;
+}
+
 __global__ void k_adam_scalar(int n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                               float* __restrict__ v, float step_size, float bc2s, float b1, float b2, float eps)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float gg = g[i];
-    float mm = b1 * m[i] + (1.f - b1) * gg;
-    float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    p[i] -= step_size * (mm / (sqrtf(vv) / bc2s + eps));
-    m[i] = mm; v[i] = vv;
+    adam_scalar_update(g[i], p[i], m[i], v[i], step_size, bc2s, b1, b2, eps);
 }
 
 __global__ void k_sum(int n, const float* __restrict__ x, float* __restrict__ out)
@@ -333,13 +342,17 @@ __global__ void k_rays_from_pixels(int n, const int* pi, const int* pj, float fx
     }
 }
 
-__global__ __launch_bounds__(256) void k_rays_backward(int n, const int* pi, const int* pj, float fx, float fy, float cx, float cy,
-                                                       int mode, const float* g_ro, const float* g_rd, float* g_c2w)
+// d loss / d c2w of the rays [r0, r0 + n) of a batch by one block of 256 threads: a partial per thread over r = r0 + t, r0 + t + 256, ..., the
+// butterfly over a wave's 64 lanes, ((s0 + s1) + s2) + s3 over the four waves; threads 0..11 store the 12 sums to `out` (global or shared: the
+// caller puts its own barrier behind it).  ONE body for k_rays_backward, k_pose_step and k_pose_multi, and no contraction in it: the three are
+// asserted to agree bit for bit, and with hipcc's default (a * b + c fused per instantiation) they did not -- see camera_matrix below.
+__device__ __forceinline__ void rays_backward_block(int r0, int n, const int* pi, const int* pj, float fx, float fy, float cx, float cy, int mode,
+                                                    const float* g_ro, const float* g_rd, float (*sh)[12], float* out)
 {
-    __shared__ float sh[4][12];
+#pragma clang fp contract(off)
     float acc[12];
     for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int r = threadIdx.x; r < n; r += 256) {
+    for (int r = r0 + threadIdx.x; r < r0 + n; r += 256) {
         float i = (float)pi[r], j = (float)pj[r];
         float dir[3] = {(i - cx) / fx, (mode & 1) ? (i - cy) / fy : -(j - cy) / fy, -1.f};
         for (int a = 0; a < 3; ++a) {
@@ -349,7 +362,14 @@ __global__ __launch_bounds__(256) void k_rays_backward(int n, const int* pi, con
     }
     for (int k = 0; k < 12; ++k) { float s = wave_sum(acc[k]); if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s; }
     __syncthreads();
-    if (threadIdx.x < 12) g_c2w[threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (threadIdx.x < 12) out[threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_rays_backward(int n, const int* pi, const int* pj, float fx, float fy, float cx, float cy,
+                                                       int mode, const float* g_ro, const float* g_rd, float* g_c2w)
+{
+    __shared__ float sh[4][12];
+    rays_backward_block(0, n, pi, pj, fx, fy, cx, cy, mode, g_ro, g_rd, sh, g_c2w);
 }
 
 // quad2rotation / get_camera_from_tensor, reference include/torchlib/utils.h:174-210
@@ -374,6 +394,9 @@ __global__ void k_camera_from_tensor(const float* cam, float* c2w) { camera_matr
 
 __device__ __forceinline__ void camera_matrix_backward(const float* cam, const float* g_c2w, float* g_cam)
 {
+    // no contraction, for camera_matrix's reason: inlined into k_camera_backward, k_pose_step and k_pose_multi, which must give the same bits --
+    // with the default the rotation gradients of the fused kernels differed from k_camera_backward's in the last bits (tests/test_gpu_pose.py)
+#pragma clang fp contract(off)
     float q[4] = {cam[0], cam[1], cam[2], cam[3]};
     float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
     float two_s = 2.f / n2;
@@ -417,30 +440,14 @@ __global__ __launch_bounds__(256) void k_pose_step(int n, const int* pi, const i
 {
     __shared__ float sh[4][12];
     __shared__ float g_c2w[12];
-    float acc[12];
-    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int r = threadIdx.x; r < n; r += 256) {
-        float i = (float)pi[r], j = (float)pj[r];
-        float dir[3] = {(i - cx) / fx, (mode & 1) ? (i - cy) / fy : -(j - cy) / fy, -1.f};
-        for (int a = 0; a < 3; ++a) {
-            for (int b = 0; b < 3; ++b) acc[4 * a + b] += g_rd[3 * r + a] * dir[b];
-            acc[4 * a + 3] += g_ro[3 * r + a];
-        }
-    }
-    for (int k = 0; k < 12; ++k) { float s = wave_sum(acc[k]); if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s; }
-    __syncthreads();
-    if (threadIdx.x < 12) g_c2w[threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    rays_backward_block(0, n, pi, pj, fx, fy, cx, cy, mode, g_ro, g_rd, sh, g_c2w);
     __syncthreads();
     if (threadIdx.x == 0) {
         float g[7];
         camera_matrix_backward(cam, g_c2w, g);
         for (int k = 0; k < 7; ++k) {              // k_adam_scalar's update
-            float gg = g[k];
-            float mm = b1 * m[k] + (1.f - b1) * gg;
-            float vv = b2 * v[k] + (1.f - b2) * gg * gg;
-            cam[k] -= step_size * (mm / (sqrtf(vv) / bc2s + eps));
-            m[k] = mm; v[k] = vv;
-            if (g_cam_out) g_cam_out[k] = gg;
+            adam_scalar_update(g[k], cam[k], m[k], v[k], step_size, bc2s, b1, b2, eps);
+            if (g_cam_out) g_cam_out[k] = g[k];
         }
     }
 }
@@ -468,19 +475,7 @@ __global__ __launch_bounds__(256) void k_pose_multi(PoseFrames F, int nframes, c
         return;
     }
     const int n = F.active[f] ? F.count[f] : 0, r0 = F.first[f];
-    float acc[12];
-    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int r = r0 + threadIdx.x; r < r0 + n; r += 256) {
-        float i = (float)pi[r], j = (float)pj[r];
-        float dir[3] = {(i - cx) / fx, (mode & 1) ? (i - cy) / fy : -(j - cy) / fy, -1.f};
-        for (int a = 0; a < 3; ++a) {
-            for (int b = 0; b < 3; ++b) acc[4 * a + b] += g_rd[3 * r + a] * dir[b];
-            acc[4 * a + 3] += g_ro[3 * r + a];
-        }
-    }
-    for (int k = 0; k < 12; ++k) { float s = wave_sum(acc[k]); if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s; }
-    __syncthreads();
-    if (threadIdx.x < 12) g_c2w[threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    rays_backward_block(r0, n, pi, pj, fx, fy, cx, cy, mode, g_ro, g_rd, sh, g_c2w);
     __syncthreads();
     if (threadIdx.x == 0) {
         float* cam = cams + 8 * f;
@@ -489,13 +484,7 @@ __global__ __launch_bounds__(256) void k_pose_multi(PoseFrames F, int nframes, c
         if (g_out) for (int k = 0; k < 8; ++k) g_out[8 * f + k] = g[k];
         if (adam && F.active[f]) {
             float* m = ms + 8 * f; float* v = vs + 8 * f;
-            for (int k = 0; k < 7; ++k) {              // k_adam_scalar's update
-                float gg = g[k];
-                float mm = b1 * m[k] + (1.f - b1) * gg;
-                float vv = b2 * v[k] + (1.f - b2) * gg * gg;
-                cam[k] -= step_size * (mm / (sqrtf(vv) / bc2s + eps));
-                m[k] = mm; v[k] = vv;
-            }
+            for (int k = 0; k < 7; ++k) adam_scalar_update(g[k], cam[k], m[k], v[k], step_size, bc2s, b1, b2, eps);      // k_adam_scalar's update
         }
     }
 }

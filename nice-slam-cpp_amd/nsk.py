@@ -1493,15 +1493,17 @@ class Context:
         return ro, rd
 
     @_ordered
-    def rays_from_camera(self, pix_i, pix_j, intr, cam, mode=0):
-        """camera_from_tensor + rays_from_pixels in one launch -> (rays_o, rays_d)"""
+    def rays_from_camera(self, pix_i, pix_j, intr, cam, mode=0, want_c2w=False):
+        """camera_from_tensor + rays_from_pixels in one launch -> (rays_o, rays_d); want_c2w: -> (rays_o, rays_d, c2w [3, 4]), the matrix the
+        launch formed from the pose"""
         import torch
         n = pix_i.shape[0]
         ro = torch.empty(n, 3, device=cam.device); rd = torch.empty(n, 3, device=cam.device)
+        c2w = torch.empty(3, 4, device=cam.device) if want_c2w else None
         fx, fy, cx, cy = intr
         _chk(lib().nsk_rays_from_camera(self.h, n, _ptr(pix_i), _ptr(pix_j), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
-                                        _ptr(cam), mode, _ptr(ro), _ptr(rd), None))
-        return ro, rd
+                                        _ptr(cam), mode, _ptr(ro), _ptr(rd), _ptr(c2w)))
+        return (ro, rd, c2w) if want_c2w else (ro, rd)
 
     @_ordered
     def pose_step(self, pix_i, pix_j, intr, g_ro, g_rd, cam, m, v, lr, step, mode=0, b1=0.9, b2=0.999, eps=1e-8, g_cam_out=None):

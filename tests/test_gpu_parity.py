@@ -634,7 +634,9 @@ def test_graph_is_refused_after_a_mask_change(oracle32):
 
 def test_fused_pose_kernels_equal_their_parts():
     """nsk_rays_from_camera = camera_from_tensor + rays_from_pixels and nsk_pose_step = rays_backward + camera_backward +
-    adam_vector: same arithmetic, so the same bits (the parts are checked against the oracle in test_losses_and_pose_kernels)"""
+    adam_vector: same arithmetic, so the same bits.  One camera and one batch here; the parts themselves are checked in tests/test_gpu_pose.py
+    (forward to the bit, the two backward kernels component by component inside derived fp64 bounds), which also repeats this claim across
+    quaternion kinds, batch sizes and consecutive steps"""
     sc = scenes.make_scene(1, grid_shapes=scenes.SMALL_GRID_SHAPES)
     ctx = make_ctx(sc)
     rng = np.random.default_rng(9)
