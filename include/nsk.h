@@ -203,7 +203,10 @@ int nsk_set_mask(nsk_ctx* ctx, int level, const uint8_t* h_mask_zyx);
  * a depth image (d_depth [H][W], device) and the current pose h_c2w (16 floats, row-major [4][4]) and installs it like
  * nsk_set_mask; h_mask_out [Z*Y*X] (host, may be NULL) receives a copy.  A voxel is kept if its centre projects inside the image
  * with 0 <= depth_along_-z <= sampled_depth + 0.5 (zero depths count as the maximum sampled depth) or lies within 0.5 m of the
- * camera centre; grid_coarse keeps every voxel.  Unmarked voxels' gradients: as for nsk_set_mask. */
+ * camera centre; grid_coarse keeps every voxel.  Unmarked voxels' gradients: as for nsk_set_mask.
+ * The maximum sampled depth has the floor 0: it is max(0, max over the voxels of the sampled depth).  A zero depth means "no reading",
+ * so an image without a positive sample (all zeros, or all negative) has the maximum 0 and a negative sample never becomes it.  Every
+ * call takes the maximum of its own image; nothing is carried from one call to the next (tests/test_gpu_keyframe.py). */
 int nsk_frustum_mask(nsk_ctx* ctx, int level, const float* d_depth, int H, int W, float fx, float fy, float cx, float cy,
                      const float h_c2w[16], uint8_t* h_mask_out);
 
@@ -359,7 +362,12 @@ int nsk_rays_backward(nsk_ctx* ctx, int n, const int32_t* d_pix_i, const int32_t
 /* get_camera_from_tensor / quad2rotation (utils.h:174-210): cam = (qw,qx,qy,qz,tx,ty,tz) -> c2w [3][4] */
 int nsk_camera_from_tensor(nsk_ctx* ctx, const float* d_cam, float* d_c2w);
 int nsk_camera_backward(nsk_ctx* ctx, const float* d_cam, const float* d_g_c2w, float* d_g_cam);
-/* inside-bbox pre-filter (src/Mapper.cpp:416-427, src/Tracker.cpp:48-58): d_keep[n] = (t >= gt_depth) */
+/* inside-bbox pre-filter (src/Mapper.cpp:416-427, src/Tracker.cpp:48-58): d_keep[n] = (t >= gt_depth), t = min over the axes of max over
+ * the two sides of (bound - o) / d, every operation a correctly rounded fp32 one.  NaN rule: as torch.max / torch.min hand a NaN on, a NaN
+ * in ANY of the six quotients (0/0: an origin on a bound plane with a zero direction component along that axis) drops the ray, whichever
+ * plane and axis it is; so does a NaN gt_depth.  Bit for bit the ATen expression on the CPU (tests/test_keyframe_cpu.py,
+ * tests/test_gpu_keyframe.py); the filter inside nsk_prepare_rays is the same function.  The box exit of the sampling kernels (the in-face
+ * note at nsk_render_forward) is a different text and unchanged: a ray this filter drops never reaches them with a meaning. */
 int nsk_inside_filter(nsk_ctx* ctx, int N, const float* d_rays_o, const float* d_rays_d, const float* d_gt_depth,
                       uint8_t* d_keep);
 /* Registers the NEXT batch, so that its sampling and cell sort leave the front of its own step: call it BEFORE the nsk_map_step of the current

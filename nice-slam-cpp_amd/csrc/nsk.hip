@@ -493,7 +493,7 @@ __global__ void k_inside_filter(RParams R, int N, const float* ro, const float* 
 {
     int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    keep[n] = ray_box_far(R.bound, ro[3 * n], ro[3 * n + 1], ro[3 * n + 2], rd[3 * n], rd[3 * n + 1], rd[3 * n + 2]) >= gt[n];
+    keep[n] = ray_inside(R.bound, ro[3 * n], ro[3 * n + 1], ro[3 * n + 2], rd[3 * n], rd[3 * n + 1], rd[3 * n + 2], gt[n]);
 }
 
 // the whole ray preparation of an iteration in one launch (nsk_prepare_rays): the bodies of k_sample_pixels, k_gather_pixels,
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256) void k_prepare_rays(PrepArgs A)
         o[a] = c2w[4 * a + 3];
         A.rd[3 * t + a] = d[a]; A.ro[3 * t + a] = o[a];
     }
-    if (A.keep) A.keep[t] = ray_box_far(A.R.bound, o[0], o[1], o[2], d[0], d[1], d[2]) >= gd;                        // k_inside_filter
+    if (A.keep) A.keep[t] = ray_inside(A.R.bound, o[0], o[1], o[2], d[0], d[1], d[2], gd);                           // k_inside_filter
 }
 
 // in-bound override for eval_points (reference src/Renderer.cpp:26-36)

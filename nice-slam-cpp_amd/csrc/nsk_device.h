@@ -78,6 +78,25 @@ __device__ __forceinline__ float ray_box_far(const float* bound, float ox, float
     return far;
 }
 
+// the inside-bbox pre-filter (reference src/Mapper.cpp:416-427, src/Tracker.cpp:48-58): t >= gt with ATen's max / min, which hand a NaN on.
+// A NaN in any of the six quotients (0/0: an origin on a bound plane, no direction component across it) drops the ray, whichever plane or
+// axis it is; without one the comparisons below are ATen's max and min.  ray_box_far above, what the sampling kernels call, keeps its own text.
+__device__ __forceinline__ bool ray_inside(const float* bound, float ox, float oy, float oz, float dx, float dy, float dz, float gt)
+{
+    float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
+    float far = 0.f;
+    bool nan = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float t0 = div_rn(sub_rn(bound[2 * k], o[k]), d[k]);
+        float t1 = div_rn(sub_rn(bound[2 * k + 1], o[k]), d[k]);
+        nan = nan || t0 != t0 || t1 != t1;
+        float m = t0 > t1 ? t0 : t1;
+        if (k == 0 || m < far) far = m;
+    }
+    return !nan && far >= gt;
+}
+
 __device__ __forceinline__ uint32_t hash_u32(unsigned long long seed, uint32_t a, uint32_t b)
 {
     unsigned long long x = seed ^ (0x9E3779B97F4A7C15ull * ((unsigned long long)a + 1)) ^

@@ -147,6 +147,23 @@ static real ray_box_far(const real* bound, const real* o, const real* d)
     return far;
 }
 
+/* The inside-bbox pre-filter (src/Mapper.cpp:416-427, src/Tracker.cpp:48-58): t >= gt_depth with ATen's max / min, which hand a NaN on.
+ * A NaN in any of the six quotients (0/0: an origin on a bound plane with no direction component across it) drops the ray, whichever
+ * plane or axis it is; without one the comparisons are ATen's max and min.  ray_box_far above, what the sampling calls, keeps its text. */
+static int ray_inside(const real* bound, const real* o, const real* d, real gt)
+{
+    real far = 0;
+    int nan = 0;
+    for (int k = 0; k < 3; ++k) {
+        real t0 = (bound[2 * k] - o[k]) / d[k];
+        real t1 = (bound[2 * k + 1] - o[k]) / d[k];
+        nan = nan || t0 != t0 || t1 != t1;
+        real m = t0 > t1 ? t0 : t1;
+        if (k == 0 || m < far) far = m;
+    }
+    return !nan && far >= gt;
+}
+
 /* src/Renderer.cpp:44-119: z values of one ray, sorted ascending.  Returns S. */
 static int ray_z_vals(const nso_opts* o, int n, const real* ro, const real* rd, int has_gt, real gt,
                       real gt_max, real* z)
@@ -1066,7 +1083,7 @@ NSO_API int nso_inside_filter(const real* bound, int N, const real* rays_o, cons
                               unsigned char* keep)
 {
     int c = 0;
-    for (int n = 0; n < N; ++n) { keep[n] = ray_box_far(bound, rays_o + 3 * n, rays_d + 3 * n) >= gt_depth[n]; c += keep[n]; }
+    for (int n = 0; n < N; ++n) { keep[n] = (unsigned char)ray_inside(bound, rays_o + 3 * n, rays_d + 3 * n, gt_depth[n]); c += keep[n]; }
     return c;
 }
 
@@ -1140,7 +1157,7 @@ NSO_API int nso_frustum_mask(const real* bound, int Z, int Y, int X, const real*
     real* dep = (real*)malloc(n * sizeof(real));
     real* zz = (real*)malloc(n * sizeof(real));
     unsigned char* inimg = (unsigned char*)malloc(n);
-    real dmax = 0; int first = 1;
+    real dmax = 0;                                          /* the floor: a zero depth is "no reading", and so is a negative sample */
     for (int iz = 0; iz < Z; ++iz) for (int iy = 0; iy < Y; ++iy) for (int ix = 0; ix < X; ++ix) {
         size_t v = ((size_t)iz * Y + iy) * X + ix;
         real p[3];
@@ -1155,7 +1172,7 @@ NSO_API int nso_frustum_mask(const real* bound, int Z, int Y, int X, const real*
         real d = bilinear_zero(depth_img, H, W, u, vv);
         dep[v] = d; zz[v] = z;
         inimg[v] = u < (real)W && u > 0 && vv < (real)H && vv > 0;
-        if (first || d > dmax) { dmax = d; first = 0; }
+        if (d > dmax) dmax = d;
     }
     int cnt = 0;
     for (int iz = 0; iz < Z; ++iz) for (int iy = 0; iy < Y; ++iy) for (int ix = 0; ix < X; ++ix) {
