@@ -1101,6 +1101,23 @@ int nsk_debug_last_split(nsk_ctx* ctx, int dir, int* h_out);
  * decoder has no image in pieces), -1 on failure; h_out = NULL only asks for the size, otherwise capacity (bytes) must hold the image.
  * Changes nothing a step reads. */
 int nsk_debug_decoder_images(nsk_ctx* ctx, int which, int what, void* h_out, size_t capacity);
+/* nsk_decoder_image_table: the index table an upload builds image `what` (numbered as above) of decoder `which` through; needs no context and
+ * no device.  pieces = 2 or 3 is the piece count of image 2 (the table itself does not depend on it, the image's size and layout do; ignored
+ * for the other images).  Returns the number of entries (0 for images 2 and 3 of the coarse decoder, which has none), -1 on a bad argument;
+ * copies the entries when h_idx is not NULL and capacity (entries) suffices, h_idx = NULL only asks for the count.
+ *   How an image follows from its table idx and the packed parameters P (nsk_decoder_download):
+ *   - entry t holds parameter idx[t], or zero where idx[t] = -1;
+ *   - images 0 and 1 are plain: float t of the image is entry t;
+ *   - images 2 and 3 keep np 16-bit pieces per entry (image 2: pieces; image 3: always 2): with fg = t / 512, lane = (t / 8) % 64, j = t % 8,
+ *     piece p of entry t is unsigned short ((fg * np + p) * 64 + lane) * 8 + j of the image;
+ *   - the pieces of a value x (store_pieces of csrc/nsk_bf16.h), every conversion rounding to nearest even:
+ *       np = 2: h = fp16(x), l = fp16((x - float(h)) * 2048), differences and products in fp32;
+ *       np = 3: h = bf16(x), m = bf16(x - float(h)), l = bf16((x - float(h)) - float(m));
+ *     fp16 results below the smallest normal are kept as subnormals, not flushed;
+ *   - the fragments' entries * np unsigned shorts are followed by an fp32 tail: the image's last tail_n floats equal the last tail_n floats of
+ *     the fp32 sibling, image what - 2 (tail_n = 740 for image 2: biases, output weight and bias, embedding matrix; 416 for image 3: output
+ *     weight, embedding matrix). */
+int nsk_decoder_image_table(int which, int what, int pieces, int32_t* h_idx, size_t capacity);
 
 #ifdef __cplusplus
 }

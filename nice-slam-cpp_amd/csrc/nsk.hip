@@ -16,6 +16,7 @@
 #include "nsk_reduce.h"
 #include "nsk_buf.h"
 #include "nsk_split.h"
+#include "nsk_images.h"
 #include "nsk_hull_plan.h"
 
 #include <dlfcn.h>
@@ -52,9 +53,9 @@ __global__ void k_pack(float* __restrict__ img, const int* __restrict__ idx, con
 
 struct AdamSeg { float* p; float* g; float* m; float* v; const int* idx; int nidx; int n; float step_size, bc2s; int blk_end;      // idx: the marked voxels (nullptr = all)
                  const int* inv_f; const int* inv_b; float* fimg; float* bimg;      // decoders: image position of each parameter (-1 none)
-                 const int* inv16; unsigned short* img16; float* img16_tail; int tail_off; int np16;
+                 const int* inv16; unsigned short* img16; float* img16_tail; int tail_off; int np16;      // forward image in np16 pieces (MlpFwdImgB), its fp32 tail
                  const int* invh; unsigned short* imgh; float* imgh_tail; int btail_off;      // fp16 backward image (MlpBwdImgH) and its fp32 tail
-                 const float* slabs; int nslabs, slab_stride; };                      // pending per-workgroup gradient slabs (k_decode_bwd_multi)   // bf16 3-piece image (nsk_bf16.h), its fp32 tail
+                 const float* slabs; int nslabs, slab_stride; };                      // pending per-workgroup gradient slabs (k_decode_bwd_multi)
 struct AdamArgs { AdamSeg s[8]; int n; float b1, b2, eps;
                   PlaceArgs place; int adam_blocks; };       // optional (place.nblocks > 0): the NEXT batch's cell-sort placement rides behind the segments (nsk_map_prepare)
 // all parameter groups of one optimiser step in one launch (3 grid levels + trainable decoders)
@@ -713,17 +714,13 @@ struct GridState {
     Buf<int> midx; int nmask = 0; bool midx_dirty = true;      // ascending list of the marked voxels (packed gradient exchange)
     Buf<uint8_t> live; bool live_dirty = true;                 // per cell: any corner voxel marked (k_cell_live); rebuilt like midx when the mask changed
 };
+// One derived copy of a decoder's parameters (nsk_images.h): the image, the table an upload builds it through, the inverse table the optimiser
+// launch rewrites it through.  dirty: the image lags behind the parameters and is rebuilt before use (image 3 alone is ever left so).
+struct DecImage { Buf<float> data; Buf<int> idx, inv; ImageSpec spec; bool dirty = false; };
 struct DecState {
     int n = 0;                                    // parameter count; set once the one-time setup is complete (0 = never uploaded)
     Buf<float> p, m, s;
-    Buf<float> fimg, bimg;
-    Buf<int> fidx, bidx;
-    Buf<int> finv, binv;                          // inverse of fidx / bidx: image position of each canonical parameter
-    Buf<int> inv16;                               // inverse of fidx16
-    Buf<int> invh;                                // inverse of bidx16 (fp16 backward image)
-    Buf<float> bimg16; Buf<int> bidx16; int bfrag16_n = 0; bool bimg16_dirty = true;   // bf16 3-piece backward image (frozen chain), repacked lazily
-    Buf<float> fimg16; Buf<int> fidx16; int frag16_n = 0, fimg16_f = 0, tail_off = 0, tail16_off = 0, np16 = 3, cq16 = 2;   // forward image in pieces: 3 bf16 (mode 1) or 2 fp16 (mode 2)
-    int fimg_n = 0, bimg_n = 0;
+    DecImage img[NSK_NUM_IMAGES];                 // by `what` of nsk_images.h; 2 and 3 of the coarse decoder stay empty
     int trainable = 0;
     bool loaded = false;
     size_t g_off = 0;
@@ -1158,7 +1155,7 @@ extern "C" int nsk_sync(nsk_ctx* c)
 }
 extern "C" void* nsk_stream(nsk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
-static int repack16(nsk_ctx* c, int w);
+static int pack_image(nsk_ctx* c, DecState& D, int what);
 extern "C" int nsk_set_matmul_mode(nsk_ctx* c, int mode)
 {
     if (!c) return fail("null ctx");
@@ -1168,7 +1165,7 @@ extern "C" int nsk_set_matmul_mode(nsk_ctx* c, int mode)
     c->matmul_mode = mode;
     if (relayout) {              // the forward images change their piece format: rebuild those of the loaded decoders
         HIPCHK(hipSetDevice(c->device));
-        for (int w = 1; w < 4; ++w) if (c->dec[w].loaded && c->dec[w].fimg16) CHK(repack16(c, w));
+        for (int w = 1; w < 4; ++w) if (c->dec[w].loaded) CHK(pack_image(c, c->dec[w], 2));
         invalidate_graphs(c);
     }
     return 0;
@@ -1385,142 +1382,37 @@ extern "C" int nsk_set_mask(nsk_ctx* c, int level, const uint8_t* h_mask)
 }
 
 // ---- decoder images -------------------------------------------------------------------------------------
-static void seg_fwd(std::vector<int>& idx, int quad0, int KQ, int Wofs, int ld, int col0, int kvalid)
+// One image from the parameters (tables and sizes: nsk_images.h): the fragments through its table, the fp32 tail through the sibling's.  The
+// forward image in pieces takes its piece count from the matmul mode: 2 fp16 under mode 2, 3 bf16 under modes 0 and 1 (mode 0 reads the fp32
+// image; the 3-piece one is kept so that a switch to mode 1 changes no layout).
+static int pack_image(nsk_ctx* c, DecState& D, int what)
 {
-    for (int rt = 0; rt < 2; ++rt) for (int q = 0; q < KQ; ++q) for (int lane = 0; lane < 64; ++lane) for (int i = 0; i < 4; ++i) {
-        int o = 16 * rt + (lane & 15), k = 16 * q + 4 * (lane >> 4) + i;
-        idx[((size_t)(quad0 + rt * KQ + q) * 64 + lane) * 4 + i] = k < kvalid ? Wofs + o * ld + col0 + k : -1;
-    }
-}
-static void seg_bwd(std::vector<int>& idx, int quad0, int RT, int Wofs, int ld, int col0, int rvalid)
-{
-    const int KQ = 2;
-    for (int rt = 0; rt < RT; ++rt) for (int q = 0; q < KQ; ++q) for (int lane = 0; lane < 64; ++lane) for (int i = 0; i < 4; ++i) {
-        int r = 16 * rt + (lane & 15), k = 16 * q + 4 * (lane >> 4) + i;
-        idx[((size_t)(quad0 + rt * KQ + q) * 64 + lane) * 4 + i] = r < rvalid ? Wofs + k * ld + col0 + r : -1;
-    }
-}
-
-template <int CQ>
-static void build_mlp_fwd_idx(const DecLayout& L, std::vector<int>& idx)
-{
-    typedef MlpFwdImg<CQ> I;
-    idx.assign(I::TOTAL, -1);
-    seg_fwd(idx, I::W0E, 6, L.oW[0], NSK_E, 0, NSK_E);
-    for (int l = 0; l < 5; ++l) seg_fwd(idx, I::F(l), CQ, L.oFw[l], L.c_dim, 0, L.c_dim);
-    seg_fwd(idx, I::W1, 2, L.oW[1], 32, 0, 32);
-    seg_fwd(idx, I::W2, 2, L.oW[2], 32, 0, 32);
-    seg_fwd(idx, I::W3E, 6, L.oW[3], 125, 0, NSK_E);
-    seg_fwd(idx, I::W3H, 2, L.oW[3], 125, NSK_E, 32);
-    seg_fwd(idx, I::W4, 2, L.oW[4], 32, 0, 32);
-    for (int l = 0; l < 5; ++l) for (int o = 0; o < 32; ++o) { idx[I::P_B + 32 * l + o] = L.ob[l] + o; idx[I::P_BC + 32 * l + o] = L.oFb[l] + o; }
-    for (int o = 0; o < L.out_dim; ++o) { for (int k = 0; k < 32; ++k) idx[I::P_WO + 32 * o + k] = L.oWo + 32 * o + k; idx[I::P_BO + o] = L.obo + o; }
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < NSK_E; ++k) idx[I::P_BM + 96 * a + k] = L.oB + NSK_E * a + k;
+    DecImage& I = D.img[what];
+    if (!I.data) return 0;
+    if (what == 2) I.spec = with_pieces(I.spec, c->matmul_mode == 2 ? 2 : 3);
+    const ImageSpec& s = I.spec;
+    if (s.pieces) k_pack_bf16<<<(s.entries + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(I.data.get()), I.idx, D.p, s.entries, s.pieces);
+    else k_pack<<<(s.entries + 255) / 256, 256, 0, c->stream>>>(I.data, I.idx, D.p, s.entries);
+    if (s.tail_n) k_pack<<<(s.tail_n + 255) / 256, 256, 0, c->stream>>>(I.data + s.tail_off, D.img[what - 2].idx + s.sib_off, D.p, s.tail_n);
+    HIPCHK(hipGetLastError());
+    I.dirty = false;
+    return 0;
 }
 
-static void build_idx(int w, std::vector<int>& fidx, std::vector<int>& bidx)
+// the fp16 backward image follows the parameters lazily: marked stale by uploads, rebuilt before use (the optimiser launch rewrites it in place)
+static int ensure_image(nsk_ctx* c, int w, int what)
 {
-    DecLayout L = nsk_dec_layout(w);
-    if (w == 0) {
-        typedef CoarseFwdImg I; typedef CoarseBwdImg J;
-        fidx.assign(I::TOTAL, -1); bidx.assign(J::TOTAL, -1);
-        seg_fwd(fidx, I::W0, 2, L.oW[0], 32, 0, 32); seg_fwd(fidx, I::W1, 2, L.oW[1], 32, 0, 32); seg_fwd(fidx, I::W2, 2, L.oW[2], 32, 0, 32);
-        seg_fwd(fidx, I::W3C, 2, L.oW[3], 64, 0, 32); seg_fwd(fidx, I::W3H, 2, L.oW[3], 64, 32, 32); seg_fwd(fidx, I::W4, 2, L.oW[4], 32, 0, 32);
-        for (int l = 0; l < 5; ++l) for (int o = 0; o < 32; ++o) fidx[I::P_B + 32 * l + o] = L.ob[l] + o;
-        for (int k = 0; k < 32; ++k) fidx[I::P_WO + k] = L.oWo + k;
-        fidx[I::P_BO] = L.obo;
-        seg_bwd(bidx, J::W0T, 2, L.oW[0], 32, 0, 32); seg_bwd(bidx, J::W1T, 2, L.oW[1], 32, 0, 32); seg_bwd(bidx, J::W2T, 2, L.oW[2], 32, 0, 32);
-        seg_bwd(bidx, J::W3CT, 2, L.oW[3], 64, 0, 32); seg_bwd(bidx, J::W3HT, 2, L.oW[3], 64, 32, 32); seg_bwd(bidx, J::W4T, 2, L.oW[4], 32, 0, 32);
-        for (int k = 0; k < 32; ++k) bidx[J::P_WO + k] = L.oWo + k;
-        return;
-    }
-    if (w == 2) build_mlp_fwd_idx<4>(L, fidx); else build_mlp_fwd_idx<2>(L, fidx);
-    typedef MlpBwdImg J;
-    bidx.assign(J::TOTAL, -1);
-    for (int l = 0; l < 5; ++l) seg_bwd(bidx, J::FT(l), 2, L.oFw[l], L.c_dim, 0, 32);
-    for (int l = 1; l < 5; ++l) seg_bwd(bidx, J::WT(l), 2, L.oW[l], L.in_dim[l], l == 3 ? NSK_E : 0, 32);
-    seg_bwd(bidx, J::W0ET, 6, L.oW[0], NSK_E, 0, NSK_E);
-    seg_bwd(bidx, J::W3ET, 6, L.oW[3], 125, 0, NSK_E);
-    for (int o = 0; o < L.out_dim; ++o) for (int k = 0; k < 32; ++k) bidx[J::P_WO + 32 * o + k] = L.oWo + 32 * o + k;
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < NSK_E; ++k) bidx[J::P_BM + 96 * a + k] = L.oB + NSK_E * a + k;
-}
-
-static void seg16(std::vector<int>& idx, int blk0, int NB, int Wofs, int ld, int col0, int kvalid)
-{
-    for (int b = 0; b < NB; ++b) for (int rt = 0; rt < 2; ++rt) for (int lane = 0; lane < 64; ++lane) for (int j = 0; j < 8; ++j) {
-        int fg = 2 * (blk0 + b) + rt, o = 16 * rt + (lane & 15), k = 32 * b + nsk_bf16_kperm(lane >> 4, j);
-        idx[((size_t)fg * 64 + lane) * 8 + j] = k < kvalid ? Wofs + o * ld + col0 + k : -1;
-    }
-}
-template <int CQ>
-static void build_idx16(const DecLayout& L, std::vector<int>& idx)
-{
-    typedef MlpFwdImgB<CQ> I;
-    idx.assign((size_t)I::NBLK * 2 * 512, -1);
-    seg16(idx, I::W0E, 3, L.oW[0], NSK_E, 0, NSK_E);
-    for (int l = 0; l < 5; ++l) seg16(idx, I::F(l), I::CB, L.oFw[l], L.c_dim, 0, L.c_dim);
-    seg16(idx, I::W1, 1, L.oW[1], 32, 0, 32); seg16(idx, I::W2, 1, L.oW[2], 32, 0, 32); seg16(idx, I::W4, 1, L.oW[4], 32, 0, 32);
-    seg16(idx, I::W3E, 3, L.oW[3], 125, 0, NSK_E); seg16(idx, I::W3H, 1, L.oW[3], 125, NSK_E, 32);
-}
-
-static void build_idx16b(const DecLayout& L, std::vector<int>& idx)
-{
-    typedef MlpBwdImgH J;
-    idx.assign((size_t)J::NFG * 512, -1);
-    auto seg = [&](int fg0, int nrt, int Wofs, int ld, int col0, int rows) {   // transposed: row o = input column, k = output row of the forward weight
-        for (int rt = 0; rt < nrt; ++rt) for (int lane = 0; lane < 64; ++lane) for (int j = 0; j < 8; ++j) {
-            const int o = 16 * rt + (lane & 15), k = nsk_bf16_kperm(lane >> 4, j);
-            idx[((size_t)(fg0 + rt) * 64 + lane) * 8 + j] = o < rows ? Wofs + k * ld + col0 + o : -1;
-        }
-    };
-    for (int l = 0; l < 5; ++l) seg(J::FT(l), 2, L.oFw[l], L.c_dim, 0, 32);
-    for (int l = 1; l < 5; ++l) seg(J::WT(l), 2, L.oW[l], L.in_dim[l], l == 3 ? NSK_E : 0, 32);
-    seg(J::W0ET, 6, L.oW[0], NSK_E, 0, NSK_E);
-    seg(J::W3ET, 6, L.oW[3], 125, 0, NSK_E);
-}
-
-// the fp16 backward image (MlpBwdImgH) follows the parameters lazily: marked stale by uploads and by Adam steps on a decoder whose image
-// the optimiser launch does not rewrite itself, rebuilt before use
-static int ensure_bimg16(nsk_ctx* c, int w)
-{
-    DecState& D = c->dec[w];
-    if (!D.bimg16 || !D.bimg16_dirty) return 0;
+    if (!c->dec[w].img[what].dirty) return 0;
     ProfScope ps(c, "pack_bwd_bf16");
-    k_pack_bf16<<<(D.bfrag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.bimg16.get()), D.bidx16, D.p, D.bfrag16_n, 2);
-    k_pack<<<2, 256, 0, c->stream>>>(D.bimg16 + MlpBwdImgH::P_WO, D.bidx + MlpBwdImg::P_WO, D.p, 128 + 288);     // fp32 tail: Wo, B
-    HIPCHK(hipGetLastError());
-    D.bimg16_dirty = false;
-    return 0;
-}
-
-// the forward image holds 3 bf16 pieces (matmul modes 0 / 1) or 2 fp16 pieces (mode 2) per weight; the fp32 tail follows the fragments
-static void set_np16(DecState& D, int np)
-{
-    D.np16 = np;
-    if (D.cq16 == 4) { D.fimg16_f = np == 2 ? MlpFwdImgB<4, 2>::TOTAL_F : MlpFwdImgB<4, 3>::TOTAL_F; D.tail16_off = np == 2 ? MlpFwdImgB<4, 2>::P_F32 : MlpFwdImgB<4, 3>::P_F32; }
-    else { D.fimg16_f = np == 2 ? MlpFwdImgB<2, 2>::TOTAL_F : MlpFwdImgB<2, 3>::TOTAL_F; D.tail16_off = np == 2 ? MlpFwdImgB<2, 2>::P_F32 : MlpFwdImgB<2, 3>::P_F32; }
-}
-
-static int repack16(nsk_ctx* c, int w)
-{
-    DecState& D = c->dec[w];
-    if (!D.fimg16) return 0;
-    set_np16(D, c->matmul_mode == 2 ? 2 : 3);
-    k_pack_bf16<<<(D.frag16_n + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<unsigned short*>(D.fimg16.get()), D.fidx16, D.p, D.frag16_n, D.np16);
-    k_pack<<<(740 + 255) / 256, 256, 0, c->stream>>>(D.fimg16 + D.tail16_off, D.fidx + D.tail_off, D.p, 740);     // fp32 tail: biases, Wo, bo, B
-    HIPCHK(hipGetLastError());
-    return 0;
+    return pack_image(c, c->dec[w], what);
 }
 
 static int repack(nsk_ctx* c, int w)
 {
     DecState& D = c->dec[w];
     ProfScope ps(c, "pack_images");
-    k_pack<<<(D.fimg_n + 255) / 256, 256, 0, c->stream>>>(D.fimg, D.fidx, D.p, D.fimg_n);
-    k_pack<<<(D.bimg_n + 255) / 256, 256, 0, c->stream>>>(D.bimg, D.bidx, D.p, D.bimg_n);
-    HIPCHK(hipGetLastError());
-    CHK(repack16(c, w));
-    D.bimg16_dirty = true;
+    for (int what = 0; what < 3; ++what) CHK(pack_image(c, D, what));
+    D.img[3].dirty = (bool)D.img[3].data;
     return 0;
 }
 
@@ -1539,37 +1431,22 @@ static int dec_setup(int w, size_t n, DecState& D)
         HIPCHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
         return 0;
     };
-    // image position of each canonical parameter (-1 none)
-    auto inverse = [&](Buf<int>& d, const std::vector<int>& idx, const char* image) -> int {
-        std::vector<int> inv(n4, -1);
-        for (size_t k = 0; k < idx.size(); ++k) if (idx[k] >= 0) { if (inv[idx[k]] != -1) return fail("decoder %d: parameter %d appears twice in the %s image", w, idx[k], image); inv[idx[k]] = (int)k; }
-        return table(d, inv, "a decoder's inverse index table");
-    };
     CHK(dev_alloc(D.p, n4, "a decoder's parameters")); CHK(dev_alloc(D.m, n4, "a decoder's first moment")); CHK(dev_alloc(D.s, n4, "a decoder's second moment"));
     HIPCHK(hipMemset(D.p, 0, n4 * 4));
-    std::vector<int> fi, bi;
-    build_idx(w, fi, bi);
-    D.fimg_n = (int)fi.size(); D.bimg_n = (int)bi.size();
-    CHK(dev_alloc(D.fimg, fi.size(), "a decoder's forward image")); CHK(dev_alloc(D.bimg, bi.size(), "a decoder's backward image"));
-    CHK(table(D.fidx, fi, "a decoder's index table")); CHK(table(D.bidx, bi, "a decoder's index table"));
-    if (w != 0) {
-        std::vector<int> i16;
-        if (w == 2) { build_idx16<4>(nsk_dec_layout(w), i16); D.cq16 = 4; D.tail_off = MlpFwdImg<4>::P_B; }
-        else { build_idx16<2>(nsk_dec_layout(w), i16); D.cq16 = 2; D.tail_off = MlpFwdImg<2>::P_B; }
-        set_np16(D, 3);          // allocate for the larger (3-piece) form
-        D.frag16_n = (int)i16.size();
-        CHK(dev_alloc(D.fimg16, (size_t)D.fimg16_f, "a decoder's forward image in pieces")); CHK(table(D.fidx16, i16, "a decoder's index table"));
-        HIPCHK(hipMemset(D.fimg16, 0, (size_t)D.fimg16_f * 4));
-        std::vector<int> ib;
-        build_idx16b(nsk_dec_layout(w), ib);
-        D.bfrag16_n = (int)ib.size();
-        CHK(dev_alloc(D.bimg16, (size_t)MlpBwdImgH::TOTAL_F, "a decoder's backward image in pieces")); CHK(table(D.bidx16, ib, "a decoder's index table"));
-        HIPCHK(hipMemset(D.bimg16, 0, (size_t)MlpBwdImgH::TOTAL_F * 4));
-        CHK(inverse(D.invh, ib, "fp16 backward"));
-        CHK(inverse(D.inv16, i16, "bf16"));
+    static const char* const names[NSK_NUM_IMAGES] = {"forward", "backward", "forward in pieces", "fp16 backward"};
+    std::vector<int> idx, inv;
+    for (int what = 0; what < NSK_NUM_IMAGES; ++what) {
+        DecImage& I = D.img[what];
+        I.spec = image_spec(w, what, 3);          // the forward image in pieces is allocated for its larger (3-piece) form
+        if (!I.spec.floats) continue;
+        build_image_table(w, what, idx);
+        CHK(dev_alloc(I.data, (size_t)I.spec.floats, "a decoder's image"));
+        if (I.spec.pieces) HIPCHK(hipMemset(I.data, 0, (size_t)I.spec.floats * 4));
+        CHK(table(I.idx, idx, "a decoder's index table"));
+        const int twice = invert_table(idx, n4, inv);      // image position of each canonical parameter (-1 none)
+        if (twice >= 0) return fail("decoder %d: parameter %d appears twice in the %s image", w, twice, names[what]);
+        CHK(table(I.inv, inv, "a decoder's inverse index table"));
     }
-    CHK(inverse(D.finv, fi, "forward"));
-    CHK(inverse(D.binv, bi, "backward"));
     D.n = (int)n;
     return 0;
 }
@@ -1703,11 +1580,12 @@ static void fill_args(nsk_ctx* c, DecArgs& A, int w, int M, int S, const float* 
     memcpy(A.bound, c->R.bound, sizeof(A.bound));
     A.grid = grid_dev(c, w, false);
     if (w == 2) A.grid_mid = grid_dev(c, 1, false);
-    A.img = reinterpret_cast<const f4*>(c->dec[w].fimg.get());
-    A.bimg = reinterpret_cast<const f4*>(c->dec[w].bimg.get());
-    A.img_f4 = c->dec[w].fimg_n / 4;
-    A.img16 = c->dec[w].fimg16;
-    A.bimg16 = c->dec[w].bimg16;
+    const DecImage* I = c->dec[w].img;
+    A.img = reinterpret_cast<const f4*>(I[0].data.get());
+    A.bimg = reinterpret_cast<const f4*>(I[1].data.get());
+    A.img_f4 = I[0].spec.floats / 4;
+    A.img16 = I[2].data;
+    A.bimg16 = I[3].data;
     A.out = w == 3 ? c->ws.rgb4 : c->ws.occ[w];
 }
 
@@ -1765,7 +1643,7 @@ static int fill_bwd_role(nsk_ctx* c, DecArgs& A, int w, int M, int S, const floa
     A.g_raw = c->ws.g_raw;
     A.g_rays_o = g_ro; A.g_rays_d = g_rd;
     A.g_dec = train ? c->ws.dec_slabs : c->slab + c->dec[w].g_off;
-    if (w != 0 && (!train || w != 2)) CHK(ensure_bimg16(c, w));      // the chains on fp16 pieces: every frozen MLP decoder, trainable middle / colour
+    if (w != 0 && (!train || w != 2)) CHK(ensure_image(c, w, 3));      // the chains on fp16 pieces: every frozen MLP decoder, trainable middle / colour
     if (train && w != 2) {
         if (c->ws.hsave_M[w] != M) return fail("backward of trainable decoder %d: its forward must run with the decoder already trainable (block outputs not saved)", w);
         A.hsave = c->ws.hsave[w];
@@ -1837,12 +1715,12 @@ static int launch_decode_fwd_stage(nsk_ctx* c, int stage, int M, int S, const fl
     }
     ProfScope ps(c, "decode_fwd_multi");
     if (P.merged) {
-        size_t lds_occ = ((size_t)c->dec[1].fimg16_f + (size_t)c->dec[2].fimg16_f) * 4;
-        if (n == 3) lds_occ = std::max(lds_occ, (size_t)c->dec[3].fimg16_f * 4);
+        size_t lds_occ = ((size_t)c->dec[1].img[2].spec.floats + (size_t)c->dec[2].img[2].spec.floats) * 4;
+        if (n == 3) lds_occ = std::max(lds_occ, (size_t)c->dec[3].img[2].spec.floats * 4);
         k_decode_fwd_multi_occ<8><<<MA.wg_end[MA.n - 1], 512, lds_occ, c->stream>>>(MA);
     } else if (c->matmul_mode != 0) {
         size_t lds16 = 0;
-        for (int r = 0; r < n; ++r) lds16 = std::max(lds16, MA.which[r] == 0 ? fwd_img_floats(0) * 4 : (size_t)c->dec[MA.which[r]].fimg16_f * 4);
+        for (int r = 0; r < n; ++r) lds16 = std::max(lds16, MA.which[r] == 0 ? fwd_img_floats(0) * 4 : (size_t)c->dec[MA.which[r]].img[2].spec.floats * 4);
         if (c->matmul_mode == 2) k_decode_fwd_multi_bf16<8, 2><<<MA.wg_end[n - 1], 512, lds16, c->stream>>>(MA);
         else k_decode_fwd_multi_bf16<8><<<MA.wg_end[n - 1], 512, lds16, c->stream>>>(MA);       // 12 waves (168 VGPRs) spill: 59 -> 71 us (the two-piece form at 12 waves: 50 spilled registers, K3 forward 139 -> 202 us, round 4)
     } else
@@ -3027,7 +2905,7 @@ extern "C" int nsk_debug_last_split(nsk_ctx* c, int dir, int* h_out)
     return 0;
 }
 // one of a decoder's device images, to the host (layout: include/nsk.h).  Reads only: the one thing it may launch is the rebuild of a stale fp16
-// backward image (ensure_bimg16), which the next backward that reads that image would launch itself.
+// backward image (ensure_image), which the next backward that reads that image would launch itself.
 extern "C" int nsk_debug_decoder_images(nsk_ctx* c, int which, int what, void* h_out, size_t capacity)
 {
     if (!c || !which_ok(which)) return fail("nsk_debug_decoder_images: bad argument");
@@ -3036,10 +2914,9 @@ extern "C" int nsk_debug_decoder_images(nsk_ctx* c, int which, int what, void* h
     DecState& D = c->dec[which];
     if (!D.loaded) return fail("decoder %d not uploaded", which);
     HIPCHK(hipSetDevice(c->device));
-    if (what == 3) CHK(ensure_bimg16(c, which));
-    const float* src = what == 0 ? D.fimg.get() : (what == 1 ? D.bimg.get() : (what == 2 ? D.fimg16.get() : D.bimg16.get()));
-    const size_t floats = what == 0 ? (size_t)D.fimg_n : (what == 1 ? (size_t)D.bimg_n : (what == 2 ? (size_t)D.fimg16_f : (size_t)MlpBwdImgH::TOTAL_F));
-    const size_t bytes = src ? floats * 4 : 0;               // the coarse decoder has no image in pieces
+    CHK(ensure_image(c, which, what));
+    const float* src = D.img[what].data;
+    const size_t bytes = (size_t)D.img[what].spec.floats * 4;               // 0: the coarse decoder has no image in pieces
     if (bytes > (size_t)0x7fffffff) return fail("nsk_debug_decoder_images: image too large");
     if (h_out && bytes) {
         if (capacity < bytes) return fail("nsk_debug_decoder_images: the image has %zu bytes, the buffer %zu", bytes, capacity);
@@ -3047,6 +2924,21 @@ extern "C" int nsk_debug_decoder_images(nsk_ctx* c, int which, int what, void* h
         HIPCHK(hipMemcpy(h_out, src, bytes, hipMemcpyDeviceToHost));
     }
     return (int)bytes;
+}
+// the index table behind one of those images (nsk_images.h); needs no context and no device
+extern "C" int nsk_decoder_image_table(int which, int what, int pieces, int32_t* h_idx, size_t capacity)
+{
+    if (!which_ok(which)) return fail("nsk_decoder_image_table: decoder %d out of range", which);
+    if (what < 0 || what >= NSK_NUM_IMAGES) return fail("nsk_decoder_image_table: what = 0 (fp32 forward), 1 (fp32 backward), 2 (forward in pieces), 3 (fp16 backward)");
+    if (pieces != 2 && pieces != 3) return fail("nsk_decoder_image_table: pieces = 2 (fp16) or 3 (bf16)");
+    const int n = image_spec(which, what, pieces).entries;
+    if (h_idx && n) {
+        if (capacity < (size_t)n) return fail("nsk_decoder_image_table: the table has %d entries, capacity %zu", n, capacity);
+        std::vector<int> idx;
+        build_image_table(which, what, idx);
+        memcpy(h_idx, idx.data(), (size_t)n * 4);
+    }
+    return n;
 }
 // the ReLU inputs of decoder `which` over the samples of the last step (same rays), by the forward body of the current matmul mode
 extern "C" int nsk_debug_preact(nsk_ctx* c, int which, int N, const float* ro, const float* rd, float* d_out /*[M][5][32] device*/)
@@ -3061,8 +2953,8 @@ extern "C" int nsk_debug_preact(nsk_ctx* c, int which, int N, const float* ro, c
     A.dump = d_out;
     const int grid = std::max(1, std::min(((M + 15) / 16 + 7) / 8, c->num_cu));
     if (c->matmul_mode == 0) k_decode_fwd_dump<0><<<grid, 512, fwd_img_floats(which) * 4, c->stream>>>(A, which);
-    else if (c->matmul_mode == 1) k_decode_fwd_dump<1><<<grid, 512, (size_t)c->dec[which].fimg16_f * 4, c->stream>>>(A, which);
-    else k_decode_fwd_dump<2><<<grid, 512, (size_t)c->dec[which].fimg16_f * 4, c->stream>>>(A, which);
+    else if (c->matmul_mode == 1) k_decode_fwd_dump<1><<<grid, 512, (size_t)c->dec[which].img[2].spec.floats * 4, c->stream>>>(A, which);
+    else k_decode_fwd_dump<2><<<grid, 512, (size_t)c->dec[which].img[2].spec.floats * 4, c->stream>>>(A, which);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4058,6 +3950,15 @@ extern "C" int nsk_adam_vector(nsk_ctx* c, int n, float* p, const float* g, floa
 }
 
 // ---- optimiser ------------------------------------------------------------------------------------------------
+// where the launch rewrites a trainable decoder's images: every image the decoder has, image 3 included (it stays as fresh or as stale as it was)
+static void adam_images(AdamSeg& S, DecState& D)
+{
+    const DecImage* I = D.img;
+    S.inv_f = I[0].inv; S.inv_b = I[1].inv; S.fimg = I[0].data; S.bimg = I[1].data;
+    if (I[2].data) { S.inv16 = I[2].inv; S.img16 = reinterpret_cast<unsigned short*>(I[2].data.get()); S.img16_tail = I[2].data + I[2].spec.tail_off; S.tail_off = I[2].spec.sib_off; S.np16 = I[2].spec.pieces; }
+    if (I[3].data) { S.invh = I[3].inv; S.imgh = reinterpret_cast<unsigned short*>(I[3].data.get()); S.imgh_tail = I[3].data + I[3].spec.tail_off; S.btail_off = I[3].spec.sib_off; }
+}
+
 extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b1, float b2, float eps)
 {
     if (!c || !lr) return fail("nsk_adam_step: null argument");
@@ -4092,14 +3993,11 @@ extern "C" int nsk_adam_step(nsk_ctx* c, const float lr[NSK_NUM_GROUPS], float b
             AdamSeg& S = AA.s[AA.n++];
             adam_consts(lr[NSK_GROUP_DECODERS], b1, b2, step, S.step_size, S.bc2s);
             S.p = D.p; S.g = c->slab + D.g_off; S.m = D.m; S.v = D.s; S.idx = nullptr; S.nidx = 0; S.n = n4;
-            S.inv_f = D.finv; S.inv_b = D.binv; S.fimg = D.fimg; S.bimg = D.bimg;
-            if (D.bimg16) { S.invh = D.invh; S.imgh = reinterpret_cast<unsigned short*>(D.bimg16.get()); S.imgh_tail = D.bimg16 + MlpBwdImgH::P_WO; S.btail_off = MlpBwdImg::P_WO; }
-            else D.bimg16_dirty = true;
+            adam_images(S, D);
             if (c->pend_w == w) {
                 S.slabs = c->ws.dec_slabs; S.nslabs = c->pend_nb; S.slab_stride = n4; c->pend_w = -1;
                 blocks += (n4 / 4 + 7) / 8 - (n4 / 4 + 255) / 256;         // 8 float4 per block (see k_adam_multi)
             }
-            if (D.fimg16) { S.inv16 = D.inv16; S.img16 = reinterpret_cast<unsigned short*>(D.fimg16.get()); S.img16_tail = D.fimg16 + D.tail16_off; S.tail_off = D.tail_off; S.np16 = D.np16; }
             blocks += (n4 / 4 + 255) / 256; S.blk_end = blocks;
         }
         c->touched[NSK_GROUP_DECODERS] = false;

@@ -16,34 +16,7 @@
 #pragma once
 #include "nsk_device.h"
 
-template <int CQ, int NP = 3>                     // NP pieces per weight: 3 = bf16 split (mode 1), 2 = fp16 split (mode 2)
-struct MlpFwdImgB {                               // block (K=32) indices of the segments; fragment group = 2*blk + rt
-    static constexpr int CB = CQ / 2;
-    static constexpr int W0E = 0;                 // 3 blocks
-    static constexpr int F0 = W0E + 3;
-    static constexpr int W1 = F0 + CB;
-    static constexpr int F1 = W1 + 1;
-    static constexpr int W2 = F1 + CB;
-    static constexpr int F2 = W2 + 1;
-    static constexpr int W3E = F2 + CB;           // 3 blocks
-    static constexpr int W3H = W3E + 3;
-    static constexpr int F3 = W3H + 1;
-    static constexpr int W4 = F3 + CB;
-    static constexpr int F4 = W4 + 1;
-    static constexpr int NBLK = F4 + CB;          // 15 (CQ=2), 20 (CQ=4)
-    static constexpr int FRAG_BYTES = NBLK * 2 * NP * 1024;
-    static constexpr int P_F32 = FRAG_BYTES / 4;  // float offset of the plain fp32 tail (same order as MlpFwdImg)
-    static constexpr int P_B = P_F32;
-    static constexpr int P_BC = P_B + 160;
-    static constexpr int P_WO = P_BC + 160;
-    static constexpr int P_BO = P_WO + 128;
-    static constexpr int P_BM = P_BO + 4;
-    static constexpr int TOTAL_F = P_BM + 288;    // total size in floats
-    __host__ __device__ static constexpr int W(int l) { return l == 1 ? W1 : (l == 2 ? W2 : (l == 4 ? W4 : -1)); }
-    __host__ __device__ static constexpr int F(int l) { return l == 0 ? F0 : (l == 1 ? F1 : (l == 2 ? F2 : (l == 3 ? F3 : F4))); }
-};
-
-__host__ __device__ inline int nsk_bf16_kperm(int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); }
+// MlpFwdImgB (the image's segments) and nsk_bf16_kperm (f above): nsk_layout.h
 
 // the pieces of one weight: np = 3 -> bf16 h, m, l; np = 2 -> fp16 h and the 2048-fold low piece
 __device__ __forceinline__ void store_pieces(unsigned short* __restrict__ img, int t, float x, int np)

@@ -608,20 +608,7 @@ __device__ __forceinline__ H2 mask_block_h(const H2& x, unsigned bits)
     return r;
 }
 
-// Backward (transposed) image of an MLP decoder in fp16 pieces (two per weight, the low one 2048-fold), K = 32 output features each:
-// fragment group FT(l) + rt: fc[l]^T rows 16rt.. (grid features 0..31); WT(l) + rt: pts_linear[l]^T (h part); W0ET / W3ET + rt: the
-// e parts of pts_linear[0] / [3] transposed (96 rows, rt < 6).  Used by the frozen decoders' chain (the first 18 groups) and by the
-// trainable decoder's chain (all of it).  The fp32 tail is the one of MlpBwdImg (output weight, embedding matrix): same total size.
-struct MlpBwdImgH {
-    static constexpr int NFG = 30;
-    static constexpr int FRAG_BYTES = NFG * 2 * 1024;
-    static constexpr int P_WO = FRAG_BYTES / 4;      // float offset of the output weight [4][32]
-    static constexpr int P_BM = P_WO + 128;          // embedding B [3][96]
-    static constexpr int TOTAL_F = P_BM + 288;
-    static constexpr int W0ET = 18, W3ET = 24;
-    __host__ __device__ static constexpr int FT(int l) { return 2 * l; }
-    __host__ __device__ static constexpr int WT(int l) { return 10 + 2 * (l - 1); }
-};
+// MlpBwdImgH, the backward (transposed) image in fp16 pieces these read: nsk_layout.h
 // accH[rt] / accL[rt] += (fragment groups fg0, fg0+1) x   (three fp16 MFMAs per row tile)
 __device__ __forceinline__ void gemm_h(const h8* __restrict__ img, int fg0, int lane, const H2& x, f4 (&accH)[2], f4 (&accL)[2])
 {
@@ -885,7 +872,7 @@ struct DecArgs {
     const f4* img;            // forward image (global)
     const void* img16;        // bf16 3-piece forward image (nsk_bf16.h) or nullptr
     const f4* bimg;           // backward image (global)
-    const void* bimg16;       // bf16 3-piece backward image (MlpBwdImgB) or nullptr
+    const void* bimg16;       // fp16 2-piece backward image (MlpBwdImgH) or nullptr
     int img_f4;               // forward image size in f4
     float* out;               // occupancy [M] (which<3) or rgb4 [M][4] (color)
     unsigned long long* masks;   // [M][4] ReLU bits or nullptr

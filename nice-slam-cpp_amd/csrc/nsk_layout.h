@@ -10,7 +10,17 @@
 // A "quad" is 64 lanes x 4 floats = 256 floats = 1 KiB.
 #pragma once
 
-#define NSK_E 93        // GaussianFFT mapping size (reference src/models/MLP.cpp:21)
+// a plain host compiler reads this header too (nsk_images.h, host/test/images_test.cpp)
+#ifndef __HIPCC__
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
+
+#define NSK_E 93       // GaussianFFT mapping size (reference src/models/MLP.cpp:21)
 #define NSK_HID 32        // hidden size (reference src/main.cpp:29)
 
 // ---- forward image of MLP (middle / fine / color), CQ = c_dim/16 --------------------------------------
@@ -50,6 +60,52 @@ struct MlpBwdImg {
     static constexpr int TOTAL = P_BM + 288;
     __host__ __device__ static constexpr int FT(int l) { return FT0 + 4 * l; }
     __host__ __device__ static constexpr int WT(int l) { return WT1 + 4 * (l - 1); }
+};
+
+// ---- forward image of MLP in 16-bit pieces (nsk_bf16.h): fragments of K = 32, then the fp32 tail of MlpFwdImg -------
+template <int CQ, int NP = 3>                     // NP pieces per weight: 3 = bf16 split (mode 1), 2 = fp16 split (mode 2)
+struct MlpFwdImgB {                               // block (K=32) indices of the segments; fragment group = 2*blk + rt
+    static constexpr int CB = CQ / 2;
+    static constexpr int W0E = 0;                 // 3 blocks
+    static constexpr int F0 = W0E + 3;
+    static constexpr int W1 = F0 + CB;
+    static constexpr int F1 = W1 + 1;
+    static constexpr int W2 = F1 + CB;
+    static constexpr int F2 = W2 + 1;
+    static constexpr int W3E = F2 + CB;           // 3 blocks
+    static constexpr int W3H = W3E + 3;
+    static constexpr int F3 = W3H + 1;
+    static constexpr int W4 = F3 + CB;
+    static constexpr int F4 = W4 + 1;
+    static constexpr int NBLK = F4 + CB;          // 15 (CQ=2), 20 (CQ=4)
+    static constexpr int FRAG_BYTES = NBLK * 2 * NP * 1024;
+    static constexpr int P_F32 = FRAG_BYTES / 4;  // float offset of the plain fp32 tail (same order as MlpFwdImg)
+    static constexpr int P_B = P_F32;
+    static constexpr int P_BC = P_B + 160;
+    static constexpr int P_WO = P_BC + 160;
+    static constexpr int P_BO = P_WO + 128;
+    static constexpr int P_BM = P_BO + 4;
+    static constexpr int TOTAL_F = P_BM + 288;    // total size in floats
+    __host__ __device__ static constexpr int W(int l) { return l == 1 ? W1 : (l == 2 ? W2 : (l == 4 ? W4 : -1)); }
+    __host__ __device__ static constexpr int F(int l) { return l == 0 ? F0 : (l == 1 ? F1 : (l == 2 ? F2 : (l == 3 ? F3 : F4))); }
+};
+
+// the k order of a 16-bit fragment: lane group g supplies k = f(g, j), j < 8 (nsk_bf16.h)
+__host__ __device__ inline int nsk_bf16_kperm(int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); }
+
+// Backward (transposed) image of an MLP decoder in fp16 pieces (two per weight, the low one 2048-fold), K = 32 output features each:
+// fragment group FT(l) + rt: fc[l]^T rows 16rt.. (grid features 0..31); WT(l) + rt: pts_linear[l]^T (h part); W0ET / W3ET + rt: the
+// e parts of pts_linear[0] / [3] transposed (96 rows, rt < 6).  Used by the frozen decoders' chain (the first 18 groups) and by the
+// trainable decoder's chain (all of it).  The fp32 tail is the one of MlpBwdImg (output weight, embedding matrix): same total size.
+struct MlpBwdImgH {
+    static constexpr int NFG = 30;
+    static constexpr int FRAG_BYTES = NFG * 2 * 1024;
+    static constexpr int P_WO = FRAG_BYTES / 4;      // float offset of the output weight [4][32]
+    static constexpr int P_BM = P_WO + 128;          // embedding B [3][96]
+    static constexpr int TOTAL_F = P_BM + 288;
+    static constexpr int W0ET = 18, W3ET = 24;
+    __host__ __device__ static constexpr int FT(int l) { return 2 * l; }
+    __host__ __device__ static constexpr int WT(int l) { return 10 + 2 * (l - 1); }
 };
 
 // ---- coarse decoder (MLP_no_xyz) ----------------------------------------------------------------------

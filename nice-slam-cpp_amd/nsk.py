@@ -24,7 +24,7 @@ SYMBOLS = (
     "nsk_camera_from_tensor", "nsk_camera_backward", "nsk_inside_filter", "nsk_adam_vector", "nsk_adam_step",
     "nsk_adam_reset", "nsk_graph_begin", "nsk_graph_end", "nsk_graph_launch", "nsk_graph_destroy", "nsk_zero_grads", "nsk_prepare_rays", "nsk_map_prepare", "nsk_grad_slab", "nsk_grad_pack", "nsk_grad_unpack", "nsk_allreduce_grads", "nsk_last_call_stats",
     "nsk_profile_begin", "nsk_profile_end", "nsk_debug_relu_bits", "nsk_debug_preact", "nsk_debug_fetch", "nsk_debug_live_tiles", "nsk_debug_last_split",
-    "nsk_debug_decoder_images",
+    "nsk_debug_decoder_images", "nsk_decoder_image_table",
     "nsk_pose_step_multi", "nsk_set_depth_max_batch", "nsk_grad_extra", "nsk_set_backward_mode",
     "nsk_eval_lattice", "nsk_eval_lattice_masked", "nsk_mesh_extract", "nsk_mesh_buffers", "nsk_mesh_download", "nsk_mesh_table",
     "nsk_lattice_seen", "nsk_mesh_filter",
@@ -175,6 +175,8 @@ def lib():
         L.nsk_lattice_in_hull.restype = C.c_int
         L.nsk_lattice_in_hull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_longlong)]
+        L.nsk_decoder_image_table.restype = C.c_int
+        L.nsk_decoder_image_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -199,6 +201,19 @@ def mesh_table(case):
     if n < 0:
         raise NskError(lib().nsk_last_error().decode())
     return [(int(buf[3 * t]), int(buf[3 * t + 1]), int(buf[3 * t + 2])) for t in range(n)]
+
+
+def decoder_image_table(which, what, pieces=2):
+    """int32 array: the index table of image `what` (a name of Context.DECODER_IMAGES or its index) of decoder `which` (include/nsk.h: how the
+    image follows from it); empty for an image the decoder does not have; needs no GPU"""
+    import numpy as np
+    w = STAGES[which] if isinstance(which, str) else int(which)
+    code = Context.DECODER_IMAGES.index(what) if isinstance(what, str) else int(what)
+    n = lib().nsk_decoder_image_table(w, code, int(pieces), None, 0)
+    out = np.zeros(max(n, 0), np.int32)
+    if n < 0 or lib().nsk_decoder_image_table(w, code, int(pieces), out.ctypes.data_as(C.c_void_p), out.size) != n:
+        raise NskError(lib().nsk_last_error().decode())
+    return out
 
 
 def frame_plan(color_size, depth_size, intr, distortion=None, crop_size=None, crop_edge=0, png_depth_scale=1.0, scale=1.0, swap_rb=False):
