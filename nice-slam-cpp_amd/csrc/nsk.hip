@@ -1082,6 +1082,22 @@ static size_t bwd_lds_bytes(int w, bool train)
     size_t img = w == 2 ? 0 : bwd_img_floats(w);          // saved-activation form: only the backward image sits in LDS
     return (img + PN_FLOATS(w == 2 ? 4 : 2)) * 4;            // the per-wave scatter scratch lives in panel rows 0..63
 }
+// dynamic LDS of a backward launch with roles (nsk_split.h: BwdKernel): the largest of its roles' needs in that kernel
+static size_t bwd_form_lds_bytes(BwdKernel k, int n, const int* which, const int* train)
+{
+    size_t lds = 0;
+    for (int r = 0; r < n; ++r) {
+        // the full-width chains keep a trainable role's panel beside the image (CQ 2 for every decoder)
+        if (k == BWD_MULTI_FULL || k == BWD_MULTI_FULL_RAYS) lds = std::max(lds, bwd_img_floats(which[r]) * 4 + (train[r] ? PN_FLOATS(2) * 4 : 8 * 3840));
+        else lds = std::max(lds, bwd_lds_bytes(which[r], train[r] != 0));
+    }
+    if (k == BWD_TRACK) lds += NSK_DYN_LDS_BYTES;                                        // the residuals and the median's counters
+    if (k == BWD_FROZEN) lds += (size_t)(NSK_FROZEN_NW - 8) * 3840;                      // image + one scatter scratch per wave
+    return lds;
+}
+static_assert(BWD_FROZEN_WAVES == NSK_FROZEN_NW && BWD_MEDIAN_MAX_RAYS == NSK_MEDIAN_FUSED_MAX, "nsk_split.h mirrors nsk_device.h");
+static_assert(NSK_SPLIT_BWD_SEPARATE == 1 && NSK_SPLIT_BWD_MULTI == 2 && NSK_SPLIT_BWD_MULTI_FULL == 3 && NSK_SPLIT_BWD_FROZEN == 4 && NSK_SPLIT_BWD_TRACK == 5,
+              "bwd_split_form (nsk_split.h) returns the values of include/nsk.h");
 
 extern "C" int nsk_ctx_create(int device, void* hip_stream, nsk_ctx** out)
 {
@@ -1659,8 +1675,8 @@ static int launch_decode_bwd(nsk_ctx* c, int w, int M, int S, const float* ro, c
     A.flags = flags;
     int ntasks = (M + 15) / 16;
     size_t lds = bwd_lds_bytes(w, train);
-    int grid = std::max(1, std::min((ntasks + 7) / 8, c->num_cu));
-    if (c->deterministic) { grid = 1; A.flags |= 0x8000u; }      // one workgroup, its waves scatter one after the other
+    const int grid = bwd_separate_grid(c->num_cu, ntasks, c->deterministic != 0);
+    if (c->deterministic) A.flags |= 0x8000u;      // one workgroup, its waves scatter one after the other
     static const char* names[8] = {"decode_bwd_coarse", "decode_bwd_middle", "decode_bwd_fine", "decode_bwd_color",
                                    "decode_bwd_coarse_train", "decode_bwd_middle_train", "decode_bwd_fine_train", "decode_bwd_color_train"};
     {
@@ -2511,9 +2527,8 @@ static int flush_pending(nsk_ctx* c)
     return 0;
 }
 
-// The steps of backward_core.  BwdRoles: the launch's roles in launch order (colour, fine, middle) and their costs in the split; train_role -2:
-// more than one trainable decoder, or the fine one (its body is not part of k_decode_bwd_multi) -> separate launches
-struct BwdRoles { int n = 0, cost[3] = {0, 0, 0}, train_role = -1; size_t lds = 0; };
+// The steps of backward_core.  BwdRoles: the launch's roles in launch order (colour, fine, middle) and their costs in the split
+struct BwdRoles { int n = 0, cost[3] = {0, 0, 0}; };
 
 // collect: every decoder of the stage that has a gradient to compute becomes a role of MA; marks the parameter groups the launch writes
 static int collect_bwd_roles(nsk_ctx* c, MultiArgs& MA, BwdRoles& R, int stage, int N, int S, const float* ro, const float* rd, unsigned flags,
@@ -2531,8 +2546,6 @@ static int collect_bwd_roles(nsk_ctx* c, MultiArgs& MA, BwdRoles& R, int stage, 
         A.flags = flags & 0xffu;
         MA.which[R.n] = w; MA.train[R.n] = train ? 1 : 0;
         R.cost[R.n] = bwd_role_cost(train, w, rays, c->tune);
-        R.lds = std::max(R.lds, bwd_lds_bytes(w, train));
-        if (train) R.train_role = (R.train_role == -1 && w != 2) ? R.n : -2;
         if (train) c->touched[NSK_GROUP_DECODERS] = true;
         if (grids) c->touched[NSK_GROUP_COARSE + w] = true;
         ++R.n;
@@ -2541,17 +2554,15 @@ static int collect_bwd_roles(nsk_ctx* c, MultiArgs& MA, BwdRoles& R, int stage, 
 }
 
 // Dead-tile skip: a frozen role whose level carries an optimiser mask walks the slots' liveness bytes (forward_core) and runs only the tiles
-// with a sample that reaches a marked voxel.  Never with ray gradients (d/dp flows through every sample), the Tracker's launch or the
-// full-width chains (`eligible`).  The roles count what they ran (counted[]); the count of an EARLIER step of the same kind (whatever has arrived
+// with a sample that reaches a marked voxel, where the launch form allows it (BwdForm::skip_eligible).  The roles count what they ran (counted[]); the count of an EARLIER step of the same kind (whatever has arrived
 // in live_host: nobody waits for it) tells the split how long the frozen roles really are (tasks[]) -- the first step of a kind assumes every
 // tile runs.
-static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, int stage, int M, unsigned flags, bool eligible, bool frozen_only,
-                         int* tasks, bool* counted)
+static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, const BwdForm& F, int stage, int M, unsigned flags, int* tasks, bool* counted)
 {
     const int ntasks = (M + 15) / 16;
     for (int r = 0; r < 3; ++r) { tasks[r] = ntasks; counted[r] = false; }
-    if (!c->live_ok || !eligible || c->tune_no_dead_skip) return;
-    const int key[8] = {stage, M, (int)(flags & 0xffu), c->sorted ? 1 : 0, c->live_epoch, R.n, R.train_role, frozen_only ? 1 : 0};
+    if (!c->live_ok || !F.skip_eligible) return;
+    const int key[8] = {stage, M, (int)(flags & 0xffu), c->sorted ? 1 : 0, c->live_epoch, R.n, F.train_role, F.kernel == BWD_FROZEN ? 1 : 0};
     if (memcmp(key, c->live_key, sizeof(key)) != 0) { memcpy(c->live_key, key, sizeof(key)); ++c->live_tag; }
     const volatile int* h = c->live_host;
     const bool fresh = h[3] == c->live_tag;
@@ -2565,32 +2576,30 @@ static void bwd_liveness(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, int stage
     }
 }
 
-// scan_wgs: of prep_ride_scan; extra: the workgroup that sums the per-ray losses
-static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, const BwdRoles& R, bool rays, bool full, bool frozen_only, bool track, int scan_wgs, int extra, const DealRoles* deal)
+// grid: bwd_grid of the form, the split and the riders
+static void launch_bwd_roles(nsk_ctx* c, MultiArgs& MA, BwdKernel kernel, int grid, const DealRoles& deal)
 {
-    const int n = R.n; const size_t lds = R.lds;
+    const size_t lds = bwd_form_lds_bytes(kernel, MA.n, MA.which, MA.train);
     ProfScope ps(c, "decode_bwd_multi");
-    if (track) {
+    switch (kernel) {
+    case BWD_TRACK:
         MA.dyn_seed = c->ws.tmp_rgb; MA.dyn_thr_out = c->scal + 1;
-        k_decode_bwd_track<<<MA.wg_end[n - 1] + 1, 512, lds + NSK_DYN_LDS_BYTES, c->stream>>>(MA);
-    } else if (full) {
-        size_t ldsf = 0;
-        for (int r = 0; r < n; ++r) ldsf = std::max(ldsf, bwd_img_floats(MA.which[r]) * 4 + (MA.train[r] ? PN_FLOATS(2) * 4 : 8 * 3840));
-        if (rays) k_decode_bwd_multi_full<true><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
-        else k_decode_bwd_multi_full<false><<<MA.wg_end[n - 1] + extra, 512, ldsf, c->stream>>>(MA);
-    } else if (frozen_only) {
-        const size_t lds16 = lds - 8 * 3840 + (size_t)NSK_FROZEN_NW * 3840;      // image + one scatter scratch per wave
-        k_decode_bwd_frozen<<<MA.wg_end[n - 1] + scan_wgs + extra, 64 * NSK_FROZEN_NW, lds16, c->stream>>>(MA);
-    } else if (rays) k_decode_bwd_multi<true><<<MA.wg_end[n - 1] + extra, 512, lds, c->stream>>>(MA);
-    else if (deal) k_decode_bwd_multi_deal<<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA, *deal);
-    else k_decode_bwd_multi<false><<<MA.wg_end[n - 1] + scan_wgs + extra, 512, lds, c->stream>>>(MA);
+        k_decode_bwd_track<<<grid, 512, lds, c->stream>>>(MA);
+        break;
+    case BWD_MULTI_FULL_RAYS: k_decode_bwd_multi_full<true><<<grid, 512, lds, c->stream>>>(MA); break;
+    case BWD_MULTI_FULL: k_decode_bwd_multi_full<false><<<grid, 512, lds, c->stream>>>(MA); break;
+    case BWD_FROZEN: k_decode_bwd_frozen<<<grid, 64 * NSK_FROZEN_NW, lds, c->stream>>>(MA); break;
+    case BWD_MULTI_RAYS: k_decode_bwd_multi<true><<<grid, 512, lds, c->stream>>>(MA); break;
+    case BWD_MULTI_DEAL: k_decode_bwd_multi_deal<<<grid, 512, lds, c->stream>>>(MA, deal); break;
+    case BWD_MULTI: k_decode_bwd_multi<false><<<grid, 512, lds, c->stream>>>(MA); break;
+    case BWD_NONE: case BWD_SEPARATE: break;      // (backward_core has left before)
+    }
 }
 
 // dyn_resid: the Tracker's deferred median mask (composite mode 5 wrote the residuals there and the seeds to ws.tmp_rgb): k_decode_bwd_track
 static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, const float* rd, unsigned flags, float* g_ro, float* g_rd,
                          float* d_loss = nullptr, const float* dyn_resid = nullptr)
 {
-    const bool rays = (flags & NSK_GRAD_RAYS) != 0, grids = (flags & NSK_GRAD_GRIDS) != 0;
     const int M = N * S, ntasks = (M + 15) / 16;
     for (int k = 0; k < 3; ++k) { c->dbg_live[k] = -1; c->dbg_counted[k] = false; c->dbg_wgs[k] = 0; }      // (nsk_debug_live_tiles: this backward's, whichever way it leaves)
     c->dbg_ntasks = ntasks;
@@ -2600,39 +2609,34 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
     memset(&MA, 0, sizeof(MA));
     BwdRoles R;
     CHK(collect_bwd_roles(c, MA, R, stage, N, S, ro, rd, flags, g_ro, g_rd, dyn_resid));
-    const int n = R.n, train_role = R.train_role;
-    if (dyn_resid && (train_role != -1 || !rays || c->deterministic || c->bwd_mode == 0 || n == 0 || N > NSK_MEDIAN_FUSED_MAX))
-        return fail("backward_core: the deferred median mask needs the Tracker's launch (frozen decoders, ray gradients)");      // the caller checked the same
-    const int separate = c->deterministic ? 1 : 0;      // debug mode: one launch per decoder, in a fixed order
-    if ((n == 0 || train_role == -2 || separate) && d_loss) { ProfScope ps(c, "loss_sum"); k_sum<<<1, 1024, 0, c->stream>>>(N, c->ws.ray_loss, d_loss); }
+    BwdFormIn in;
+    in.n = R.n; memcpy(in.which, MA.which, sizeof(in.which)); memcpy(in.train, MA.train, sizeof(in.train));
+    in.rays = (flags & NSK_GRAD_RAYS) != 0; in.grids = (flags & NSK_GRAD_GRIDS) != 0;
+    in.full = c->bwd_mode == 0; in.deterministic = c->deterministic != 0; in.track = dyn_resid != nullptr;
+    in.N = N;
+    in.no_frozen_kernel = c->tune_no_frozen_kernel; in.no_dead_skip = c->tune_no_dead_skip; in.static_deal = c->tune_static_deal;
+    const BwdForm F = bwd_form(in);                 // which launch goes out, and what may ride in it: nsk_split.h
+    const int n = R.n;
+    if (!F.mask_ok) return fail("backward_core: the deferred median mask needs the Tracker's launch (frozen decoders, ray gradients)");
+    if ((F.kernel == BWD_NONE || F.kernel == BWD_SEPARATE) && d_loss) { ProfScope ps(c, "loss_sum"); k_sum<<<1, 1024, 0, c->stream>>>(N, c->ws.ray_loss, d_loss); }
     memset(c->dbg_split[1], 0, sizeof(c->dbg_split[1]));
-    if (n == 0) return 0;
+    if (F.kernel == BWD_NONE) return 0;
     for (int r = 0; r < n; ++r) if (!MA.train[r] && MA.which[r] >= 1) c->dbg_live[MA.which[r] - 1] = ntasks;      // until a role counts fewer
-    if (train_role == -2 || separate) {      // rare configuration (several trainable decoders share one slab buffer): one launch each
-        record_split(c, 1, NSK_SPLIT_BWD_SEPARATE, n, MA.which, MA.train, nullptr, 0, 0, ntasks, c->deterministic ? 1 : std::max(1, std::min((ntasks + 7) / 8, c->num_cu)));
+    if (F.kernel == BWD_SEPARATE) {      // rare configuration (several trainable decoders share one slab buffer), or the debug mode: one launch each
+        record_split(c, 1, bwd_split_form(F.kernel), n, MA.which, MA.train, nullptr, 0, 0, ntasks, bwd_separate_grid(c->num_cu, ntasks, in.deterministic));
         for (int r = 0; r < n; ++r)
-            CHK(launch_decode_bwd(c, MA.which[r], M, S, ro, rd, MA.train[r] != 0, rays, flags, g_ro, g_rd));
+            CHK(launch_decode_bwd(c, MA.which[r], M, S, ro, rd, MA.train[r] != 0, in.rays, flags, g_ro, g_rd));
         return 0;
     }
     MA.n = n;
-    // no trainable role and no ray gradients (the fine / middle / coarse stages of the Mapper): the 16-wave frozen kernel (nsk_device.h); with ray
-    // gradients the frozen bodies need 160 VGPRs (the Tracker: 600 tiles, latency-bound either way) and stay in k_decode_bwd_multi
-    const bool full = c->bwd_mode == 0;                 // every chain on the fp32 MFMA: k_decode_bwd_multi_full, nothing rides
-    const bool frozen_only = train_role == -1 && !rays && !c->tune_no_frozen_kernel && !full;
     int tasks[3]; bool counted[3];
-    bwd_liveness(c, MA, R, stage, M, flags, grids && !rays && !full && !dyn_resid, frozen_only, tasks, counted);
-    plan_bwd(c->num_cu, ntasks, n, R.cost, train_role, frozen_only ? NSK_FROZEN_NW : 8, tasks, MA.wg_end);
-    // Queue dealing of the skipping roles (decode_bwd_body: Dealing).  Only where a wave has rounds enough for a claimed tail to even out: K2 and the
-    // K4 shard (11 and 10 rounds per wave, the trainable role's iterations being the launch) gain nothing, and the K4 shard pays 1.2 - 1.6 us for the claims.
-    // Not in the 16-wave kernel of the all-frozen launches: a role there is ~2000 waves of ~8 tiles, every wave claims at least twice, and adds on
-    // one address serialise at ~25 ns (K3 fine stage 83 -> 114 us with per-wave claims).  Never in the deterministic mode,
-    // which has no skipping roles.
+    bwd_liveness(c, MA, R, F, stage, M, flags, tasks, counted);
+    plan_bwd(c->num_cu, ntasks, n, R.cost, F.train_role, F.waves, tasks, MA.wg_end);
+    // Queue dealing of the skipping roles (decode_bwd_body: Dealing), where bwd_deal_role finds rounds enough
     bool dealt = false; DealRoles DR;
     memset(&DR, 0, sizeof(DR));
-    for (int r = 0; r < n && !c->tune_static_deal && !frozen_only && !rays && !full && !dyn_resid; ++r) {
-        if (!counted[r]) continue;
-        const int rounds = (ntasks + role_wgs(MA.wg_end, r) * 8 - 1) / (role_wgs(MA.wg_end, r) * 8);
-        if (rounds < c->tune_deal_min_rounds) continue;
+    for (int r = 0; r < n; ++r) {
+        if (!bwd_deal_role(ntasks, role_wgs(MA.wg_end, r), counted[r], F, c->tune_deal_min_rounds)) continue;
         DR.r[r] = DealArgs{c->deal_cur + (MA.which[r] - 1) * NSK_DEAL_STRIDE, c->tune_deal_head_pct, c->tune_deal_chunk};
         dealt = true;
     }
@@ -2643,19 +2647,15 @@ static int backward_core(nsk_ctx* c, int stage, int N, int S, const float* ro, c
         if (MA.which[r] >= 1) c->dbg_wgs[MA.which[r] - 1] = role_wgs(MA.wg_end, r);
     }
     MA.live_cnt = c->live_cnt; MA.live_out = c->live_host_dev; MA.live_tag = c->live_tag;
-    const int extra = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
+    const int loss_wg = d_loss ? 1 : 0;          // one more workgroup sums the per-ray losses written by k_composite
     if (d_loss) { MA.sum_src = c->ws.ray_loss; MA.sum_dst = d_loss; MA.sum_n = N; }
-    const int scan_wgs = prep_ride_scan(c, MA, !rays && !full, frozen_only ? NSK_FROZEN_NW / 4 : 2);
-    {
-        const bool track = dyn_resid != nullptr;
-        const int form = track ? NSK_SPLIT_BWD_TRACK : (full ? NSK_SPLIT_BWD_MULTI_FULL : (frozen_only ? NSK_SPLIT_BWD_FROZEN : NSK_SPLIT_BWD_MULTI));
-        const int riders = track ? 1 : scan_wgs + extra;      // (the Tracker's one rider finds the median and sums the loss; launch_bwd_roles adds the same)
-        record_split(c, 1, form, n, MA.which, MA.train, MA.wg_end, track ? 0 : scan_wgs, track ? (d_loss ? 1 : 0) : extra, ntasks, MA.wg_end[n - 1] + riders);
-        c->dbg_split[1][15] = track ? 1 : 0;
-    }
-    launch_bwd_roles(c, MA, R, rays, full, frozen_only, dyn_resid != nullptr, scan_wgs, extra, dealt ? &DR : nullptr);
+    const int scan_wgs = prep_ride_scan(c, MA, F.scan_may_ride, F.scan_halves);
+    const int grid = bwd_grid(F, MA.wg_end, n, scan_wgs, loss_wg);
+    record_split(c, 1, bwd_split_form(F.kernel), n, MA.which, MA.train, MA.wg_end, scan_wgs, loss_wg, ntasks, grid);
+    c->dbg_split[1][15] = F.kernel == BWD_TRACK ? 1 : 0;
+    launch_bwd_roles(c, MA, bwd_launch_kernel(F, dealt), grid, DR);
     HIPCHK(hipGetLastError());
-    if (train_role >= 0) { c->pend_w = MA.which[train_role]; c->pend_nb = role_wgs(MA.wg_end, train_role); }      // summed by k_adam_multi, or by flush_pending when someone reads the slab first
+    if (F.train_role >= 0) { c->pend_w = MA.which[F.train_role]; c->pend_nb = role_wgs(MA.wg_end, F.train_role); }      // summed by k_adam_multi, or by flush_pending when someone reads the slab first
     return 0;
 }
 
@@ -2752,33 +2752,34 @@ extern "C" int nsk_track_step(nsk_ctx* c, int stage, int N, const float* ro, con
     CHK(forward_core(c, stage, N, S, ro, rd, gt, gtmax, true, sort_pays(c, stage, N * S, flags)));
     CompArgs A;
     comp_args(c, A, stage, N, S, ro, rd);
-    // One launch (k_composite mode 4: residuals -> grid barrier -> median -> loss and backward) while the grid is at most one
-    // workgroup per CU, i.e. certainly resident as a whole; three launches otherwise (and in the deterministic debug mode)
-    // (round 3 tried ONE 16-wave workgroup for up to 256 rays -- render, select the median in LDS, render again, no grid barrier: 70 us at 200 rays
-    // against 21, a wave's rays run one after the other at ~2.5 us each)
-    const bool fused_median = handle_dynamic && !c->deterministic && !c->tune_no_fused_median && N <= NSK_MEDIAN_FUSED_MAX && (N + 3) / 4 <= c->num_cu;
-    // Round 4: with ray gradients and frozen decoders (the Tracker as the reference runs it) not even that barrier -- the mask is one factor per
-    // ray on what the compositing hands on, and the backward's workgroups apply it (composite mode 5, k_decode_bwd_track)
-    bool deferred = handle_dynamic && !c->deterministic && !c->tune_no_fused_median && !c->tune_no_deferred_median && N <= NSK_MEDIAN_FUSED_MAX &&
-                    (flags & NSK_GRAD_RAYS) && c->bwd_mode != 0;
-    for (int q = 0; q < 3 && deferred; ++q) {
+    // which median form runs when: median_form (nsk_split.h).  any_trainable: by collect_bwd_roles' rule for a trainable role -- the two must agree
+    bool any_trainable = false;
+    for (int q = 0; q < 3; ++q) {
         const int w = STAGE_DEC[stage][q];
-        if (w >= 0 && (flags & NSK_GRAD_DECODERS) && c->dec[w].trainable) deferred = false;
+        if (w >= 0 && (flags & NSK_GRAD_DECODERS) && c->dec[w].trainable) any_trainable = true;
     }
-    if (handle_dynamic && !fused_median && !deferred) {                     // forward pass for the median (Tracker.cpp:69-70)
+    const MedianForm median = median_form(handle_dynamic != 0, c->deterministic != 0, c->tune_no_fused_median, c->tune_no_deferred_median, N, c->num_cu,
+                                          (flags & NSK_GRAD_RAYS) != 0, c->bwd_mode == 0, any_trainable);
+    if (median == MEDIAN_THREE) {                                            // forward pass for the median (Tracker.cpp:69-70)
         A.mode = 0; A.depth = c->ws.tmp_depth;
         k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A);
         CHK(median_thr(c, N, gt, c->ws.tmp_depth));
         A.depth = nullptr;
     }
-    A.mode = deferred ? 5 : (fused_median ? 4 : 3); A.gt_depth = gt; A.gt_color = gtc; A.w_color = w_color; A.use_color = use_color;
+    A.gt_depth = gt; A.gt_color = gtc; A.w_color = w_color; A.use_color = use_color;
     A.thr = c->scal + 1; A.handle_dynamic = handle_dynamic; A.detach_var = detach_var; A.loss = c->ws.ray_loss;
-    if (deferred) { A.resid = c->ws.tmp_depth; A.g_seed = c->ws.tmp_rgb; }
-    else if (fused_median) { c->median_fused_pending = true; A.resid = c->ws.tmp_depth; A.bar = reinterpret_cast<unsigned*>(c->scal + 5); A.thr_out = c->scal + 1; }
+    switch (median) {
+    case MEDIAN_NONE: case MEDIAN_THREE: A.mode = 3; break;
+    case MEDIAN_BARRIER:
+        A.mode = 4; c->median_fused_pending = true;
+        A.resid = c->ws.tmp_depth; A.bar = reinterpret_cast<unsigned*>(c->scal + 5); A.thr_out = c->scal + 1;
+        break;
+    case MEDIAN_DEFERRED: A.mode = 5; A.resid = c->ws.tmp_depth; A.g_seed = c->ws.tmp_rgb; break;      // the backward's workgroups apply the mask
+    }
     if (flags & NSK_GRAD_RAYS) { A.g_rays_o = g_ro; A.g_rays_d = g_rd; }
     { ProfScope ps(c, "composite"); k_composite<<<(N + 3) / 4, 256, 0, c->stream>>>(A); }
     HIPCHK(hipGetLastError());
-    CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd, d_loss, deferred ? c->ws.tmp_depth : nullptr));
+    CHK(backward_core(c, stage, N, S, ro, rd, flags, g_ro, g_rd, d_loss, median == MEDIAN_DEFERRED ? c->ws.tmp_depth : nullptr));
     account(c, stage, N * S, first_pass_samples(c, N, S), true, flags);
     return 0;
 }

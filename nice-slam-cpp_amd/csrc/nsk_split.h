@@ -1,5 +1,9 @@
-// nsk_split.h -- how a decoder launch divides its workgroups over its roles: cost model and split arithmetic in host integers, nothing of HIP
-// (host/test/split_test.cpp builds it with a plain host compiler: tests/test_split_cpu.py)
+// nsk_split.h -- how a decoder launch divides its workgroups over its roles, and which launch goes out: cost model, split arithmetic and the
+// backward's launch form in host integers, nothing of HIP (host/test/split_test.cpp builds it with a plain host compiler: tests/test_split_cpu.py)
+//   split_wgs, split_wgs_balanced, split_wgs_train, split_makespan      the split arithmetic
+//   plan_fwd, plan_bwd                                                  which split a forward / backward launch takes (and the forward's form)
+//   bwd_form, bwd_deal_role, bwd_grid                                   which backward launch goes out, with which riders, on how many workgroups
+//   median_form                                                         which of the Tracker's median forms runs in front of it
 #pragma once
 #include <algorithm>
 
@@ -160,4 +164,124 @@ static inline void plan_bwd(int num_cu, int ntasks, int n, const int* cost, int 
 {
     if (train_role >= 0 && n > 1) split_wgs_train(num_cu, ntasks, n, cost, train_role, wg_end, tasks);
     else split_wgs_balanced(num_cu, ntasks, n, cost, wg_end, waves, tasks);
+}
+
+// ---- The backward's launch form.  One decision, taken once in backward_core (nsk.hip) from the facts below; the launch, the liveness pass, the
+// riders and nsk_debug_last_split all read its answer.
+//
+//   kernel              runs when                                                                      waves  skip  deal  scan rider
+//   BWD_NONE            no decoder of the stage has a gradient to compute                              -      -     -     -
+//   BWD_SEPARATE        deterministic mode; or several trainable roles, or the fine one (its body is   8      -     -     -
+//                       not part of k_decode_bwd_multi): one launch per decoder, in a fixed order
+//   BWD_TRACK           the Tracker handed in its deferred median mask (see median_form)               8      -     -     -
+//   BWD_MULTI_FULL      bwd_mode 0: every chain on the fp32 MFMA; _RAYS: with ray gradients            8      -     -     -
+//   BWD_FROZEN          no trainable role, no ray gradients, no_frozen_kernel off: 16-wave workgroups  16     yes   -     yes
+//   BWD_MULTI_RAYS      ray gradients (bundle adjustment; the Tracker without a mask)                  8      -     -     -
+//   BWD_MULTI           the rest (one trainable role beside frozen ones: the Mapper's colour stage)    8      yes   yes   yes
+//   BWD_MULTI_DEAL      BWD_MULTI with at least one role that claims its tiles from a cursor: bwd_deal_role says which, once the split is
+//                       known, and bwd_launch_kernel then names the kernel that goes out
+//
+// skip (frozen roles under an optimiser mask skip their dead tiles) also needs grid gradients and no_dead_skip off: with ray gradients d/dp
+// flows through every sample.  deal also needs static_deal off.  The scan rider is the next batch's cell-sort scan (prep_ride_scan).
+static const int BWD_FROZEN_WAVES = 16;             // = NSK_FROZEN_NW (nsk_device.h; nsk.hip asserts it)
+static const int BWD_MEDIAN_MAX_RAYS = 1024;        // = NSK_MEDIAN_FUSED_MAX
+
+enum BwdKernel { BWD_NONE = 0, BWD_SEPARATE, BWD_TRACK, BWD_MULTI_FULL, BWD_MULTI_FULL_RAYS, BWD_FROZEN, BWD_MULTI_RAYS, BWD_MULTI, BWD_MULTI_DEAL };
+
+struct BwdFormIn {
+    int n = 0, which[3] = {0, 0, 0}, train[3] = {0, 0, 0};      // the collected roles, in launch order
+    bool rays = false, grids = false;                            // NSK_GRAD_RAYS, NSK_GRAD_GRIDS
+    bool full = false, deterministic = false;                    // bwd_mode == 0; the deterministic debug mode
+    bool track = false;                                          // a deferred median mask was handed in
+    int N = 0;                                                   // rays
+    int no_frozen_kernel = 0, no_dead_skip = 0, static_deal = 0;      // nsk_set_tuning keys of the same names (deal_min_rounds: bwd_deal_role)
+};
+
+struct BwdForm {
+    BwdKernel kernel = BWD_NONE;
+    int train_role = -1;              // the one trainable role; -1: none; -2: several, or the fine decoder (-> BWD_SEPARATE)
+    int waves = 8;                    // per workgroup
+    bool skip_eligible = false, deal_eligible = false, scan_may_ride = false;
+    int scan_halves = 2;              // the scan rider's 256-cell chunks per workgroup
+    bool mask_ok = true;              // false: a deferred mask with inputs the Tracker's launch does not serve
+};
+
+static inline BwdForm bwd_form(const BwdFormIn& in)
+{
+    BwdForm F;
+    for (int r = 0; r < in.n; ++r) if (in.train[r]) F.train_role = (F.train_role == -1 && in.which[r] != 2) ? r : -2;
+    F.mask_ok = !in.track || (F.train_role == -1 && in.rays && !in.deterministic && !in.full && in.n > 0 && in.N <= BWD_MEDIAN_MAX_RAYS);
+    if (in.n == 0 || !F.mask_ok) return F;
+    if (in.deterministic || F.train_role == -2) { F.kernel = BWD_SEPARATE; return F; }
+    if (in.track) F.kernel = BWD_TRACK;
+    else if (in.full) F.kernel = in.rays ? BWD_MULTI_FULL_RAYS : BWD_MULTI_FULL;
+    else if (in.rays) F.kernel = BWD_MULTI_RAYS;
+    else F.kernel = (F.train_role == -1 && !in.no_frozen_kernel) ? BWD_FROZEN : BWD_MULTI;
+    const bool plain = F.kernel == BWD_FROZEN || F.kernel == BWD_MULTI;      // two-piece chains, no ray gradients, no mask of the Tracker's
+    if (F.kernel == BWD_FROZEN) { F.waves = BWD_FROZEN_WAVES; F.scan_halves = BWD_FROZEN_WAVES / 4; }
+    F.skip_eligible = plain && in.grids && !in.no_dead_skip;
+    // Dealing only where a wave has rounds enough for a claimed tail to even out (bwd_deal_role), and not in the 16-wave kernel: a role there is
+    // ~2000 waves of ~8 tiles, every wave claims at least twice, and adds on one address serialise at ~25 ns (K3 fine stage 83 -> 114 us with
+    // per-wave claims)
+    F.deal_eligible = F.skip_eligible && F.kernel == BWD_MULTI && !in.static_deal;
+    F.scan_may_ride = plain;
+    return F;
+}
+
+// the form as nsk_debug_last_split reports it (NSK_SPLIT_BWD_*, include/nsk.h; 0: no launch)
+static inline int bwd_split_form(BwdKernel k)
+{
+    switch (k) {
+    case BWD_NONE: return 0;
+    case BWD_SEPARATE: return 1;
+    case BWD_MULTI_RAYS: case BWD_MULTI: case BWD_MULTI_DEAL: return 2;
+    case BWD_MULTI_FULL: case BWD_MULTI_FULL_RAYS: return 3;
+    case BWD_FROZEN: return 4;
+    case BWD_TRACK: return 5;
+    }
+    return 0;
+}
+
+// Does role r claim its tiles from its cursor (k_decode_bwd_multi_deal)?  counted: the role skips dead tiles (bwd_liveness).  K2 and the K4 shard
+// (11 and 10 rounds per wave, the trainable role's iterations being the launch) gain nothing, and the K4 shard pays 1.2 - 1.6 us for the claims.
+// deal_min_rounds: the nsk_set_tuning key.
+static inline bool bwd_deal_role(int ntasks, int role_workgroups, bool counted, const BwdForm& F, int deal_min_rounds)
+{
+    if (!F.deal_eligible || !counted) return false;
+    return (ntasks + role_workgroups * 8 - 1) / (role_workgroups * 8) >= deal_min_rounds;
+}
+// the kernel that goes out: the form's, or the dealing one when a role claims (any_dealt: bwd_deal_role of some role; only BWD_MULTI is eligible)
+static inline BwdKernel bwd_launch_kernel(const BwdForm& F, bool any_dealt) { return any_dealt ? BWD_MULTI_DEAL : F.kernel; }
+
+// workgroups of the launch: the roles', then the riders (the Tracker's one rider finds the median and sums the loss, asked for or not)
+static inline int bwd_grid(const BwdForm& F, const int* wg_end, int n, int scan_wgs, int loss_wg)
+{
+    return wg_end[n - 1] + (F.kernel == BWD_TRACK ? 1 : scan_wgs + loss_wg);
+}
+// one launch per decoder (BWD_SEPARATE): persistent, one workgroup per CU; in the deterministic mode one workgroup, its waves one after the other
+static inline int bwd_separate_grid(int num_cu, int ntasks, bool deterministic)
+{
+    return deterministic ? 1 : std::max(1, std::min((ntasks + 7) / 8, num_cu));
+}
+
+// ---- The Tracker's median threshold (handle_dynamic: rays whose depth residual exceeds 10 x the batch median leave the loss), in front of the
+// backward.  Which form runs when:
+//   MEDIAN_NONE      handle_dynamic off: composite mode 3, no threshold
+//   MEDIAN_DEFERRED  ray gradients, frozen decoders, two-piece chains, at most BWD_MEDIAN_MAX_RAYS rays (the Tracker as the reference runs it):
+//                    composite mode 5 writes residuals and seeds, the backward's workgroups find the median and apply the mask (BWD_TRACK)
+//   MEDIAN_BARRIER   else, while the compositing grid is at most one workgroup per CU, i.e. certainly resident as a whole: composite mode 4
+//                    (residuals -> grid barrier -> median -> loss and backward) in one launch
+//   MEDIAN_THREE     else, in the deterministic mode and under no_fused_median: a forward, the median's own launch, composite mode 3
+// no_deferred_median leaves out the deferred form alone.  any_trainable: a decoder of the stage is trainable and the flags ask for decoder
+// gradients -- the rule by which collect_bwd_roles (nsk.hip) marks a role trainable; the two must agree, or bwd_form refuses the mask.
+// (Round 3 tried ONE 16-wave workgroup for up to 256 rays -- render, select the median in LDS, render again, no grid barrier: 70 us at 200 rays
+// against 21, a wave's rays run one after the other at ~2.5 us each.)
+enum MedianForm { MEDIAN_NONE = 0, MEDIAN_THREE, MEDIAN_BARRIER, MEDIAN_DEFERRED };
+static inline MedianForm median_form(bool handle_dynamic, bool deterministic, int no_fused_median, int no_deferred_median, int N, int num_cu,
+                                     bool rays, bool full, bool any_trainable)
+{
+    if (!handle_dynamic) return MEDIAN_NONE;
+    if (deterministic || no_fused_median || N > BWD_MEDIAN_MAX_RAYS) return MEDIAN_THREE;
+    if (!no_deferred_median && rays && !full && !any_trainable) return MEDIAN_DEFERRED;
+    return (N + 3) / 4 <= num_cu ? MEDIAN_BARRIER : MEDIAN_THREE;
 }

@@ -1,6 +1,7 @@
 // The workgroup-split planner of the decoder launches (csrc/nsk_split.h) on the CPU: no torch, no HIP.  tests/test_split_cpu.py runs it.
 //   split_test <table>   the literal cases below, then every row of the recorded table (tests/golden/wg_splits.txt) recomputed and compared,
-//                        then the planner swept at the extremes of its tuning keys (knob_sweep: properties, nothing recorded)
+//                        then the planner swept at the extremes of its tuning keys (knob_sweep: properties, nothing recorded), then the
+//                        backward's launch form and the Tracker's median form over every combination of their inputs (form_sweep: properties)
 //   split_test --dump    prints the sweep in the table's format (how the table was recorded: see the table's header)
 // Row: <fn> <num_cu> <ntasks> <n> <waves> <train_role>  c0 c1 c2  t0 t1 t2 | w0 w1 w2 <makespan>      fn: S split_wgs, B split_wgs_balanced,
 // T split_wgs_train; t0 = -1: no tasks; unused columns 0; w: workgroups per role; makespan: split_makespan of that split (same waves and tasks)
@@ -211,6 +212,134 @@ static long knob_sweep()
     return plans;
 }
 
+// The backward's launch form (bwd_form, bwd_deal_role, bwd_grid) and the Tracker's median form (median_form) over every combination of their
+// boolean inputs, the role sets of the four stages x their trainable subsets, N in {1, 200, 1024, 1025} and num_cu in {50, 256}.  The properties
+// are those the launch code stated in its comments before the decision had one home: they are written from the inputs, not from the functions.
+static long form_sweep()
+{
+    long forms = 0;
+    static const int stage_dec[4][3] = {{0, -1, -1}, {1, -1, -1}, {1, 2, -1}, {1, 2, 3}};      // the decoders a stage runs
+    static const int Ns[4] = {1, 200, 1024, 1025}, cus[2] = {50, 256};
+    auto bad = [&](const char* what, const BwdFormIn& in, const BwdForm& F) {
+        if (++failures < 20)
+            fprintf(stderr, "FAIL form sweep %s: n %d which %d %d %d train %d %d %d rays %d grids %d full %d det %d track %d N %d knobs %d %d %d -> kernel %d\n", what, in.n,
+                    in.which[0], in.which[1], in.which[2], in.train[0], in.train[1], in.train[2], in.rays, in.grids, in.full, in.deterministic, in.track, in.N,
+                    in.no_frozen_kernel, in.no_dead_skip, in.static_deal, (int)F.kernel);
+    };
+    for (int stage = 0; stage < 4; ++stage)
+    for (int tmask = 0; tmask < 8; ++tmask)          // bit q: decoder stage_dec[stage][q] is trainable and the flags ask for decoder gradients
+    for (int bits = 0; bits < 256; ++bits)
+    for (int N : Ns) {
+        if (tmask >> (stage < 2 ? 1 : stage)) continue;      // (bits of decoders the stage does not have)
+        BwdFormIn in;
+        in.rays = bits & 1; in.grids = bits & 2; in.full = bits & 4; in.deterministic = bits & 8; in.track = bits & 16;
+        in.no_frozen_kernel = (bits >> 5) & 1; in.no_dead_skip = (bits >> 6) & 1; in.static_deal = (bits >> 7) & 1; in.N = N;
+        int ntrain = 0; bool fine_train = false;
+        for (int q = 2; q >= 0; --q) {                  // launch order: colour, fine, middle (collect_bwd_roles)
+            const int w = stage_dec[stage][q];
+            if (w < 0) continue;
+            const bool train = (tmask >> q) & 1;
+            if (!train && !in.grids && !in.rays) continue;
+            in.which[in.n] = w; in.train[in.n] = train; ++in.n;
+            ntrain += train; fine_train = fine_train || (train && w == 2);
+        }
+        const BwdForm F = bwd_form(in);
+        ++forms;
+        // a deferred mask is legal only for the Tracker's launch; an illegal one launches nothing
+        const bool mask_ok = !in.track || (ntrain == 0 && in.rays && !in.deterministic && !in.full && in.n > 0 && N <= 1024);
+        if (F.mask_ok != mask_ok) bad("mask_ok", in, F);
+        if (!mask_ok) { if (F.kernel != BWD_NONE || F.skip_eligible || F.deal_eligible || F.scan_may_ride) bad("illegal mask launches", in, F); continue; }
+        // exactly one kernel
+        const bool separate = in.n > 0 && (in.deterministic || ntrain > 1 || fine_train);
+        if ((F.kernel == BWD_NONE) != (in.n == 0)) bad("none", in, F);
+        if ((F.kernel == BWD_SEPARATE) != separate) bad("separate", in, F);
+        if (F.kernel == BWD_TRACK && !(in.track && in.rays && ntrain == 0 && !in.deterministic && !in.full && N <= 1024)) bad("track", in, F);
+        if (in.track && F.kernel != BWD_TRACK) bad("a legal mask takes the Tracker's launch", in, F);
+        const bool frozen = in.n > 0 && ntrain == 0 && !in.rays && !in.full && !in.no_frozen_kernel && !separate;
+        if ((F.kernel == BWD_FROZEN) != frozen) bad("frozen", in, F);
+        if ((F.kernel == BWD_MULTI_FULL) != (in.n > 0 && !separate && in.full && !in.rays)) bad("full", in, F);
+        if ((F.kernel == BWD_MULTI_FULL_RAYS) != (in.n > 0 && !separate && in.full && in.rays)) bad("full<rays>", in, F);
+        if ((F.kernel == BWD_MULTI_RAYS) != (in.n > 0 && !separate && !in.full && !in.track && in.rays)) bad("multi<rays>", in, F);
+        if ((F.kernel == BWD_MULTI) != (in.n > 0 && !separate && !in.full && !in.rays && !frozen)) bad("multi", in, F);
+        if (F.kernel == BWD_MULTI_DEAL) bad("dealing is decided after the split", in, F);
+        // the one trainable role, where the launch has roles
+        if (F.kernel != BWD_NONE && F.kernel != BWD_SEPARATE) {
+            int want = -1;
+            for (int r = 0; r < in.n; ++r) if (in.train[r]) want = r;
+            if (F.train_role != want) bad("train_role", in, F);
+        }
+        // workgroup shape, riders
+        if (F.waves != (frozen ? 16 : 8) || F.scan_halves != (frozen ? 4 : 2)) bad("waves", in, F);
+        if (F.skip_eligible && !(in.grids && !in.rays && !in.full && !in.track && !in.no_dead_skip && !separate)) bad("skip_eligible", in, F);
+        if (F.skip_eligible != (in.n > 0 && in.grids && !in.rays && !in.full && !in.track && !in.no_dead_skip && !separate)) bad("skip_eligible (iff)", in, F);
+        if (F.deal_eligible && !(F.skip_eligible && F.kernel != BWD_FROZEN && !in.static_deal)) bad("deal_eligible", in, F);
+        if (F.deal_eligible != (F.skip_eligible && !frozen && !in.static_deal)) bad("deal_eligible (iff)", in, F);
+        if (F.scan_may_ride && (in.rays || in.full || in.track || separate)) bad("scan_may_ride", in, F);
+        if (F.scan_may_ride != (in.n > 0 && !in.rays && !in.full && !separate)) bad("scan_may_ride (iff)", in, F);
+        // what nsk_debug_last_split reports (NSK_SPLIT_BWD_*: include/nsk.h)
+        const int split_form = in.n == 0 ? 0 : (separate ? 1 : (in.track ? 5 : (in.full ? 3 : (frozen ? 4 : 2))));
+        if (bwd_split_form(F.kernel) != split_form) bad("split form", in, F);
+        // dealing: a counted role of an eligible launch with at least deal_min_rounds rounds of 8 waves (here 12: 96 tiles per workgroup)
+        for (int wgs = 1; wgs <= 3; ++wgs)
+            for (int ntasks : {96 * wgs - 8, 96 * wgs - 7, 96 * wgs})           // 11 rounds, 12 rounds (the first tile of the twelfth), 12 rounds
+                for (int counted = 0; counted < 2; ++counted) {
+                    const int rounds = (ntasks + 8 * wgs - 1) / (8 * wgs);
+                    const bool deals = bwd_deal_role(ntasks, wgs, counted != 0, F, 12);
+                    if (deals != (F.deal_eligible && counted && rounds >= 12)) bad("bwd_deal_role", in, F);
+                    if (bwd_launch_kernel(F, deals) != (deals ? BWD_MULTI_DEAL : F.kernel) || (deals && F.kernel != BWD_MULTI)) bad("bwd_launch_kernel", in, F);
+                }
+        // the grid: the roles' workgroups, then the Tracker's one rider or the scan's and the loss's
+        if (in.n > 0 && !separate) {
+            const int wg_end[3] = {5, 9, 12};
+            for (int scan = 0; scan <= 3; scan += 3)
+                for (int loss = 0; loss < 2; ++loss)
+                    if (bwd_grid(F, wg_end, in.n, scan, loss) != wg_end[in.n - 1] + (in.track ? 1 : scan + loss)) bad("bwd_grid", in, F);
+        }
+        // the median in front of the launch (track unset above: the form decides whether a mask is handed in)
+        if (in.track || in.n == 0) continue;
+        for (int num_cu : cus)
+            for (int mb = 0; mb < 8; ++mb) {
+                const bool hd = mb & 1; const int no_fused = (mb >> 1) & 1, no_deferred = (mb >> 2) & 1;
+                const MedianForm m = median_form(hd, in.deterministic, no_fused, no_deferred, N, num_cu, in.rays, in.full, ntrain > 0);
+                ++forms;
+                if ((m == MEDIAN_NONE) != !hd) bad("median none", in, F);
+                if (hd && no_fused && m != MEDIAN_THREE) bad("no_fused_median", in, F);
+                if (hd && in.deterministic && m != MEDIAN_THREE) bad("median, deterministic", in, F);
+                if (m == MEDIAN_DEFERRED) {
+                    BwdFormIn tin = in;
+                    tin.track = true;
+                    if (no_deferred || !bwd_form(tin).mask_ok || bwd_form(tin).kernel != BWD_TRACK) bad("deferred without the Tracker's launch", in, F);
+                }
+                if (m == MEDIAN_BARRIER && !((N + 3) / 4 <= num_cu && N <= 1024)) bad("barrier beyond one workgroup per CU", in, F);
+                // the fastest legal form runs: deferred where the backward takes the mask, else the barrier where the grid is resident
+                const bool fused_ok = hd && !in.deterministic && !no_fused && N <= 1024;
+                const bool can_defer = fused_ok && !no_deferred && in.rays && !in.full && ntrain == 0;
+                const MedianForm want = !hd ? MEDIAN_NONE : (can_defer ? MEDIAN_DEFERRED : (fused_ok && (N + 3) / 4 <= num_cu ? MEDIAN_BARRIER : MEDIAN_THREE));
+                if (m != want) bad("median form", in, F);
+            }
+    }
+    // the forms of the steps the pipeline runs
+    BwdFormIn K;
+    K.n = 3; K.which[0] = 3; K.which[1] = 2; K.which[2] = 1; K.train[0] = 1; K.grids = true; K.N = 1000;
+    BwdForm F = bwd_form(K);                               // the Mapper's colour stage: one trainable role beside two frozen ones
+    if (F.kernel != BWD_MULTI || F.train_role != 0 || !F.skip_eligible || !F.deal_eligible || !F.scan_may_ride || F.waves != 8) { ++failures; fprintf(stderr, "FAIL form: colour stage\n"); }
+    K.n = 2; K.which[0] = 2; K.which[1] = 1; K.train[0] = 0;
+    F = bwd_form(K);                                       // its fine stage: the 16-wave kernel, which never deals
+    if (F.kernel != BWD_FROZEN || F.train_role != -1 || !F.skip_eligible || F.deal_eligible || F.waves != 16 || F.scan_halves != 4) { ++failures; fprintf(stderr, "FAIL form: fine stage\n"); }
+    K.n = 3; K.which[0] = 3; K.which[1] = 2; K.which[2] = 1; K.grids = false; K.rays = true; K.track = true; K.N = 200;
+    F = bwd_form(K);                                       // the Tracker
+    if (F.kernel != BWD_TRACK || !F.mask_ok || F.skip_eligible || F.scan_may_ride) { ++failures; fprintf(stderr, "FAIL form: Tracker\n"); }
+    if (median_form(true, false, 0, 0, 200, 256, true, false, false) != MEDIAN_DEFERRED || median_form(true, false, 0, 1, 200, 256, true, false, false) != MEDIAN_BARRIER ||
+        median_form(true, false, 0, 1, 1024, 256, true, false, false) != MEDIAN_BARRIER || median_form(true, false, 0, 1, 1025, 256, true, false, false) != MEDIAN_THREE ||
+        median_form(true, false, 0, 1, 201, 50, true, false, false) != MEDIAN_THREE || median_form(true, false, 0, 1, 200, 50, true, false, false) != MEDIAN_BARRIER) {
+        ++failures; fprintf(stderr, "FAIL form: median at its boundaries\n");
+    }
+    if (bwd_separate_grid(256, 3000, false) != 256 || bwd_separate_grid(256, 9, false) != 2 || bwd_separate_grid(256, 0, false) != 1 || bwd_separate_grid(256, 3000, true) != 1) {
+        ++failures; fprintf(stderr, "FAIL form: bwd_separate_grid\n");
+    }
+    return forms;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 2 && !strcmp(argv[1], "--dump")) return dump();
@@ -239,6 +368,9 @@ int main(int argc, char** argv)
     const int table_failures = failures;
     const long plans = knob_sweep();
     printf("split_test: knob sweep %ld plans, %d failures\n", plans, failures - table_failures);
+    const int knob_failures = failures;
+    const long forms = form_sweep();
+    printf("split_test: form sweep %ld forms, %d failures\n", forms, failures - knob_failures);
     printf("split_test: %ld rows, %d failures\n", rows, failures);
     return failures ? 1 : 0;
 }

@@ -22,3 +22,8 @@ def test_the_split_planner_reproduces_its_recorded_table():
     assert r.returncode == 0 and "split_test: %d rows, 0 failures" % rows in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
     m = re.search(r"split_test: knob sweep (\d+) plans, 0 failures", r.stdout)
     assert m and int(m.group(1)) > 100000, r.stdout[-1500:] + r.stderr[-3000:]
+    # which backward launch goes out and which median form runs in front of it (bwd_form, bwd_deal_role, bwd_grid, median_form): every combination of
+    # the boolean inputs, the four stages' role sets x trainable subsets, N in {1, 200, 1024, 1025}, num_cu in {50, 256}, against the properties
+    # the launch code states (exactly one kernel; what the Tracker's launch, the frozen kernel, the dead-tile skip, dealing and the scan rider need)
+    m = re.search(r"split_test: form sweep (\d+) forms, 0 failures", r.stdout)
+    assert m and int(m.group(1)) > 50000, r.stdout[-1500:] + r.stderr[-3000:]
