@@ -946,6 +946,50 @@ int nsk_hull_upload(nsk_ctx* ctx, const float* h_xyz, int n_vertices, const int3
 int nsk_lattice_in_hull(nsk_ctx* ctx, const float h_origin[3], const float h_step[3], int nx, int ny, int nz, double scale,
                         int accumulate, uint8_t* d_valid, long long* n_inside);
 
+/* ---- a mesh made smaller: uniform vertex clustering (Rossignac-Borrel).  All vertices in one cell of a uniform grid collapse to one
+ * representative, triangles are re-indexed, collapsed and duplicate triangles and unreferenced vertices go ------------------------------ */
+/* nsk_mesh_simplify: d_vertices [n_vertices][3] float32, d_triangles [n_triangles][3] int32 (device, the caller's) -> d_out_vertices
+ * [out_vertices][3], d_out_triangles [out_triangles][3] and, unless NULL, d_vertex_map [n_vertices]: buffers of the caller, on the device,
+ * sized for the input, not aliasing it (as in nsk_mesh_select).  At most (2^31 - 1) / 3 vertices and triangles; empty inputs and empty
+ * results are valid.  Every decision is made on integers, so two runs, a fresh context and tests/simplify_checks.py give the same bytes:
+ *   1. cell is finite and > 0, else an error.  A vertex with a non-finite coordinate is left out and counted; a triangle with an index
+ *      outside [0, n_vertices), or naming a left-out vertex, is dropped and counted (invalid);
+ *   2. lo_a / hi_a: the finite vertices' minimum / maximum per axis, widened to double;  g_a = (double(p_a) - lo_a) / double(cell);
+ *      c_a = (int64) floor(g_a);  n_a = c_a(hi_a) + 1: every operation an fp64 operation of its own, no contraction.  The cell index is
+ *      (c_z n_y + c_y) n_x + c_x.  More than 2^28 cells is an error that names the count; so is an axis of more than 2^21 - 1 cells
+ *      (h_info[7] packs 21 bits per axis).  The context stays usable after either;
+ *   3. the representative of a cell is a fixed-point mean, so that no floating-point atomic decides a bit:
+ *      q_a = (int64) rint((g_a - c_a) * 2^20), ties to even; per cell the member count and the three sums of q_a over ALL its finite
+ *      vertices (referenced by a triangle or not) are accumulated with integer atomics -- with count < 2^31 every sum is < 2^51;
+ *      m_a = double(sum_a) / double(count);  the position is float(lo_a + (double(c_a) + m_a / 2^20) * double(cell)), each operation fp64,
+ *      then one rounding to float;
+ *   4. a triangle's corners map to their cells.  It is COLLAPSED (dropped, counted) when two corners share a cell.  Unless flags & 1 it is
+ *      a DUPLICATE (dropped, counted) when a valid, not collapsed triangle with a lower input index has the same corner cells in the same
+ *      cyclic order: the triples are compared after rotating the smallest cell to the front.  The mirrored triple (a, c, b) is NOT a
+ *      duplicate: the two sides of a thin wall stay.  Kept triangles keep their relative order and their own corner order.  (With
+ *      flags & 1 the output of a closed oriented mesh still has every directed edge as often as its reverse: identifying vertices commutes
+ *      with the boundary.  Removing a duplicate can break that balance.)
+ *   5. the output vertices are the cells a kept triangle names, in ascending cell index; the triangles are re-indexed;
+ *      d_vertex_map[i] = the output vertex of input vertex i, or -1 (left out, or its cell is named by no kept triangle);
+ *   6. h_info: [0] finite vertices, [1] vertices left out, [2] triangles dropped as invalid, [3] collapsed, [4] duplicates, [5] occupied
+ *      cells, [6] cells, [7] n_x | n_y << 21 | n_z << 42.  Without a finite vertex there is no grid: [5] = [6] = [7] = 0, every triangle
+ *      is invalid, every map entry -1.
+ * Passes (csrc/nsk_simplify.h): the bounds (the first pass of nsk_points_hull), the vertices' cells and a 4-byte occupancy flag per cell,
+ * the multi-launch scan of nsk_mesh_extract over the flags, so that count and sums (28 B) and the cell index (4 B) exist per OCCUPIED cell
+ * only, the integer accumulation (a run of equal cells inside a wave is summed by shuffles and adds once per word), the triangles'
+ * corner cells, duplicate detection without a sort (every surviving triangle is registered under its smallest corner by count -> scan ->
+ * placement through an integer cursor; a triangle is a duplicate iff its list holds an equal rotated triple with a lower input index,
+ * whatever order the cursor gave: one thread searches a list of up to nsk_mesh_simplify_list_threshold() triangles, a workgroup a
+ * longer one; a list of k triangles costs k^2 comparisons), the collapsed count derived from the others, flags -> scans ->
+ * compaction without an atomic append.  Device memory: 4 B per vertex, 4 B per cell, 40 B per occupied cell, 20 B per triangle (+ the
+ * scans' levels, 1 / 255 of the flags).  Three synchronisations: the bounds size the flags, the occupied count sizes the sums, the last
+ * fetches the counts.  A failing allocation names its byte count; the context stays usable.  Not while a graph is being captured. */
+int nsk_mesh_simplify(nsk_ctx* ctx, const float* d_vertices, int n_vertices, const int32_t* d_triangles, int n_triangles, float cell, int flags,
+                      float* d_out_vertices, int32_t* d_out_triangles, int32_t* d_vertex_map, int* out_vertices, int* out_triangles,
+                      long long h_info[8]);
+/* the longest smallest-corner list one thread searches (a first choice, not tuned) */
+int nsk_mesh_simplify_list_threshold(void);
+
 /* nsk_mesh_vertex_normals: the area-weighted unit normal of every vertex of a mesh (d_vertices [n_vertices][3] float32, d_triangles
  * [n_triangles][3] int32) into d_normals [n_vertices][3].  With the winding of nsk_mesh_extract the normals point to free space.  Every
  * operation below is an fp32 operation of its own (no FMA contraction).

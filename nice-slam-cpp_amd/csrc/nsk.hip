@@ -920,6 +920,16 @@ struct nsk_ctx {
             for (size_t k = 0; k < t.size(); ++k) local[k] = (int)(std::lower_bound(verts.begin(), verts.end(), t[k]) - verts.begin());
         }
     } hull;
+    // mesh simplification by vertex clustering (nsk_simplify.h): scratch that grows to the largest call and stays
+    struct Simplify {
+        Buf<float> part;                                     // the bounds pass's partial boxes
+        Buf<unsigned> vcell;                                 // [vertices] the cell of every vertex
+        Buf<unsigned> occ;                                   // [cells + 1 + scan levels] occupancy flag -> rank among the occupied cells
+        Buf<unsigned> cnt, cellof; Buf<unsigned long long> sums;     // [occupied], [occupied], [occupied][3]: members, cell index, sums of q
+        Buf<unsigned> loff, vflag;                           // [occupied + 1 + scan levels] each: the smallest-corner lists' ends; referenced flag -> output index
+        Buf<unsigned> tkey, tflag, list, longq;              // [triangles][3] corner ranks, [triangles + 1 + scan levels] kept flag -> output index, [triangles] the lists, the long lists' queue
+        Buf<unsigned> counters;                              // [0] invalid, [2] duplicates, [3] the queue's length
+    } simplify;
     // the optional count of an entry point (count_begin / count_end): nsk_lattice_seen, nsk_points_seen, nsk_tsdf_integrate, nsk_tsdf_volume,
     // nsk_lattice_in_hull
     Buf<unsigned long long> count;
@@ -3921,6 +3931,9 @@ extern "C" int nsk_depth_views(nsk_ctx* c, const float* d_vertices, int n_vertic
 
 // ---- convex hull of a point cloud, lattice nodes inside the scaled hull (kernels and entry points: nsk_hull.h) ---------------------------
 #include "nsk_hull.h"
+
+// ---- mesh simplification by uniform vertex clustering (kernels and entry points: nsk_simplify.h) -----------------------------------------
+#include "nsk_simplify.h"
 
 // ---- raw frames prepared on the device: undistort, resize, crop (kernel and entry points: nsk_frame.h) -----------------------------------
 #include "nsk_frame.h"

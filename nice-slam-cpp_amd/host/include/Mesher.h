@@ -78,6 +78,14 @@ struct CulledMesh {
     int skipped = 0;                        // triangles with an index out of range (in neither part)
 };
 
+// what Mesher::simplify_mesh returns: the mesh clustered on a uniform grid (nsk_mesh_simplify)
+struct SimplifiedMesh {
+    std::vector<float> xyz;                 // [vertices][3]: one representative per cell a kept triangle names, in ascending cell index
+    std::vector<int32_t> triangles;         // [triangles][3]: the triangles that are neither collapsed nor duplicates, re-indexed, in their old order
+    std::vector<int32_t> vertex_map;        // [input vertices]: the output vertex of every input vertex, or -1
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // nsk_mesh_simplify's h_info: finite, left out, invalid, collapsed, duplicates, occupied cells, cells, packed dimensions
+};
+
 class Mesher {
   public:
     Mesher(YAML::Node ns_config, torch::Tensor bound_3x2 = torch::Tensor(), float padding = 0.f);
@@ -180,6 +188,13 @@ class Mesher {
     static CulledMesh cull_mesh(const std::string& in_ply, const std::string& out_ply, const float* w2c, int K, int H, int W, float fx, float fy,
                                 float cx, float cy, const float* depths = nullptr, const std::string& occlusion = "none", int edge = 0,
                                 float eps = 0.03f, int frames_per_batch = 32);
+    // Uniform vertex clustering on the device (nsk_mesh_simplify, include/nsk.h states the rule): all vertices in one cell of a grid of
+    // edge `cell` (m) collapse to their fixed-point mean; collapsed triangles go, and unless keep_duplicates so do triangles that repeat an
+    // earlier one's cells in the same cyclic order; vertices no kept triangle names go.  Host arrays; needs no map.
+    static SimplifiedMesh simplify_mesh(const float* xyz, int n_vertices, const int32_t* triangles, int n_triangles, float cell,
+                                        bool keep_duplicates = false);
+    // the same from a PLY file (read_ply_mesh) into a PLY file (write_ply, no colours)
+    static SimplifiedMesh simplify_mesh(const std::string& in_ply, const std::string& out_ply, float cell, bool keep_duplicates = false);
     // n area-weighted samples [n][3] of the part of the mesh that was not seen (nsk_mesh_select part 1, then nsk_mesh_sample): what
     // eval_recon_depth takes as unseen_xyz.  Empty when n = 0 or every valid triangle was seen.
     static std::vector<float> unseen_points(const float* xyz, int n_vertices, const int32_t* triangles, int n_triangles, const uint8_t* seen,
@@ -199,6 +214,12 @@ class Mesher {
                                 // frustum selection lets voxels train (nsk_frustum_mask)
     int seen_edge = 0;          // pixels ignored along the image border
     int last_vertices = 0, last_triangles = 0;
+    // The cell edge (m) of the vertex clustering that get_mesh, get_clean_mesh, get_fused_mesh, get_rendered_mesh and get_hull_mesh apply
+    // to the mesh behind the component filter and in front of colours and normals, which are then those of the mesh that is written.
+    // 0: off, every PLY is what it is without this member.  last_vertices / last_triangles stay the counts in front of the clustering.
+    float simplify_cell = 0.f;
+    int last_simplified_vertices = 0, last_simplified_triangles = 0;      // what was written (= last_vertices / last_triangles with simplify_cell 0)
+    int last_collapsed = 0, last_duplicates = 0;                          // triangles the clustering dropped
     int last_components = 0, last_kept = 0;     // get_clean_mesh: components before the filter, components kept
     long long last_seen = 0;                    // get_clean_mesh: lattice nodes at least one keyframe saw
     long long last_evaluated = 0;               // lattice nodes the decoders ran on (get_mesh without valid: all of them)

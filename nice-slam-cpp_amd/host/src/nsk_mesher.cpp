@@ -123,15 +123,30 @@ static void write_context_mesh(Mesher& M, const std::string& path, bool color, i
     if (M.color_method != "direct_point_query" && M.color_method != "render_ray_along_normal")
         throw std::runtime_error("Mesher: color_method must be direct_point_query or render_ray_along_normal, not " + M.color_method);
     const bool along = color && M.color_method == "render_ray_along_normal", want_normals = M.write_normals || along;
+    if (!(M.simplify_cell >= 0.f) || !std::isfinite(M.simplify_cell)) throw std::runtime_error("Mesher: simplify_cell must be >= 0 and finite");
+    // simplify_cell > 0: the context's mesh clustered into buffers of this call (nsk_mesh_simplify); colours and normals are then those of
+    // the smaller mesh.  0: the context's mesh as it is
+    M.last_simplified_vertices = nv; M.last_simplified_triangles = nt; M.last_collapsed = M.last_duplicates = 0;
+    DevArr<float> sv; DevArr<int32_t> st;
+    const bool simplified = M.simplify_cell > 0.f;
+    if (simplified) {
+        float* d_verts = nullptr; int32_t* d_tris = nullptr;
+        check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
+        sv.ensure((size_t)nv * 3); st.ensure((size_t)nt * 3);
+        long long info[8];
+        check(nsk_mesh_simplify(ctx(), nv > 0 ? d_verts : nullptr, nv, nt > 0 ? d_tris : nullptr, nt, M.simplify_cell, 0, sv.p(), st.p(), nullptr, &nv, &nt, info));
+        M.last_simplified_vertices = nv; M.last_simplified_triangles = nt; M.last_collapsed = (int)info[3]; M.last_duplicates = (int)info[4];
+    }
     std::vector<float> xyz((size_t)nv * 3);
     std::vector<int32_t> tris((size_t)nt * 3);
-    check(nsk_mesh_download(ctx(), xyz.data(), tris.data()));
+    if (simplified) { sv.download(xyz.data(), xyz.size()); st.download(tris.data(), tris.size()); }
+    else check(nsk_mesh_download(ctx(), xyz.data(), tris.data()));
     std::vector<uint8_t> rgb;
     std::vector<float> normals;
     M.last_color_fallback = M.last_normals_zero = 0;
     if ((color || want_normals) && nv > 0) {
-        float* d_verts = nullptr; int32_t* d_tris = nullptr;
-        check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
+        float* d_verts = sv.p(); int32_t* d_tris = st.p();
+        if (!simplified) check(nsk_mesh_buffers(ctx(), &d_verts, &d_tris));
         const size_t nf = (size_t)nv * 3;
         DevArr<float> dn(want_normals ? nf : 0), raw(color ? nf : 0);
         if (want_normals) {
@@ -790,6 +805,32 @@ CulledMesh Mesher::cull_mesh(const std::string& in_ply, const std::string& out_p
     read_ply_mesh(in_ply, xyz, tris);
     CulledMesh R = cull_mesh(xyz.data(), (int)(xyz.size() / 3), tris.data(), (int)(tris.size() / 3), w2c, K, H, W, fx, fy, cx, cy, depths, occlusion,
                              edge, eps, frames_per_batch);
+    write_ply(out_ply, R.xyz.data(), nullptr, (int)(R.xyz.size() / 3), R.triangles.data(), (int)(R.triangles.size() / 3));
+    return R;
+}
+
+// ---- a mesh made smaller: vertex clustering -------------------------------------------------------------------------------------------------
+SimplifiedMesh Mesher::simplify_mesh(const float* xyz, int nv, const int32_t* tris, int nt, float cell, bool keep_duplicates)
+{
+    if (nv < 0 || nt < 0) throw std::runtime_error("Mesher::simplify_mesh: negative count");
+    const DevMesh in(xyz, nv, tris, nt);
+    DevArr<float> ov((size_t)nv * 3);
+    DevArr<int32_t> ot((size_t)nt * 3), vmap((size_t)nv);
+    SimplifiedMesh R;
+    int onv = 0, ont = 0;
+    check(nsk_mesh_simplify(ctx(), nv > 0 ? in.v.p() : nullptr, nv, nt > 0 ? in.t.p() : nullptr, nt, cell, keep_duplicates ? 1 : 0, ov.p(), ot.p(), vmap.p(),
+                            &onv, &ont, R.info));
+    R.xyz.resize((size_t)onv * 3); R.triangles.resize((size_t)ont * 3); R.vertex_map.resize((size_t)nv);
+    ov.download(R.xyz.data(), R.xyz.size()); ot.download(R.triangles.data(), R.triangles.size()); vmap.download(R.vertex_map.data(), R.vertex_map.size());
+    return R;
+}
+
+SimplifiedMesh Mesher::simplify_mesh(const std::string& in_ply, const std::string& out_ply, float cell, bool keep_duplicates)
+{
+    std::vector<float> xyz;
+    std::vector<int32_t> tris;
+    read_ply_mesh(in_ply, xyz, tris);
+    SimplifiedMesh R = simplify_mesh(xyz.data(), (int)(xyz.size() / 3), tris.data(), (int)(tris.size() / 3), cell, keep_duplicates);
     write_ply(out_ply, R.xyz.data(), nullptr, (int)(R.xyz.size() / 3), R.triangles.data(), (int)(R.triangles.size() / 3));
     return R;
 }

@@ -1,8 +1,9 @@
 // mesh_test.cpp -- driver of the Mesher for tests/test_mesh_cpu.py and tests/test_gpu_mesh.py.
 //   mesh_test ply <file.ply> <color 0|1>        write a small fixed mesh, read it back, compare (no GPU)
-//   mesh_test scene <dir> <resolution> <color 0|1> [padding]
+//   mesh_test scene <dir> <resolution> <color 0|1> [padding [simplify_cell]]
 //        the scene in <dir> (bound.npy [3,2], grid_{coarse,middle,fine,color}.npy [1,32,Z,Y,X], dec_{coarse,middle,fine,color}.npy packed,
-//        optional valid.npy [resolution^3] as float 0 / 1) through Mesher::get_mesh -> <dir>/mesh.ply
+//        optional valid.npy [resolution^3] as float 0 / 1) through Mesher::get_mesh -> <dir>/mesh.ply; simplify_cell given: the member is set
+//        to it (0 included), else it is never touched
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -71,8 +72,11 @@ int main(int argc, char** argv)
         Mesher mesher(ns, load_npy(dir + "bound.npy"), argc > 5 ? (float)std::atof(argv[5]) : 0.f);
         torch::Tensor valid;
         if (exists(dir + "valid.npy")) valid = load_npy(dir + "valid.npy").ne(0).to(torch::kUInt8);
+        if (argc > 6) mesher.simplify_cell = (float)std::atof(argv[6]);
         mesher.get_mesh(dir + "mesh.ply", decoders, c, std::atoi(argv[4]) != 0, valid);
         std::printf("mesh_test scene ok: %d vertices, %d triangles\n", mesher.last_vertices, mesher.last_triangles);
+        if (argc > 6) std::printf("simplified: %d vertices, %d triangles, %d collapsed, %d duplicates\n", mesher.last_simplified_vertices,
+                                  mesher.last_simplified_triangles, mesher.last_collapsed, mesher.last_duplicates);
         return 0;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "mesh_test failed: %s\n", e.what());

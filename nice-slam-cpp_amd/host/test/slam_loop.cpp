@@ -1,9 +1,11 @@
 // slam_loop.cpp -- the frame loop BASELINE.json's K5 describes (Tracker on every frame, Mapper on every `every`-th, over a posed RGB-D
 // sequence) through the C++ classes with the reference's surface and a SequenceReader; src/main.cpp wires up the Tracker only.
-//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull]
+//   slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull] [--mesh-simplify CELL]
 // --mesh FILE: after the last frame the scene mesh (Mesher, meshing.resolution / meshing.level_set of nice_slam.yaml) goes to FILE as a PLY.
 // --mesh-hull: with --mesh, the loop keeps the mapped frames' depth images and estimated poses and the mesh is bounded as upstream's get_mesh
 //              bounds it (Mesher::get_hull_mesh: the convex hull of the frames' fusion and the camera centres, meshing.clean_mesh_bound_scale).
+// --mesh-simplify CELL: with --mesh, the mesh is clustered on a uniform grid of edge CELL metres before it is coloured and written
+//              (Mesher::simplify_cell, nsk_mesh_simplify).
 // When the cam block of <cofusion.yaml> has a crop_size, a distortion or a crop_edge > 0 (upstream NICE-SLAM's TUM and ScanNet blocks), every
 // frame goes through nskh::FramePrep (undistort, resize, crop on the device from the reader's raw bytes) and the Tracker and the Mapper get
 // its camera; without them the loop is what it was, byte for byte.  A block without png_depth_scale takes the reader's.
@@ -52,6 +54,14 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    float mesh_simplify = 0.f;
+    for (int a = 1; a + 1 < argc; ++a)
+        if (std::string(argv[a]) == "--mesh-simplify") {
+            mesh_simplify = (float)std::atof(argv[a + 1]);
+            for (int b = a; b + 2 < argc; ++b) argv[b] = argv[b + 2];
+            argc -= 2;
+            break;
+        }
     bool mesh_hull = false;
     for (int a = 1; a < argc; ++a)
         if (std::string(argv[a]) == "--mesh-hull") {
@@ -60,7 +70,7 @@ int main(int argc, char** argv)
             argc -= 1;
             break;
         }
-    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull]\n"); return 2; }
+    if (argc < 6) { std::fprintf(stderr, "usage: slam_loop <tum|replica|scannet> <sequence dir> <nice_slam.yaml> <cofusion.yaml> <out dir> [frames] [map every] [--mesh FILE] [--mesh-hull] [--mesh-simplify CELL]\n"); return 2; }
     mesh_hull = mesh_hull && !mesh_path.empty();
     const std::string kind = argv[1], seq = argv[2], out = std::string(argv[5]) + "/";
     const int max_frames = argc > 6 ? std::atoi(argv[6]) : -1, every = argc > 7 ? std::atoi(argv[7]) : 1;
@@ -156,6 +166,7 @@ int main(int argc, char** argv)
         for (auto k : keys) save_npy(out + k + ".npy", c.at(k));
         if (!mesh_path.empty()) {
             Mesher mesher(ns, bound);
+            mesher.simplify_cell = mesh_simplify;
             if (mesh_hull) {
                 std::vector<torch::Tensor> poses;
                 for (int i : hull_frames) poses.push_back(est[(size_t)i]);
@@ -167,7 +178,11 @@ int main(int argc, char** argv)
                             mesher.last_inside, (long long)mesher.resolution * mesher.resolution * mesher.resolution, (double)mesher.clean_mesh_bound_scale);
             } else
                 mesher.get_mesh(mesh_path, decoders, c, true);
-            std::printf("mesh: %d vertices, %d triangles -> %s\n", mesher.last_vertices, mesher.last_triangles, mesh_path.c_str());
+            if (mesh_simplify > 0.f)
+                std::printf("simplified (cell %.4g m): %d of %d vertices, %d of %d triangles, %d collapsed, %d duplicates\n", (double)mesh_simplify,
+                            mesher.last_simplified_vertices, mesher.last_vertices, mesher.last_simplified_triangles, mesher.last_triangles, mesher.last_collapsed,
+                            mesher.last_duplicates);
+            std::printf("mesh: %d vertices, %d triangles -> %s\n", mesher.last_simplified_vertices, mesher.last_simplified_triangles, mesh_path.c_str());
         }
         std::printf("slam_loop ok\n");
         return 0;

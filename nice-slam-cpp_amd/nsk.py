@@ -38,6 +38,7 @@ SYMBOLS = (
     "nsk_frame_plan", "nsk_frame_prepare",
     "nsk_set_importance", "nsk_get_importance", "nsk_importance_resample",
     "nsk_points_hull", "nsk_hull_download", "nsk_hull_upload", "nsk_lattice_in_hull",
+    "nsk_mesh_simplify", "nsk_mesh_simplify_list_threshold",
 )
 
 FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
@@ -175,6 +176,11 @@ def lib():
         L.nsk_lattice_in_hull.restype = C.c_int
         L.nsk_lattice_in_hull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_longlong)]
+        L.nsk_mesh_simplify.restype = C.c_int
+        L.nsk_mesh_simplify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        L.nsk_mesh_simplify_list_threshold.restype = C.c_int
+        L.nsk_mesh_simplify_list_threshold.argtypes = []
         L.nsk_decoder_image_table.restype = C.c_int
         L.nsk_decoder_image_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         _lib = L
@@ -192,6 +198,11 @@ def _ptr(t):
         return None
     assert t.is_cuda and t.is_contiguous(), "expected a contiguous CUDA tensor"
     return C.c_void_p(t.data_ptr())
+
+
+def simplify_list_threshold():
+    """the longest smallest-corner list one thread of nsk_mesh_simplify searches (a longer one takes a workgroup); needs no GPU"""
+    return int(lib().nsk_mesh_simplify_list_threshold())
 
 
 def mesh_table(case):
@@ -993,6 +1004,32 @@ class Context:
                                    _ptr(ov) if nv else None, _ptr(ot) if nt else None, _ptr(src) if nv else None, C.byref(a), C.byref(b),
                                    C.byref(sk)))
         return ov[:a.value].clone(), ot[:b.value].clone(), src[:a.value].clone(), int(sk.value)
+
+    @_ordered
+    def simplify_mesh(self, verts, tris, cell, keep_duplicates=False, want_map=False, want_info=False):
+        """nsk_mesh_simplify: (verts [nv, 3] float32, tris [nt, 3] int32, cuda) clustered on a uniform grid of edge `cell`: every occupied
+        cell's vertices collapse to their fixed-point mean, collapsed triangles and (unless keep_duplicates) same-orientation duplicates
+        go, unreferenced vertices go -> (verts, tris[, vertex_map int32 [nv]: the output vertex of every input vertex or -1][, info: numpy
+        int64 [8], include/nsk.h]).  Synchronises."""
+        import numpy as np
+        import torch
+        assert verts.dtype == torch.float32 and tris.dtype == torch.int32 and verts.shape[-1] == 3 and tris.shape[-1] == 3
+        nv, nt = int(verts.shape[0]), int(tris.shape[0])
+        dev = "cuda:%d" % self.device
+        ov = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        ot = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        vmap = torch.empty((nv,), dtype=torch.int32, device=dev) if want_map else None
+        a, b = C.c_int(0), C.c_int(0)
+        info = (C.c_longlong * 8)()
+        _chk(lib().nsk_mesh_simplify(self.h, _ptr(verts) if nv else None, nv, _ptr(tris) if nt else None, nt, C.c_float(cell),
+                                     1 if keep_duplicates else 0, _ptr(ov) if nv else None, _ptr(ot) if nt else None,
+                                     _ptr(vmap) if want_map and nv else None, C.byref(a), C.byref(b), info))
+        out = [ov[:a.value].clone(), ot[:b.value].clone()]
+        if want_map:
+            out.append(vmap)
+        if want_info:
+            out.append(np.array(list(info), np.int64))
+        return tuple(out)
 
     @_ordered
     def points_view_counts(self, points, w2c, HW, intr, edge=0):
